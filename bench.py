@@ -16,10 +16,14 @@ word-id range, an all-gather of the per-rank 2-NN candidates and an int64 all-re
 one independent frame stream per GPU with no data-path collective, `"scaling": "weak"`.  The other split is measured in the same
 run and reported next to it (`config.shard_value` / `config.replicas_value`).
 
-Prints ONE JSON line (rank 0).  `roofline` is the dominant kernel of the step, `roofline_score` / `roofline_knn` are the two big
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed step computed
+(DIR/<name>.npy: the frame's word ids and its likelihood vector), the inputs being seeded, so that two builds can be compared.
+Everything else takes `--full`: `roofline` is the dominant kernel of the step, `roofline_score` / `roofline_knn` are the two big
 kernels under fixed keys (HIP events around each launch inside the timed region, on the stream it is launched on);
 `cpu_baseline` times the reference-style CPU path on this box's host cores in the same run (three variants); `parity` re-runs
-frames of this configuration through a fresh engine and the oracle side by side.
+frames of this configuration through a fresh engine and the oracle side by side; the step distribution, the steady-state and
+secondary measurements, the HBM counter passes, the secondary legs and (N > 1) the other parallelism.
 """
 import argparse
 import json
@@ -138,6 +142,12 @@ class Stepper:
         self.oldest += 1
         self.first_new += Q          # (only without the device's numbering: an upper bound per frame, ids only have to ascend)
 
+    def last_word_ids(self):
+        """The device buffer the last call wrote its word ids to (a row of the log while the log has room)."""
+        if self.log_base and 0 < self.n_calls <= self.d_words_log.shape[0]:
+            return self.d_words_log[self.n_calls - 1]
+        return self.d_words
+
 
 # Bayes/PredictionLC as BayesFilter::setPredictionLC parses the default string (reference Parameters.h:363; uStr2Float -> double)
 PREDICTION_LC = np.asarray([0.1, 0.36, 0.30, 0.16, 0.062, 0.0151, 0.00255, 0.000324, 2.5e-05, 1.3e-06, 4.8e-08, 1.2e-09, 1.9e-11, 2.2e-13,
@@ -239,6 +249,24 @@ def timed_loop(torch, dist, world, stream, step, steps, warmup, profile_eng=None
     return {"wall": wall, "dev_ms": evs[0].elapsed_time(evs[steps]), "host_enqueue": host_enqueue, "per_step_ms": per_step}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 kept, anything else as float64 (integer ids are exact).  An array over its
+    share of the 64 MB is replaced by a fixed, seeded sample of its elements, written beside it with their flat indices (<name>_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_MAX_BYTES - 4096 * len(arrays)) // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // (a.itemsize + 8), replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # The pass / fail rule for Rtabmap::adjustLikelihood's value on the replays (the advisor's round-5 finding: the check must gate, not inform).
 ADJ_GATE_NOTE = ("adjusted_value_ok = for every sampled frame: |device - formula with exactly rounded (double) statistics| <= 1e-4 relative AND "
                  "|device - reference value with its float statistics| <= 1e-4 + e_ref, where e_ref = |reference float value - double value| measured on "
@@ -263,7 +291,7 @@ def measure_pmc(extra_args=()):
         return "rocprofv3 not found: traffic from the committed profile"
     base = tempfile.mkdtemp(prefix="lcd_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp", LCD_BENCH_INNER="1")
-    inner = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras", "--steps", "30", "--warmup", "5"] + list(extra_args)
+    inner = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--steps", "30", "--warmup", "5"] + list(extra_args)
     sums = {}
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
@@ -284,7 +312,7 @@ def measure_pmc(extra_args=()):
         for k, fe in sums["FETCH_SIZE"].items():
             w = sums["WRITE_SIZE"].get(k, 0.0)
             PMC_LIVE[k] = {"fetch_kb": fe, "write_kb": w, "hbm_bytes_per_launch": (2.0 * fe + w) * 1024.0}
-        return "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes over `bench.py --no-cpu-baseline --no-extras --steps 30 --warmup 5%s`" % \
+        return "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes over `bench.py --full --no-cpu-baseline --no-extras --steps 30 --warmup 5%s`" % \
                ("".join(" " + x for x in extra_args))
     except Exception as e:  # noqa: BLE001
         return "PMC measurement failed (%s): traffic from the committed profile" % type(e).__name__
@@ -739,18 +767,18 @@ def p2p_exchange_leg():
 
 def secondary_legs(budget_s=165.0):
     """The other configurations as short runs of this same script, so that what profiles/ claims for them is observed by whoever runs the
-    default command (the previous review's item 8): config 3 on 300 ORB frames, 125 000 words (one GPU's share of config 4) for 50 steps,
+    command with --full (the previous review's item 8): config 3 on 300 ORB frames, 125 000 words (one GPU's share of config 4) for 50 steps,
     10^6 signatures for 30 steps -- each with its own roofline and one frame of parity.  A leg that would not fit the time budget is skipped
     and says so; a leg that fails reports its error instead of costing the line."""
     import subprocess
     # (expected seconds on the MI355X box of round 6: 8 / 27 / 52 -- drawing 5 x 10^8 Zipf words and the numpy restatement of ONE likelihood over them
     # take most of the last one; a slower host skips it and says so; LCD_BENCH_LEGS=all lifts the budget)
-    legs = [("orb_stream_300_frames", ["--config", "orb_stream", "--steps", "300"], 15.0),
-            ("words_125k", ["--words", "125000", "--steps", "50", "--warmup", "5", "--leg"], 35.0),
-            ("signatures_1m", ["--signatures", "1000000", "--steps", "30", "--warmup", "5", "--leg"], 70.0),
+    legs = [("orb_stream_300_frames", ["--full", "--config", "orb_stream", "--steps", "300"], 15.0),
+            ("words_125k", ["--full", "--words", "125000", "--steps", "50", "--warmup", "5", "--leg"], 35.0),
+            ("signatures_1m", ["--full", "--signatures", "1000000", "--steps", "30", "--warmup", "5", "--leg"], 70.0),
             # the config-5 stand-in whose dictionary grows from empty (update -> addNewWords -> computeLikelihood -> adjustLikelihood every frame, a clean every
             # frame, retirements, rebuilds), 50 000 frames of the 10^6 of profiles/r06_bench_replay_growing_1m.json
-            ("replay_growing_50k_frames", ["--config", "replay_growing", "--signatures", "50000"], 30.0)]
+            ("replay_growing_50k_frames", ["--full", "--config", "replay_growing", "--signatures", "50000"], 30.0)]
     if os.environ.get("LCD_BENCH_LEGS", "") == "all":
         budget_s = 1200.0
     out = {"note": "short runs of `python bench.py <args>` by this run; the full-size lines are profiles/r06_bench_*.json"}
@@ -759,7 +787,7 @@ def secondary_legs(budget_s=165.0):
     for name, extra, expect in legs:
         left = budget_s - (time.perf_counter() - t_start)
         if left < 0.6 * expect:
-            out[name] = {"skipped": "time budget of the default command (%.0f s left, the leg needs ~%.0f s)" % (left, expect)}
+            out[name] = {"skipped": "time budget of the --full command (%.0f s left, the leg needs ~%.0f s)" % (left, expect)}
             continue
         t0 = time.perf_counter()
         try:
@@ -798,7 +826,7 @@ def run_orb_stream(args):
     import rtabmap_amd
     from rtabmap_amd import synth
     import oracle as O
-    n_frames, q, W, n_check, n_tail = (args.steps if args.steps != 200 else 2000), 500, 1000, 60, 20
+    n_frames, q, W, n_check, n_tail = (args.steps if args.steps is not None else 2000), 500, 1000, 60, 20
     base = synth.vocab_orb(200000)
     # Queries-ORB of SURVEY.md 8d, a fresh draw per frame: 90 % noisy copies (each bit flipped w.p. 0.1) of rows of the hidden 200k-row
     # Vocab-ORB -- they come back in later frames and keep their words alive --, 10 % uniform random descriptors: words that die when their
@@ -1515,7 +1543,8 @@ def run_replay_growing(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; --config orb_stream: frames of the stream, default 2000; "
+                    "the replays run one frame per signature, --signatures)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--signatures", type=int, default=N_SIG)
     ap.add_argument("--words", type=int, default=N_WORDS, help="vocabulary size (the headline is 49 000; 125 000 = one GPU's share of config 4, "
@@ -1547,10 +1576,23 @@ def main():
     ap.add_argument("--diag", default="", help="diagnostics only (not the benchmark): comma list of no-new (new words get no references), "
                     "no-retire (the oldest signature is not retired), bound-ids (the caller numbers new words with an upper bound per frame instead of "
                     "the device numbering them as ++_lastWordId does)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: rooflines, the step distribution and steady state, the "
+                    "secondary measurements, HBM counter passes, parity against the oracle, CPU baselines, the secondary legs and (N > 1) the "
+                    "other parallelism; the --no-* options above trim it.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy: "
+                    "word_ids (the frame's word ids as lcd_frame_dev returns them: -(k+1) = the frame's k-th new word) and likelihood (every "
+                    "signature slot); float32 / float64, at most 64 MB")
     args = ap.parse_args()
 
     if args.leg:
+        args.full = True
         args.no_extras = True; args.no_pmc = True; args.no_legs = True
+    if args.pmc and not args.full:
+        ap.error("--pmc needs --full")
+    if args.dump_outputs and args.config != "headline":
+        ap.error("--dump-outputs: the headline configuration only")
+    if not args.full:
+        args.no_extras = True; args.no_pmc = True; args.no_legs = True; args.no_cpu_baseline = True
     DIAG.update(x for x in args.diag.split(",") if x)
     if args.knn_mode:
         globals()["KNN_MODE"] = args.knn_mode
@@ -1566,6 +1608,8 @@ def main():
         raise SystemExit("bench.py needs a GPU: the engine has no CPU fallback")
     if args.config == "orb_stream":
         return run_orb_stream(args)
+    if args.steps is None:
+        args.steps = 200
     if args.config == "replay":
         return run_replay(args)
     if args.config == "replay_growing":
@@ -1632,8 +1676,8 @@ def main():
             state["next"] += 1
             state["old"] += 1
             state["first_new"] += Q
-        res = timed_loop(torch, dist, world, stream, step, args.steps, args.warmup, profile_eng=sh.eng)
-        roofs = rooflines(sh.eng, sh.hi - sh.lo, n_sig, True)
+        res = timed_loop(torch, dist, world, stream, step, args.steps, args.warmup, profile_eng=sh.eng if args.full else None)
+        roofs = rooflines(sh.eng, sh.hi - sh.lo, n_sig, True) if args.full else (None, None)
         like = sh.flush().cpu().numpy()                    # the last frame's (every timed step finalised its predecessor's); flush waits for the engine stream
         sh.close()
         return res, roofs, like, build_s, src
@@ -1672,6 +1716,7 @@ def main():
     # ---- primary measurement
     if shard:
         res, (roof_knn, roof_score), like, build_s, src = run_shard()
+        last_words = None                                  # (the sharded frame's word ids stay inside ShardedLoopClosure)
         frames_total = args.steps
     else:
         src, frames_np = make_frames(rank)                 # replicas: every rank has its own stream of frames
@@ -1686,24 +1731,29 @@ def main():
         log("[bench] rank %d: %d signatures bulk-loaded in %.2fs" % (rank, n_sig, build_s))
         log_frames = (args.warmup + args.steps) if (world == 1 and not args.no_cpu_baseline and args.warmup + args.steps <= 4096) else 0
         step = Stepper(eng, torch, d_frames, n_sig, cap, log_frames=log_frames)
-        eng.set_option("profile_likelihood", 0)           # the timed region brackets launch A only (the dominant kernel)
-        try:
-            eng.set_option("profile_skip", args.steps // 2 if args.steps >= 10 else 0)   # ... of the steps in the middle of the region, not of the first launches behind an idle queue
-        except Exception:                                 # (an older variant library of an A/B run: it samples the first launches)
-            pass
-        res = timed_loop(torch, dist, world, stream, step, args.steps, args.warmup, profile_eng=eng, eng=eng, per_step_events=False, prof_n=max(1, args.steps // 20))
-        knn_series = eng.profile_read()
+        if args.full:
+            eng.set_option("profile_likelihood", 0)       # the timed region brackets launch A only (the dominant kernel)
+            try:
+                eng.set_option("profile_skip", args.steps // 2 if args.steps >= 10 else 0)   # ... of the steps in the middle of the region, not of the first launches behind an idle queue
+            except Exception:                             # (an older variant library of an A/B run: it samples the first launches)
+                pass
+        res = timed_loop(torch, dist, world, stream, step, args.steps, args.warmup, profile_eng=eng if args.full else None, eng=eng,
+                         per_step_events=False, prof_n=max(1, args.steps // 20))
+        knn_series = eng.profile_read() if args.full else None
         st = eng.stats()                                  # (drains the engine's thread)
         like = step.d_like[: n_sig + args.steps + args.warmup].cpu().numpy()
-        eng.set_option("profile_likelihood", 1)           # launch B: bracketed in 24 further steps that do not count for `value`
-        eng.profile_begin(10)
-        for i in range(24):
-            step(args.warmup + args.steps + i)
-        roof_knn, roof_score = rooflines(eng, N_WORDS, n_sig, False, knn_timed=knn_series)
-        roof_knn["measured_in"] = ("%d launch(es) of the timed region (steps from its middle on) + %d of the 24 steps right behind it (HIP events attached to the dispatch); "
-                                   "in the timed region alone: %.4f ms" % (knn_series[1], roof_knn["samples"] - knn_series[1], knn_series[0]))
-        if roof_score:
-            roof_score["measured_in"] = "24 steps after the timed region (HIP events around launch B of 10 of them)"
+        last_words = step.last_word_ids().cpu().numpy() if args.dump_outputs else None
+        roof_knn = roof_score = None
+        if args.full:
+            eng.set_option("profile_likelihood", 1)       # launch B: bracketed in 24 further steps that do not count for `value`
+            eng.profile_begin(10)
+            for i in range(24):
+                step(args.warmup + args.steps + i)
+            roof_knn, roof_score = rooflines(eng, N_WORDS, n_sig, False, knn_timed=knn_series)
+            roof_knn["measured_in"] = ("%d launch(es) of the timed region (steps from its middle on) + %d of the 24 steps right behind it (HIP events attached to the dispatch); "
+                                       "in the timed region alone: %.4f ms" % (knn_series[1], roof_knn["samples"] - knn_series[1], knn_series[0]))
+            if roof_score:
+                roof_score["measured_in"] = "24 steps after the timed region (HIP events around launch B of 10 of them)"
         frames_total = world * args.steps
         host_in_c = 1e-6 * st["frame_host_ns"] / max(st["frame_calls"], 1)
     wall = res["wall"]
@@ -1730,8 +1780,13 @@ def main():
 
     if not shard:
         config["host_ms_inside_lcd_frame_dev"] = host_in_c
+    if rank == 0 and args.dump_outputs:
+        outputs = {"likelihood": like}
+        if last_words is not None:
+            outputs["word_ids"] = last_words
+        dump_outputs(args.dump_outputs, outputs)
     # ---- the distribution needs >= 50 frames: extra, untimed-for-`value` steps when the driver asked for fewer
-    if not shard:
+    if not shard and args.full:
         extra = timed_loop(torch, dist, world, stream, step, max(64, min(args.steps, 256)), 0, eng=eng)
         config["step_ms_median"] = float(np.median(extra["per_step_ms"]))
         config["step_ms_p95"] = float(np.percentile(extra["per_step_ms"], 95))
@@ -1740,7 +1795,7 @@ def main():
 
     # ---- the same step over >= 200 further frames without any event in the stream: what the 20-step figure converges to once its
     # pipeline fill / drain (3 of 23 launch pairs) and the box-to-box noise of a 0.8 ms region stop mattering (the previous review's item 8)
-    if not shard and world == 1:
+    if not shard and world == 1 and args.full:
         n_steady = max(200, args.steps)
         steady = timed_loop(torch, dist, world, stream, step, n_steady, 0, eng=eng, per_step_events=False)
         config["steady_ms_per_step"] = 1e3 * steady["wall"] / n_steady
@@ -1755,12 +1810,13 @@ def main():
             "ms_per_step": 1e3 * wall / args.steps, "higher_is_better": True, "scaling": "strong" if shard else "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic", "config": config,
         }
-        if roof_score is not None and roof_score["ms"] > roof_knn["ms"]:
-            out["roofline"] = roof_score
-        else:
-            out["roofline"] = roof_knn
-        out["roofline_score"] = roof_score
-        out["roofline_knn"] = roof_knn
+        if roof_knn is not None:
+            if roof_score is not None and roof_score["ms"] > roof_knn["ms"]:
+                out["roofline"] = roof_score
+            else:
+                out["roofline"] = roof_knn
+            out["roofline_score"] = roof_score
+            out["roofline_knn"] = roof_knn
         if rank == 0:
             exp_top = int(src[last]) + 1
             got_top = int(np.argmax(like[:n_sig])) + 1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""What the driver's timed region is made of, from a rocprofv3 --kernel-trace CSV of `bench.py --steps K --warmup W --no-cpu-baseline --no-extras --no-pmc`:
+"""What the driver's timed region is made of, from a rocprofv3 --kernel-trace CSV of `bench.py --full --steps K --warmup W --no-cpu-baseline --no-extras --no-pmc`:
     python tools/pair_stats.py <kernel_trace.csv> [label] [--dump]      (--dump: also every launch of the region: start, duration, gap in front, grid)
 The fused launches (frame_a_kernel*, frame_b_kernel*) are split into runs at gaps > 60 us; the TIMED region is the first run of at least
 2 K + 4 launches (the warm-up's run is shorter, the per-step-event leg behind it has a gap in front of every launch).  Printed (us):
