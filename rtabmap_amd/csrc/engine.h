@@ -13,6 +13,77 @@
 #include "bayes.h"
 #include "tfidf.h"
 
+// Host mirror of the vocabulary's row order (the tie-break contract): key = word id the row was appended with, live = not tombstoned.
+// While the keys are ascending (the usual case: word ids only grow) a word's row is found by binary search; only a vocabulary with
+// out-of-order appends (re-activated old words) needs the id -> row map, built lazily.
+struct RowMirror {
+    std::vector<int32_t> h_row_key;
+    std::vector<char> h_row_live;
+    bool rows_sorted = true;
+    std::unordered_map<int32_t, int32_t> word_row;      // only valid when !rows_sorted && word_row_valid
+    bool word_row_valid = false;
+    // one past the highest word id this handle has seen (rows appended by any call; "next_word_id" sets it: VWDictionary::_lastWordId + 1)
+    int32_t next_word_id = 1;
+    int find(int32_t word_id);                          // row of a live word, -1 if absent
+    void push(int32_t id, int64_t row);                 // a row enters the mirror (the caller adds to n_rows / n_live)
+    void kill(int64_t row);                             // a row is tombstoned (the caller takes it out of n_live)
+    void clear() { std::vector<int32_t> none; reset(none); }
+    void reset(std::vector<int32_t>& keys);             // every row live, keys ascending (taken from `keys`)
+    int32_t key(int64_t row) const { return h_row_key[(size_t)row]; }
+    bool live(int64_t row) const { return h_row_live[(size_t)row] != 0; }
+};
+
+struct ShardOwnership { int32_t world = 0, rank = 0, first = 0, block = 0; };   // the new words a rank appends (world 0: not sharded, every word)
+
+// The device's record of the rows frames appended (lcd_frame_args.append_new_words): the decision loop's workgroup turns the frame's new
+// words into vocabulary rows, so the row count lives on the device (d_vcnt: two alternating counters + a log of rows appended per frame).
+// The host plans launches for an upper bound (the pinned report the appender writes, + q per younger frame) and catches up with the exact
+// rows (RowMirror) the next time the handle is drained (lcd_engine::reconcile()).
+struct AppendLog {
+    static constexpr int VLOG = 4096;
+    lcd::DevBuf d_vcnt;                                 // int32: [0], [1] row counters, [16 .. 16 + VLOG) rows appended by frame seq % VLOG
+    unsigned long long* h_vmirror = nullptr;            // pinned: (seq + 1) << 32 | rows after that frame's append
+    struct DevAppend { uint64_t seq; int32_t first_id; int32_t q; bool enabled;
+                       // sharded append (lcd_shard_frame_dev): the log holds the frame's TOTAL of new words, this rank owns the ids the rule gives it
+                       ShardOwnership own; };
+    // LCD_NEW_WORD_IDS_AUTO: the words frames create are numbered on the device, id = row + id_delta (AppendArgs::first_id <= 0; DevAppend::first_id = -id_delta).
+    // id_delta is fixed while appends are unreconciled (every new word is one row and one id), auto_window says the unreconciled appenders are numbered that way
+    int32_t id_delta = 1; bool auto_window = false;
+    std::deque<DevAppend> unreconciled;                 // frames whose appends the host mirror has not caught up with
+    uint64_t vseq = 0;                                  // sequence number of the next frame in the chain: it reads counter vseq & 1, writes the other
+    bool vcnt_active = false;                           // the counters hold the row count (set when the first appending frame arrives)
+    uint32_t est_tag = 0; int64_t est_cnt = 0; double est_new = 0.0;   // last report seen, decaying maximum of new rows per appending frame
+
+    struct Report { uint32_t tag; int64_t rows; };      // what the newest finished appender wrote (tag 0: nothing yet)
+    Report report() const;
+    // rows the vocabulary can have by now: exact when nothing was appended on the device since the last reconciliation, else the count the
+    // newest finished appender reported (read without synchronising) + q per younger appending frame
+    int64_t rows_ub(int64_t n_rows) const;
+    // The rows the FILTER of chain frame `fseq` will most likely see (the count its launch reads is the one written a launch earlier: the
+    // words of the frames up to fseq - 2): what the newest finished appender reported + an estimate per appending frame between that one
+    // and fseq - 2, from the growth the reports have shown.  Only the launch PLAN is made for it -- correctness does not rest on it: the
+    // filter masks rows beyond the device's count, and the re-rank scans exactly everything from min(plan, device count) on.
+    int64_t rows_plan(uint64_t fseq, int64_t n_rows);
+    int32_t* count_before(uint64_t seq) const { return d_vcnt.as<int32_t>() + (seq & 1); }         // the counter frame `seq` reads
+    int32_t* count_after(uint64_t seq) const { return d_vcnt.as<int32_t>() + ((seq + 1) & 1); }    // ... and writes
+    int32_t* log_slot(uint64_t seq) const { return d_vcnt.as<int32_t>() + 16 + seq % VLOG; }
+    // (no-op while active) the first appending frame since the host last changed the vocabulary: the device counters take over the row count
+    hipError_t activate(int64_t n_rows, hipStream_t s, int64_t* bytes_device);
+    void restart() { vcnt_active = false; }             // the host changed the vocabulary: the counters start over from its count
+    int32_t first_id(int32_t first_new_word_id) const { return first_new_word_id == LCD_NEW_WORD_IDS_AUTO ? -id_delta : first_new_word_id; }
+    uint64_t record(int32_t first_new_word_id, int32_t q, bool enabled, ShardOwnership own = ShardOwnership());   // returns the frame's sequence number
+    // the launches are planned for an upper bound that grows by q per unreported frame: the caller stays within 8 frames of the device
+    hipError_t throttle(hipStream_t s) const;
+    // the log is a ring (half full: catch up); removals keep their postings keys out of circulation until the host has caught up (512 frames)
+    bool must_reconcile(bool rm_pending, int frames) const { return unreconciled.size() >= (size_t)VLOG / 2 || (rm_pending && frames >= 512); }
+    // the id of the k-th new word of `e`, which became row `row` (first_id <= 0: the id follows the row)
+    static int32_t id_of(const DevAppend& e, int k, int64_t row) { return e.first_id > 0 ? e.first_id + k : (int32_t)row - e.first_id; }
+    static bool owns(const DevAppend& e, int32_t id) {                              // the sharded ownership rule
+        return e.own.world <= 0 || (e.own.block > 0 ? (id >= e.own.first && ((id - e.own.first) / e.own.block) % e.own.world == e.own.rank)
+                                                    : e.own.rank == e.own.world - 1);
+    }
+    void release(int64_t* bytes_device) { d_vcnt.release(bytes_device); if (h_vmirror) (void)hipHostFree(h_vmirror); h_vmirror = nullptr; }
+};
 
 struct lcd_engine {
     int device = 0;
@@ -29,17 +100,9 @@ struct lcd_engine {
     lcd::DevBuf vocab, row_id, row_wslot;
     lcd::DevBuf vocab_alt, row_id_alt, row_wslot_alt;   // rebuild target (swapped in)
     int64_t n_rows = 0, n_live = 0;
-    // host mirror of the row order (the tie-break contract): key = word id the row was appended with, live = not tombstoned.
-    // While the keys are ascending (the usual case: word ids only grow) a word's row is found by binary search; only a
-    // vocabulary with out-of-order appends (re-activated old words) needs the id -> row map, built lazily.
-    std::vector<int32_t> h_row_key;
-    std::vector<char> h_row_live;
-    bool rows_sorted = true;
-    std::unordered_map<int32_t, int32_t> word_row;      // only valid when !rows_sorted && word_row_valid
-    bool word_row_valid = false;
+    RowMirror mirror;
     lcd::DevBuf row_norm_alt;
     lcd::DevBuf vocab_bf;                               // hi/lo bf16 split of the rows (256 B per row) for the bf16x3 filter
-    int find_row(int32_t word_id);
 
     // ---- per-call scratch
     lcd::DevBuf d_queries, d_partial, d_knn_row, d_knn_word, d_knn_wslot, d_knn_dist, d_selfdist, d_out_word, d_out_wslot,
@@ -78,7 +141,7 @@ struct lcd_engine {
     struct DeferredLink { std::vector<int32_t> triples, restart; };
     struct InFlight {
         lcd_frame_args a; lcd::ResolveArgs r; int set = 0;
-        uint64_t vseq = 0; bool chained = false;        // the frame takes part in the device row-count chain (vcnt_active at its call)
+        uint64_t vseq = 0; bool chained = false;        // the frame takes part in the device row-count chain (applog.vcnt_active at its call)
         bool has_shadow = false;                        // its query pre-split also wrote its shadow rows (FrameScratch::d_shadow_bf)
         bool slots_are_rows = false;                    // its decision loop left vocabulary ROWS in r.out_wslot (PipeOpts::slots_from_rows): the registration looks the keys up
         lcd::WsRuns runs; bool reserved = false;        // postings keys of its new words (reserved when its decision loop is prepared)
@@ -89,25 +152,9 @@ struct lcd_engine {
         int cleans_after = 0;                           // lcd_vocab_remove_unused_async calls ...
     };
     std::deque<InFlight> inflight;                      // oldest first
-    // ---- VWDictionary::update()'s append branch on the device (lcd_frame_args.append_new_words): the decision loop's workgroup turns the
-    // frame's new words into vocabulary rows, so the row count lives on the device (d_vcnt: two alternating counters + a log of rows
-    // appended per frame).  The host plans launches for an upper bound (the pinned mirror the appender writes, + q per younger frame)
-    // and catches up with the exact rows (h_row_key ...) the next time the handle is drained (reconcile()).
-    static constexpr int VLOG = 4096;
-    lcd::DevBuf d_vcnt;                                 // int32: [0], [1] row counters, [16 .. 16 + VLOG) rows appended by frame seq % VLOG
+    // ---- VWDictionary::update()'s append branch on the device (lcd_frame_args.append_new_words): see AppendLog
+    AppendLog applog;
     int64_t vocab_capacity_cfg = 0;                     // lcd_config.vocab_capacity: every per-row buffer is sized for it
-    unsigned long long* h_vmirror = nullptr;            // pinned: (seq + 1) << 32 | rows after that frame's append
-    struct DevAppend { uint64_t seq; int32_t first_id; int32_t q; bool enabled;
-                       // sharded append (lcd_shard_frame_dev): the log holds the frame's TOTAL of new words, this rank owns the ids the rule gives it
-                       int32_t own_world = 0, own_rank = 0, own_first = 0, own_block = 0; };
-    // LCD_NEW_WORD_IDS_AUTO: the words frames create are numbered on the device, id = row + id_delta (AppendArgs::first_id <= 0; DevAppend::first_id = -id_delta).
-    // next_word_id: one past the highest word id this handle has seen (rows appended by any call; "next_word_id" sets it: VWDictionary::_lastWordId + 1);
-    // id_delta is fixed while appends are unreconciled (every new word is one row and one id), auto_window says the unreconciled appenders are numbered that way
-    int32_t next_word_id = 1, id_delta = 1; bool auto_window = false;
-    std::deque<DevAppend> unreconciled;                 // frames whose appends the host mirror has not caught up with
-    uint64_t vseq = 0;                                  // sequence number of the next frame in the chain: it reads counter vseq & 1, writes the other
-    bool vcnt_active = false;                           // the counters hold the row count (set when the first appending frame arrives)
-    bool tail_dirty = true;                             // the host wrote (or reallocated) behind the rows since the tail was last filled
     int64_t tail_filled_rows = 0;                       // rows [n_rows, tail_filled_rows) carry +inf norms and a zero bf16 split
     // ---- Memory::cleanUnusedWords on the device without completing the frames in flight (lcd_vocab_remove_unused_async): the rows a
     // clean_unused_kernel tombstoned are logged on the device; the host's row mirror and the postings keys of the removed words catch up
@@ -121,14 +168,6 @@ struct lcd_engine {
     bool clean_armed = false;                           // a clean waits for the next fused launch pair, whose registration applies the
                                                         // retirements asked for before it (they ride there: no launches of their own)
     int reconcile();
-    void mirror_push_row(int32_t id, int64_t row);     // a row the device appended enters h_row_key / h_row_live / word_row
-    int64_t rows_ub() const;
-    // The rows the FILTER of chain frame `fseq` will most likely see (the count its launch reads is the one written a launch earlier: the
-    // words of the frames up to fseq - 2): what the newest finished appender reported + an estimate per appending frame between that one
-    // and fseq - 2, from the growth the reports have shown.  Only the launch PLAN is made for it -- correctness does not rest on it: the
-    // filter masks rows beyond the device's count, and the re-rank scans exactly everything from min(plan, device count) on.
-    int64_t rows_plan(uint64_t fseq);
-    uint32_t est_tag = 0; int64_t est_cnt = 0; double est_new = 0.0;   // last report seen, decaying maximum of new rows per appending frame
     // sharded vocabulary, balanced growth (lcd_set_option "shard_growth_first" / "shard_growth_block"): the words frames create (ids >=
     // shard_first) belong to rank ((id - shard_first) / shard_block) % world; 0 = they belong to the last rank
     int32_t shard_first = 0, shard_block = 0;

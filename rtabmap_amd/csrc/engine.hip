@@ -21,22 +21,110 @@ using namespace lcd;
 
 static_assert(sizeof(lcd::HypothesisOut) == sizeof(lcd_hypothesis), "lcd_hypothesis is the kernel's output record");
 
-// row of a live word, -1 if absent
-int lcd_engine::find_row(int32_t word_id) {
+// ---- the host's row mirror (engine.h)
+int RowMirror::find(int32_t word_id) {
     if (rows_sorted) {
-        auto it = std::lower_bound(h_row_key.begin(), h_row_key.begin() + n_rows, word_id);
-        if (it == h_row_key.begin() + n_rows || *it != word_id) return -1;
+        auto it = std::lower_bound(h_row_key.begin(), h_row_key.end(), word_id);
+        if (it == h_row_key.end() || *it != word_id) return -1;
         const int r = (int)(it - h_row_key.begin());
         return h_row_live[r] ? r : -1;
     }
     if (!word_row_valid) {
         word_row.clear();
-        word_row.reserve((size_t)n_rows * 2);
-        for (int64_t r = 0; r < n_rows; ++r) if (h_row_live[r]) word_row[h_row_key[r]] = (int32_t)r;
+        word_row.reserve(h_row_key.size() * 2);
+        for (size_t r = 0; r < h_row_key.size(); ++r) if (h_row_live[r]) word_row[h_row_key[r]] = (int32_t)r;
         word_row_valid = true;
     }
     auto it = word_row.find(word_id);
     return it == word_row.end() ? -1 : it->second;
+}
+
+void RowMirror::push(int32_t id, int64_t row) {
+    if (rows_sorted && !h_row_key.empty() && id <= h_row_key.back()) rows_sorted = false;   // out-of-order id
+    if (word_row_valid) word_row[id] = (int32_t)row;
+    h_row_key.push_back(id);
+    if (id >= next_word_id) next_word_id = id + 1;
+    h_row_live.push_back(1);
+}
+
+void RowMirror::kill(int64_t row) {
+    h_row_live[(size_t)row] = 0;
+    if (word_row_valid) word_row.erase(h_row_key[(size_t)row]);
+}
+
+void RowMirror::reset(std::vector<int32_t>& keys) {
+    h_row_key.swap(keys);
+    h_row_live.assign(h_row_key.size(), 1);
+    rows_sorted = true;
+    word_row.clear();
+    word_row_valid = false;
+}
+
+// ---- the device append log (engine.h)
+AppendLog::Report AppendLog::report() const {
+    if (!h_vmirror) return Report{0, 0};
+    const unsigned long long v = *(volatile const unsigned long long*)h_vmirror;
+    return Report{(uint32_t)(v >> 32), (int64_t)(uint32_t)v};
+}
+
+int64_t AppendLog::rows_ub(int64_t n_rows) const {
+    if (unreconciled.empty()) return n_rows;
+    const Report r = report();
+    int64_t extra = 0;
+    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
+        if (r.tag != 0 && (uint32_t)(it->seq + 1) == r.tag) return r.rows + extra;
+        if (it->enabled) extra += it->q;
+    }
+    return n_rows + extra;
+}
+
+int64_t AppendLog::rows_plan(uint64_t fseq, int64_t n_rows) {
+    if (unreconciled.empty()) return n_rows;
+    const Report r = report();
+    if (r.tag == 0) return rows_ub(n_rows);                          // nothing reported yet
+    if (est_tag != 0 && r.tag != est_tag) {                          // the reports moved on: rows per frame since the last look
+        const double per = (double)(r.rows - est_cnt) / (double)(uint32_t)(r.tag - est_tag);
+        est_new = std::max(est_new * 0.9, per);
+    }
+    est_tag = r.tag; est_cnt = r.rows;
+    const int64_t ub = rows_ub(n_rows);
+    int64_t frames = 0; bool found = false;
+    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
+        if ((uint32_t)(it->seq + 1) == r.tag) { found = true; break; }
+        if (it->enabled && it->seq + 2 <= fseq) frames += 1;          // an appender the filter's count includes, not reported yet
+    }
+    if (!found) return ub;
+    const int64_t est = r.rows + (int64_t)std::ceil((double)frames * (est_new * 1.25 + 8.0));
+    return std::min(std::max(est, r.rows), ub);
+}
+
+hipError_t AppendLog::activate(int64_t n_rows, hipStream_t s, int64_t* bytes_device) {
+    if (vcnt_active) return hipSuccess;
+    hipError_t e = d_vcnt.reserve((size_t)(16 + VLOG) * 4, 0, s, bytes_device);
+    if (e == hipSuccess && !h_vmirror) {
+        e = hipHostMalloc((void**)&h_vmirror, 64, hipHostMallocDefault);
+        if (e == hipSuccess) *h_vmirror = 0ull;
+    }
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)d_vcnt.p, (int)n_rows, 2, s);
+    if (e == hipSuccess) vcnt_active = true;
+    return e;
+}
+
+uint64_t AppendLog::record(int32_t first_new_word_id, int32_t q, bool enabled, ShardOwnership own) {
+    unreconciled.push_back(DevAppend{vseq, first_id(first_new_word_id), q, enabled, own});
+    return vseq++;
+}
+
+// (the wait spins for the few microseconds a frame takes, then yields; a stream that makes no progress for a long time -- a caller-provided
+// one may legitimately sit behind an event -- is waited for with hipStreamSynchronize instead of failing)
+hipError_t AppendLog::throttle(hipStream_t s) const {
+    if (!h_vmirror || unreconciled.size() <= 8) return hipSuccess;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int spins = 0;; ++spins) {
+        if ((uint32_t)vseq - report().tag <= 8u) return hipSuccess;
+        if (spins > 4096) std::this_thread::yield();
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return hipStreamSynchronize(s);
+    }
 }
 
 #define LCD_CHECK_HANDLE(h) do { if (!(h)) return LCD_ERR_INVALID; } while (0)
@@ -52,20 +140,9 @@ int lcd_engine::find_row(int32_t word_id) {
 // as the append log has room and the caller is within 8 frames of the device (the bound grows by q per unreported frame).
 static int drain_keep_rows_lazy(lcd_engine* h) {
     { int rc = h->drain(false); if (rc) return rc; }
-    const bool lazy = h->vcnt_active && h->shard_append && !h->rm_pending && h->unreconciled.size() < (size_t)lcd_engine::VLOG / 2;
+    const bool lazy = h->applog.vcnt_active && h->shard_append && !h->rm_pending && !h->applog.must_reconcile(h->rm_pending, h->frames_since_reconcile);
     if (!lazy) return h->reconcile();
-    if (h->h_vmirror && h->unreconciled.size() > 8) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int spins = 0;; ++spins) {
-            const uint32_t tag = (uint32_t)(*(volatile const unsigned long long*)h->h_vmirror >> 32);
-            if ((uint32_t)h->vseq - tag <= 8u) break;
-            if (spins > 4096) std::this_thread::yield();
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                if (hipStreamSynchronize(h->stream) != hipSuccess) return h->fail(LCD_ERR_HIP, "hipStreamSynchronize");
-                break;
-            }
-        }
-    }
+    LCD_HIP(h, h->applog.throttle(h->stream));
     return LCD_OK;
 }
 
@@ -74,7 +151,6 @@ int lcd_engine::sync_all() {
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(stream)");
     return LCD_OK;
 }
-#define LCD_JOIN_K(h) do { } while (0)
 
 namespace {
 
@@ -225,7 +301,7 @@ int64_t vocab_cap_rows(const lcd_engine* h) {
 
 // the row buffers hold `rows` rows; what lies behind the rows in use carries +inf norms and a zero bf16 split
 int ensure_append_capacity(lcd_engine* h, int64_t rows) {
-    const int64_t keep = h->rows_ub();
+    const int64_t keep = h->applog.rows_ub(h->n_rows);
     if (rows > vocab_cap_rows(h)) {
         LCD_HIP(h, dreserve(h, h->vocab, (size_t)rows * h->row_bytes, (size_t)keep * h->row_bytes));
         LCD_HIP(h, dreserve(h, h->row_id, (size_t)rows * 4, (size_t)keep * 4));
@@ -242,21 +318,6 @@ int ensure_append_capacity(lcd_engine* h, int64_t rows) {
         LCD_HIP(h, hipMemsetAsync(h->row_id.as<int32_t>() + first, 0, (size_t)(cap - first) * 4, h->stream));
         h->tail_filled_rows = cap;
     }
-    return LCD_OK;
-}
-
-// the first appending frame since the host last changed the vocabulary: the device counters take over the row count
-int activate_dev_rows(lcd_engine* h) {
-    if (h->vcnt_active) return LCD_OK;
-    LCD_HIP(h, dreserve(h, h->d_vcnt, (size_t)(16 + lcd_engine::VLOG) * 4));
-    if (!h->h_vmirror) {
-        LCD_HIP(h, hipHostMalloc((void**)&h->h_vmirror, 64, hipHostMallocDefault));
-        *h->h_vmirror = 0ull;
-    }
-    LCD_HIP(h, hipMemsetD32Async((hipDeviceptr_t)h->d_vcnt.p, (int)h->n_rows, 2, h->stream));
-    if (h->tail_dirty) h->tail_filled_rows = 0;                      // host-side appends / rebuilds wrote behind the rows (or reallocated)
-    h->tail_dirty = false;
-    h->vcnt_active = true;
     return LCD_OK;
 }
 
@@ -277,92 +338,40 @@ void fill_append(lcd_engine* h, const lcd_frame_args& a, uint64_t vseq, bool ena
     ap.vocab = h->vocab.as<uint32_t>(); ap.row_id = h->row_id.as<int32_t>(); ap.row_wslot = h->row_wslot.as<int32_t>();
     ap.row_norm = h->row_norm.as<float>(); ap.norm_max_bits = h->norm_max.as<uint32_t>(); ap.vocab_bf = h->vocab_bf.as<uint32_t>();
     ap.wrow = h->tfidf.wrow.as<uint32_t>(); ap.f16 = h->f16();
-    ap.cnt_in = h->d_vcnt.as<int32_t>() + (vseq & 1); ap.cnt_out = h->d_vcnt.as<int32_t>() + ((vseq + 1) & 1);
-    ap.log_slot = h->d_vcnt.as<int32_t>() + 16 + (vseq % lcd_engine::VLOG);
-    ap.first_id = a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO ? -h->id_delta : a.first_new_word_id; ap.capacity = vocab_cap_rows(h);
+    ap.cnt_in = h->applog.count_before(vseq); ap.cnt_out = h->applog.count_after(vseq); ap.log_slot = h->applog.log_slot(vseq);
+    ap.first_id = h->applog.first_id(a.first_new_word_id); ap.capacity = vocab_cap_rows(h);
     ap.first_out = (int32_t*)a.d_first_new_word_id;
-    ap.host_mirror = h->h_vmirror; ap.tag = (uint32_t)(vseq + 1);
+    ap.host_mirror = h->applog.h_vmirror; ap.tag = (uint32_t)(vseq + 1);
 }
 
 }  // namespace
 
-// rows the vocabulary can have by now: exact when nothing was appended on the device since the last reconciliation, else the count the
-// newest finished appender reported (pinned memory, read without synchronising) + q per younger appending frame
-int64_t lcd_engine::rows_ub() const {
-    if (unreconciled.empty()) return n_rows;
-    uint32_t tag = 0; int64_t cnt = 0;
-    if (h_vmirror) { const unsigned long long v = *(volatile const unsigned long long*)h_vmirror; tag = (uint32_t)(v >> 32); cnt = (int64_t)(uint32_t)v; }
-    int64_t extra = 0;
-    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
-        if (tag != 0 && (uint32_t)(it->seq + 1) == tag) return cnt + extra;
-        if (it->enabled) extra += it->q;
-    }
-    return n_rows + extra;
-}
-
-int64_t lcd_engine::rows_plan(uint64_t fseq) {
-    if (unreconciled.empty() || !h_vmirror) return n_rows;
-    const unsigned long long v = *(volatile const unsigned long long*)h_vmirror;
-    const uint32_t tag = (uint32_t)(v >> 32);
-    const int64_t cnt = (int64_t)(uint32_t)v;
-    if (tag == 0) return rows_ub();                                  // nothing reported yet
-    if (est_tag != 0 && tag != est_tag) {                             // the reports moved on: rows per frame since the last look
-        const double per = (double)(cnt - est_cnt) / (double)(uint32_t)(tag - est_tag);
-        est_new = std::max(est_new * 0.9, per);
-    }
-    est_tag = tag; est_cnt = cnt;
-    const int64_t ub = rows_ub();
-    int64_t frames = 0; bool found = false;
-    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
-        if ((uint32_t)(it->seq + 1) == tag) { found = true; break; }
-        if (it->enabled && it->seq + 2 <= fseq) frames += 1;          // an appender the filter's count includes, not reported yet
-    }
-    if (!found) return ub;
-    const int64_t est = cnt + (int64_t)std::ceil((double)frames * (est_new * 1.25 + 8.0));
-    return std::min(std::max(est, cnt), ub);
-}
-
-// one row the device appended enters the host's row mirror (the caller adds to n_rows / n_live)
-void lcd_engine::mirror_push_row(int32_t id, int64_t row) {
-    if (rows_sorted && !h_row_key.empty() && id <= h_row_key.back()) rows_sorted = false;
-    if (word_row_valid) word_row[id] = (int32_t)row;
-    h_row_key.push_back(id);
-    if (id >= next_word_id) next_word_id = id + 1;
-    h_row_live.push_back(1);
-}
-
 // the host's row mirror catches up with the device (synchronises)
 int lcd_engine::reconcile() {
-    if (unreconciled.empty() && !rm_pending) return LCD_OK;
+    if (applog.unreconciled.empty() && !rm_pending) return LCD_OK;
     { int rc = sync_all(); if (rc) return rc; }
+    const int VLOG = AppendLog::VLOG;
     std::vector<int32_t> log((size_t)VLOG);
-    if (!unreconciled.empty()) {   // the log is a ring: the entries of the frames to catch up with form at most two stretches of it
-        const size_t first = (size_t)(unreconciled.front().seq % VLOG), n = unreconciled.size();
+    if (!applog.unreconciled.empty()) {   // the log is a ring: the entries of the frames to catch up with form at most two stretches of it
+        const size_t first = (size_t)(applog.unreconciled.front().seq % VLOG), n = applog.unreconciled.size();
         const size_t n1 = std::min(n, (size_t)VLOG - first);
-        hipError_t e = hipMemcpy(log.data() + first, d_vcnt.as<int32_t>() + 16 + first, n1 * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && n > n1) e = hipMemcpy(log.data(), d_vcnt.as<int32_t>() + 16, std::min(n - n1, (size_t)VLOG) * 4, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(log.data() + first, applog.log_slot(first), n1 * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && n > n1) e = hipMemcpy(log.data(), applog.log_slot(0), std::min(n - n1, (size_t)VLOG) * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpy(append log)");
     }
     std::vector<std::pair<int64_t, int> > auto_rows;
-    for (const DevAppend& a : unreconciled) {
+    for (const AppendLog::DevAppend& a : applog.unreconciled) {
         if (!a.enabled) continue;
         const int n = log[(size_t)(a.seq % VLOG)];
-        est_new = std::max(est_new * 0.9, (double)n);                 // (the estimate the launch plans and the shadow-score switch use: rows_plan() only sees it move while frames are in flight)
-        int taken = 0;
+        applog.est_new = std::max(applog.est_new * 0.9, (double)n);             // (the estimate the launch plans and the shadow-score switch use: rows_plan() only sees it move while frames are in flight)
         const int64_t rows0 = n_rows;
         for (int k = 0; k < n; ++k) {
-            const int32_t id = a.first_id > 0 ? a.first_id + k : (int32_t)(n_rows + taken) - a.first_id;   // (<= 0: the id follows the row)
-            if (a.own_world > 0) {                                    // a sharded append: n is the frame's total, this rank wrote the ids it owns
-                const bool mine = a.own_block > 0 ? (id >= a.own_first && ((id - a.own_first) / a.own_block) % a.own_world == a.own_rank)
-                                                  : a.own_rank == a.own_world - 1;
-                if (!mine) continue;
-            }
-            mirror_push_row(id, n_rows + taken);
-            taken += 1;
+            const int32_t id = AppendLog::id_of(a, k, n_rows);
+            if (!AppendLog::owns(a, id)) continue;                    // a sharded append: n is the frame's total, this rank wrote the ids it owns
+            mirror.push(id, n_rows);
+            n_rows += 1; n_live += 1;
         }
-        n_rows += taken;
-        n_live += taken;
-        if (a.first_id <= 0 && taken > 0) auto_rows.push_back(std::pair<int64_t, int>(rows0, taken));
+        if (a.first_id <= 0 && n_rows > rows0) auto_rows.push_back(std::pair<int64_t, int>(rows0, (int)(n_rows - rows0)));
     }
     if (!auto_rows.empty()) {
         // words numbered on the device: the host learns their postings keys from the rows themselves, in ONE copy (with ids the caller supplies
@@ -372,10 +381,10 @@ int lcd_engine::reconcile() {
         hipError_t e = hipMemcpy(keys.data(), row_wslot.as<int32_t>() + r0, keys.size() * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpy(row keys)");
         for (const std::pair<int64_t, int>& ar : auto_rows)
-            for (int k = 0; k < ar.second; ++k) tfidf.adopt_key(h_row_key[(size_t)(ar.first + k)], keys[(size_t)(ar.first + k - r0)]);
+            for (int k = 0; k < ar.second; ++k) tfidf.adopt_key(mirror.key(ar.first + k), keys[(size_t)(ar.first + k - r0)]);
     }
-    unreconciled.clear();
-    auto_window = false;
+    applog.unreconciled.clear();
+    applog.auto_window = false;
     if (rm_pending) {
         // rows tombstoned by the device-side cleanUnusedWords since the last reconciliation: the words are gone (removeWords,
         // VWDictionary.cpp:1595-1607), their postings keys go to the batched check that recycles them once nothing references them
@@ -395,11 +404,10 @@ int lcd_engine::reconcile() {
             if (e != hipSuccess) return hip_fail(e, "wrow_unlog_kernel");
             for (size_t i = 0; i < ent.size(); i += 2) {
                 const int32_t r = ent[i];
-                if (r < 0 || r >= n_rows || !h_row_live[(size_t)r]) continue;
-                h_row_live[(size_t)r] = 0;
+                if (r < 0 || r >= n_rows || !mirror.live(r)) continue;
+                const int32_t id = mirror.key(r);
+                mirror.kill(r);
                 n_live -= 1;
-                const int32_t id = h_row_key[(size_t)r];
-                if (word_row_valid) word_row.erase(id);
                 tfidf.forget_word(id, ent[i + 1]);
             }
             rm_seen = n;
@@ -411,7 +419,7 @@ int lcd_engine::reconcile() {
 }
 
 int lcd_engine::enqueue_clean(const int32_t* reg_cnt) {
-    const int64_t rows = rows_ub();
+    const int64_t rows = applog.rows_ub(n_rows);
     if (rows <= 0) return LCD_OK;
     hipError_t e = tfidf.flush_retire();                 // retirements ride with the next registration otherwise: the counts would be stale
     if (e != hipSuccess) return hip_fail(e, "flush_retire");
@@ -423,8 +431,8 @@ int lcd_engine::enqueue_clean(const int32_t* reg_cnt) {
         if (e != hipSuccess) return hip_fail(e, "removal log");
     }
     e = launch_clean_unused(row_id.as<int32_t>(), row_wslot.as<int32_t>(), tfidf.nw.as<uint32_t>(), tfidf.wrow.as<uint32_t>(),
-                            dtype == LCD_F32 ? row_norm.as<float>() : nullptr, (int)rows, vcnt_active ? d_vcnt.as<int32_t>() : nullptr,
-                            vcnt_active ? reg_cnt : nullptr, d_rmlog.as<int32_t>(), (int)((d_rmlog.cap / 4 - 16) / 2), stream);
+                            dtype == LCD_F32 ? row_norm.as<float>() : nullptr, (int)rows, applog.vcnt_active ? applog.d_vcnt.as<int32_t>() : nullptr,
+                            applog.vcnt_active ? reg_cnt : nullptr, d_rmlog.as<int32_t>(), (int)((d_rmlog.cap / 4 - 16) / 2), stream);
     if (e != hipSuccess) return hip_fail(e, "clean_unused_kernel");
     rm_pending = true;
     return LCD_OK;
@@ -523,9 +531,8 @@ void lcd_destroy(lcd_engine* h) {
                      &h->d_fail_list, &h->d_fail_count, &h->d_partial3, &h->row_norm_alt, &h->vocab_bf, &h->d_hyp_scratch, &h->d_adj_scratch,
                      &h->d_shard_selfdist};
     for (DevBuf* d : all) d->release(&h->bytes_device);
-    h->d_vcnt.release(&h->bytes_device);
+    h->applog.release(&h->bytes_device);
     h->d_rmlog.release(&h->bytes_device);
-    if (h->h_vmirror) (void)hipHostFree(h->h_vmirror);
     h->h_in.release(); h->h_out.release(); h->h_out2.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -567,15 +574,11 @@ int lcd_vocab_clear(lcd_engine* h) {
     LCD_DEV(h);
     { int rc = h->sync_all(); if (rc) return rc; }
     h->n_rows = 0; h->n_live = 0;
-    h->vcnt_active = false; h->tail_dirty = true;
+    h->applog.restart(); h->tail_filled_rows = 0;
     LCD_HIP(h, h->tfidf.rows_clear());
     if (h->d_rmlog.p) LCD_HIP(h, hipMemsetAsync(h->d_rmlog.p, 0, 4, h->stream));
     h->rm_seen = 0;
-    h->h_row_key.clear();
-    h->h_row_live.clear();
-    h->rows_sorted = true;
-    h->word_row.clear();
-    h->word_row_valid = false;
+    h->mirror.clear();
     return LCD_OK;
     LCD_CATCH(h)
 }
@@ -589,7 +592,7 @@ int lcd_vocab_append(lcd_engine* h, const void* rows, int n, const int32_t* word
     { int rc = h->sync_all(); if (rc) return rc; }                   // the 2-NN stage of a pipelined frame may still read the vocabulary
     for (int i = 0; i < n; ++i) {
         if (word_ids[i] <= 0) return h->fail(LCD_ERR_INVALID, "lcd_vocab_append: word ids must be > 0");
-        if (h->find_row(word_ids[i]) >= 0) return h->fail(LCD_ERR_STATE, "lcd_vocab_append: word already in the vocabulary");
+        if (h->mirror.find(word_ids[i]) >= 0) return h->fail(LCD_ERR_STATE, "lcd_vocab_append: word already in the vocabulary");
     }
     {   // the same id twice in one call would create two live rows for one word
         std::vector<int32_t> sorted(word_ids, word_ids + n);
@@ -634,16 +637,10 @@ int lcd_vocab_append(lcd_engine* h, const void* rows, int n, const int32_t* word
         }
     }
     LCD_HIP(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; ++i) {
-        if (h->rows_sorted && !h->h_row_key.empty() && word_ids[i] <= h->h_row_key.back()) h->rows_sorted = false;   // out-of-order id
-        if (h->word_row_valid) h->word_row[word_ids[i]] = (int32_t)(h->n_rows + i);
-        h->h_row_key.push_back(word_ids[i]);
-        if (word_ids[i] >= h->next_word_id) h->next_word_id = word_ids[i] + 1;
-        h->h_row_live.push_back(1);
-    }
+    for (int i = 0; i < n; ++i) h->mirror.push(word_ids[i], h->n_rows + i);
     h->n_rows = total;
     h->n_live += n;
-    h->vcnt_active = false; h->tail_dirty = true;                    // the device row counters (appends by frames) start over from this count
+    h->applog.restart(); h->tail_filled_rows = 0;                    // the device row counters (appends by frames) start over from this count
     return LCD_OK;
     LCD_CATCH(h)
 }
@@ -680,7 +677,7 @@ int lcd_vocab_remove_unused(lcd_engine* h, int32_t* out_word_ids, int capacity, 
     { int rc = download(h, rows.data(), d_cnt + 16, (size_t)n * 4, h->h_out); if (rc) return rc; }
     std::sort(rows.begin(), rows.end());
     std::vector<int32_t> ids((size_t)n);
-    for (int i = 0; i < n; ++i) ids[(size_t)i] = h->h_row_key[(size_t)rows[(size_t)i]];
+    for (int i = 0; i < n; ++i) ids[(size_t)i] = h->mirror.key(rows[(size_t)i]);
     { int rc = vocab_remove_ids(h, ids.data(), n); if (rc) return rc; }
     if (out_n) *out_n = n;
     for (int i = 0; i < n && i < capacity; ++i) out_word_ids[i] = ids[(size_t)i];
@@ -704,7 +701,7 @@ static int vocab_remove_ids(lcd_engine* h, const int32_t* word_ids, int n) {
     std::vector<int32_t> rows;
     rows.reserve(n);
     for (int i = 0; i < n; ++i) {
-        const int r = h->find_row(word_ids[i]);
+        const int r = h->mirror.find(word_ids[i]);
         if (r >= 0) { rows.push_back(r); continue; }
         // not a row: a word that was created by a frame (_notIndexedWords) and dies before update() indexed it only gives its
         // postings key back (removeWords erases it from _notIndexedWords, :1602); anything else is an error
@@ -728,10 +725,9 @@ static int vocab_remove_ids(lcd_engine* h, const int32_t* word_ids, int n) {
         LCD_HIP(h, launch_tombstone(h->row_id.as<int32_t>(), h->d_tmp_i32.as<int32_t>(), nr, h->stream));
         if (h->dtype == LCD_F32) LCD_HIP(h, launch_norm_tombstone(h->row_norm.as<float>(), h->d_tmp_i32.as<int32_t>(), nr, h->stream));
         LCD_HIP(h, hipStreamSynchronize(h->stream));
-        for (int i = 0; i < nr; ++i) h->h_row_live[rows[i]] = 0;
-        h->vcnt_active = false;                                      // the counters restart: the next frame's filter sees every row (tombstones carry
+        for (int i = 0; i < nr; ++i) h->mirror.kill(rows[i]);
+        h->applog.restart();                                         // the counters restart: the next frame's filter sees every row (tombstones carry
                                                                      // +inf norms), its re-rank has no pending rows -- one of them might be gone now
-        if (h->word_row_valid) for (int i = 0; i < n; ++i) h->word_row.erase(word_ids[i]);
         h->n_live -= nr;
     }
     // removeWords: the words are gone; their postings keys come back once the device has found them unreferenced
@@ -749,11 +745,11 @@ int lcd_vocab_rebuild(lcd_engine* h) {
     // the sort is only needed after out-of-order appends (re-activated old words).
     std::vector<int32_t> perm;
     perm.reserve((size_t)h->n_live);
-    for (int64_t r = 0; r < h->n_rows; ++r) if (h->h_row_live[r]) perm.push_back((int32_t)r);
-    if (!h->rows_sorted)
-        std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return h->h_row_key[a] < h->h_row_key[b]; });
+    for (int64_t r = 0; r < h->n_rows; ++r) if (h->mirror.live(r)) perm.push_back((int32_t)r);
+    if (!h->mirror.rows_sorted)
+        std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return h->mirror.key(a) < h->mirror.key(b); });
     const int n = (int)perm.size();
-    if (n == (int)h->n_rows && h->rows_sorted) return LCD_OK;       // nothing to drop, nothing to reorder
+    if (n == (int)h->n_rows && h->mirror.rows_sorted) return LCD_OK;       // nothing to drop, nothing to reorder
     LCD_HIP(h, dreserve(h, h->vocab_alt, std::max<size_t>(h->vocab.cap, 4)));
     LCD_HIP(h, dreserve(h, h->row_id_alt, std::max<size_t>(h->row_id.cap, 4)));
     LCD_HIP(h, dreserve(h, h->row_wslot_alt, std::max<size_t>(h->row_wslot.cap, 4)));
@@ -791,15 +787,11 @@ int lcd_vocab_rebuild(lcd_engine* h) {
         LCD_HIP(h, launch_vocab_bf16(h->vocab.p, 0, n, h->kdim, h->vocab_bf.p, h->stream, h->f16()));
     }
     std::vector<int32_t> keys(n);
-    for (int i = 0; i < n; ++i) keys[i] = h->h_row_key[perm[i]];
-    h->h_row_key.swap(keys);
-    h->h_row_live.assign((size_t)n, 1);
-    h->rows_sorted = true;
-    h->word_row.clear();
-    h->word_row_valid = false;
+    for (int i = 0; i < n; ++i) keys[i] = h->mirror.key(perm[i]);
+    h->mirror.reset(keys);
     h->n_rows = n;
     h->n_live = n;
-    h->vcnt_active = false; h->tail_dirty = true;
+    h->applog.restart(); h->tail_filled_rows = 0;
     h->rebuilds += 1;
     return LCD_OK;
     LCD_CATCH(h)
@@ -840,7 +832,6 @@ int lcd_knn2(lcd_engine* h, const void* queries, int q, int32_t* out_word_ids, f
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV(h);
-    LCD_JOIN_K(h);
     if (q < 0 || (q > 0 && (!queries || !out_word_ids || !out_dist))) return h->fail(LCD_ERR_INVALID, "lcd_knn2: null input");
     if (q == 0) return LCD_OK;
     int rc = upload_rows(h, queries, q, h->d_queries);
@@ -858,7 +849,6 @@ int lcd_selfdist(lcd_engine* h, const void* queries, int q, float* out_qxq) {
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV(h);
-    LCD_JOIN_K(h);
     if (q < 0 || (q > 0 && (!queries || !out_qxq))) return h->fail(LCD_ERR_INVALID, "lcd_selfdist: null input");
     if (q == 0) return LCD_OK;
     int rc = upload_rows(h, queries, q, h->d_queries);
@@ -967,7 +957,6 @@ int lcd_quantize(lcd_engine* h, const void* descriptors, int q, int flags, float
     LCD_CHECK_HANDLE(h);
     lcd_engine::Range range__(h, "lcd_quantize");
     LCD_DEV(h);
-    LCD_JOIN_K(h);
     if (q < 0 || (q > 0 && (!descriptors || !out_word_ids))) return h->fail(LCD_ERR_INVALID, "lcd_quantize: null input");
     if (out_n_new) *out_n_new = 0;
     if (q == 0) return LCD_OK;
@@ -989,7 +978,6 @@ int lcd_find_nn(lcd_engine* h, const void* queries, int q, const void* extra_row
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV(h);
-    LCD_JOIN_K(h);
     if (q < 0 || n_extra < 0 || (q > 0 && (!queries || !out_word_ids)) || (n_extra > 0 && (!extra_rows || !extra_word_ids)))
         return h->fail(LCD_ERR_INVALID, "lcd_find_nn: null input");
     if (q == 0) return LCD_OK;
@@ -1245,13 +1233,13 @@ static int id_window(lcd_engine* h, const lcd_frame_args& a) {
     if (is_auto && !frame_appends(h, a))
         return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: LCD_NEW_WORD_IDS_AUTO needs append_new_words on an incremental dictionary of unpadded rows");
     if (!frame_appends(h, a)) return LCD_OK;
-    if (!h->unreconciled.empty() && h->auto_window != is_auto) { int rc = h->drain(); if (rc) return rc; }
-    if (h->unreconciled.empty()) {
-        h->auto_window = is_auto;
+    if (!h->applog.unreconciled.empty() && h->applog.auto_window != is_auto) { int rc = h->drain(); if (rc) return rc; }
+    if (h->applog.unreconciled.empty()) {
+        h->applog.auto_window = is_auto;
         if (is_auto) {
-            const int64_t d = (int64_t)h->next_word_id - h->n_rows;
+            const int64_t d = (int64_t)h->mirror.next_word_id - h->n_rows;
             if (d < 1 || d >= (1ll << 28)) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: next_word_id lies below the ids the vocabulary holds (lcd_set_option \"next_word_id\")");
-            h->id_delta = (int32_t)d;
+            h->applog.id_delta = (int32_t)d;
         }
     }
     return LCD_OK;
@@ -1347,8 +1335,8 @@ static int build_knn(lcd_engine* h, lcd_engine::InFlight& f, PipeKnn* kp, const 
     const bool incremental = (a.flags & LCD_Q_INCREMENTAL) != 0;
     const bool together = incremental && (a.flags & LCD_Q_NEW_WORDS_COMPARED);
     const int ld = (q + 63) / 64 * 64, bw = ld / 32;
-    const int64_t rows_bound = f.chained ? h->rows_ub() : h->n_rows;   // a true upper bound: the exact redo and the buffers are sized for it
-    const int64_t plan_rows = f.chained ? h->rows_plan(f.vseq) : h->n_rows;
+    const int64_t rows_bound = f.chained ? h->applog.rows_ub(h->n_rows) : h->n_rows;   // a true upper bound: the exact redo and the buffers are sized for it
+    const int64_t plan_rows = f.chained ? h->applog.rows_plan(f.vseq, h->n_rows) : h->n_rows;
     if (plan_rows > 0x7FFFFFF0ll) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_dev: more than 2^31 rows");
     // The distance tiles get compute units of their own (a tile that shares one with a strip takes twice as long, and so does the
     // strip); the two tail workgroups do not: a filter workgroup holds 66 KB of LDS, so two of the launch's workgroups can share a
@@ -1393,7 +1381,7 @@ static int build_knn(lcd_engine* h, lcd_engine::InFlight& f, PipeKnn* kp, const 
     k.out_row = sc.d_knn_row.as<int32_t>(); k.out_word = sc.d_knn_word.as<int32_t>(); k.out_dist = sc.d_knn_dist.as<float>();
     k.fail_list = sc.d_fail_list.as<int32_t>(); k.fail_count = sc.d_fail_count.as<int32_t>();
     k.n_lo = nullptr; k.n_hi = nullptr;
-    if (f.chained) { k.n_lo = h->d_vcnt.as<int32_t>() + ((f.vseq + 1) & 1); k.n_hi = h->d_vcnt.as<int32_t>() + (f.vseq & 1); }
+    if (f.chained) { k.n_lo = h->applog.count_after(f.vseq); k.n_hi = h->applog.count_before(f.vseq); }
     k.cb = CandBits();
     if (together) { k.cb.selfdist = sc.d_selfdist.as<float>(); k.cb.ld = ld; k.cb.nq = q; k.cb.have_index = 1; cand_bits_layout(k.cb, sc.d_bits.as<uint32_t>(), q, bw); }
     if (!sc.fail_count_clean) LCD_HIP(h, hipMemsetAsync(sc.d_fail_count.p, 0, 8, h->stream));
@@ -1446,9 +1434,9 @@ static int pipeline_launch(lcd_engine* h, const QSplitArgs* qs) {
         // (rows instead of postings keys in out_wslot: NULL is the decision loop's "knn_row already holds the word slot"; the registration translates)
         // (built-in: only while the stream creates words, like the shadow scores -- the gather leaves the decision loop's chain for the registration's, and once frames
         // revisit, the decision loop is short and the registration is what ends launch A: 13.8 -> 14.5 us in the revisit phase with the rows always on, r06_ab_notes.txt 10)
-        f_res->slots_are_rows = h->popt.slots_from_rows && (h->popt.slots_from_rows >= 2 || h->est_new >= 16.0) && tl_res.r.row_wslot && tl_res.r.knn_row && tl_res.r.q <= 1024;
+        f_res->slots_are_rows = h->popt.slots_from_rows && (h->popt.slots_from_rows >= 2 || h->applog.est_new >= 16.0) && tl_res.r.row_wslot && tl_res.r.knn_row && tl_res.r.q <= 1024;
         if (f_res->slots_are_rows) { tl_res.r.row_wslot = nullptr; tl_res.r.slots_are_rows = 1; }
-        tl_res.r.straight = (h->popt.decision_straight >= 2 || (h->popt.decision_straight == 1 && h->est_new >= 16.0)) ? 1 : 0;
+        tl_res.r.straight = (h->popt.decision_straight >= 2 || (h->popt.decision_straight == 1 && h->applog.est_new >= 16.0)) ? 1 : 0;
         if (f_res->chained) fill_append(h, f_res->a, f_res->vseq, frame_appends(h, f_res->a), &tl_res.r, h->ring[f_res->set].d_applist.as<uint32_t>());
         // the pinned row-count mirror is a store to HOST memory, waited for at the end of the decision loop's chain: with "mirror_from_b" a
         // workgroup of launch B of this pair (which writes the frame's rows anyway) stores it instead
@@ -1522,7 +1510,7 @@ static int pipeline_launch(lcd_engine* h, const QSplitArgs* qs) {
         // with its registration, in the NEXT launch A: the clean stops at the count f_res started from (the counter it read, untouched
         // until the next decision loop writes it) -- addNewWords references a word as it creates it, cleanUnusedWords never sees one
         h->clean_armed = false;
-        const int32_t* reg_cnt = f_res && f_res->chained ? h->d_vcnt.as<int32_t>() + (f_res->vseq & 1) : nullptr;
+        const int32_t* reg_cnt = f_res && f_res->chained ? h->applog.count_before(f_res->vseq) : nullptr;
         int rc = h->enqueue_clean(reg_cnt); if (rc) return rc;        // (flushes what more than four retirements per frame left over)
     }
     if (f_res) f_res->stage = 2;
@@ -1556,34 +1544,21 @@ static int frame_pipelined(lcd_engine* h, const lcd_frame_args* a) {
     if (a->sig_id != 0 && t.sig_slot.count(a->sig_id)) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: signature already registered");
     const int64_t slots_after = t.n_slots + owed_slots + (a->sig_id != 0 ? 1 : 0);
     if (a->d_likelihood && a->likelihood_capacity < slots_after) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: likelihood buffer too small");
-    if (h->unreconciled.size() >= (size_t)lcd_engine::VLOG / 2) { int rc = h->drain(); if (rc) return rc; }   // the append log is a ring
-    // rows tombstoned by enqueued cleans keep their postings keys out of circulation until the host has caught up with the log: a stream
-    // that never completes anything does so every 512 frames (three fused launch pairs, ~0.2 us per frame)
-    if (h->rm_pending && ++h->frames_since_reconcile >= 512) { int rc = h->drain(); if (rc) return rc; }
+    // (a stream that never completes anything catches up every 512 frames with removals pending: three fused launch pairs, ~0.2 us per frame)
+    if (h->rm_pending) h->frames_since_reconcile += 1;
+    if (h->applog.must_reconcile(h->rm_pending, h->frames_since_reconcile)) { int rc = h->drain(); if (rc) return rc; }
     { int rc = id_window(h, *a); if (rc) return rc; }
     // rows appended on the device: the counters take over the row count, the buffers keep room for the words of the frames in flight
     const bool app = frame_appends(h, *a);
-    if (app) { int rc = activate_dev_rows(h); if (rc) return rc; }
-    const bool chained = h->vcnt_active;
-    if (chained && h->h_vmirror && h->unreconciled.size() > 8) {
-        // The launches are planned for an upper bound of the row count: what the newest FINISHED appender reported + q per younger
-        // frame.  A caller that enqueues frames much faster than the device runs them would inflate that bound without limit (the
-        // filter would scan mostly empty rows): such a caller waits here until the device is at most 8 frames behind.
-        // (the wait spins for the few microseconds a frame takes, then yields; a stream that makes no progress for a long time --
-        // a caller-provided one may legitimately sit behind an event -- is waited for with hipStreamSynchronize instead of failing)
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int spins = 0;; ++spins) {
-            const uint32_t tag = (uint32_t)(*(volatile const unsigned long long*)h->h_vmirror >> 32);
-            if ((uint32_t)h->vseq - tag <= 8u) break;
-            if (spins > 4096) std::this_thread::yield();
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                LCD_HIP(h, hipStreamSynchronize(h->stream));
-                break;
-            }
-        }
+    if (app) LCD_HIP(h, h->applog.activate(h->n_rows, h->stream, &h->bytes_device));
+    const bool chained = h->applog.vcnt_active;
+    // The launches are planned for an upper bound of the row count: what the newest FINISHED appender reported + q per younger frame.  A
+    // caller that enqueues frames much faster than the device runs them would inflate that bound without limit (the filter would scan
+    // mostly empty rows): such a caller waits here until the device is at most 8 frames behind.
+    if (chained) {
+        LCD_HIP(h, h->applog.throttle(h->stream));
+        int rc = ensure_append_capacity(h, h->applog.rows_ub(h->n_rows) + 3 * (int64_t)q); if (rc) return rc;
     }
-    if (chained) { int rc = ensure_append_capacity(h, h->rows_ub() + 3 * (int64_t)q); if (rc) return rc; }
-    const uint64_t vseq = h->vseq;
     const int set = (int)(h->frame_seq % lcd_engine::PIPE_SETS);
     lcd_engine::FrameScratch& sc = h->ring[set];
     const bool incremental = (a->flags & LCD_Q_INCREMENTAL) != 0;
@@ -1610,7 +1585,7 @@ static int frame_pipelined(lcd_engine* h, const lcd_frame_args* a) {
     // ~3.5 us per frame whose predecessor appended ~150 rows, nothing when it appended none; est_new is the decaying maximum of rows per appending frame
     // that the launch plans already keep.  "shadow_rows" = 2: always)
     const bool with_shadow = chained && app && h->popt.shadow_rows && h->dtype == LCD_F32 && h->kdim == 64 && q <= 4096 &&
-                             (h->popt.shadow_rows >= 2 || h->est_new >= 16.0);
+                             (h->popt.shadow_rows >= 2 || h->applog.est_new >= 16.0);
     if (with_shadow) {
         LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_shadow_bf, (size_t)ld * 256));
         LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_shadow_norm, (size_t)(ld + 1) * 8));
@@ -1624,8 +1599,8 @@ static int frame_pipelined(lcd_engine* h, const lcd_frame_args* a) {
     { int rc = pipeline_launch(h, &qs); if (rc) return rc; }
     // ---- this frame's filter, re-rank, decision loop, registration and scoring are owed from here on
     lcd_engine::InFlight nf;
-    nf.a = *a; nf.set = set; nf.stage = 0; nf.vseq = vseq; nf.chained = chained; nf.has_shadow = with_shadow;
-    if (chained) { h->unreconciled.push_back(lcd_engine::DevAppend{vseq, a->first_new_word_id == LCD_NEW_WORD_IDS_AUTO ? -h->id_delta : a->first_new_word_id, q, app}); h->vseq += 1; }
+    nf.a = *a; nf.set = set; nf.stage = 0; nf.chained = chained; nf.has_shadow = with_shadow;
+    if (chained) nf.vseq = h->applog.record(a->first_new_word_id, q, app);
     h->inflight.push_back(std::move(nf));
     h->frame_seq += 1;
     return LCD_OK;
@@ -1701,17 +1676,16 @@ int lcd_frame_host(lcd_engine* h, const lcd_frame_host_args* a) {
     if (a->n_slots) *a->n_slots = slots_after;
     // The word ids are here and the stream is idle: the rows this frame appended on the device are known without asking the device's log
     // (the k-th new word carries the code -(k + 1)), so the host's row mirror catches up now -- the next call finds nothing to reconcile
-    // (a synchronisation and two small blocking copies less per frame).  Only when this frame is the one unreconciled appender.
-    if (h->unreconciled.size() == 1 && h->unreconciled.front().enabled && h->unreconciled.front().own_world == 0 && !h->rm_pending &&
-        h->unreconciled.front().first_id == a->first_new_word_id && h->h_vmirror) {
+    // (a synchronisation and two small blocking copies less per frame).  Only when this frame is the one unreconciled appender, with ids the
+    // caller gave: the postings keys of words numbered on the device are learnt from the rows (reconcile(), at the next drain).
+    const AppendLog::DevAppend* e = h->applog.unreconciled.size() == 1 ? &h->applog.unreconciled.front() : nullptr;
+    if (e && e->enabled && e->own.world == 0 && e->first_id > 0 && !h->rm_pending) {
         int n_new = 0;
         for (int i = 0; i < q; ++i) n_new = std::max(n_new, -a->word_ids[i]);
-        const unsigned long long v = *(volatile const unsigned long long*)h->h_vmirror;   // what the appender reported: (tag << 32) | rows
-        if ((uint32_t)(v >> 32) == (uint32_t)(h->unreconciled.front().seq + 1) && (int64_t)(uint32_t)v == h->n_rows + n_new) {
-            for (int k = 0; k < n_new; ++k) h->mirror_push_row(a->first_new_word_id + k, h->n_rows + k);
-            h->n_rows += n_new;
-            h->n_live += n_new;
-            h->unreconciled.clear();
+        const AppendLog::Report r = h->applog.report();
+        if (r.tag == (uint32_t)(e->seq + 1) && r.rows == h->n_rows + n_new) {
+            for (int k = 0; k < n_new; ++k) { h->mirror.push(AppendLog::id_of(*e, k, h->n_rows), h->n_rows); h->n_rows += 1; h->n_live += 1; }
+            h->applog.unreconciled.clear();
             h->frames_since_reconcile = 0;                               // (what reconcile() leaves: nothing is owed to the mirror)
         }
     }
@@ -1734,34 +1708,25 @@ static int frame_dev_body(lcd_engine* h, const lcd_frame_args* a) {
     // A stream of appending frames on a plain handle with the exact scan (ORB: config 3) does not wait for the device between frames:
     // the host's row mirror lags (as on a pipelined handle), the scan is planned for an upper bound of the row count.  Anything else
     // completes what is owed and brings the mirror up to date first.
-    const bool lazy = app && h->inflight.empty() && h->vcnt_active && h->n_live >= 2 && !(h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim)) &&
-                      h->unreconciled.size() < (size_t)lcd_engine::VLOG / 2 && !(h->rm_pending && h->frames_since_reconcile >= 512);
+    const bool lazy = app && h->inflight.empty() && h->applog.vcnt_active && h->n_live >= 2 && !(h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim)) &&
+                      !h->applog.must_reconcile(h->rm_pending, h->frames_since_reconcile);
     if (!lazy) { int rc = h->drain(); if (rc) return rc; }         // (also brings the host's row mirror up to date)
     else {
         if (h->rm_pending) h->frames_since_reconcile += 1;
-        if (h->h_vmirror && h->unreconciled.size() > 8) {           // the bound grows by q per unreported frame: stay within 8 frames of the device
-            const auto t0 = std::chrono::steady_clock::now();
-            for (int spins = 0;; ++spins) {
-                const uint32_t tag = (uint32_t)(*(volatile const unsigned long long*)h->h_vmirror >> 32);
-                if ((uint32_t)h->vseq - tag <= 8u) break;
-                if (spins > 4096) std::this_thread::yield();
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) { LCD_HIP(h, hipStreamSynchronize(h->stream)); break; }
-            }
-        }
+        LCD_HIP(h, h->applog.throttle(h->stream));
     }
     LCD_HIP(h, dreserve(h, h->d_out_wslot, (size_t)q * 4));
     if (app) {
-        { int rc = activate_dev_rows(h); if (rc) return rc; }
-        { int rc = ensure_append_capacity(h, h->rows_ub() + 2 * (int64_t)q); if (rc) return rc; }
+        LCD_HIP(h, h->applog.activate(h->n_rows, h->stream, &h->bytes_device));
+        { int rc = ensure_append_capacity(h, h->applog.rows_ub(h->n_rows) + 2 * (int64_t)q); if (rc) return rc; }
     }
     // 2-NN + same-frame distances, then ONE single-workgroup launch: decision loop -> pending retirements -> registration / idf
     ResolveArgs r;
     int rc = prepare_resolve(h, a->d_descriptors, q, a->flags, a->nndr_ratio, a->d_word_ids, h->d_out_wslot.as<int32_t>(), &r, true,
-                             lazy ? h->rows_ub() : -1);
+                             lazy ? h->applog.rows_ub(h->n_rows) : -1);
     if (rc) return rc;
     if (h->d_fail_count.p) { r.fail_count = h->d_fail_count.as<int32_t>(); h->fail_count_clean = true; }   // the tail resets the counters
-    const uint64_t vseq = h->vseq;
-    if (app) { h->unreconciled.push_back(lcd_engine::DevAppend{vseq, a->first_new_word_id == LCD_NEW_WORD_IDS_AUTO ? -h->id_delta : a->first_new_word_id, q, true}); h->vseq += 1; }
+    const uint64_t vseq = app ? h->applog.record(a->first_new_word_id, q, true) : 0;
     return frame_stage_s(h, *a, r, app, vseq);
 }
 
@@ -1769,7 +1734,6 @@ int lcd_knn2_dev(lcd_engine* h, const void* d_queries, int q, int32_t* d_word_id
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV(h);
-    LCD_JOIN_K(h);
     if (q <= 0 || !d_queries || !d_word_ids || !d_dist) return h->fail(LCD_ERR_INVALID, "lcd_knn2_dev: bad argument");
     if (((uintptr_t)d_queries & 15u) != 0) return h->fail(LCD_ERR_INVALID, "lcd_knn2_dev: d_queries must be 16-byte aligned");
     LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
@@ -1957,10 +1921,9 @@ int lcd_shard_knn2_dev(lcd_engine* h, const void* d_descriptors, int q, lcd_shar
     LCD_CHECK_HANDLE(h);
     LCD_DEV_NODRAIN(h);
     { int rc = drain_keep_rows_lazy(h); if (rc) return rc; }
-    LCD_JOIN_K(h);
     if (q <= 0 || !d_descriptors || !d_cand) return h->fail(LCD_ERR_INVALID, "lcd_shard_knn2_dev: bad argument");
     if (((uintptr_t)d_descriptors & 15u) != 0) return h->fail(LCD_ERR_INVALID, "lcd_shard_knn2_dev: d_descriptors must be 16-byte aligned");
-    const int64_t rows_scan = h->rows_ub();                           // == n_rows unless this rank appended on the device since the mirror last caught up
+    const int64_t rows_scan = h->applog.rows_ub(h->n_rows);                           // == n_rows unless this rank appended on the device since the mirror last caught up
     if (rows_scan >= (1 << 26)) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_shard_knn2_dev: a shard holds at most 2^26 - 1 rows (merge key: 26-bit row, 6-bit rank)");
     LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
     LCD_HIP(h, dreserve(h, h->d_knn_word, (size_t)q * 2 * 4));
@@ -2005,7 +1968,6 @@ int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int fla
     LCD_CHECK_HANDLE(h);
     LCD_DEV_NODRAIN(h);
     { int rc = drain_keep_rows_lazy(h); if (rc) return rc; }
-    LCD_JOIN_K(h);
     const bool matrix_left = h->shard_sd_desc != nullptr && h->shard_sd_desc == d_descriptors && h->shard_sd_q == q;   // by this frame's search
     h->shard_sd_desc = nullptr;                                       // (one frame call per search: whatever happens below, it is used up)
     if (q <= 0 || q > 8192 || !d_descriptors || !d_all_cand || !d_word_ids || world < 1 || world > 64 || rank < 0 || rank >= world)
@@ -2079,14 +2041,13 @@ int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int fla
         // VWDictionary::update()'s append branch, this rank's share, on the device: the words the frame created that this rank owns become
         // rows of its shard before the next frame is searched (lcd_shard_knn2_dev catches the host's row mirror up: one synchronisation,
         // no lcd_vocab_append, nothing read back by the caller)
-        { int rc = activate_dev_rows(h); if (rc) return rc; }
-        { int rc = ensure_append_capacity(h, h->rows_ub() + (int64_t)q); if (rc) return rc; }
+        LCD_HIP(h, h->applog.activate(h->n_rows, h->stream, &h->bytes_device));
+        { int rc = ensure_append_capacity(h, h->applog.rows_ub(h->n_rows) + (int64_t)q); if (rc) return rc; }
         lcd_frame_args fa;
         std::memset(&fa, 0, sizeof(fa));
         fa.d_descriptors = d_descriptors; fa.first_new_word_id = first_new_word_id; fa.q = q;
         ResolveArgs ra;
-        const uint64_t vseq = h->vseq;
-        fill_append(h, fa, vseq, true, &ra);
+        fill_append(h, fa, h->applog.vseq, true, &ra);
         // ... as a second workgroup of the registration's launch (the two chains need nothing of each other: one launch less per frame and rank)
         app.ap = ra.ap; app.new_ws = new_ws;               // (n == 0 on a rank that owns nothing in last-rank mode: it appends nothing either)
         app.codes = d_word_ids; app.q = q; app.rank = rank; app.world = world;
@@ -2094,12 +2055,7 @@ int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int fla
     }
     if (sig_id != 0) LCD_HIP(h, t.register_dev(sig_id, h->d_out_wslot.as<int32_t>(), q, q, N, nullptr, false, nullptr, nullptr, dev_append ? &app : nullptr));
     else LCD_HIP(h, t.query_dev(h->d_out_wslot.as<int32_t>(), q, N, nullptr, false, nullptr, nullptr, dev_append ? &app : nullptr));
-    if (dev_append) {                                      // (enqueued: the host's record of it)
-        lcd_engine::DevAppend da{h->vseq, first_new_word_id, q, true};
-        da.own_world = world; da.own_rank = rank; da.own_first = app.own_first; da.own_block = app.own_block;
-        h->unreconciled.push_back(da);
-        h->vseq += 1;
-    }
+    if (dev_append) h->applog.record(first_new_word_id, q, true, ShardOwnership{world, rank, app.own_first, app.own_block});   // (enqueued: the host's record of it)
     if (d_lfix) {
         LCD_HIP(h, t.score_fix((long long*)d_lfix));       // every slot written: no zero-fill needed
         h->likelihood_launches += 1;
@@ -2226,7 +2182,7 @@ int lcd_set_option(lcd_engine* h, const char* key, int64_t value) {
     if (!std::strcmp(key, "filter_delay") && value >= 0 && value <= 127) { h->popt.filter_delay = (int)value; return LCD_OK; }
     if (!std::strcmp(key, "shadow_rows") && value >= -1 && value <= 2) { h->popt.shadow_rows = value < 0 ? 1 : (int)value; return LCD_OK; }   // (-1: built-in = 1)
     if (!std::strcmp(key, "mirror_from_b") && value >= -1 && value <= 1) { h->popt.mirror_from_b = value != 0 ? 1 : 0; return LCD_OK; }
-    if (!std::strcmp(key, "next_word_id") && value >= 1 && value < (1ll << 28)) { h->next_word_id = std::max(h->next_word_id, (int32_t)value); return LCD_OK; }   // (the drain above has brought the row mirror up to date)
+    if (!std::strcmp(key, "next_word_id") && value >= 1 && value < (1ll << 28)) { h->mirror.next_word_id = std::max(h->mirror.next_word_id, (int32_t)value); return LCD_OK; }   // (the drain above has brought the row mirror up to date)
     if (!std::strcmp(key, "profile_skip") && value >= 0 && value <= (1 << 20)) { h->prof_skip = (int)value; return LCD_OK; }
     if (!std::strcmp(key, "decision_straight") && value >= -1 && value <= 2) { h->popt.decision_straight = value >= 0 ? (int)value : PipeOpts().decision_straight; return LCD_OK; }
     if (!std::strcmp(key, "slots_from_rows") && value >= -1 && value <= 2) { h->popt.slots_from_rows = value >= 0 ? (int)value : PipeOpts().slots_from_rows; return LCD_OK; }

@@ -544,12 +544,16 @@ def test_bulk_load_matches_incremental_registration(oracle):
     a.close(); b.close()
 
 
-@pytest.mark.parametrize("kind,pipeline", [("surf", False), ("orb", False), ("surf", True)])
-def test_frame_host_is_frame_dev_with_the_copies(kind, pipeline):
+@pytest.mark.parametrize("kind,pipeline,auto", [pytest.param("surf", False, False, id="surf-False"), pytest.param("orb", False, False, id="orb-False"),
+                                                 pytest.param("surf", True, False, id="surf-True"), pytest.param("surf", False, True, id="surf-False-auto"),
+                                                 pytest.param("surf", True, True, id="surf-True-auto")])
+def test_frame_host_is_frame_dev_with_the_copies(kind, pipeline, auto):
     """lcd_frame_host (ABI v5: host descriptors in, word ids + dense likelihood out, one synchronisation -- what the reference-interface
     mirror calls per frame) against lcd_frame_dev on a twin engine fed through device pointers: the same bits, frame after frame, with
-    update()'s append on the device, a retirement per frame, and lcd_slot_count telling the caller how large its likelihood buffer must be."""
+    update()'s append on the device, a retirement per frame, and lcd_slot_count telling the caller how large its likelihood buffer must be.
+    auto: lcd_frame_host numbers the new words on the device (LCD_NEW_WORD_IDS_AUTO), the twin is given the ids -- the same words, rows and ids."""
     import rtabmap_amd
+    from rtabmap_amd import capi
     n_words, q, n_bulk, n_frames = 3000, 96, 40, 12
     rng = np.random.default_rng(91)
     base = synth.vocab_surf(n_words, seed=92) if kind == "surf" else synth.vocab_orb(n_words, seed=92)
@@ -576,10 +580,15 @@ def test_frame_host_is_frame_dev_with_the_copies(kind, pipeline):
         dev.frame_dev(d.data_ptr(), q, sid, float(n_bulk + 1), d_w.data_ptr(), d_l.data_ptr(), cap, first_new_word_id=first_new, append_new_words=True)
         dev.synchronize()
         exp_w, exp_l = d_w.cpu().numpy(), d_l[:sid].cpu().numpy()
-        got_w, got_l = host.frame_host(desc, sid, float(n_bulk + 1), first_new_word_id=first_new, append_new_words=True)
+        got_w, got_l = host.frame_host(desc, sid, float(n_bulk + 1), first_new_word_id=capi.LCD_NEW_WORD_IDS_AUTO if auto else first_new,
+                                       append_new_words=True)
         np.testing.assert_array_equal(got_w, exp_w, err_msg="frame %d" % t)
         assert got_l.shape[0] == sid
         np.testing.assert_array_equal(got_l, exp_l, err_msg="frame %d" % t)
+        if auto:
+            rows = dev.vocab_count()
+            assert host.vocab_count() == rows, "frame %d" % t
+            np.testing.assert_array_equal(host.vocab_read(0, rows[0])[1], dev.vocab_read(0, rows[0])[1], err_msg="frame %d" % t)
         n_new = int(-exp_w.min()) if exp_w.min() < 0 else 0
         created += n_new
         first_new += n_new
