@@ -171,7 +171,8 @@ int lcd_find_nn(lcd_engine* h, const void* queries, int q, const void* extra_row
 
 /* one signature's references: word_ids[n] in keypoint order, duplicates = occurrences (== n x addWordRef :880 for
  * ids > 0; ids <= 0 are features without a word: they only count in ni).  ni = Signature::getWords().size()
- * (Memory.cpp:4961), normally n.  The signature must not be registered already. */
+ * (Memory.cpp:4961), normally n.  The signature must not be registered already.  At most 8192 entries (n > 8192:
+ * LCD_ERR_UNSUPPORTED, nothing registered, the handle stays usable; the same limit per signature for lcd_sig_add_bulk). */
 int lcd_sig_add(lcd_engine* h, int32_t sig_id, const int32_t* word_ids, int n, int32_t ni);
 /* Memory::disableWordsRef (:6877-6897) == removeAllWordRef(word, sig) for every word of the signature */
 int lcd_sig_remove(lcd_engine* h, int32_t sig_id);
@@ -187,7 +188,8 @@ int lcd_word_nrefs(lcd_engine* h, int32_t word_id, int32_t* out_nw);
  *   out[k] = sum over unique word ids w > 0 of the query of  (nwi(w, sig_ids[k]) * log10(N / nw(w))) / ni(sig_ids[k])
  * query_word_ids[nq]: the query signature's words (any order, duplicates allowed, ids <= 0 ignored);
  * sig_ids[n_ids]: the signatures to score (unknown / retired ids and the virtual place score 0);
- * N = (float)Memory::getSignatures().size() as the caller counts it (:2248).  out[n_ids] pairs with sig_ids. */
+ * N = (float)Memory::getSignatures().size() as the caller counts it (:2248).  out[n_ids] pairs with sig_ids.
+ * At most 8192 query entries (nq > 8192: LCD_ERR_UNSUPPORTED, the handle stays usable). */
 int lcd_likelihood(lcd_engine* h, const int32_t* query_word_ids, int nq, const int32_t* sig_ids, int n_ids,
                    float N, float* out);
 

@@ -95,3 +95,65 @@ def matlab_compute_likelihood(sign, mem, dic):
                 if ni:
                     L[pos] += (nwi * lg) / ni
     return L
+
+
+# ---- planted signatures for the inverted index's encoding limits (tests/test_gpu_index_limits.py)
+
+def spread_slots(n_post, key, n_slots=256):
+    """n_post distinct slot numbers in [0, n_slots) picked by `key` (an odd stride over the bucket: distinct while n_post <= n_slots)."""
+    start = (int(key) * 53) % n_slots
+    step = 2 * (int(key) % 61) + 1
+    return (start + step * np.arange(n_post)) % n_slots
+
+
+def signatures_from_postings(postings, n_slots=256):
+    """postings: iterable of (word id, slot, count).  Returns n_slots int32 word lists (a word repeated `count` times), ascending word ids."""
+    per = [[] for _ in range(n_slots)]
+    for w, s, c in postings:
+        per[int(s)].extend([int(w)] * int(c))
+    return [np.array(sorted(p), np.int32) for p in per]
+
+
+def tfidf_f64(sigs, query, live=None):
+    """Memory::computeLikelihood's TF-IDF sum in float64 over plain word lists (ids <= 0 count in ni only, ni = len).
+    Returns (L[len(sigs)], (sig index, word id, term) of every posting of a query word).  The host-side yardstick the
+    sensitivity guards edit; the parity checks themselves use the C++ oracle."""
+    n = len(sigs)
+    live = np.ones(n, bool) if live is None else np.asarray(live, bool)
+    q = np.unique(np.asarray(query, np.int64))
+    q = q[q > 0]
+    ni = np.array([len(s) for s in sigs], np.float64)
+    L = np.zeros(n)
+    if n == 0 or q.size == 0:
+        return L, (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0))
+    rows = np.repeat(np.arange(n, dtype=np.int64), [len(s) for s in sigs])
+    words = np.concatenate([np.asarray(s, np.int64) for s in sigs]) if n else np.zeros(0, np.int64)
+    m = np.isin(words, q) & live[rows]
+    uk, cnt = np.unique(rows[m] * (1 << 32) + words[m], return_counts=True)
+    s, w = uk >> 32, uk & 0xFFFFFFFF
+    _, inv, nw = np.unique(w, return_inverse=True, return_counts=True)
+    term = cnt * np.log10(float(live.sum()) / nw[inv]) / ni[s]
+    np.add.at(L, s, term)
+    return L, (s, w, term)
+
+
+def max_rel_change(base, edited):
+    """Largest relative move of a score between two float64 score vectors (scores that are 0 in both do not count)."""
+    base, edited = np.asarray(base, np.float64), np.asarray(edited, np.float64)
+    d = np.abs(edited - base)
+    ref = np.maximum(np.abs(base), np.abs(edited))
+    ok = ref > 0
+    return float((d[ok] / ref[ok]).max()) if ok.any() else 0.0
+
+
+def min_word_visibility(sigs, query, live=None):
+    """min over the query's words (those with a nonzero term) of max over signatures of term(w, s) / L(s): dropping the postings of
+    ANY one of these words moves at least one score by this much, relative."""
+    L, (s, w, term) = tfidf_f64(sigs, query, live)
+    keep = term != 0
+    s, w, term = s[keep], w[keep], term[keep]
+    rel = term / L[s]
+    uw, inv = np.unique(w, return_inverse=True)
+    best = np.zeros(uw.size)
+    np.maximum.at(best, inv, rel)
+    return float(best.min()) if best.size else 0.0
