@@ -2,8 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <deque>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -85,6 +89,169 @@ struct AppendLog {
     void release(int64_t* bytes_device) { d_vcnt.release(bytes_device); if (h_vmirror) (void)hipHostFree(h_vmirror); h_vmirror = nullptr; }
 };
 
+inline AppendLog::Report AppendLog::report() const {
+    if (!h_vmirror) return Report{0, 0};
+    const unsigned long long v = *(volatile const unsigned long long*)h_vmirror;
+    return Report{(uint32_t)(v >> 32), (int64_t)(uint32_t)v};
+}
+
+inline int64_t AppendLog::rows_ub(int64_t n_rows) const {
+    if (unreconciled.empty()) return n_rows;
+    const Report r = report();
+    int64_t extra = 0;
+    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
+        if (r.tag != 0 && (uint32_t)(it->seq + 1) == r.tag) return r.rows + extra;
+        if (it->enabled) extra += it->q;
+    }
+    return n_rows + extra;
+}
+
+inline int64_t AppendLog::rows_plan(uint64_t fseq, int64_t n_rows) {
+    if (unreconciled.empty()) return n_rows;
+    const Report r = report();
+    if (r.tag == 0) return rows_ub(n_rows);                          // nothing reported yet
+    if (est_tag != 0 && r.tag != est_tag) {                          // the reports moved on: rows per frame since the last look
+        const double per = (double)(r.rows - est_cnt) / (double)(uint32_t)(r.tag - est_tag);
+        est_new = std::max(est_new * 0.9, per);
+    }
+    est_tag = r.tag; est_cnt = r.rows;
+    const int64_t ub = rows_ub(n_rows);
+    int64_t frames = 0; bool found = false;
+    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
+        if ((uint32_t)(it->seq + 1) == r.tag) { found = true; break; }
+        if (it->enabled && it->seq + 2 <= fseq) frames += 1;          // an appender the filter's count includes, not reported yet
+    }
+    if (!found) return ub;
+    const int64_t est = r.rows + (int64_t)std::ceil((double)frames * (est_new * 1.25 + 8.0));
+    return std::min(std::max(est, r.rows), ub);
+}
+
+inline hipError_t AppendLog::activate(int64_t n_rows, hipStream_t s, int64_t* bytes_device) {
+    if (vcnt_active) return hipSuccess;
+    hipError_t e = d_vcnt.reserve((size_t)(16 + VLOG) * 4, 0, s, bytes_device);
+    if (e == hipSuccess && !h_vmirror) {
+        e = hipHostMalloc((void**)&h_vmirror, 64, hipHostMallocDefault);
+        if (e == hipSuccess) *h_vmirror = 0ull;
+    }
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)d_vcnt.p, (int)n_rows, 2, s);
+    if (e == hipSuccess) vcnt_active = true;
+    return e;
+}
+
+inline uint64_t AppendLog::record(int32_t first_new_word_id, int32_t q, bool enabled, ShardOwnership own) {
+    unreconciled.push_back(DevAppend{vseq, first_id(first_new_word_id), q, enabled, own});
+    return vseq++;
+}
+
+// (the wait spins for the few microseconds a frame takes, then yields; a stream that makes no progress for a long time -- a caller-provided
+// one may legitimately sit behind an event -- is waited for with hipStreamSynchronize instead of failing)
+inline hipError_t AppendLog::throttle(hipStream_t s) const {
+    if (!h_vmirror || unreconciled.size() <= 8) return hipSuccess;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int spins = 0;; ++spins) {
+        if ((uint32_t)vseq - report().tag <= 8u) return hipSuccess;
+        if (spins > 4096) std::this_thread::yield();
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return hipStreamSynchronize(s);
+    }
+}
+
+// The software pipeline of lcd_frame_dev (lcd_config.pipeline): four frames are in flight.  With frame t the newest, its call launches
+//        A = query pre-split of frame t  +  filter of frame t - 1  +  decision loop of frame t - 2  +  retirement / registration of frame t - 3
+//        B = re-rank of frame t - 1  +  scoring of frame t - 3            (then the decision stage of frame t - 3, if asked for)
+// so every single-workgroup latency chain hides behind the matrix-core filter.  The scratch a frame's stages hand to each other
+// lives in a ring indexed by the frame's sequence number; what a frame still owes (`stage`) and the calls made behind it
+// (retirements, neighbour lists, event records, cleans) wait in `inflight` until a later lcd_frame_dev carries them or any other call
+// on the handle completes them stand-alone (lcd_engine::drain()).  The rules are the methods below; the launches are frame_pipeline.hip's.
+struct FramePipeline {
+    static constexpr int PIPE_SETS = 4;                 // a frame's set is in use for four calls (pre-split .. registration)
+    static constexpr int DEPTH = PIPE_SETS - 1;         // lcd_pipeline_depth(): the later calls that still enqueue work of a frame (callers rotate DEPTH + 1 buffer sets)
+    struct FrameScratch {
+        lcd::DevBuf d_knn_row, d_knn_word, d_knn_dist, d_selfdist, d_bits, d_partial2, d_partial3, d_fail_list, d_fail_count, d_out_wslot;
+        lcd::DevBuf d_qsplit, d_qnorm;                  // the frame's queries pre-split into bf16 matrix-core operands, their norms
+        lcd::DevBuf d_applist;                          // deferred append: which descriptors of the frame became words (AppendArgs::list_out)
+        lcd::DevBuf d_cross;                            // the frame's distances to the descriptors of the frame before it (PipeKnn::cross)
+        lcd::DevBuf d_shadow_bf, d_shadow_norm, d_newmask;   // shadow rows: the frame's descriptors as operand-table rows + augmentation entries (written by its
+                                                        // query pre-split), its final new-word mask + prefix sums (written by its decision loop)
+        bool fail_count_clean = false;
+    };
+    struct DeferredLink { std::vector<int32_t> triples, restart; };
+    enum class Stage { Filter, Decision, Registration };   // what a frame owes next: filter + re-rank / the decision loop / registration + scoring
+    struct InFlight {
+        lcd_frame_args a; lcd::ResolveArgs r; int set = 0;
+        uint64_t vseq = 0; bool chained = false;        // the frame takes part in the device row-count chain (applog.vcnt_active at its call)
+        bool has_shadow = false;                        // its query pre-split also wrote its shadow rows (FrameScratch::d_shadow_bf)
+        bool slots_are_rows = false;                    // its decision loop left vocabulary ROWS in r.out_wslot (PipeOpts::slots_from_rows): the registration looks the keys up
+        lcd::WsRuns runs; bool reserved = false;        // postings keys of its new words (reserved when its decision loop is prepared)
+        Stage stage = Stage::Filter;
+        std::vector<int32_t> retire_after;              // lcd_sig_remove calls made while this was the newest frame
+        std::vector<void*> events_after;                // lcd_record_event calls ...
+        std::vector<DeferredLink> links_after;          // lcd_bayes_set_neighbors calls ...
+        int cleans_after = 0;                           // lcd_vocab_remove_unused_async calls ...
+    };
+    FrameScratch ring[PIPE_SETS];
+    std::deque<InFlight> inflight;                      // oldest first
+    uint64_t frame_seq = 0;                             // frames submitted so far
+    uint64_t advances = 0;                              // launch pairs that moved the frames in flight on (progress())
+    bool clean_armed = false;                           // a clean waits for the next fused launch pair, whose registration applies the
+                                                        // retirements asked for before it (they ride there: no launches of their own)
+
+    // frames in flight hold pointers into their ring sets: the OTHER sets may only be resized while this holds
+    bool empty() const { return inflight.empty(); }
+    const InFlight& newest() const { return inflight.back(); }
+    // the signatures the frames in flight register: each gets a slot when its registration runs
+    int64_t owed_sigs() const { int64_t n = 0; for (const InFlight& f : inflight) if (f.a.sig_id != 0) n += 1; return n; }
+    bool registers(int32_t id) const {
+        for (const InFlight& f : inflight) if (f.a.sig_id != 0 && f.a.sig_id == id) return true;
+        return false;
+    }
+    bool retirement_queued(int32_t id) const {
+        for (const InFlight& f : inflight) if (std::find(f.retire_after.begin(), f.retire_after.end(), id) != f.retire_after.end()) return true;
+        return false;
+    }
+    // the slot signature `id` has, or will get: an owed signature gets n_slots + its rank among the owed ones, in frame order.  -1: not held, or on its way out
+    int64_t slot_of(int32_t id, const lcd::Tfidf& t) const {
+        int64_t k = 0;
+        for (const InFlight& f : inflight) {
+            if (f.a.sig_id == 0) continue;
+            if (f.a.sig_id == id) return retirement_queued(id) ? -1 : t.n_slots + k;
+            k += 1;
+        }
+        auto it = t.sig_slot.find(id);
+        return it == t.sig_slot.end() || retirement_queued(id) ? -1 : it->second;
+    }
+    // a call made with frames in flight takes its place behind the newest: it runs, in call order, once every stage of that frame is enqueued
+    void queue_retire(int32_t sig_id) { inflight.back().retire_after.push_back(sig_id); }
+    void queue_event(void* event) { inflight.back().events_after.push_back(event); }
+    void queue_link(DeferredLink&& dl) { inflight.back().links_after.push_back(std::move(dl)); }
+    void queue_clean() { inflight.back().cleans_after += 1; }
+
+    // stages advance oldest first, one per launch pair: a pair carries the oldest frame owing each stage
+    struct Owing { InFlight* reg = nullptr; InFlight* res = nullptr; InFlight* knn = nullptr; };
+    Owing owing() {
+        Owing o;
+        for (InFlight& f : inflight) {
+            if (f.stage == Stage::Registration && !o.reg) o.reg = &f;
+            else if (f.stage == Stage::Decision && !o.res) o.res = &f;
+            else if (f.stage == Stage::Filter && !o.knn) o.knn = &f;
+        }
+        return o;
+    }
+    // the pair that carried `o` is enqueued: each frame owes its next stage.  True: a registration ran, that frame is complete -- it is the
+    // oldest entry (stages advance in order) and leaves with pop_oldest()
+    bool advance(const Owing& o) {
+        if (o.res) o.res->stage = Stage::Registration;
+        if (o.knn) o.knn->stage = Stage::Decision;
+        advances += 1;
+        return o.reg != nullptr;
+    }
+    InFlight pop_oldest() { InFlight f = std::move(inflight.front()); inflight.pop_front(); return f; }
+    uint64_t progress() const { return advances; }      // changes whenever advance() ran: a failed launch pair that left it alone moved nothing
+    // a frame's ring set is seq % PIPE_SETS: its own for the PIPE_SETS calls from its pre-split to its registration
+    int next_set() const { return (int)(frame_seq % PIPE_SETS); }
+    FrameScratch& scratch(const InFlight& f) { return ring[f.set]; }
+    void submit(InFlight&& f) { f.set = next_set(); f.stage = Stage::Filter; inflight.push_back(std::move(f)); frame_seq += 1; }
+};
+
 struct lcd_engine {
     int device = 0;
     int dtype = 0;
@@ -116,42 +283,11 @@ struct lcd_engine {
     int f16() const { return knn_mode == 3 ? 1 : 0; }
     int knn_mode = 2;                                   // f32 dim 64: 2 = bf16x3 MFMA filter + exact re-rank (default), 3 = fp16 one-product filter, 1 = f32 MFMA filter
                                                         // + exact re-rank, 0 = exact VALU scan only (lcd_config.knn_mode)
-    // ---- pipelined frames (lcd_config.pipeline): three frames are in flight.  The call for frame t launches
-    //        A = filter of frame t  +  decision loop of frame t - 1  +  retirement / registration of frame t - 2
-    //        B = re-rank of frame t  +  scoring of frame t - 2            (then the decision stage of frame t - 2, if asked for)
-    // so every single-workgroup latency chain hides behind the matrix-core filter.  The scratch a frame's stages hand to each other
-    // lives in a ring indexed by the frame's sequence number; what a frame still owes (`stage`) and the calls made behind it
-    // (retirements, neighbour lists, event records) wait in `inflight` until a later lcd_frame_dev carries them or any other call
-    // on the handle completes them stand-alone (drain()).
+    // ---- pipelined frames (lcd_config.pipeline): see FramePipeline
     int pipeline = 0;
     hipStream_t kst = nullptr;                          // the stream the 2-NN stage is enqueued on (== stream)
-    struct FrameScratch {
-        lcd::DevBuf d_knn_row, d_knn_word, d_knn_dist, d_selfdist, d_bits, d_partial2, d_partial3, d_fail_list, d_fail_count, d_out_wslot;
-        lcd::DevBuf d_qsplit, d_qnorm;                  // the frame's queries pre-split into bf16 matrix-core operands, their norms
-        lcd::DevBuf d_applist;                          // deferred append: which descriptors of the frame became words (AppendArgs::list_out)
-        lcd::DevBuf d_cross;                            // the frame's distances to the descriptors of the frame before it (PipeKnn::cross)
-        lcd::DevBuf d_shadow_bf, d_shadow_norm, d_newmask;   // shadow rows: the frame's descriptors as operand-table rows + augmentation entries (written by its
-                                                        // query pre-split), its final new-word mask + prefix sums (written by its decision loop)
-        bool fail_count_clean = false;
-    };
-    static constexpr int PIPE_SETS = 4;                 // a frame's set is in use for four calls (pre-split .. registration)
-    FrameScratch ring[PIPE_SETS];
-    uint64_t frame_seq = 0;
+    FramePipeline pipe;
     const void* last_fail_count = nullptr;              // certificate counters of the latest pipelined frame (lcd_get_stats)
-    struct DeferredLink { std::vector<int32_t> triples, restart; };
-    struct InFlight {
-        lcd_frame_args a; lcd::ResolveArgs r; int set = 0;
-        uint64_t vseq = 0; bool chained = false;        // the frame takes part in the device row-count chain (applog.vcnt_active at its call)
-        bool has_shadow = false;                        // its query pre-split also wrote its shadow rows (FrameScratch::d_shadow_bf)
-        bool slots_are_rows = false;                    // its decision loop left vocabulary ROWS in r.out_wslot (PipeOpts::slots_from_rows): the registration looks the keys up
-        lcd::WsRuns runs; bool reserved = false;        // postings keys of its new words (reserved when its decision loop is prepared)
-        int stage = 0;                                  // what is owed next: 0 filter + re-rank, 1 the decision loop, 2 registration + scoring
-        std::vector<int32_t> retire_after;              // lcd_sig_remove calls made while this was the newest frame
-        std::vector<void*> events_after;                // lcd_record_event calls ...
-        std::vector<DeferredLink> links_after;          // lcd_bayes_set_neighbors calls ...
-        int cleans_after = 0;                           // lcd_vocab_remove_unused_async calls ...
-    };
-    std::deque<InFlight> inflight;                      // oldest first
     // ---- VWDictionary::update()'s append branch on the device (lcd_frame_args.append_new_words): see AppendLog
     AppendLog applog;
     int64_t vocab_capacity_cfg = 0;                     // lcd_config.vocab_capacity: every per-row buffer is sized for it
@@ -165,8 +301,6 @@ struct lcd_engine {
     int frames_since_reconcile = 0;                     // pipelined frames submitted with rm_pending set
     int enqueue_clean(const int32_t* reg_cnt = nullptr);  // flush the pending retirements, launch the kernel (nothing is synchronised); reg_cnt:
                                                         // device row count as of the newest registered frame (rows behind it are not scanned)
-    bool clean_armed = false;                           // a clean waits for the next fused launch pair, whose registration applies the
-                                                        // retirements asked for before it (they ride there: no launches of their own)
     int reconcile();
     // sharded vocabulary, balanced growth (lcd_set_option "shard_growth_first" / "shard_growth_block"): the words frames create (ids >=
     // shard_first) belong to rank ((id - shard_first) / shard_block) % world; 0 = they belong to the last rank

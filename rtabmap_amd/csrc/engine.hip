@@ -4,7 +4,9 @@
 // vocabulary row order (the distance tie-break of the reference) and the signature/word slot maps.  All arithmetic
 // of the hot path runs in the gfx950 kernels (knn2_kernels.hip, resolve_kernels.hip, tfidf.hip).  There is no CPU
 // fallback: every entry point either runs on the device or returns an error status.
-#include "engine.h"
+// Here: the handle's life cycle, vocabulary, signatures, stand-alone search / quantise, Bayes, the sharded stages, profiling, options,
+// statistics.  The per-frame path (lcd_frame_dev, lcd_frame_host, lcd_engine::drain) is frame_pipeline.hip.
+#include "engine_impl.h"
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -14,7 +16,6 @@
 #include <cstring>
 #include <new>
 #include <numeric>
-#include <thread>
 #include <unordered_map>
 
 using namespace lcd;
@@ -60,80 +61,6 @@ void RowMirror::reset(std::vector<int32_t>& keys) {
     word_row_valid = false;
 }
 
-// ---- the device append log (engine.h)
-AppendLog::Report AppendLog::report() const {
-    if (!h_vmirror) return Report{0, 0};
-    const unsigned long long v = *(volatile const unsigned long long*)h_vmirror;
-    return Report{(uint32_t)(v >> 32), (int64_t)(uint32_t)v};
-}
-
-int64_t AppendLog::rows_ub(int64_t n_rows) const {
-    if (unreconciled.empty()) return n_rows;
-    const Report r = report();
-    int64_t extra = 0;
-    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
-        if (r.tag != 0 && (uint32_t)(it->seq + 1) == r.tag) return r.rows + extra;
-        if (it->enabled) extra += it->q;
-    }
-    return n_rows + extra;
-}
-
-int64_t AppendLog::rows_plan(uint64_t fseq, int64_t n_rows) {
-    if (unreconciled.empty()) return n_rows;
-    const Report r = report();
-    if (r.tag == 0) return rows_ub(n_rows);                          // nothing reported yet
-    if (est_tag != 0 && r.tag != est_tag) {                          // the reports moved on: rows per frame since the last look
-        const double per = (double)(r.rows - est_cnt) / (double)(uint32_t)(r.tag - est_tag);
-        est_new = std::max(est_new * 0.9, per);
-    }
-    est_tag = r.tag; est_cnt = r.rows;
-    const int64_t ub = rows_ub(n_rows);
-    int64_t frames = 0; bool found = false;
-    for (auto it = unreconciled.rbegin(); it != unreconciled.rend(); ++it) {
-        if ((uint32_t)(it->seq + 1) == r.tag) { found = true; break; }
-        if (it->enabled && it->seq + 2 <= fseq) frames += 1;          // an appender the filter's count includes, not reported yet
-    }
-    if (!found) return ub;
-    const int64_t est = r.rows + (int64_t)std::ceil((double)frames * (est_new * 1.25 + 8.0));
-    return std::min(std::max(est, r.rows), ub);
-}
-
-hipError_t AppendLog::activate(int64_t n_rows, hipStream_t s, int64_t* bytes_device) {
-    if (vcnt_active) return hipSuccess;
-    hipError_t e = d_vcnt.reserve((size_t)(16 + VLOG) * 4, 0, s, bytes_device);
-    if (e == hipSuccess && !h_vmirror) {
-        e = hipHostMalloc((void**)&h_vmirror, 64, hipHostMallocDefault);
-        if (e == hipSuccess) *h_vmirror = 0ull;
-    }
-    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)d_vcnt.p, (int)n_rows, 2, s);
-    if (e == hipSuccess) vcnt_active = true;
-    return e;
-}
-
-uint64_t AppendLog::record(int32_t first_new_word_id, int32_t q, bool enabled, ShardOwnership own) {
-    unreconciled.push_back(DevAppend{vseq, first_id(first_new_word_id), q, enabled, own});
-    return vseq++;
-}
-
-// (the wait spins for the few microseconds a frame takes, then yields; a stream that makes no progress for a long time -- a caller-provided
-// one may legitimately sit behind an event -- is waited for with hipStreamSynchronize instead of failing)
-hipError_t AppendLog::throttle(hipStream_t s) const {
-    if (!h_vmirror || unreconciled.size() <= 8) return hipSuccess;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int spins = 0;; ++spins) {
-        if ((uint32_t)vseq - report().tag <= 8u) return hipSuccess;
-        if (spins > 4096) std::this_thread::yield();
-        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return hipStreamSynchronize(s);
-    }
-}
-
-#define LCD_CHECK_HANDLE(h) do { if (!(h)) return LCD_ERR_INVALID; } while (0)
-#define LCD_HIP(h, x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return (h)->hip_fail(e__, #x); } while (0)
-// every entry selects the device; every entry except lcd_frame_dev / lcd_sig_remove / lcd_record_event first completes the index
-// stage a pipelined handle still owes for its last frame
-#define LCD_DEV_NODRAIN(h) LCD_HIP(h, hipSetDevice((h)->device))
-#define LCD_DEV(h) do { LCD_DEV_NODRAIN(h); int rc__ = (h)->drain(); if (rc__) return rc__; } while (0)
-
 // The sharded stages between a frame that appended on the device and the next one need no exact row mirror: the search plans for rows_ub() (the
 // rows behind the device's count carry +inf norms, a zero operand split and row id 0: no scan ranks them), the index calls do not look at rows
 // at all.  Round 6: they complete what is owed WITHOUT reconciling (drain(false)) -- the per-frame synchronisation of the sharded path -- as long
@@ -153,30 +80,6 @@ int lcd_engine::sync_all() {
 }
 
 namespace {
-
-inline hipError_t dreserve(lcd_engine* h, DevBuf& b, size_t bytes, size_t keep = 0) {
-    return b.reserve(bytes, keep, h->stream, &h->bytes_device);
-}
-
-// One scratch buffer of a pipelined frame: in the frame's own set of the ring -- and, while nothing is in flight, in every other set as
-// well, so that a steady stream of frames does not meet a hipMalloc (hundreds of microseconds) each time a set sees its first frame.
-// The other sets are NOT touched while frames are in flight: those frames' launch arguments hold pointers into them.
-inline hipError_t ring_reserve(lcd_engine* h, int own_set, DevBuf lcd_engine::FrameScratch::*member, size_t bytes) {
-    hipError_t e = dreserve(h, h->ring[own_set].*member, bytes);
-    if (e != hipSuccess || !h->inflight.empty()) return e;
-    for (lcd_engine::FrameScratch& sc : h->ring) {
-        e = dreserve(h, sc.*member, bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// ... for a buffer whose size follows the vocabulary: `need` bytes now; when that takes a (re)allocation, `want` >= need bytes are asked for, so that the set does
-// not outgrow the buffer again a few frames later (a reallocation with frames in flight waits for the stream, and every set of the ring pays its own)
-inline hipError_t ring_reserve_grow(lcd_engine* h, int own_set, DevBuf lcd_engine::FrameScratch::*member, size_t need, size_t want) {
-    if ((h->ring[own_set].*member).cap >= need) return hipSuccess;
-    return ring_reserve(h, own_set, member, std::max(need, want));
-}
 
 // copy `rows` host rows (h->dim columns) into a device buffer laid out with h->row_bytes per row (u8 rows zero-padded)
 int upload_rows(lcd_engine* h, const void* rows, int n, DevBuf& dst) {
@@ -289,61 +192,6 @@ int download(lcd_engine* h, void* dst, const void* d_src, size_t bytes, PinBuf& 
     return LCD_OK;
 }
 
-// ---- VWDictionary::update()'s append branch on the device (see engine.h)
-int64_t vocab_cap_rows(const lcd_engine* h) {
-    int64_t c = (int64_t)(h->vocab.cap / (size_t)h->row_bytes);
-    c = std::min<int64_t>(c, (int64_t)(h->row_id.cap / 4));
-    c = std::min<int64_t>(c, (int64_t)(h->row_wslot.cap / 4));
-    if (h->dtype == LCD_F32) c = std::min<int64_t>(c, (int64_t)(h->row_norm.cap / 8) - 1);
-    if (knn_mfma_supported(h->dtype, h->kdim)) c = std::min<int64_t>(c, (int64_t)(h->vocab_bf.cap / 256));
-    return std::max<int64_t>(c, 0);
-}
-
-// the row buffers hold `rows` rows; what lies behind the rows in use carries +inf norms and a zero bf16 split
-int ensure_append_capacity(lcd_engine* h, int64_t rows) {
-    const int64_t keep = h->applog.rows_ub(h->n_rows);
-    if (rows > vocab_cap_rows(h)) {
-        LCD_HIP(h, dreserve(h, h->vocab, (size_t)rows * h->row_bytes, (size_t)keep * h->row_bytes));
-        LCD_HIP(h, dreserve(h, h->row_id, (size_t)rows * 4, (size_t)keep * 4));
-        LCD_HIP(h, dreserve(h, h->row_wslot, (size_t)rows * 4, (size_t)keep * 4));
-        if (h->dtype == LCD_F32) LCD_HIP(h, dreserve(h, h->row_norm, ((size_t)rows + 1) * 8, ((size_t)keep + 1) * 8));
-        if (knn_mfma_supported(h->dtype, h->kdim)) LCD_HIP(h, dreserve(h, h->vocab_bf, (size_t)rows * 256, (size_t)keep * 256));
-        h->tail_filled_rows = std::min(h->tail_filled_rows, keep);
-    }
-    const int64_t cap = vocab_cap_rows(h);
-    const int64_t first = std::max(h->tail_filled_rows, keep);
-    if (first < cap) {
-        if (knn_mfma_supported(h->dtype, h->kdim)) LCD_HIP(h, launch_vocab_tail(h->row_norm.as<float>(), h->vocab_bf.p, first, cap - first, h->stream));
-        // row id 0 behind the rows: a scan planned for an upper bound of the row count skips what does not exist yet like a tombstone
-        LCD_HIP(h, hipMemsetAsync(h->row_id.as<int32_t>() + first, 0, (size_t)(cap - first) * 4, h->stream));
-        h->tail_filled_rows = cap;
-    }
-    return LCD_OK;
-}
-
-// the vocabulary buffers may have been reallocated since a frame's arguments were stored (device-side appends grow them)
-void refresh_vocab_ptrs(lcd_engine* h, ResolveArgs* r) {
-    r->row_wslot = h->row_wslot.as<int32_t>();
-    if (r->rp.enabled) { r->rp.vocab = (const float*)h->vocab.p; r->rp.row_id = h->row_id.as<int32_t>(); }
-}
-
-// the append (or, for a frame that appends nothing, the hand-over of the row count) that rides with the decision loop of chain frame `vseq`
-void fill_append(lcd_engine* h, const lcd_frame_args& a, uint64_t vseq, bool enabled, ResolveArgs* r, uint32_t* list_out = nullptr) {
-    AppendArgs& ap = r->ap;
-    ap = AppendArgs();
-    ap.enabled = enabled ? 1 : 0;
-    // pipelined frames of 64-float rows: the decision loop publishes the list, workgroups of launch B write the rows (append_rows_body)
-    if (list_out && knn_mfma_supported(h->dtype, h->kdim)) { ap.defer_rows = 1; ap.list_out = list_out; }
-    ap.descriptors = (const float*)a.d_descriptors; ap.row_dwords = h->row_bytes / 4; ap.is_f32_64 = knn_mfma_supported(h->dtype, h->kdim) ? 1 : 0;
-    ap.vocab = h->vocab.as<uint32_t>(); ap.row_id = h->row_id.as<int32_t>(); ap.row_wslot = h->row_wslot.as<int32_t>();
-    ap.row_norm = h->row_norm.as<float>(); ap.norm_max_bits = h->norm_max.as<uint32_t>(); ap.vocab_bf = h->vocab_bf.as<uint32_t>();
-    ap.wrow = h->tfidf.wrow.as<uint32_t>(); ap.f16 = h->f16();
-    ap.cnt_in = h->applog.count_before(vseq); ap.cnt_out = h->applog.count_after(vseq); ap.log_slot = h->applog.log_slot(vseq);
-    ap.first_id = h->applog.first_id(a.first_new_word_id); ap.capacity = vocab_cap_rows(h);
-    ap.first_out = (int32_t*)a.d_first_new_word_id;
-    ap.host_mirror = h->applog.h_vmirror; ap.tag = (uint32_t)(vseq + 1);
-}
-
 }  // namespace
 
 // the host's row mirror catches up with the device (synchronises)
@@ -438,15 +286,86 @@ int lcd_engine::enqueue_clean(const int32_t* reg_cnt) {
     return LCD_OK;
 }
 
-// No exception crosses the C-ABI (lcd.h): the bookkeeping of every entry point uses std:: containers, whose allocations may throw
-static int lcd_catch(const lcd_engine* h, int code, const char* what) noexcept {
-    if (h) { try { const_cast<lcd_engine*>(h)->err = what; } catch (...) { } }
-    return code;
+// device part of addNewWords up to (not including) the decision loop: 2-NN, same-frame distances + candidate bits.
+// Fills the decision loop's arguments.
+int prepare_resolve(lcd_engine* h, const void* d_desc, int q, int flags, float nndr, int32_t* d_out_word, int32_t* d_out_wslot,
+                    ResolveArgs* r, bool defer_redo, int64_t rows_now) {
+    r->rp = RowparArgs{};
+    if (rows_now < 0) rows_now = h->n_rows;
+    const int have_index = h->n_live >= 2 ? 1 : 0;                  // VWDictionary.cpp:1015
+    const bool incremental = (flags & LCD_Q_INCREMENTAL) != 0;
+    const bool together = incremental && (flags & LCD_Q_NEW_WORDS_COMPARED);
+    int ld = (q + 63) / 64 * 64;
+    const int bw = ld / 32;
+    if (together) {
+        LCD_HIP(h, dreserve(h, h->d_selfdist, (size_t)q * ld * 4));
+        LCD_HIP(h, dreserve(h, h->d_bits, cand_bits_bytes(q, bw)));
+    }
+    // With the MFMA filter the same-frame distance matrix does not wait for the 2-NN: extra workgroups of the filter launch
+    // compute it, and the re-rank workgroup of a query -- the first to know the query's second neighbour -- derives the query's
+    // candidate bits from its (symmetric) row: two launches fewer per frame.
+    const int64_t knn_rows = have_index ? rows_now : 0;
+    const bool side = together && h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim) && knn_rows >= 256 && q > 0;
+    int rc;
+    if (side) {
+        CandBits cb;
+        cb.selfdist = h->d_selfdist.as<float>(); cb.ld = ld; cb.nq = q; cb.have_index = have_index;
+        cand_bits_layout(cb, h->d_bits.as<uint32_t>(), q, bw);
+        LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
+        LCD_HIP(h, dreserve(h, h->d_knn_word, (size_t)q * 2 * 4));
+        LCD_HIP(h, dreserve(h, h->d_knn_dist, (size_t)q * 2 * 4));
+        rc = run_knn2_raw(h, d_desc, q, h->vocab.p, h->row_id.as<int32_t>(), knn_rows, true, h->d_knn_row.as<int32_t>(),
+                          h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), &cb, defer_redo ? &r->rp : nullptr);
+        if (rc) return rc;
+    } else if (together && h->dtype == LCD_U8 && q > 0) {
+        // Hamming frames (config 3): the scan, then ONE launch for the merge of its partial keys, the same-frame distance matrix and the candidate
+        // bit rows (round 6: they were two dependent launches of ~5 us each behind the scan)
+        LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
+        LCD_HIP(h, dreserve(h, h->d_knn_word, (size_t)q * 2 * 4));
+        LCD_HIP(h, dreserve(h, h->d_knn_dist, (size_t)q * 2 * 4));
+        const KnnPlan p = knn_plan(q, (int)knn_rows, h->row_bytes);
+        LCD_HIP(h, dreserve(h, h->d_partial, knn_partial_bytes(p)));
+        const bool prof = h->prof_cap > 0 && h->prof_n < h->prof_cap;
+        if (prof) LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n], h->kst));
+        LCD_HIP(h, launch_knn2_partial(h->dtype, h->kdim, h->vocab.p, h->row_id.as<int32_t>(), d_desc, p, h->d_partial.as<uint64_t>(), h->kst));
+        if (prof) { LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n + 1], h->kst)); h->prof_n += 1; h->prof_kernel = "knn2_hamming_kernel"; }
+        LCD_HIP(h, launch_knn2_merge_selfdist_hamming(p, h->d_partial.as<uint64_t>(), h->row_id.as<int32_t>(), h->d_knn_row.as<int32_t>(),
+                                                      h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), d_desc, h->kdim, h->d_selfdist.as<float>(), ld,
+                                                      have_index, h->d_bits.as<uint32_t>(), bw, h->kst));
+        h->knn_launches += 1;
+    } else {
+        rc = run_knn2(h, d_desc, q, h->vocab.p, h->row_id.as<int32_t>(), h->row_wslot.as<int32_t>(), knn_rows, h->d_knn_row, h->d_knn_word,
+                      h->d_knn_dist);
+        if (rc) return rc;
+        if (together)
+            LCD_HIP(h, launch_selfdist(h->dtype, h->kdim, d_desc, q, h->d_selfdist.as<float>(), ld, h->kst, have_index,
+                                       h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), h->d_bits.as<uint32_t>(), bw));
+    }
+    r->q = q;
+    r->flags = (incremental ? LCD_Q_INCREMENTAL : 0) | (together ? LCD_Q_NEW_WORDS_COMPARED : 0);
+    r->nndr = nndr;
+    r->have_index = have_index;
+    r->knn_word = h->d_knn_word.as<int32_t>();
+    r->knn_dist = h->d_knn_dist.as<float>();
+    r->selfdist = together ? h->d_selfdist.as<float>() : nullptr;
+    r->ld = ld;
+    r->cand_bits = together ? h->d_bits.as<uint32_t>() : nullptr;
+    r->bw = bw;
+    r->out_word = d_out_word;
+    r->out_n_new = h->d_n_new.as<int32_t>();
+    r->knn_row = h->d_knn_row.as<int32_t>();
+    r->row_wslot = h->row_wslot.as<int32_t>();
+    r->out_wslot = d_out_wslot;
+    r->new_ws = WsRuns();
+    r->cand_list = nullptr; r->cand_cnt = nullptr;
+    if (side) {                                                      // the re-rank also left the compact candidate lists
+        CandBits lay;
+        cand_bits_layout(lay, h->d_bits.as<uint32_t>(), q, bw);
+        r->cand_list = lay.list; r->cand_cnt = lay.cnt;
+    }
+    r->fail_count = nullptr;
+    return LCD_OK;
 }
-#define LCD_TRY try {
-#define LCD_CATCH(h) } catch (const std::bad_alloc&) { return lcd_catch(h, LCD_ERR_NOMEM, "out of host memory"); } \
-    catch (const std::exception& e__) { return lcd_catch(h, LCD_ERR_STATE, e__.what()); } \
-    catch (...) { return lcd_catch(h, LCD_ERR_STATE, "unexpected exception"); }
 
 extern "C" {
 
@@ -495,7 +414,7 @@ int lcd_create(const lcd_config* cfg, lcd_engine** out) {
     if (cfg->pipeline < 0 || cfg->pipeline > 1) { delete h; return LCD_ERR_INVALID; }
     h->pipeline = cfg->pipeline;
     if (cfg->pipeline) {
-        for (lcd_engine::FrameScratch& sc : h->ring) {
+        for (FramePipeline::FrameScratch& sc : h->pipe.ring) {
             if (e == hipSuccess) e = sc.d_fail_count.reserve(64, 0, h->stream, &h->bytes_device);
             if (e == hipSuccess) e = hipMemsetAsync(sc.d_fail_count.p, 0, 64, h->stream);
             sc.fail_count_clean = true;
@@ -517,7 +436,7 @@ void lcd_destroy(lcd_engine* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->tfidf.destroy();
     h->bayes.destroy();
-    for (lcd_engine::FrameScratch& sc : h->ring) {
+    for (FramePipeline::FrameScratch& sc : h->pipe.ring) {
         DevBuf* all[] = {&sc.d_knn_row, &sc.d_knn_word, &sc.d_knn_dist, &sc.d_selfdist, &sc.d_bits, &sc.d_partial2, &sc.d_partial3, &sc.d_fail_list,
                          &sc.d_fail_count, &sc.d_out_wslot, &sc.d_qsplit, &sc.d_qnorm, &sc.d_applist, &sc.d_cross};
         for (DevBuf* d : all) d->release(&h->bytes_device);
@@ -554,14 +473,14 @@ int lcd_synchronize(lcd_engine* h) {
 
 void* lcd_stream(lcd_engine* h) { return h ? (void*)h->stream : nullptr; }
 
-int lcd_pipeline_depth(const lcd_engine* h) { return (h && h->pipeline) ? 3 : 0; }
+int lcd_pipeline_depth(const lcd_engine* h) { return (h && h->pipeline) ? FramePipeline::DEPTH : 0; }
 
 int lcd_record_event(lcd_engine* h, void* event) {
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     if (!event) return h->fail(LCD_ERR_INVALID, "lcd_record_event: null event");
     LCD_DEV_NODRAIN(h);
-    if (!h->inflight.empty()) { h->inflight.back().events_after.push_back(event); return LCD_OK; }   // recorded behind the stages still owed
+    if (!h->pipe.empty()) { h->pipe.queue_event(event); return LCD_OK; }   // recorded behind the stages still owed
     LCD_HIP(h, hipEventRecord((hipEvent_t)event, h->stream));
     return LCD_OK;
     LCD_CATCH(h)
@@ -691,7 +610,7 @@ int lcd_vocab_remove_unused_async(lcd_engine* h) {
     LCD_DEV_NODRAIN(h);
     // a pipelined handle still owes stages of its latest frames: the clean takes its place behind the newest of them (its registration
     // and the retirements asked for since), like lcd_sig_remove -- nothing is completed, nothing is synchronised
-    if (!h->inflight.empty()) { h->inflight.back().cleans_after += 1; return LCD_OK; }
+    if (!h->pipe.empty()) { h->pipe.queue_clean(); return LCD_OK; }
     return h->enqueue_clean();
     LCD_CATCH(h)
 }
@@ -859,89 +778,6 @@ int lcd_selfdist(lcd_engine* h, const void* queries, int q, float* out_qxq) {
     LCD_CATCH(h)
 }
 
-// device part of addNewWords up to (not including) the decision loop: 2-NN, same-frame distances + candidate bits.
-// Fills the decision loop's arguments.
-static int prepare_resolve(lcd_engine* h, const void* d_desc, int q, int flags, float nndr, int32_t* d_out_word, int32_t* d_out_wslot,
-                           ResolveArgs* r, bool defer_redo = false /* the caller's next launch is the fused frame tail */,
-                           int64_t rows_now = -1 /* rows to scan when the host's count lags the device's (an upper bound: the rows behind the
-                                                    device's count carry row id 0 and are skipped like tombstones) */) {
-    r->rp = RowparArgs{};
-    if (rows_now < 0) rows_now = h->n_rows;
-    const int have_index = h->n_live >= 2 ? 1 : 0;                  // VWDictionary.cpp:1015
-    const bool incremental = (flags & LCD_Q_INCREMENTAL) != 0;
-    const bool together = incremental && (flags & LCD_Q_NEW_WORDS_COMPARED);
-    int ld = (q + 63) / 64 * 64;
-    const int bw = ld / 32;
-    if (together) {
-        LCD_HIP(h, dreserve(h, h->d_selfdist, (size_t)q * ld * 4));
-        LCD_HIP(h, dreserve(h, h->d_bits, cand_bits_bytes(q, bw)));
-    }
-    // With the MFMA filter the same-frame distance matrix does not wait for the 2-NN: extra workgroups of the filter launch
-    // compute it, and the re-rank workgroup of a query -- the first to know the query's second neighbour -- derives the query's
-    // candidate bits from its (symmetric) row: two launches fewer per frame.
-    const int64_t knn_rows = have_index ? rows_now : 0;
-    const bool side = together && h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim) && knn_rows >= 256 && q > 0;
-    int rc;
-    if (side) {
-        CandBits cb;
-        cb.selfdist = h->d_selfdist.as<float>(); cb.ld = ld; cb.nq = q; cb.have_index = have_index;
-        cand_bits_layout(cb, h->d_bits.as<uint32_t>(), q, bw);
-        LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
-        LCD_HIP(h, dreserve(h, h->d_knn_word, (size_t)q * 2 * 4));
-        LCD_HIP(h, dreserve(h, h->d_knn_dist, (size_t)q * 2 * 4));
-        rc = run_knn2_raw(h, d_desc, q, h->vocab.p, h->row_id.as<int32_t>(), knn_rows, true, h->d_knn_row.as<int32_t>(),
-                          h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), &cb, defer_redo ? &r->rp : nullptr);
-        if (rc) return rc;
-    } else if (together && h->dtype == LCD_U8 && q > 0) {
-        // Hamming frames (config 3): the scan, then ONE launch for the merge of its partial keys, the same-frame distance matrix and the candidate
-        // bit rows (round 6: they were two dependent launches of ~5 us each behind the scan)
-        LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
-        LCD_HIP(h, dreserve(h, h->d_knn_word, (size_t)q * 2 * 4));
-        LCD_HIP(h, dreserve(h, h->d_knn_dist, (size_t)q * 2 * 4));
-        const KnnPlan p = knn_plan(q, (int)knn_rows, h->row_bytes);
-        LCD_HIP(h, dreserve(h, h->d_partial, knn_partial_bytes(p)));
-        const bool prof = h->prof_cap > 0 && h->prof_n < h->prof_cap;
-        if (prof) LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n], h->kst));
-        LCD_HIP(h, launch_knn2_partial(h->dtype, h->kdim, h->vocab.p, h->row_id.as<int32_t>(), d_desc, p, h->d_partial.as<uint64_t>(), h->kst));
-        if (prof) { LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n + 1], h->kst)); h->prof_n += 1; h->prof_kernel = "knn2_hamming_kernel"; }
-        LCD_HIP(h, launch_knn2_merge_selfdist_hamming(p, h->d_partial.as<uint64_t>(), h->row_id.as<int32_t>(), h->d_knn_row.as<int32_t>(),
-                                                      h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), d_desc, h->kdim, h->d_selfdist.as<float>(), ld,
-                                                      have_index, h->d_bits.as<uint32_t>(), bw, h->kst));
-        h->knn_launches += 1;
-    } else {
-        rc = run_knn2(h, d_desc, q, h->vocab.p, h->row_id.as<int32_t>(), h->row_wslot.as<int32_t>(), knn_rows, h->d_knn_row, h->d_knn_word,
-                      h->d_knn_dist);
-        if (rc) return rc;
-        if (together)
-            LCD_HIP(h, launch_selfdist(h->dtype, h->kdim, d_desc, q, h->d_selfdist.as<float>(), ld, h->kst, have_index,
-                                       h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), h->d_bits.as<uint32_t>(), bw));
-    }
-    r->q = q;
-    r->flags = (incremental ? LCD_Q_INCREMENTAL : 0) | (together ? LCD_Q_NEW_WORDS_COMPARED : 0);
-    r->nndr = nndr;
-    r->have_index = have_index;
-    r->knn_word = h->d_knn_word.as<int32_t>();
-    r->knn_dist = h->d_knn_dist.as<float>();
-    r->selfdist = together ? h->d_selfdist.as<float>() : nullptr;
-    r->ld = ld;
-    r->cand_bits = together ? h->d_bits.as<uint32_t>() : nullptr;
-    r->bw = bw;
-    r->out_word = d_out_word;
-    r->out_n_new = h->d_n_new.as<int32_t>();
-    r->knn_row = h->d_knn_row.as<int32_t>();
-    r->row_wslot = h->row_wslot.as<int32_t>();
-    r->out_wslot = d_out_wslot;
-    r->new_ws = WsRuns();
-    r->cand_list = nullptr; r->cand_cnt = nullptr;
-    if (side) {                                                      // the re-rank also left the compact candidate lists
-        CandBits lay;
-        cand_bits_layout(lay, h->d_bits.as<uint32_t>(), q, bw);
-        r->cand_list = lay.list; r->cand_cnt = lay.cnt;
-    }
-    r->fail_count = nullptr;
-    return LCD_OK;
-}
-
 // device part of addNewWords: d_queries already holds q descriptors.  Leaves d_out_word[q], d_n_new[1].
 static int quantize_dev(lcd_engine* h, const void* d_desc, int q, int flags, float nndr, int32_t* d_out_word, int32_t* d_out_wslot = nullptr) {
     ResolveArgs r;
@@ -1076,15 +912,11 @@ int lcd_sig_remove(lcd_engine* h, int32_t sig_id) {
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV_NODRAIN(h);
-    if (!h->inflight.empty()) {
+    if (!h->pipe.empty()) {
         // a pipelined handle still owes stages of its latest frames: the retirement takes its place behind the newest of them
-        bool known = h->tfidf.sig_slot.count(sig_id) != 0, queued = false;
-        for (const lcd_engine::InFlight& f : h->inflight) {
-            if (f.a.sig_id != 0 && f.a.sig_id == sig_id) known = true;
-            if (std::find(f.retire_after.begin(), f.retire_after.end(), sig_id) != f.retire_after.end()) queued = true;
-        }
-        if (!known || queued) return h->fail(LCD_ERR_STATE, "lcd_sig_remove: unknown signature");
-        h->inflight.back().retire_after.push_back(sig_id);
+        const bool known = h->tfidf.sig_slot.count(sig_id) != 0 || h->pipe.registers(sig_id);
+        if (!known || h->pipe.retirement_queued(sig_id)) return h->fail(LCD_ERR_STATE, "lcd_sig_remove: unknown signature");
+        h->pipe.queue_retire(sig_id);
         return LCD_OK;
     }
     if (!h->tfidf.sig_slot.count(sig_id)) return h->fail(LCD_ERR_STATE, "lcd_sig_remove: unknown signature");
@@ -1179,557 +1011,6 @@ int lcd_adjust_likelihood_dev(lcd_engine* h, float* d_likelihood, int n, float v
     LCD_CATCH(h)
 }
 
-// ------------------------------------------------------------------------------------------------ device-resident frame
-namespace {
-struct FrameHostTimer {   // host time spent inside lcd_frame_dev (lcd_stats.frame_host_ns)
-    lcd_engine* h; std::chrono::steady_clock::time_point t0;
-    explicit FrameHostTimer(lcd_engine* e) : h(e), t0(std::chrono::steady_clock::now()) {}
-    ~FrameHostTimer() { h->frame_host_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); h->frame_calls += 1; }
-};
-}  // namespace
-
-// the index stage of a frame, launched on its own: registration (or query preparation), scoring, hypothesis
-// Rtabmap::adjustLikelihood + the best candidate (Rtabmap.cpp:2121-2158), then the Bayes filter's update and its highest
-// hypothesis (Rtabmap.cpp:2133-2158), without any vector leaving the device.  The frame's likelihood is already enqueued.
-static int hypothesis_stage(lcd_engine* h, const lcd_frame_args& a) {
-    Tfidf& t = h->tfidf;
-    const bool bayes = a.d_posterior || a.d_bayes;
-    if (!(a.d_hypothesis || a.d_adjusted || bayes)) return LCD_OK;
-    const long long n_cons = (long long)t.n_slots - std::max(a.exclude_recent, 0);
-    DecideArgs d;
-    d.like = a.d_likelihood; d.ratio = a.virtual_place_ratio; d.adj_out = a.d_adjusted; d.hyp = (HypothesisOut*)a.d_hypothesis;
-    d.bayes = bayes; d.d_posterior = a.d_posterior; d.d_bayes = (BayesOut*)a.d_bayes;
-    LCD_HIP(h, h->bayes.decide(d, t.slot_sig.as<int32_t>(), t.n_slots, n_cons));
-    return LCD_OK;
-}
-
-// likelihood + decision stage of a frame whose registration (or query preparation) has just been enqueued stand-alone
-static int frame_score_s(lcd_engine* h, const lcd_frame_args& a) {
-    Tfidf& t = h->tfidf;
-    if (!a.d_likelihood) return LCD_OK;
-    if (h->prof_cap > 0 && h->prof2_n < h->prof_cap) {
-        t.prof_b = h->prof2_ev[2 * h->prof2_n]; t.prof_e = h->prof2_ev[2 * h->prof2_n + 1];
-        h->prof2_n += 1;
-        h->prof2_kernel = "score_kernel";
-    }
-    LCD_HIP(h, t.score(a.d_likelihood));
-    if (t.prof_b) { t.prof_b = t.prof_e = nullptr; h->prof2_n -= 1; }     // the launch that would have been bracketed did not happen
-    h->likelihood_launches += 1;
-    return hypothesis_stage(h, a);
-}
-
-// (any descriptor type: rows that are not 64 floats are copied without the matrix-core filter's tables -- such handles are never pipelined)
-static bool frame_appends(const lcd_engine* h, const lcd_frame_args& a) {
-    return a.append_new_words != 0 && (a.first_new_word_id > 0 || a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO) && (a.flags & LCD_Q_INCREMENTAL) != 0 &&
-           h->row_bytes == h->dim * (h->dtype == LCD_F32 ? 4 : 1);     // (rows are stored as they arrive: no padding to add on the device)
-}
-
-// Who numbers the words this frame creates.  LCD_NEW_WORD_IDS_AUTO: the device, id = row + id_delta -- exact as long as every unreconciled appender is
-// numbered that way (one new word = one row = one id), so a change of mode completes what is owed first; id_delta is set while the host's row
-// mirror is current.
-static int id_window(lcd_engine* h, const lcd_frame_args& a) {
-    const bool is_auto = a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO;
-    if (a.first_new_word_id < 0 && !is_auto) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: first_new_word_id");
-    if (is_auto && !frame_appends(h, a))
-        return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: LCD_NEW_WORD_IDS_AUTO needs append_new_words on an incremental dictionary of unpadded rows");
-    if (!frame_appends(h, a)) return LCD_OK;
-    if (!h->applog.unreconciled.empty() && h->applog.auto_window != is_auto) { int rc = h->drain(); if (rc) return rc; }
-    if (h->applog.unreconciled.empty()) {
-        h->applog.auto_window = is_auto;
-        if (is_auto) {
-            const int64_t d = (int64_t)h->mirror.next_word_id - h->n_rows;
-            if (d < 1 || d >= (1ll << 28)) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: next_word_id lies below the ids the vocabulary holds (lcd_set_option \"next_word_id\")");
-            h->applog.id_delta = (int32_t)d;
-        }
-    }
-    return LCD_OK;
-}
-
-static int reserve_frame_words(lcd_engine* h, const lcd_frame_args& a, WsRuns* runs, bool may_flush = true) {
-    *runs = WsRuns();
-    // postings keys for the words this frame may create (VisualWord(id, descriptor, signatureId) references the signature; a word that
-    // becomes a vocabulary row on the device needs its key there as well)
-    if ((a.sig_id != 0 || frame_appends(h, a)) && (a.first_new_word_id > 0 || (a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO && frame_appends(h, a))) && (a.flags & LCD_Q_INCREMENTAL)) {
-        hipError_t e = h->tfidf.reserve_new_words(a.first_new_word_id, a.q, runs, may_flush);
-        if (e == hipErrorInvalidValue) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_dev: word ids must be below 2^28");
-        LCD_HIP(h, e);
-    }
-    return LCD_OK;
-}
-
-// the whole index stage of a frame, launched on its own: decision loop + registration (one workgroup), scoring, decision stage
-// chained / vseq: the frame's place in the device row-count chain (a frame that takes part appends its new words, or hands the count on)
-static int frame_stage_s(lcd_engine* h, const lcd_frame_args& a, ResolveArgs r, bool chained = false, uint64_t vseq = 0) {
-    Tfidf& t = h->tfidf;
-    const int q = a.q;
-    if (a.sig_id != 0 && t.sig_slot.count(a.sig_id)) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: signature already registered");
-    const int64_t slots_after = t.n_slots + (a.sig_id != 0 ? 1 : 0);
-    if (a.d_likelihood && a.likelihood_capacity < slots_after) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: likelihood buffer too small");
-    { int rc = reserve_frame_words(h, a, &r.new_ws); if (rc) return rc; }
-    if (chained) fill_append(h, a, vseq, frame_appends(h, a), &r); else r.ap = AppendArgs();
-    if (a.sig_id != 0) LCD_HIP(h, t.register_dev(a.sig_id, r.out_wslot, q, q, a.N, &r));
-    else LCD_HIP(h, t.query_dev(r.out_wslot, q, a.N, &r));
-    return frame_score_s(h, a);
-}
-
-// the same for a frame whose decision loop has already run (it left the word slots in r.out_wslot, new words as codes)
-static int frame_stage_reg_s(lcd_engine* h, const lcd_frame_args& a, const ResolveArgs& r) {
-    Tfidf& t = h->tfidf;
-    if (a.sig_id != 0 && t.sig_slot.count(a.sig_id)) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: signature already registered");
-    if (a.sig_id != 0) LCD_HIP(h, t.register_dev(a.sig_id, r.out_wslot, a.q, a.q, a.N));
-    else LCD_HIP(h, t.query_dev(r.out_wslot, a.q, a.N));
-    return frame_score_s(h, a);
-}
-
-// the calls made while `f` was the newest frame of a pipelined handle, in call order, once every stage of `f` is enqueued
-static int finish_frame_ops(lcd_engine* h, lcd_engine::InFlight& f) {
-    for (int32_t sig : f.retire_after) LCD_HIP(h, h->tfidf.retire(sig));
-    f.retire_after.clear();
-    for (const lcd_engine::DeferredLink& dl : f.links_after) {
-        LCD_HIP(h, h->bayes.ensure(std::max<int64_t>(h->tfidf.n_slots, 1)));
-        const hipError_t e = h->bayes.link(dl.triples, dl.restart);
-        if (e == hipErrorInvalidValue) { f.links_after.clear(); return h->fail(LCD_ERR_UNSUPPORTED, "lcd_bayes_set_neighbors: a neighbour list longer than 8192 entries"); }
-        LCD_HIP(h, e);
-    }
-    f.links_after.clear();
-    if (f.cleans_after > 0) { f.cleans_after = 0; h->clean_armed = true; }   // runs behind the next launch pair (pipeline_launch) or the drain
-    for (void* ev : f.events_after) LCD_HIP(h, hipEventRecord((hipEvent_t)ev, h->stream));
-    f.events_after.clear();
-    return LCD_OK;
-}
-
-static int pipeline_launch(lcd_engine* h, const QSplitArgs* qs);
-struct HostLap {   // section timer of the pipelined frame's host path (host_prof)
-    lcd_engine* h; std::chrono::steady_clock::time_point t;
-    explicit HostLap(lcd_engine* e) : h(e), t(std::chrono::steady_clock::now()) {}
-    void lap(int i) { const auto n = std::chrono::steady_clock::now(); h->host_prof[i] += std::chrono::duration_cast<std::chrono::nanoseconds>(n - t).count(); t = n; }
-};
-
-int lcd_engine::drain(bool rows) {
-    int rc_all = LCD_OK;
-    Range range__(inflight.empty() ? nullptr : this, "lcd:drain");
-    while (!inflight.empty()) {                                      // three fused launch pairs complete what is owed, oldest first
-        const size_t before = inflight.size();
-        const int stage_front = inflight.front().stage;
-        const int rc = pipeline_launch(this, nullptr);
-        if (rc && !rc_all) rc_all = rc;
-        if (rc && inflight.size() == before && inflight.front().stage == stage_front) {   // no progress: drop the frame instead of spinning
-            InFlight f = std::move(inflight.front());
-            inflight.pop_front();
-            (void)finish_frame_ops(this, f);
-        }
-    }
-    if (clean_armed) { clean_armed = false; const int rc = enqueue_clean(); if (rc && !rc_all) rc_all = rc; }
-    const int rc3 = rows ? reconcile() : LCD_OK;                     // rows appended on the device: the host mirror catches up
-    return rc_all ? rc_all : rc3;
-}
-
-// The 2-NN stage of an in-flight frame, planned when its filter is about to be launched (the row count may have grown since the frame was
-// submitted): scratch of the frame's ring set, launch plan, and the arguments its decision loop will need one launch later.
-// f_sh: the frame whose decision loop rides in the same launch A and whose shadow rows this filter ranks (NULL: none)
-static int build_knn(lcd_engine* h, lcd_engine::InFlight& f, PipeKnn* kp, const lcd_engine::InFlight* f_sh) {
-    PipeKnn& k = *kp;
-    const lcd_frame_args& a = f.a;
-    const int q = a.q;
-    lcd_engine::FrameScratch& sc = h->ring[f.set];
-    const bool incremental = (a.flags & LCD_Q_INCREMENTAL) != 0;
-    const bool together = incremental && (a.flags & LCD_Q_NEW_WORDS_COMPARED);
-    const int ld = (q + 63) / 64 * 64, bw = ld / 32;
-    const int64_t rows_bound = f.chained ? h->applog.rows_ub(h->n_rows) : h->n_rows;   // a true upper bound: the exact redo and the buffers are sized for it
-    const int64_t plan_rows = f.chained ? h->applog.rows_plan(f.vseq, h->n_rows) : h->n_rows;
-    if (plan_rows > 0x7FFFFFF0ll) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_dev: more than 2^31 rows");
-    // The distance tiles get compute units of their own (a tile that shares one with a strip takes twice as long, and so does the
-    // strip); the two tail workgroups do not: a filter workgroup holds 66 KB of LDS, so two of the launch's workgroups can share a
-    // compute unit, and one strip less per workgroup is worth more than the two shared units (49 000 words x 500 descriptors:
-    // 219 seven-tile strips + 36 tiles + 2 = 257 workgroups, frame 31.6 us; 192 eight-tile strips 32.1; 256 six-tile strips 34.5).
-    k.plan = knn_bf16_plan_pipelined(q, (int)plan_rows, together ? knn_selfdist_wgs(q) : 0, h->filter_units);
-    k.plan.f16 = h->f16();
-    if (h->strip_tiles > 0 && plan_rows > 0) {                       // timing experiments: a fixed strip length, one workgroup per strip
-        const int n_tiles = (int)((plan_rows + 31) / 32);
-        k.plan.tiles_per_block = h->strip_tiles; k.plan.n_blocks = (n_tiles + h->strip_tiles - 1) / h->strip_tiles; k.plan.one_strip = 1;
-        k.plan.f16 = h->f16();
-    }
-    if (f_sh && !knn_bf16_persistent(k.plan) && plan_rows < (int64_t)SHADOW_ROW_BASE) {
-        const lcd_engine::FrameScratch& ss = h->ring[f_sh->set];
-        k.plan.n_shadow = 1;
-        k.sh_bf = ss.d_shadow_bf.p; k.sh_norm = ss.d_shadow_norm.as<float>(); k.sh_rows = (f_sh->a.q + 63) / 64 * 64;
-        k.sh_mask = ss.d_newmask.as<uint32_t>(); k.sh_q = f_sh->a.q;
-        k.sh_ld = k.sh_rows;
-        LCD_HIP(h, ring_reserve(h, f.set, &lcd_engine::FrameScratch::d_cross, (size_t)q * k.sh_ld * 4));   // (the buffer the cross-frame tiles use: never both)
-        k.sh_x = sc.d_cross.as<float>();
-    }
-    {   // the candidate records: sized for this plan AND for the one the upper bound would get (a growing vocabulary crosses the planner's
-        // thresholds: a reallocation drains the stream)
-        // ... and, when that takes an allocation, for a vocabulary half as large again: a set that outgrows its buffers while frames are in flight reallocates
-        // behind a synchronisation of the stream, and so does each of the other sets when its turn comes -- four stalls of ~0.24 ms in a row where
-        // 125 000 rows happen to fill their allocation (profiles/dead_ends_r06.txt 15)
-        size_t bytes = knn_bf16_partial_bytes(k.plan), want = 0;
-        if (f.chained) {
-            bytes = std::max(bytes, knn_bf16_partial_bytes(knn_bf16_plan_pipelined(q, (int)(rows_bound + 8 * (int64_t)q), together ? knn_selfdist_wgs(q) : 0, h->filter_units)));
-            want = knn_bf16_partial_bytes(knn_bf16_plan_pipelined(q, (int)std::min<int64_t>(rows_bound + rows_bound / 2 + 65536, 0x7FFFFF00ll), together ? knn_selfdist_wgs(q) : 0, h->filter_units));
-        }
-        LCD_HIP(h, ring_reserve_grow(h, f.set, &lcd_engine::FrameScratch::d_partial2, bytes, want));
-    }
-    {
-        const int64_t rows3 = rows_bound + (f.chained ? 8 * (int64_t)q : 0);
-        LCD_HIP(h, ring_reserve_grow(h, f.set, &lcd_engine::FrameScratch::d_partial3, knn_rowpar_partial_bytes((int)rows3, q),
-                                     f.chained ? knn_rowpar_partial_bytes((int)std::min<int64_t>(rows3 + rows3 / 2 + 65536, 0x7FFFFF00ll), q) : 0));
-    }
-    k.vocab = h->vocab.p; k.vocab_bf = h->vocab_bf.p; k.row_norm = h->row_norm.as<float>(); k.norm_max_bits = h->norm_max.as<uint32_t>();
-    k.row_id = h->row_id.as<int32_t>(); k.queries = a.d_descriptors; k.partial = sc.d_partial2.p;
-    k.qsplit = sc.d_qsplit.p; k.qnorm = sc.d_qnorm.as<float>();
-    k.out_row = sc.d_knn_row.as<int32_t>(); k.out_word = sc.d_knn_word.as<int32_t>(); k.out_dist = sc.d_knn_dist.as<float>();
-    k.fail_list = sc.d_fail_list.as<int32_t>(); k.fail_count = sc.d_fail_count.as<int32_t>();
-    k.n_lo = nullptr; k.n_hi = nullptr;
-    if (f.chained) { k.n_lo = h->applog.count_after(f.vseq); k.n_hi = h->applog.count_before(f.vseq); }
-    k.cb = CandBits();
-    if (together) { k.cb.selfdist = sc.d_selfdist.as<float>(); k.cb.ld = ld; k.cb.nq = q; k.cb.have_index = 1; cand_bits_layout(k.cb, sc.d_bits.as<uint32_t>(), q, bw); }
-    if (!sc.fail_count_clean) LCD_HIP(h, hipMemsetAsync(sc.d_fail_count.p, 0, 8, h->stream));
-    sc.fail_count_clean = true;                                      // the frame's decision loop (a later launch A) resets the counters
-    h->last_fail_count = sc.d_fail_count.p;
-    // ---- the decision loop's arguments (launched one call later), the redo of rejected queries riding with it
-    ResolveArgs& r = f.r;
-    r = ResolveArgs();
-    r.q = q; r.flags = (incremental ? LCD_Q_INCREMENTAL : 0) | (together ? LCD_Q_NEW_WORDS_COMPARED : 0); r.nndr = a.nndr_ratio; r.have_index = 1;
-    r.knn_word = k.out_word; r.knn_dist = k.out_dist; r.selfdist = together ? sc.d_selfdist.as<float>() : nullptr; r.ld = ld;
-    r.cand_bits = together ? sc.d_bits.as<uint32_t>() : nullptr; r.bw = bw; r.out_word = a.d_word_ids; r.out_n_new = h->d_n_new.as<int32_t>();
-    r.cand_list = together ? k.cb.list : nullptr; r.cand_cnt = together ? k.cb.cnt : nullptr;
-    r.knn_row = k.out_row; r.row_wslot = h->row_wslot.as<int32_t>(); r.out_wslot = sc.d_out_wslot.as<int32_t>(); r.new_ws = WsRuns();
-    r.fail_count = sc.d_fail_count.as<int32_t>();
-    RowparArgs& rp = r.rp;
-    rp.enabled = 1; rp.vocab = (const float*)h->vocab.p; rp.row_id = h->row_id.as<int32_t>(); rp.n_rows = (int)rows_bound;
-    rp.n_rows_dev = k.n_hi;                                          // the rows that exist when the redo runs: after the previous frame's append
-    rp.queries = (const float*)a.d_descriptors; rp.fail_list = sc.d_fail_list.as<int32_t>(); rp.partial = (unsigned long long*)sc.d_partial3.p;
-    rp.out_row = k.out_row; rp.out_word = k.out_word; rp.out_dist = k.out_dist;
-    if (together) rp.cb = k.cb;
-    return LCD_OK;
-}
-
-// One pair of fused launches of a pipelined handle.  With frame t the newest:
-//   A = queries of frame t pre-split into matrix-core operands  +  filter (+ same-frame distance tiles) of frame t-1
-//       + decision loop of frame t-2 (+ its redo helpers, + the append of its new words)  +  retirement / registration of frame t-3
-//   B = re-rank of frame t-1  +  scoring of frame t-3   (then the decision stage of frame t-3 and the calls queued behind it)
-// qs == NULL: nothing new -- drain() advances what is in flight with the same fused launches.
-static int pipeline_launch(lcd_engine* h, const QSplitArgs* qs) {
-    Tfidf& t = h->tfidf;
-    lcd_engine::InFlight* f_reg = nullptr; lcd_engine::InFlight* f_res = nullptr; lcd_engine::InFlight* f_knn = nullptr;
-    for (lcd_engine::InFlight& f : h->inflight) {
-        if (f.stage == 2 && !f_reg) f_reg = &f;
-        else if (f.stage == 1 && !f_res) f_res = &f;
-        else if (f.stage == 0 && !f_knn) f_knn = &f;
-    }
-    TailLaunch tl_reg, tl_res; ScoreArgs sa; int score_wgs = 0;
-    bool reg_like = false;
-    HostLap lap(h);
-    if (f_res) {
-        // FIRST, before any launch argument is built: the reservation may move the word-indexed tables (they double when the keys run
-        // out -- every ~3 000 frames at 150 new words per frame), and the registration / scoring arguments below hold pointers into
-        // them.  The postings keys of the words that frame may create are reserved now (the batched check of older reservations waits until
-        // launch A is enqueued: the registration that rides in it may still use some of those keys)
-        { int rc = reserve_frame_words(h, f_res->a, &f_res->runs, false); if (rc) return rc; }
-        f_res->reserved = true;
-        tl_res.r = f_res->r;
-        tl_res.r.new_ws = f_res->runs;
-        refresh_vocab_ptrs(h, &tl_res.r);
-        // (rows instead of postings keys in out_wslot: NULL is the decision loop's "knn_row already holds the word slot"; the registration translates)
-        // (built-in: only while the stream creates words, like the shadow scores -- the gather leaves the decision loop's chain for the registration's, and once frames
-        // revisit, the decision loop is short and the registration is what ends launch A: 13.8 -> 14.5 us in the revisit phase with the rows always on, r06_ab_notes.txt 10)
-        f_res->slots_are_rows = h->popt.slots_from_rows && (h->popt.slots_from_rows >= 2 || h->applog.est_new >= 16.0) && tl_res.r.row_wslot && tl_res.r.knn_row && tl_res.r.q <= 1024;
-        if (f_res->slots_are_rows) { tl_res.r.row_wslot = nullptr; tl_res.r.slots_are_rows = 1; }
-        tl_res.r.straight = (h->popt.decision_straight >= 2 || (h->popt.decision_straight == 1 && h->applog.est_new >= 16.0)) ? 1 : 0;
-        if (f_res->chained) fill_append(h, f_res->a, f_res->vseq, frame_appends(h, f_res->a), &tl_res.r, h->ring[f_res->set].d_applist.as<uint32_t>());
-        // the pinned row-count mirror is a store to HOST memory, waited for at the end of the decision loop's chain: with "mirror_from_b" a
-        // workgroup of launch B of this pair (which writes the frame's rows anyway) stores it instead
-        if (h->popt.mirror_from_b && tl_res.r.ap.enabled && tl_res.r.ap.defer_rows) tl_res.r.ap.mirror_later = 1;
-        resolve_launch_info(tl_res.r, pipe_block_size(), &tl_res.n_redo, &tl_res.shmem_resolve);
-    }
-    lap.lap(2);
-    if (f_reg) {
-        const lcd_frame_args& pa = f_reg->a;
-        if (pa.sig_id != 0) LCD_HIP(h, t.register_dev(pa.sig_id, f_reg->r.out_wslot, pa.q, pa.q, pa.N, nullptr, false, &tl_reg));
-        else LCD_HIP(h, t.query_dev(f_reg->r.out_wslot, pa.q, pa.N, nullptr, false, &tl_reg));
-        if (f_reg->slots_are_rows) tl_reg.a.row_wslot = h->row_wslot.as<int32_t>();
-        if (pa.d_likelihood) {
-            LCD_HIP(h, t.score_args(pa.d_likelihood, nullptr, pipe_b_block_size(), &sa, &score_wgs));
-            reg_like = true;
-            h->likelihood_launches += 1;
-        }
-    }
-    lap.lap(3);
-    PipeKnn k;
-    // shadow rows: f_res's new words are not rows when f_knn's filter runs (its decision loop rides in the same launch) -- the filter ranks f_res's
-    // descriptors from the operand rows its query pre-split left, the re-rank keeps the ones the mask f_res's decision loop publishes names
-    const bool sh_ok = f_knn && f_res && f_res->has_shadow && f_res->chained && f_knn->chained && tl_res.r.ap.enabled && tl_res.r.ap.defer_rows && tl_res.r.ap.is_f32_64 &&
-                       h->popt.shadow_rows && !h->popt.cross_frames && h->popt.append_from_rerank;
-    if (f_knn) { int rc = build_knn(h, *f_knn, &k, sh_ok ? f_res : nullptr); if (rc) return rc; h->knn_launches += 1; }
-    if (f_res && f_res->has_shadow && tl_res.r.ap.enabled && tl_res.r.ap.defer_rows) tl_res.r.ap.mask_out = h->ring[f_res->set].d_newmask.as<uint32_t>();
-    if (f_knn && f_res && tl_res.r.ap.enabled && tl_res.r.ap.defer_rows && tl_res.r.ap.is_f32_64 && h->popt.cross_frames) {
-        // The rows f_res appends (its decision loop rides in this launch A) are descriptors of f_res, and f_knn's re-rank (this launch B)
-        // must scan them exactly: extra distance tiles of launch A compute f_knn x f_res in the reference's arithmetic, the re-rank reads
-        // its pending rows' distances there instead of staging the rows (the buffer was sized when f_knn was submitted: no reallocation here)
-        const int ncols = f_res->a.q, ldx = (ncols + 63) / 64 * 64;
-        lcd::DevBuf& xb = h->ring[f_knn->set].d_cross;
-        if (ncols > 0 && f_knn->a.q > 0 && xb.cap >= (size_t)f_knn->a.q * ldx * 4) {
-            k.cross = xb.as<float>(); k.cross_ld = ldx; k.cross_cols = tl_res.r.ap.descriptors; k.cross_ncols = ncols;
-        }
-    }
-    lap.lap(4);
-    bool prof = f_knn && h->prof_cap > 0 && h->prof_n < h->prof_cap;
-    if (prof && h->prof_skip > 0) { h->prof_skip -= 1; prof = false; }     // ("profile_skip": not the first launches behind an idle queue)
-    h->popt.f16 = h->f16();
-    if (h->roctx_push) h->roctx_push("lcd:launch_A");
-    const hipError_t ea__ = launch_frame_a(f_knn ? &k : nullptr, qs, f_res ? &tl_res : nullptr, f_reg ? &tl_reg : nullptr, h->stream,
-                              prof ? h->prof_ev[2 * h->prof_n] : nullptr, prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr, h->popt);
-    if (h->roctx_pop) h->roctx_pop();
-    LCD_HIP(h, ea__);
-    if (prof) {
-        h->prof_n += 1;
-        if (h->f16())
-            h->prof_kernel = knn_bf16_persistent(k.plan) ? "frame_a_kernel_p (persistent fp16 filter of frame t-1 + query pre-split of t + decision loop of t-2 + registration of t-3)"
-                                                         : "frame_a_kernel (fp16 filter of frame t-1 + query pre-split of t + decision loop of t-2 + registration of t-3)";
-        else
-            h->prof_kernel = knn_bf16_persistent(k.plan) ? "frame_a_kernel_p (persistent bf16 filter of frame t-1 + query pre-split of t + decision loop of t-2 + registration of t-3)"
-                                                         : "frame_a_kernel (bf16 filter of frame t-1 + query pre-split of t + decision loop of t-2 + registration of t-3)";
-    }
-    lap.lap(5);
-    const bool prof2 = f_knn && reg_like && h->prof_likelihood && h->prof_cap > 0 && h->prof2_n < h->prof_cap;
-    AppendRowsArgs app;
-    if (f_res && tl_res.r.ap.enabled && tl_res.r.ap.defer_rows) { app.ap = tl_res.r.ap; app.new_ws = tl_res.r.new_ws; }
-    if (h->roctx_push) h->roctx_push("lcd:launch_B");
-    const hipError_t eb__ = launch_frame_b(f_knn ? &k : nullptr, reg_like ? &sa : nullptr, score_wgs, h->stream, prof2 ? h->prof2_ev[2 * h->prof2_n] : nullptr,
-                                           prof2 ? h->prof2_ev[2 * h->prof2_n + 1] : nullptr, app.ap.enabled ? &app : nullptr, h->popt);
-    if (h->roctx_pop) h->roctx_pop();
-    LCD_HIP(h, eb__);
-    lap.lap(6);
-    LCD_HIP(h, t.flush_held_if_due());                               // (behind launch B: the rows it writes claim their postings keys there)
-    if (prof2) { h->prof2_n += 1; h->prof2_kernel = "frame_b_kernel (re-rank of frame t-1 + scoring of frame t-3)"; }
-    if (h->clean_armed && f_reg) {
-        // cleanUnusedWords asked for behind an earlier frame: the retirements made in front of it rode with the registration of this
-        // launch A, the reference counts are what Memory::preUpdate would see -- one kernel, between this launch B and the next launch A
-        // f_res's decision loop ran in this launch A and its new words are rows since this launch B, but they get their first reference
-        // with its registration, in the NEXT launch A: the clean stops at the count f_res started from (the counter it read, untouched
-        // until the next decision loop writes it) -- addNewWords references a word as it creates it, cleanUnusedWords never sees one
-        h->clean_armed = false;
-        const int32_t* reg_cnt = f_res && f_res->chained ? h->applog.count_before(f_res->vseq) : nullptr;
-        int rc = h->enqueue_clean(reg_cnt); if (rc) return rc;        // (flushes what more than four retirements per frame left over)
-    }
-    if (f_res) f_res->stage = 2;
-    if (f_knn) f_knn->stage = 1;
-    if (f_reg) {                                                     // that frame is complete: its decision stage and the calls queued behind it
-        lcd_engine::InFlight done = std::move(*f_reg);
-        h->inflight.pop_front();                                     // (f_reg is the oldest entry: stages advance in order)
-        if (done.a.d_likelihood) { int rc = hypothesis_stage(h, done.a); if (rc) return rc; }
-        int rc = finish_frame_ops(h, done);
-        if (rc) return rc;
-    }
-    lap.lap(7);
-    return LCD_OK;
-}
-
-// Pipelined handle, matrix-core 2-NN (knn_mfma_kernels.hip, frame_a_kernel / frame_b_kernel): four frames are in flight.  The call for
-// frame t pre-splits its queries and carries one stage of each of the three frames before it (pipeline_launch); what the frames still
-// owe afterwards waits in h->inflight.
-static int frame_pipelined(lcd_engine* h, const lcd_frame_args* a) {
-    Tfidf& t = h->tfidf;
-    const int q = a->q;
-    HostLap lap0(h);
-    h->host_prof[8] += 1;
-    // validate against the index as it will be once the owed stages have run
-    int64_t owed_slots = 0;
-    for (const lcd_engine::InFlight& f : h->inflight) {
-        if (f.a.sig_id == 0) continue;
-        if (f.a.sig_id == a->sig_id) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: signature already registered");
-        owed_slots += 1;
-    }
-    if (a->sig_id != 0 && t.sig_slot.count(a->sig_id)) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: signature already registered");
-    const int64_t slots_after = t.n_slots + owed_slots + (a->sig_id != 0 ? 1 : 0);
-    if (a->d_likelihood && a->likelihood_capacity < slots_after) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: likelihood buffer too small");
-    // (a stream that never completes anything catches up every 512 frames with removals pending: three fused launch pairs, ~0.2 us per frame)
-    if (h->rm_pending) h->frames_since_reconcile += 1;
-    if (h->applog.must_reconcile(h->rm_pending, h->frames_since_reconcile)) { int rc = h->drain(); if (rc) return rc; }
-    { int rc = id_window(h, *a); if (rc) return rc; }
-    // rows appended on the device: the counters take over the row count, the buffers keep room for the words of the frames in flight
-    const bool app = frame_appends(h, *a);
-    if (app) LCD_HIP(h, h->applog.activate(h->n_rows, h->stream, &h->bytes_device));
-    const bool chained = h->applog.vcnt_active;
-    // The launches are planned for an upper bound of the row count: what the newest FINISHED appender reported + q per younger frame.  A
-    // caller that enqueues frames much faster than the device runs them would inflate that bound without limit (the filter would scan
-    // mostly empty rows): such a caller waits here until the device is at most 8 frames behind.
-    if (chained) {
-        LCD_HIP(h, h->applog.throttle(h->stream));
-        int rc = ensure_append_capacity(h, h->applog.rows_ub(h->n_rows) + 3 * (int64_t)q); if (rc) return rc;
-    }
-    const int set = (int)(h->frame_seq % lcd_engine::PIPE_SETS);
-    lcd_engine::FrameScratch& sc = h->ring[set];
-    const bool incremental = (a->flags & LCD_Q_INCREMENTAL) != 0;
-    const bool together = incremental && (a->flags & LCD_Q_NEW_WORDS_COMPARED);
-    const int ld = (q + 63) / 64 * 64, bw = ld / 32;
-    lap0.lap(0);
-    // ---- the frame's scratch set (what does not depend on the launch plan; the partial keys are sized when the filter is planned)
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_qsplit, knn_qsplit_bytes(q)));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_qnorm, (size_t)ld * 4));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_fail_list, (size_t)q * 4));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_knn_row, (size_t)q * 2 * 4));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_knn_word, (size_t)q * 2 * 4));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_knn_dist, (size_t)q * 2 * 4));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_out_wslot, (size_t)q * 4));
-    LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_applist, (size_t)std::max(q, 512) * 4));   // (the re-rank reads 512 entries unconditionally)
-    if (together) {
-        LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_selfdist, (size_t)q * ld * 4));
-        LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_bits, cand_bits_bytes(q, bw)));
-    }
-    if (chained && !h->inflight.empty() && h->dtype == LCD_F32 && h->kdim == 64 && (h->popt.cross_frames || h->popt.shadow_rows))   // (pipeline_launch: this frame x the frame before it)
-        LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_cross, (size_t)q * ((h->inflight.back().a.q + 63) / 64 * 64) * 4));
-    // shadow rows: a frame that appends on the device leaves its descriptors as operand-table rows too, for the filter of the frame behind it
-    // (built-in: only while the stream creates words -- the scores cost launch A ~1 us (16 more workgroups, the pre-split's extra stores) and buy launch B
-    // ~3.5 us per frame whose predecessor appended ~150 rows, nothing when it appended none; est_new is the decaying maximum of rows per appending frame
-    // that the launch plans already keep.  "shadow_rows" = 2: always)
-    const bool with_shadow = chained && app && h->popt.shadow_rows && h->dtype == LCD_F32 && h->kdim == 64 && q <= 4096 &&
-                             (h->popt.shadow_rows >= 2 || h->applog.est_new >= 16.0);
-    if (with_shadow) {
-        LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_shadow_bf, (size_t)ld * 256));
-        LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_shadow_norm, (size_t)(ld + 1) * 8));
-        LCD_HIP(h, ring_reserve(h, set, &lcd_engine::FrameScratch::d_newmask, (size_t)(2 * (ld / 32) + 4) * 4));
-    }
-    QSplitArgs qs;
-    qs.queries = (const float*)a->d_descriptors; qs.nq = q; qs.qpad = ld; qs.qsplit = (uint4*)sc.d_qsplit.p; qs.qnorm = sc.d_qnorm.as<float>(); qs.n_wgs = 0; qs.f16 = h->f16();
-    if (with_shadow) { qs.shadow_bf = sc.d_shadow_bf.as<uint32_t>(); qs.shadow_norm = sc.d_shadow_norm.as<float>(); qs.norm_max_bits = h->norm_max.as<uint32_t>(); }
-    lap0.lap(1);
-    // ---- what the frames in flight owe rides with this frame's launches
-    { int rc = pipeline_launch(h, &qs); if (rc) return rc; }
-    // ---- this frame's filter, re-rank, decision loop, registration and scoring are owed from here on
-    lcd_engine::InFlight nf;
-    nf.a = *a; nf.set = set; nf.stage = 0; nf.chained = chained; nf.has_shadow = with_shadow;
-    if (chained) nf.vseq = h->applog.record(a->first_new_word_id, q, app);
-    h->inflight.push_back(std::move(nf));
-    h->frame_seq += 1;
-    return LCD_OK;
-}
-
-static int frame_dev_body(lcd_engine* h, const lcd_frame_args* a);
-
-int lcd_frame_dev(lcd_engine* h, const lcd_frame_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    FrameHostTimer timer__(h);
-    lcd_engine::Range range__(h, "lcd_frame_dev");
-    LCD_DEV_NODRAIN(h);
-    return frame_dev_body(h, a);
-    LCD_CATCH(h)
-}
-
-// where the host time of the pipelined lcd_frame_dev calls went so far (engine.h: host_prof): out9[0..7] ns per section, out9[8] calls.  Not part of lcd.h.
-int lcd_debug_host_profile(const lcd_engine* h, int64_t* out9) {
-    if (!h || !out9) return LCD_ERR_INVALID;
-    for (int i = 0; i < 9; ++i) out9[i] = h->host_prof[i];
-    return LCD_OK;
-}
-
-int lcd_slot_count(const lcd_engine* h, int64_t* n_slots) {
-    if (!h || !n_slots) return LCD_ERR_INVALID;
-    int64_t owed = 0;
-    for (const lcd_engine::InFlight& f : h->inflight) if (f.a.sig_id != 0) owed += 1;
-    *n_slots = h->tfidf.n_slots + owed;
-    return LCD_OK;
-}
-
-int lcd_frame_host(lcd_engine* h, const lcd_frame_host_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_frame_host");
-    LCD_DEV(h);                                                      // completes what a pipelined handle owes
-    if (!a || a->struct_size != (int32_t)sizeof(lcd_frame_host_args)) return h->fail(LCD_ERR_INVALID, "lcd_frame_host: bad argument block");
-    const int q = a->q;
-    if (q <= 0 || q > 8192 || !a->descriptors || !a->word_ids) return h->fail(LCD_ERR_INVALID, "lcd_frame_host: bad argument");
-    const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-    if (src_row != (size_t)h->row_bytes) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_host: rows of this size are padded on the device (use lcd_quantize)");
-    const int64_t slots_after = h->tfidf.n_slots + (a->sig_id != 0 ? 1 : 0);
-    if (a->likelihood && a->likelihood_capacity < slots_after) return h->fail(LCD_ERR_INVALID, "lcd_frame_host: likelihood buffer too small");
-    // descriptors: host -> pinned staging -> device, on the engine's stream (the one synchronisation at the end frees the staging)
-    const size_t dbytes = (size_t)q * h->row_bytes;
-    LCD_HIP(h, h->h_frame_in.reserve(dbytes));
-    std::memcpy(h->h_frame_in.p, a->descriptors, dbytes);
-    LCD_HIP(h, dreserve(h, h->d_frame_desc, std::max<size_t>(dbytes, 16)));
-    LCD_HIP(h, dreserve(h, h->d_frame_words, (size_t)q * 4));
-    if (a->likelihood) LCD_HIP(h, dreserve(h, h->d_frame_like, (size_t)std::max<int64_t>(slots_after, 1) * 4));
-    LCD_HIP(h, hipMemcpyAsync(h->d_frame_desc.p, h->h_frame_in.p, dbytes, hipMemcpyHostToDevice, h->stream));
-    // from here on a copy out of / into the pinned staging may be in flight: a failure synchronises before it returns (the next call --
-    // the mirror falls back to the call-by-call path on the same engine straight away -- reuses h_frame_in / h_frame_out)
-    auto bail = [&](int rc) { (void)hipStreamSynchronize(h->stream); return rc; };
-#define LCD_HIP_B(h, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return bail((h)->hip_fail(e__, #call)); } while (0)
-    lcd_frame_args fa;
-    std::memset(&fa, 0, sizeof(fa));
-    fa.struct_size = (int32_t)sizeof(fa); fa.q = q; fa.d_descriptors = h->d_frame_desc.p; fa.flags = a->flags; fa.nndr_ratio = a->nndr_ratio;
-    fa.sig_id = a->sig_id; fa.first_new_word_id = a->first_new_word_id; fa.N = a->N; fa.append_new_words = a->append_new_words;
-    fa.d_word_ids = h->d_frame_words.as<int32_t>();
-    if (a->likelihood) { fa.d_likelihood = h->d_frame_like.as<float>(); fa.likelihood_capacity = (int64_t)(h->d_frame_like.cap / 4); }
-    { int rc = frame_dev_body(h, &fa); if (rc) return bail(rc); }
-    { int rc = h->drain(false); if (rc) return bail(rc); }            // a pipelined handle: the frame's stages stand-alone (the row mirror is not needed here)
-    const size_t wbytes = (size_t)q * 4, lbytes = a->likelihood ? (size_t)slots_after * 4 : 0;
-    LCD_HIP_B(h, h->h_frame_out.reserve(wbytes + lbytes + 16));
-    LCD_HIP_B(h, hipMemcpyAsync(h->h_frame_out.p, h->d_frame_words.p, wbytes, hipMemcpyDeviceToHost, h->stream));
-    if (lbytes) LCD_HIP_B(h, hipMemcpyAsync((char*)h->h_frame_out.p + wbytes, h->d_frame_like.p, lbytes, hipMemcpyDeviceToHost, h->stream));
-    LCD_HIP(h, hipStreamSynchronize(h->stream));
-#undef LCD_HIP_B
-    std::memcpy(a->word_ids, h->h_frame_out.p, wbytes);
-    if (lbytes) std::memcpy(a->likelihood, (const char*)h->h_frame_out.p + wbytes, lbytes);
-    if (a->n_slots) *a->n_slots = slots_after;
-    // The word ids are here and the stream is idle: the rows this frame appended on the device are known without asking the device's log
-    // (the k-th new word carries the code -(k + 1)), so the host's row mirror catches up now -- the next call finds nothing to reconcile
-    // (a synchronisation and two small blocking copies less per frame).  Only when this frame is the one unreconciled appender, with ids the
-    // caller gave: the postings keys of words numbered on the device are learnt from the rows (reconcile(), at the next drain).
-    const AppendLog::DevAppend* e = h->applog.unreconciled.size() == 1 ? &h->applog.unreconciled.front() : nullptr;
-    if (e && e->enabled && e->own.world == 0 && e->first_id > 0 && !h->rm_pending) {
-        int n_new = 0;
-        for (int i = 0; i < q; ++i) n_new = std::max(n_new, -a->word_ids[i]);
-        const AppendLog::Report r = h->applog.report();
-        if (r.tag == (uint32_t)(e->seq + 1) && r.rows == h->n_rows + n_new) {
-            for (int k = 0; k < n_new; ++k) { h->mirror.push(AppendLog::id_of(*e, k, h->n_rows), h->n_rows); h->n_rows += 1; h->n_live += 1; }
-            h->applog.unreconciled.clear();
-            h->frames_since_reconcile = 0;                               // (what reconcile() leaves: nothing is owed to the mirror)
-        }
-    }
-    return LCD_OK;
-    LCD_CATCH(h)
-}
-
-static int frame_dev_body(lcd_engine* h, const lcd_frame_args* a) {
-    if (!a || a->struct_size != (int32_t)sizeof(lcd_frame_args)) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: bad argument block");
-    const int q = a->q;
-    if (q <= 0 || q > 8192 || !a->d_descriptors || !a->d_word_ids) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: bad argument");
-    if (((uintptr_t)a->d_descriptors & 15u) != 0) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: d_descriptors must be 16-byte aligned");
-    if ((a->d_hypothesis || a->d_adjusted || a->d_posterior || a->d_bayes) && !a->d_likelihood)
-        return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: the hypothesis needs d_likelihood");
-    if ((a->d_posterior || a->d_bayes) && !h->bayes.configured) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: lcd_bayes_configure first");
-    if (h->pipeline && q <= 4096 && h->bf_family() && knn_mfma_supported(h->dtype, h->kdim) && h->n_live >= 2 && h->n_rows >= 256)
-        return frame_pipelined(h, a);
-    { int rc = id_window(h, *a); if (rc) return rc; }
-    const bool app = frame_appends(h, *a);
-    // A stream of appending frames on a plain handle with the exact scan (ORB: config 3) does not wait for the device between frames:
-    // the host's row mirror lags (as on a pipelined handle), the scan is planned for an upper bound of the row count.  Anything else
-    // completes what is owed and brings the mirror up to date first.
-    const bool lazy = app && h->inflight.empty() && h->applog.vcnt_active && h->n_live >= 2 && !(h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim)) &&
-                      !h->applog.must_reconcile(h->rm_pending, h->frames_since_reconcile);
-    if (!lazy) { int rc = h->drain(); if (rc) return rc; }         // (also brings the host's row mirror up to date)
-    else {
-        if (h->rm_pending) h->frames_since_reconcile += 1;
-        LCD_HIP(h, h->applog.throttle(h->stream));
-    }
-    LCD_HIP(h, dreserve(h, h->d_out_wslot, (size_t)q * 4));
-    if (app) {
-        LCD_HIP(h, h->applog.activate(h->n_rows, h->stream, &h->bytes_device));
-        { int rc = ensure_append_capacity(h, h->applog.rows_ub(h->n_rows) + 2 * (int64_t)q); if (rc) return rc; }
-    }
-    // 2-NN + same-frame distances, then ONE single-workgroup launch: decision loop -> pending retirements -> registration / idf
-    ResolveArgs r;
-    int rc = prepare_resolve(h, a->d_descriptors, q, a->flags, a->nndr_ratio, a->d_word_ids, h->d_out_wslot.as<int32_t>(), &r, true,
-                             lazy ? h->applog.rows_ub(h->n_rows) : -1);
-    if (rc) return rc;
-    if (h->d_fail_count.p) { r.fail_count = h->d_fail_count.as<int32_t>(); h->fail_count_clean = true; }   // the tail resets the counters
-    const uint64_t vseq = app ? h->applog.record(a->first_new_word_id, q, true) : 0;
-    return frame_stage_s(h, *a, r, app, vseq);
-}
-
 int lcd_knn2_dev(lcd_engine* h, const void* d_queries, int q, int32_t* d_word_ids, float* d_dist) {
     LCD_TRY
     LCD_CHECK_HANDLE(h);
@@ -1787,25 +1068,9 @@ int lcd_bayes_set_neighbors(lcd_engine* h, int n_sigs, const int32_t* sig_ids, c
     std::vector<int32_t> triples, restart;                    // restart: the slots of the listed signatures (their lists start over)
     std::unordered_map<uint64_t, int32_t> seen;
     seen.reserve((size_t)(offsets[n_sigs] - offsets[0]) * 2 + 16);
-    // the signatures of frames whose registration is still owed have no slots yet: they will get the next ones, in frame order
-    auto gone = [&](int32_t id) {
-        for (const lcd_engine::InFlight& f : h->inflight)
-            if (std::find(f.retire_after.begin(), f.retire_after.end(), id) != f.retire_after.end()) return true;
-        return false;
-    };
-    auto slot_of = [&](int32_t id) -> int64_t {
-        int64_t k = 0;
-        for (const lcd_engine::InFlight& f : h->inflight) {
-            if (f.a.sig_id == 0) continue;
-            if (f.a.sig_id == id) return gone(id) ? -1 : t.n_slots + k;
-            k += 1;
-        }
-        auto it = t.sig_slot.find(id);
-        if (it == t.sig_slot.end() || gone(id)) return -1;
-        return it->second;
-    };
+    // (the signatures of frames whose registration is still owed have no slots yet: FramePipeline::slot_of knows the ones they will get)
     for (int i = 0; i < n_sigs; ++i) {
-        const int64_t a = slot_of(sig_ids[i]);
+        const int64_t a = h->pipe.slot_of(sig_ids[i], t);
         if (offsets[i + 1] < offsets[i]) return h->fail(LCD_ERR_INVALID, "lcd_bayes_set_neighbors: offsets must not decrease");
         // a signature the engine does not hold -- one without a single word never got references, hence no slot (a featureless
         // frame, Rtabmap.cpp:2234 "bad signature") -- has no likelihood and no posterior: its list is skipped, the reference's filter
@@ -1816,7 +1081,7 @@ int lcd_bayes_set_neighbors(lcd_engine* h, int n_sigs, const int32_t* sig_ids, c
             const int32_t m = nbr_margins[e];
             if (m < 0 || m > max_margin) return h->fail(LCD_ERR_INVALID, "lcd_bayes_set_neighbors: margin outside the prediction's levels");   // UASSERT :263
             if (nbr_sig_ids[e] < 0) continue;                 // "if(iter->first>=0)" (:254)
-            const int64_t b = slot_of(nbr_sig_ids[e]);
+            const int64_t b = h->pipe.slot_of(nbr_sig_ids[e], t);
             if (b < 0) continue;                              // not in memory: it can not be in a likelihood
             const uint64_t key = ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b);
             auto st = seen.find(key);
@@ -1825,7 +1090,7 @@ int lcd_bayes_set_neighbors(lcd_engine* h, int n_sigs, const int32_t* sig_ids, c
             triples.push_back((int32_t)std::min(a, b)); triples.push_back((int32_t)std::max(a, b)); triples.push_back(m);
         }
     }
-    if (!h->inflight.empty()) { h->inflight.back().links_after.push_back(lcd_engine::DeferredLink{std::move(triples), std::move(restart)}); return LCD_OK; }
+    if (!h->pipe.empty()) { h->pipe.queue_link(FramePipeline::DeferredLink{std::move(triples), std::move(restart)}); return LCD_OK; }
     LCD_HIP(h, h->bayes.ensure(std::max<int64_t>(t.n_slots, 1)));
     const hipError_t le = h->bayes.link(triples, restart);
     if (le == hipErrorInvalidValue) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_bayes_set_neighbors: a neighbour list longer than 8192 entries");
