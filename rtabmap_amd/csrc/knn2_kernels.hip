@@ -23,6 +23,7 @@
 // Bound: VALU issue (3 VALU ops per float element, 2+ per dword for Hamming), not HBM: see DESIGN.md.
 #include "lcd_kernels.h"
 #include "shard_body.cuh"
+#include "top2_keys.cuh"
 
 namespace lcd {
 namespace {
@@ -32,21 +33,10 @@ constexpr int WAVES = 4;
 constexpr int HSHIFT = 21;                       // Hamming packed key: (dist << 21) | row-in-block
 constexpr uint32_t HROWMASK = (1u << HSHIFT) - 1;
 
-__device__ __forceinline__ void top2_push(uint64_t& best, uint64_t& second, uint64_t k) {
-    const uint64_t hi = best > k ? best : k;
-    best = best < k ? best : k;
-    second = second < hi ? second : hi;
-}
 __device__ __forceinline__ void top2_push32(uint32_t& best, uint32_t& second, uint32_t k) {
     const uint32_t hi = max(best, k);
     best = min(best, k);
     second = min(second, hi);
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl_xor(lo, m, 64);
-    hi = __shfl_xor(hi, m, 64);
-    return ((uint64_t)hi << 32) | lo;
 }
 
 // rtflann::L2<float>::operator() (dist.h:150-177), a = vocabulary row (wave-uniform), b = the lane's query
@@ -266,12 +256,7 @@ __global__ __launch_bounds__(BLOCK) void knn2_merge_kernel(int dtype, const uint
     if (qi >= nq) return;
     uint64_t best = KEY_NONE, second = KEY_NONE;
     for (int c = lane; c < n_keys; c += 64) top2_push(best, second, partial[(size_t)c * qpad + qi]);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint64_t ob = shfl_xor_u64(best, m), os = shfl_xor_u64(second, m);
-        top2_push(best, second, ob);
-        top2_push(best, second, os);
-    }
+    wave_top2_reduce(best, second);
     if (lane == 0) {
         const int qo = qi;
         const uint64_t k[2] = {best, second};
@@ -428,12 +413,7 @@ __global__ __launch_bounds__(BLOCK) void knn2_merge_selfdist_hamming_kernel(cons
     }
     uint64_t best = KEY_NONE, second = KEY_NONE;
     for (int c = lane; c < n_keys; c += 64) top2_push(best, second, partial[(size_t)c * qpad + qi]);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint64_t ob = shfl_xor_u64(best, m), os = shfl_xor_u64(second, m);
-        top2_push(best, second, ob);
-        top2_push(best, second, os);
-    }
+    wave_top2_reduce(best, second);
     // (every lane holds the merged pair) the two word ids, needed for the threshold below
     int32_t w0 = 0, w1 = 0;
     if (best != KEY_NONE) w0 = row_id[(uint32_t)best];

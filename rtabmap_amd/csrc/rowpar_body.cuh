@@ -1,29 +1,11 @@
 // rowpar_body.cuh -- the exact redo of the queries the MFMA-filter certificate rejected (device code shared by the stand-alone
-// knn_rowpar_kernel and by the extra workgroups of the fused frame tail, tfidf.hip), plus the small key helpers both use.
+// knn_rowpar_kernel and by the extra workgroups of the fused frame tail, tfidf.hip), plus the candidate-bit row both write.
 #pragma once
 #include "lcd_kernels.h"
+#include "top2_keys.cuh"
 
 namespace lcd {
 namespace {
-
-__device__ __forceinline__ void top2_push(uint64_t& best, uint64_t& second, uint64_t k) {
-    const uint64_t hi = best > k ? best : k;
-    best = best < k ? best : k;
-    second = second < hi ? second : hi;
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl_xor(lo, m, 64);
-    hi = __shfl_xor(hi, m, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl(lo, src, 64);
-    hi = __shfl(hi, src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 
 // Row `qi` of the candidate bit matrix of the addNewWords resolution (knn2_kernels.hip: bit r = dist(r, qi) < distance of qi's
 // second indexed neighbour) from the already computed same-frame distance matrix, which is symmetric bit for bit.  Called by
@@ -95,6 +77,8 @@ __device__ __forceinline__ int rowpar_body(const RowparArgs& a, int wb, int n_wb
             res = __fadd_rn(res, t);
         }
         uint64_t best = live ? (((uint64_t)__float_as_uint(res) << 32) | (uint32_t)row) : KEY_NONE, second = KEY_NONE;
+        // (wave_top2_reduce of top2_keys.cuh written out, here and below: called as the helper, the compiler moves three VALU instructions of this
+        // body across the butterfly, and the row-parallel kernels are to stay the instruction streams they were)
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
             const uint64_t ob = shfl_xor_u64(best, m), os = shfl_xor_u64(second, m);

@@ -1,4 +1,4 @@
-"""CPU check of the split-error term of eps_bf16() (rtabmap_amd/csrc/knn_mfma_kernels.hip): with x = hi + lo + d, hi = bf16(x),
+"""CPU check of the split-error term of eps_bf16() (rtabmap_amd/csrc/rerank_body.cuh): with x = hi + lo + d, hi = bf16(x),
 lo = bf16(x - hi), the bf16x3 filter replaces q.v by qh.vh + qh.vl + ql.vh.  The certificate charges
 3.1 * 2^-16 * (|q|^2 + |v|^2) for what that neglects (on the score -2 q.v).  Emulated here in numpy (bf16 = float32 rounded to
 nearest-even at bit 16, products and sums in float64 so that only the split error is measured) on random, wide-range and

@@ -13,7 +13,8 @@ from test_gpu_frame_stream import _revisit, RTOL, ATOL
 pytestmark = pytest.mark.gpu
 
 
-def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="surf", knn_mode=None, options=None, clean_every_frame=False, auto_ids=False):
+def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="surf", knn_mode=None, options=None, clean_every_frame=False, auto_ids=False,
+            fresh_frac=0.3, min_words_in_a_frame=0):
     import rtabmap_amd
     from rtabmap_amd import capi
     rng = np.random.default_rng(seed)
@@ -32,7 +33,7 @@ def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="su
     history = [base[rng.integers(0, n_words, q)] for _ in range(2)]
     frames, first_new, expected, likes = [], [], [], []
     for t in range(n_frames):
-        desc = _revisit(rng, kind, history, base, q, fresh_frac=0.3)
+        desc = _revisit(rng, kind, history, base, q, fresh_frac=fresh_frac)
         history.append(desc)
         first_new.append(m.vwd.last_word_id + 1)
         sid, exp = m.update(desc)
@@ -42,6 +43,8 @@ def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="su
         live = np.array(m.signature_ids(), np.int32)
         likes.append(m.compute_likelihood(np.array(exp, np.int32), live)[1])
     assert not m.vwd.get_unused_word_ids()
+    # (by the oracle's ids, before anything runs on the device: a caller that needs a frame with that many new words has one)
+    assert max(len(set(w for w in exp if w >= first)) for exp, first in zip(expected, first_new)) >= min_words_in_a_frame
     eng = rtabmap_amd.Engine("f32" if kind == "surf" else "u8", base.shape[1], sig_capacity=n_bulk + n_frames + 8, pipeline=pipeline, knn_mode=knn_mode)
     for key, value in (options or {}).items():
         eng.set_option(key, value)
@@ -157,6 +160,17 @@ def test_new_rows_staged_and_scanned_by_the_rerank(oracle, options, knn_mode):
     for A/B runs): every re-rank workgroup stages the rows the previous frame appended and scans them exactly -- rows written by the writer
     workgroups of the re-rank role, or (row_writer_wgs = 0) by the re-rank workgroups from their staging area; mirror stored by either launch"""
     assert _stream(oracle, True, n_words=3000, q=96, n_frames=30, seed=43, knn_mode=knn_mode, options=options) > 200
+
+
+@pytest.mark.parametrize("options", [{"shadow_rows": 0, "row_writer_wgs": 0}, {"shadow_rows": 0}, {}])
+def test_a_frame_creates_more_words_than_the_rerank_keeps_list_entries_in_lds(oracle, options):
+    """A re-rank workgroup of launch B keeps the first 512 entries of the list of descriptors that became words (two halves x 256 threads, one
+    entry each) in LDS and reads the entries behind them from memory.  Frames of 1 200 mostly fresh descriptors create more than 900 words each
+    (asserted from the oracle's ids before the device runs), so the rows behind the 512th are staged and written through the list in memory: by
+    the re-rank workgroups themselves, by the writer workgroups of the re-rank role (which then read the list past 512), and with the built-in
+    options -- word ids, likelihood and vocabulary as in every other stream.  (The first two option sets reach the staging loops because
+    "cross_frame_tiles" is 0 unless set: with the cross-frame matrix a workgroup stages only the rows it writes.)"""
+    assert _stream(oracle, True, n_words=3000, q=1200, n_frames=6, seed=47, options=options, fresh_frac=0.8, min_words_in_a_frame=513) > 3000
 
 
 @pytest.mark.parametrize("options", [{"mirror_from_b": 1}, {"mirror_from_b": 1, "row_writer_wgs": 8}, {"mirror_from_b": 1, "append_from_rerank": 0},
