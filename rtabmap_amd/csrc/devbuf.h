@@ -40,6 +40,18 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
+#define TF_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
+
+// grow a table, new part filled with `byte`
+inline hipError_t grow_filled(DevBuf& buf, size_t bytes, int byte, hipStream_t s, int64_t* total) {
+    const size_t old = buf.cap;
+    if (bytes <= old) return hipSuccess;
+    hipError_t e = buf.reserve(bytes, old, s, total);
+    if (e != hipSuccess) return e;
+    return hipMemsetAsync((char*)buf.p + old, byte, buf.cap - old, s);
+}
+inline hipError_t grow_zeroed(DevBuf& buf, size_t bytes, hipStream_t s, int64_t* total) { return grow_filled(buf, bytes, 0, s, total); }
+
 struct PinBuf {
     void* p = nullptr;
     size_t cap = 0;

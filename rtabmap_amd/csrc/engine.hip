@@ -229,7 +229,7 @@ int lcd_engine::reconcile() {
         hipError_t e = hipMemcpy(keys.data(), row_wslot.as<int32_t>() + r0, keys.size() * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpy(row keys)");
         for (const std::pair<int64_t, int>& ar : auto_rows)
-            for (int k = 0; k < ar.second; ++k) tfidf.adopt_key(mirror.key(ar.first + k), keys[(size_t)(ar.first + k - r0)]);
+            for (int k = 0; k < ar.second; ++k) tfidf.keys.adopt_key(mirror.key(ar.first + k), keys[(size_t)(ar.first + k - r0)]);
     }
     applog.unreconciled.clear();
     applog.auto_window = false;
@@ -247,8 +247,8 @@ int lcd_engine::reconcile() {
             if (e != hipSuccess) return hip_fail(e, "hipMemcpy(removal log)");
             // every batched key check enqueued so far has finished (the stream is drained): with their verdicts in, a key is either the
             // word's permanent one -- released here -- or still on its way through the reservation checks, which will find it free
-            tfidf.harvest_released(true);
-            e = tfidf.rows_unlog_keys(d_rmlog.as<int32_t>() + 16 + 2 * rm_seen, (int)(n - rm_seen));   // nothing is in flight: the keys may circulate again
+            tfidf.keys.harvest_released(true);
+            e = tfidf.keys.rows_unlog_keys(d_rmlog.as<int32_t>() + 16 + 2 * rm_seen, (int)(n - rm_seen));   // nothing is in flight: the keys may circulate again
             if (e != hipSuccess) return hip_fail(e, "wrow_unlog_kernel");
             for (size_t i = 0; i < ent.size(); i += 2) {
                 const int32_t r = ent[i];
@@ -256,7 +256,7 @@ int lcd_engine::reconcile() {
                 const int32_t id = mirror.key(r);
                 mirror.kill(r);
                 n_live -= 1;
-                tfidf.forget_word(id, ent[i + 1]);
+                tfidf.keys.forget_word(id, ent[i + 1]);
             }
             rm_seen = n;
         }
@@ -278,7 +278,7 @@ int lcd_engine::enqueue_clean(const int32_t* reg_cnt) {
         if (e == hipSuccess && fresh) e = hipMemsetAsync(d_rmlog.p, 0, 64, stream);
         if (e != hipSuccess) return hip_fail(e, "removal log");
     }
-    e = launch_clean_unused(row_id.as<int32_t>(), row_wslot.as<int32_t>(), tfidf.nw.as<uint32_t>(), tfidf.wrow.as<uint32_t>(),
+    e = launch_clean_unused(row_id.as<int32_t>(), row_wslot.as<int32_t>(), tfidf.keys.nw.as<uint32_t>(), tfidf.keys.wrow.as<uint32_t>(),
                             dtype == LCD_F32 ? row_norm.as<float>() : nullptr, (int)rows, applog.vcnt_active ? applog.d_vcnt.as<int32_t>() : nullptr,
                             applog.vcnt_active ? reg_cnt : nullptr, d_rmlog.as<int32_t>(), (int)((d_rmlog.cap / 4 - 16) / 2), stream);
     if (e != hipSuccess) return hip_fail(e, "clean_unused_kernel");
@@ -494,7 +494,7 @@ int lcd_vocab_clear(lcd_engine* h) {
     { int rc = h->sync_all(); if (rc) return rc; }
     h->n_rows = 0; h->n_live = 0;
     h->applog.restart(); h->tail_filled_rows = 0;
-    LCD_HIP(h, h->tfidf.rows_clear());
+    LCD_HIP(h, h->tfidf.keys.rows_clear());
     if (h->d_rmlog.p) LCD_HIP(h, hipMemsetAsync(h->d_rmlog.p, 0, 4, h->stream));
     h->rm_seen = 0;
     h->mirror.clear();
@@ -538,12 +538,12 @@ int lcd_vocab_append(lcd_engine* h, const void* rows, int n, const int32_t* word
     int32_t* ws = ids + n;
     for (int i = 0; i < n; ++i) {
         ids[i] = word_ids[i];
-        LCD_HIP(h, h->tfidf.wslot_of(word_ids[i], true, &ws[i]));
+        LCD_HIP(h, h->tfidf.keys.key_of(word_ids[i], true, &ws[i]));
     }
     LCD_HIP(h, hipMemcpyAsync((char*)h->vocab.p + (size_t)h->n_rows * h->row_bytes, st, rb, hipMemcpyHostToDevice, h->stream));
     LCD_HIP(h, hipMemcpyAsync(h->row_id.as<int32_t>() + h->n_rows, ids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     LCD_HIP(h, hipMemcpyAsync(h->row_wslot.as<int32_t>() + h->n_rows, ws, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    LCD_HIP(h, h->tfidf.rows_take_keys(h->row_wslot.as<int32_t>() + h->n_rows, n, h->n_rows));
+    LCD_HIP(h, h->tfidf.keys.rows_take_keys(h->row_wslot.as<int32_t>() + h->n_rows, n, h->n_rows));
     if (h->dtype == LCD_F32) {   // |row|^2 for the MFMA filter
         LCD_HIP(h, dreserve(h, h->row_norm, ((size_t)total + 1) * 8, (size_t)h->n_rows * 8));
         LCD_HIP(h, launch_row_norms(h->vocab.p, h->row_id.as<int32_t>(), (int)h->n_rows, n, h->kdim, h->row_norm.as<float>(),
@@ -587,7 +587,7 @@ int lcd_vocab_remove_unused(lcd_engine* h, int32_t* out_word_ids, int capacity, 
     LCD_HIP(h, dreserve(h, h->d_tmp_i32, ((size_t)h->n_rows + 16) * 4));
     int32_t* d_cnt = h->d_tmp_i32.as<int32_t>();
     LCD_HIP(h, hipMemsetAsync(d_cnt, 0, 4, h->stream));
-    LCD_HIP(h, launch_unused_rows(h->row_id.as<int32_t>(), h->row_wslot.as<int32_t>(), h->tfidf.nw.as<uint32_t>(), (int)h->n_rows, d_cnt + 16, d_cnt,
+    LCD_HIP(h, launch_unused_rows(h->row_id.as<int32_t>(), h->row_wslot.as<int32_t>(), h->tfidf.keys.nw.as<uint32_t>(), (int)h->n_rows, d_cnt + 16, d_cnt,
                                   (int)h->n_rows, h->stream));
     int32_t n = 0;
     { int rc = download(h, &n, d_cnt, 4, h->h_out2); if (rc) return rc; }
@@ -625,7 +625,7 @@ static int vocab_remove_ids(lcd_engine* h, const int32_t* word_ids, int n) {
         // not a row: a word that was created by a frame (_notIndexedWords) and dies before update() indexed it only gives its
         // postings key back (removeWords erases it from _notIndexedWords, :1602); anything else is an error
         int32_t ws = -1;
-        LCD_HIP(h, h->tfidf.wslot_of(word_ids[i], false, &ws));
+        LCD_HIP(h, h->tfidf.keys.key_of(word_ids[i], false, &ws));
         if (ws < 0) return h->fail(LCD_ERR_STATE, "lcd_vocab_remove: unknown word");
     }
     {   // the same word twice would be counted out of n_live twice
@@ -640,7 +640,7 @@ static int vocab_remove_ids(lcd_engine* h, const int32_t* word_ids, int n) {
         LCD_HIP(h, h->h_in.reserve((size_t)nr * 4));
         std::memcpy(h->h_in.p, rows.data(), (size_t)nr * 4);
         LCD_HIP(h, hipMemcpyAsync(h->d_tmp_i32.p, h->h_in.p, (size_t)nr * 4, hipMemcpyHostToDevice, h->stream));
-        LCD_HIP(h, h->tfidf.rows_drop_keys(h->row_wslot.as<int32_t>(), h->d_tmp_i32.as<int32_t>(), nr));
+        LCD_HIP(h, h->tfidf.keys.rows_drop_keys(h->row_wslot.as<int32_t>(), h->d_tmp_i32.as<int32_t>(), nr));
         LCD_HIP(h, launch_tombstone(h->row_id.as<int32_t>(), h->d_tmp_i32.as<int32_t>(), nr, h->stream));
         if (h->dtype == LCD_F32) LCD_HIP(h, launch_norm_tombstone(h->row_norm.as<float>(), h->d_tmp_i32.as<int32_t>(), nr, h->stream));
         LCD_HIP(h, hipStreamSynchronize(h->stream));
@@ -698,7 +698,7 @@ int lcd_vocab_rebuild(lcd_engine* h) {
     std::swap(h->row_id, h->row_id_alt);
     std::swap(h->row_wslot, h->row_wslot_alt);
     if (h->dtype == LCD_F32) std::swap(h->row_norm, h->row_norm_alt);
-    LCD_HIP(h, h->tfidf.rows_take_keys(h->row_wslot.as<int32_t>(), n, 0));   // the rows moved (the keys of dropped rows were released with them)
+    LCD_HIP(h, h->tfidf.keys.rows_take_keys(h->row_wslot.as<int32_t>(), n, 0));   // the rows moved (the keys of dropped rows were released with them)
     if (h->d_rmlog.p) LCD_HIP(h, hipMemsetAsync(h->d_rmlog.p, 0, 4, h->stream));   // (reconciled by the drain above: the log starts over)
     h->rm_seen = 0;
     if (n && knn_mfma_supported(h->dtype, h->kdim)) {   // the split is recomputed from the compacted rows
@@ -853,11 +853,11 @@ static int stage_word_ids(lcd_engine* h, const int32_t* word_ids, int64_t n, boo
     for (int64_t i = 0; i < n; ++i) {
         const int32_t id = word_ids[i];
         if (id <= 0) continue;
-        if ((size_t)id < t.id2ws.size() && t.id2ws[id] >= 0) continue;          // the common case: one vector read
+        if (t.keys.known(id)) continue;                                          // the common case: one vector read
         int32_t ws;
-        hipError_t e = t.wslot_of(id, create, &ws);
+        hipError_t e = t.keys.key_of(id, create, &ws);
         if (e == hipErrorInvalidValue) return h->fail(LCD_ERR_UNSUPPORTED, "word ids must be below 2^28");
-        if (e != hipSuccess) return h->hip_fail(e, "wslot_of");
+        if (e != hipSuccess) return h->hip_fail(e, "key_of");
     }
     LCD_HIP(h, dreserve(h, t.d_stage, (size_t)std::max<int64_t>(n, 1) * 4));
     if (n) LCD_HIP(h, hipMemcpyAsync(t.d_stage.p, word_ids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));   // caller-owned source:
@@ -941,10 +941,10 @@ int lcd_word_nrefs(lcd_engine* h, int32_t word_id, int32_t* out_nw) {
     LCD_DEV(h);
     if (!out_nw) return h->fail(LCD_ERR_INVALID, "lcd_word_nrefs: null output");
     int32_t ws = -1;
-    LCD_HIP(h, h->tfidf.wslot_of(word_id, false, &ws));
+    LCD_HIP(h, h->tfidf.keys.key_of(word_id, false, &ws));
     if (ws < 0) { *out_nw = 0; return LCD_OK; }
     LCD_HIP(h, h->tfidf.flush_retire());             // retirements ride with the next frame otherwise: nw would be stale
-    return download(h, out_nw, h->tfidf.nw.as<uint32_t>() + ws, 4, h->h_out2);
+    return download(h, out_nw, h->tfidf.keys.nw.as<uint32_t>() + ws, 4, h->h_out2);
     LCD_CATCH(h)
 }
 
@@ -1287,7 +1287,7 @@ int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int fla
     // will hold their rows, references them
     WsRuns new_ws;
     if ((sig_id != 0 || dev_append) && first_new_word_id > 0 && incremental) {
-        hipError_t e = t.reserve_new_words(first_new_word_id, q, &new_ws);
+        hipError_t e = t.keys.reserve_new_words(first_new_word_id, q, &new_ws);
         if (e == hipErrorInvalidValue) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_shard_frame_dev: word ids must be below 2^28");
         if (e != hipSuccess) return h->hip_fail(e, "reserve_new_words");
         if (cyclic) {                                      // block-cyclic ownership of the frame's new words (balanced growth)
@@ -1499,10 +1499,10 @@ int lcd_get_stats(lcd_engine* h, lcd_stats* out) {
     out->vocab_rows = h->n_rows; out->vocab_live = h->n_live;
     out->signatures = h->tfidf.live_sigs; out->postings = h->tfidf.postings_ub;
     out->knn_launches = h->knn_launches; out->likelihood_launches = h->likelihood_launches; out->rebuilds = h->rebuilds;
-    h->tfidf.harvest_released(false);
+    h->tfidf.keys.harvest_released(false);
     out->frame_calls = h->frame_calls; out->frame_host_ns = h->frame_host_ns;
     out->buckets_sealed = h->tfidf.seals;
-    out->word_slots = (int64_t)h->tfidf.n_wslots - h->tfidf.ws_free_count;
+    out->word_slots = h->tfidf.keys.in_use();
     out->dense_words = h->tfidf.h_n_dense ? (int64_t)*(volatile uint32_t*)h->tfidf.h_n_dense : 0;
     out->bytes_device = h->bytes_device;
     out->clean_divergent_refs = 0;

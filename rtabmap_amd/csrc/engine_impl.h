@@ -69,7 +69,7 @@ static inline void fill_append(lcd_engine* h, const lcd_frame_args& a, uint64_t 
     ap.descriptors = (const float*)a.d_descriptors; ap.row_dwords = h->row_bytes / 4; ap.is_f32_64 = lcd::knn_mfma_supported(h->dtype, h->kdim) ? 1 : 0;
     ap.vocab = h->vocab.as<uint32_t>(); ap.row_id = h->row_id.as<int32_t>(); ap.row_wslot = h->row_wslot.as<int32_t>();
     ap.row_norm = h->row_norm.as<float>(); ap.norm_max_bits = h->norm_max.as<uint32_t>(); ap.vocab_bf = h->vocab_bf.as<uint32_t>();
-    ap.wrow = h->tfidf.wrow.as<uint32_t>(); ap.f16 = h->f16();
+    ap.wrow = h->tfidf.keys.wrow.as<uint32_t>(); ap.f16 = h->f16();
     ap.cnt_in = h->applog.count_before(vseq); ap.cnt_out = h->applog.count_after(vseq); ap.log_slot = h->applog.log_slot(vseq);
     ap.first_id = h->applog.first_id(a.first_new_word_id); ap.capacity = vocab_cap_rows(h);
     ap.first_out = (int32_t*)a.d_first_new_word_id;

@@ -94,7 +94,7 @@ static int reserve_frame_words(lcd_engine* h, const lcd_frame_args& a, WsRuns* r
     // postings keys for the words this frame may create (VisualWord(id, descriptor, signatureId) references the signature; a word that
     // becomes a vocabulary row on the device needs its key there as well)
     if ((a.sig_id != 0 || frame_appends(h, a)) && (a.first_new_word_id > 0 || (a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO && frame_appends(h, a))) && (a.flags & LCD_Q_INCREMENTAL)) {
-        hipError_t e = h->tfidf.reserve_new_words(a.first_new_word_id, a.q, runs, may_flush);
+        hipError_t e = h->tfidf.keys.reserve_new_words(a.first_new_word_id, a.q, runs, may_flush);
         if (e == hipErrorInvalidValue) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_dev: word ids must be below 2^28");
         LCD_HIP(h, e);
     }
@@ -355,7 +355,7 @@ static int launch_b(lcd_engine* h, LaunchPair& p, HostLap& lap) {
     if (h->roctx_pop) h->roctx_pop();
     LCD_HIP(h, eb__);
     lap.lap(6);
-    LCD_HIP(h, h->tfidf.flush_held_if_due());                        // (behind launch B: the rows it writes claim their postings keys there)
+    LCD_HIP(h, h->tfidf.keys.flush_held_if_due());                        // (behind launch B: the rows it writes claim their postings keys there)
     if (prof2) { h->prof2_n += 1; h->prof2_kernel = "frame_b_kernel (re-rank of frame t-1 + scoring of frame t-3)"; }
     if (h->pipe.clean_armed && o.reg) {
         // cleanUnusedWords asked for behind an earlier frame: the retirements made in front of it rode with the registration of this

@@ -29,14 +29,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <map>
-#include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "bayes.h"
 #include "devbuf.h"
 #include "lcd_kernels.h"
+#include "postings_keys.h"
 
 namespace lcd {
 
@@ -109,7 +108,7 @@ struct AppendArgs {
     int is_f32_64 = 0;                         // rows are 64 floats: also the augmentation entries and the bf16 split
     int f16 = 0;                               // ... the split table holds IEEE half (LCD_KNN_F16) instead of bf16
     uint32_t* vocab = nullptr; int32_t* row_id = nullptr; int32_t* row_wslot = nullptr;
-    uint32_t* wrow = nullptr;                  // Tfidf::wrow: the appended rows claim their postings keys
+    uint32_t* wrow = nullptr;                  // KeyPool::wrow: the appended rows claim their postings keys
     float* row_norm = nullptr; uint32_t* norm_max_bits = nullptr; uint32_t* vocab_bf = nullptr;
     const int32_t* cnt_in = nullptr; int32_t* cnt_out = nullptr;
     int32_t* log_slot = nullptr;               // receives the number of rows appended (host reconciliation)
@@ -161,7 +160,7 @@ struct ResolveArgs {
 // kernel argument blocks of the registration / scoring launches (frame_tail_body.cuh, score_body.cuh)
 struct FwArgs {
     const int32_t* src; int n;                    // word slots of the frame (or word ids when xlate != NULL); < 0 / <= 0 = no word
-    const int32_t* xlate; long long xlate_n;      // word id -> wslot table (device copy of Tfidf::id2ws)
+    const int32_t* xlate; long long xlate_n;      // word id -> wslot table (KeyPool::xlate)
     int H; int do_register; int want_q;
     int32_t sig_id; long long slot; uint32_t slot_local; uint32_t ni; float N; uint32_t stamp;
     uint32_t* nw; const int32_t* did;
@@ -172,7 +171,7 @@ struct FwArgs {
     const int32_t* row_wslot;                     // NULL: src holds postings keys.  Otherwise its entries >= 0 are vocabulary ROWS (row_wslot[row] is the key) and its
                                                   // entries <= -2 are keys themselves, -(key + 2): the words the frame created (ResolveArgs::slots_are_rows)
                                                   // (the decision loop of a pipelined frame: the gather moved from its chain to the registration's, lcd_set_option "slots_from_rows")
-    const uint32_t* wrow;                         // Tfidf::wrow (NULL: not wanted): a registered word whose key reads 0xFFFFFFFF is a word an enqueued
+    const uint32_t* wrow;                         // KeyPool::wrow (NULL: not wanted): a registered word whose key reads 0xFFFFFFFF is a word an enqueued
                                                   // cleanUnusedWords tombstoned while this frame was in flight -- counted in q_meta[8] (lcd_stats.clean_divergent_refs)
 };
 // signatures whose retirement was requested since the last frame (Memory::disableWordsRef -> removeAllWordRef): their
@@ -278,30 +277,8 @@ struct Tfidf {
     int64_t* bytes_device = nullptr;
     // per slot
     DevBuf slot_sig, slot_ni, slot_begin, slot_cnt;
-    // per wslot
-    DevBuf nw, did;                      // references, dense id (-1: none)
-    DevBuf wrow;                         // vocabulary row that carries the key + 1 (0: none): a key held by a live row is never recycled, whatever
-                                         // its reference count (rows appended on the device get their key there, the host learns of it later)
-    DevBuf idf_tab;                      // {stamp, idf Q5.26} of the words of the current frame (valid iff stamp matches)
-    uint32_t stamp = 0;
-    // word id -> wslot: host vector (ids are small consecutive integers in the reference, ++_lastWordId) mirrored on the device
-    std::vector<int32_t> id2ws;          // -1 = none
-    DevBuf d_id2ws;
-    int64_t d_id2ws_n = 0;               // entries valid on the device
-    std::vector<int32_t> id2ws_dirty;    // ids whose device entry is out of date
-    std::map<int32_t, int32_t> ws_free;  // recycled wslots (confirmed unreferenced by the device) as intervals: start -> length
-    int64_t ws_free_count = 0;
-    // wslots on their way back: a kernel checks nw == 0 for each and reports through pinned memory.  ids[i] != 0: the wslot was
-    // reserved for new word ids[i] of a frame; if it turns out to be referenced, that word exists and keeps the wslot.
-    struct PinBlock { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; };   // pinned memory + event, recycled (one batch per frame)
-    std::vector<PinBlock> pin_free;
-    struct ReleaseBatch { std::vector<int32_t> ws, ids; PinBlock blk; const uint8_t* ok = nullptr; bool recheck = false; };
-    std::vector<ReleaseBatch> releasing;
-    std::vector<int32_t> held_ws, held_ids;   // keys of superseded reservations waiting for a batched check
-    std::vector<int32_t> ghost_ws;            // keys of removed words that a batch found still referenced: asked about again every 8th batch
-    uint32_t flushes = 0;
-    hipError_t flush_held();
-    struct Reservation { int32_t first_id = 0, n = 0; WsRuns runs; } resv;   // wslots reserved for the new words of the last frame
+    KeyPool keys;                        // the postings keys of the words and the per-key tables (nw, did, wrow, idf_tab): postings_keys.h
+    uint32_t stamp = 0;                  // of the current frame's entries in keys.idf_tab
     // per bucket
     DevBuf bkt_tab, bkt_ne, bkt_D, bkt_flags;
     std::vector<Bucket> buckets;
@@ -317,46 +294,16 @@ struct Tfidf {
     // per frame
     DevBuf q_w, q_idf, q_did, qd_did, qd_idf, q_meta;   // the frame's unique words: wslot, idf, dense id; its dense words; [0] = unique, [1] = dense
     DevBuf d_stage;                      // staged word ids of host-side calls
-    DevBuf d_pairs;                      // (id, wslot) pairs on their way into d_id2ws
-    PinBuf h_stage;
     // host maps
     std::unordered_map<int32_t, int64_t> sig_slot;    // live signature id -> slot
-    int32_t n_wslots = 0;
     int64_t n_slots = 0, live_sigs = 0;
     int64_t postings_ub = 0;
     int64_t seals = 0;
-    std::string err;
 
     hipError_t init(hipStream_t s, int64_t* bytes, int64_t sig_capacity, int64_t vocab_capacity);
     void destroy();
-    // wslot of a word id (assigned on first sight when `create`); -1 if unknown and !create
-    hipError_t wslot_of(int32_t word_id, bool create, int32_t* out);
-    // bring the device copy of id2ws up to date
-    hipError_t sync_id2ws();
-    // the word left the dictionary (VWDictionary::removeWords): its wslot is recycled once the device confirms nw == 0
+    // the words left the dictionary (VWDictionary::removeWords): pending retirements are applied, then keys.release_words
     hipError_t release_words(const int32_t* word_ids, int n);
-    // recheck: keys without a word id that turn out to be still referenced are checked again with a later batch
-    hipError_t release_wslots(const std::vector<int32_t>& ws, const std::vector<int32_t>* ids = nullptr, bool recheck = false);
-    // the vocabulary rows' claim on their keys (wrow): rows [first_row, first_row + n) carry d_ws[0 .. n); rows d_rows[0 .. n) are gone;
-    // the vocabulary was cleared
-    hipError_t rows_take_keys(const int32_t* d_ws, int n, int64_t first_row);
-    hipError_t rows_drop_keys(const int32_t* d_row_wslot, const int32_t* d_rows, int n);
-    hipError_t rows_clear();
-    // the device-side cleanUnusedWords keeps the keys of the rows it tombstones out of circulation (wrow = 0xFFFFFFFF) until the host has
-    // caught up with its log of {row, key} pairs -- with nothing in flight: then they are released like any removed word's key
-    hipError_t rows_unlog_keys(const int32_t* d_pairs, int n);
-    // the device tombstoned the row of word `word_id` (key `ws`): if that is the word's permanent key it goes to the batched check
-    void forget_word(int32_t word_id, int32_t ws);
-    void free_wslot(int32_t w);          // into the interval set
-    void free_wslot_run(int32_t start, int32_t len);   // a run of consecutive keys, one operation
-    int32_t take_wslot();                // one recycled wslot, or -1
-    void harvest_released(bool wait);
-    // reserve n wslots for the new words first_id, first_id + 1, ... of the coming frame (recycled intervals first)
-    // may_flush = false: the batched check of superseded reservations is not launched here (a pipelined handle launches it with
-    // flush_held_if_due() once the registration that may still use those keys is enqueued)
-    hipError_t reserve_new_words(int32_t first_id, int n, WsRuns* runs, bool may_flush = true);
-    void adopt_key(int32_t word_id, int32_t ws);   // a word numbered on the device: id and key read from its row at reconciliation
-    hipError_t flush_held_if_due() { return held_ws.size() >= 16384 ? flush_held() : hipSuccess; }
     // register one signature whose word slots are already on the device (d_wslots[n]; < 0 = no word); if N > 0 the
     // frame's unique words / idf are left in q_* for a following score()
     // defer != NULL (needs resolve): do not launch the frame tail, leave its launch arguments there -- sized for a workgroup of
@@ -386,7 +333,6 @@ struct Tfidf {
     hipError_t retire(int32_t sig_id);
     hipError_t seal_batch(const std::vector<int>& bucket_ids, bool bulk);
     hipError_t ensure_slots(int64_t n);
-    hipError_t ensure_wslots(int32_t n);
     hipError_t ensure_buckets(int n);
     hipError_t set_bucket(int b);          // upload one bucket descriptor (tiny kernel: the data travels as kernel arguments)
     hipError_t new_bucket();
@@ -398,11 +344,5 @@ struct Tfidf {
 
 // gather of the dense likelihood: out[k] = slots[k] >= 0 ? dense[slots[k]] : 0
 hipError_t launch_gather_f32(const float* dense, const int64_t* slots, int n, float* out, hipStream_t s);
-// one rank's share of update()'s append on a sharded vocabulary as a launch of its own (tfidf.hip, shard_append_kernel): codes = the replicated
-// decision loop's output; own_block > 0: block-cyclic owners from own_first on, else the last rank owns every new word.  lcd_shard_frame_dev no
-// longer calls it -- the append rides in the registration's launch (ShardAppendJob) -- it stays as the stand-alone form of the same body
-hipError_t launch_shard_append(const AppendArgs& ap, const WsRuns& new_ws, const int32_t* codes, int q, int rank, int world, int32_t own_first,
-                               int32_t own_block, hipStream_t s);
-
 
 }  // namespace lcd

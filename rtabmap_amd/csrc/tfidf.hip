@@ -12,9 +12,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <iterator>
 
 namespace lcd {
 namespace {
@@ -291,48 +288,6 @@ __global__ void retire_kernel(long long slot, const uint32_t* __restrict__ coo_w
     if (threadIdx.x == 0) { slot_ni[slot] = 0u; slot_sig[slot] = 0; }
 }
 
-// the words left the dictionary: a wslot may be handed out again only if nothing references it (ok[i] tells the host)
-// verdict: 1 = free (nothing references the key and no vocabulary row carries it), 2 = a live row's key (permanent, whatever its reference
-// count: a word a frame appended on the device whose signature is gone, or that never had one), 0 = still referenced
-__global__ void wslot_release_kernel(const int32_t* __restrict__ ws, int n, const uint32_t* __restrict__ nw, const uint32_t* __restrict__ wrow,
-                                     int32_t* __restrict__ did, uint2* __restrict__ idf_tab, uint8_t* __restrict__ ok) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t w = ws[i];
-    const bool is_row = wrow[w] != 0u;
-    const bool free_now = !is_row && nw[w] == 0u;
-    if (free_now) { did[w] = -1; idf_tab[w] = make_uint2(0u, 0u); }
-    ok[i] = free_now ? 1 : (is_row ? 2 : 0);
-}
-// rows [first_row, first_row + n) carry the keys ws[0 .. n)
-__global__ void wrow_set_kernel(const int32_t* __restrict__ ws, int n, long long first_row, uint32_t* __restrict__ wrow) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && ws[i] >= 0) wrow[ws[i]] = (uint32_t)(first_row + i) + 1u;
-}
-// the keys of logged removals ({row, key} pairs) leave their quarantine
-__global__ void wrow_unlog_kernel(const int32_t* __restrict__ pairs, int n, uint32_t* __restrict__ wrow) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t w = pairs[2 * i + 1];
-    if (w >= 0 && wrow[w] == 0xFFFFFFFFu) wrow[w] = 0u;
-}
-// the rows rows[0 .. n) are gone: their keys belong to no row any more
-__global__ void wrow_clear_kernel(const int32_t* __restrict__ row_wslot, const int32_t* __restrict__ rows, int n, uint32_t* __restrict__ wrow) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t w = row_wslot[rows[i]];
-    if (w >= 0) wrow[w] = 0u;
-}
-// table[pairs[2i]] = pairs[2i + 1]
-__global__ void scatter_pairs_kernel(const int32_t* __restrict__ pairs, int n, int32_t* __restrict__ table) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) table[pairs[2 * i]] = pairs[2 * i + 1];
-}
-__global__ void iota_i32_kernel(int32_t* dst, int n, int32_t first) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = first + i;
-}
-
 // ---------------------------------------------------------------------------------------------- adjustLikelihood
 inline int next_pow2(int v) { int p = 2; while (p < v) p <<= 1; return p; }
 
@@ -387,11 +342,6 @@ __device__ __forceinline__ void shard_append_body(int* s_first /* LDS [q]: the d
                                                __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-__global__ __launch_bounds__(1024) void shard_append_kernel(AppendArgs ap, WsRuns new_ws, const int32_t* __restrict__ codes, int q, int rank, int world,
-                                                           int32_t own_first, int32_t own_block) {
-    extern __shared__ int s_first[];
-    shard_append_body(s_first, ap, new_ws, codes, q, rank, world, own_first, own_block);
-}
 // the registration of a sharded frame and, beside it, this rank's share of the frame's append: two single-workgroup latency chains that need
 // nothing of each other (the registration reads wrow[] only to COUNT references to words an enqueued clean tombstoned, 0xFFFFFFFF: a key the
 // appender is claiming at that moment reads as 0 or as its row, never as that) -- one launch of two workgroups instead of two launches
@@ -405,13 +355,6 @@ __global__ __launch_bounds__(FW_BLOCK) void frame_words_append_kernel(FwArgs a, 
     __syncthreads();
     frame_words_body<FW_BLOCK, true>(fwa_dyn_smem, a);
 }
-hipError_t launch_shard_append(const AppendArgs& ap, const WsRuns& new_ws, const int32_t* codes, int q, int rank, int world, int32_t own_first,
-                               int32_t own_block, hipStream_t s) {
-    if (q <= 0 || q > 8192) return hipErrorInvalidValue;
-    shard_append_kernel<<<1, 1024, (size_t)q * 4, s>>>(ap, new_ws, codes, q, rank, world, own_first, own_block);
-    return hipGetLastError();
-}
-
 hipError_t launch_gather_f32(const float* dense, const int64_t* slots, int n, float* out, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     gather_f32_kernel<<<(n + 255) / 256, 256, 0, s>>>(dense, (const long long*)slots, n, out);
@@ -419,8 +362,6 @@ hipError_t launch_gather_f32(const float* dense, const int64_t* slots, int n, fl
 }
 
 // ================================================================================================ host side
-#define TF_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
-
 hipError_t BufPool::get(size_t bytes, DevBuf* out, int64_t* total) {
     // smallest free buffer that fits and is not more than 4x too large
     int best = -1;
@@ -446,16 +387,6 @@ void BufPool::destroy(int64_t* total) {
     free_list.clear();
 }
 
-// grow a table, new part filled with `byte`
-static hipError_t grow_filled(DevBuf& buf, size_t bytes, int byte, hipStream_t s, int64_t* total) {
-    const size_t old = buf.cap;
-    if (bytes <= old) return hipSuccess;
-    hipError_t e = buf.reserve(bytes, old, s, total);
-    if (e != hipSuccess) return e;
-    return hipMemsetAsync((char*)buf.p + old, byte, buf.cap - old, s);
-}
-static hipError_t grow_zeroed(DevBuf& buf, size_t bytes, hipStream_t s, int64_t* total) { return grow_filled(buf, bytes, 0, s, total); }
-
 // frames / signatures of thousands of words need more than the default 64 KB of dynamic LDS: allow everything the CU has left
 // after the kernel's static LDS.  A failure here is not fatal: only launches that actually ask for more than 64 KB would fail.
 static hipError_t set_max_lds(const void* fn) {
@@ -469,9 +400,10 @@ static hipError_t set_max_lds(const void* fn) {
 hipError_t Tfidf::init(hipStream_t s, int64_t* bytes, int64_t sig_capacity, int64_t vocab_capacity) {
     stream = s;
     bytes_device = bytes;
+    keys.stream = s; keys.bytes_device = bytes;
     TF_TRY(ensure_slots(sig_capacity > 0 ? sig_capacity : TF_R));
     TF_TRY(ensure_buckets((int)((sig_capacity > 0 ? sig_capacity : TF_R) / TF_R) + 64));
-    TF_TRY(ensure_wslots((int32_t)std::min<int64_t>(std::max<int64_t>(65536, 4 * vocab_capacity), 1 << 27)));   // growing later means a stream sync
+    TF_TRY(keys.ensure_keys((int32_t)std::min<int64_t>(std::max<int64_t>(65536, 4 * vocab_capacity), 1 << 27)));   // growing later means a stream sync
     // the word-major directory is sized for the same horizon (its growth is a stream sync and a copy of the whole table): blocks for
     // twice the vocabulary hint + the keys a stream of frames holds in reserve, buckets for the signature hint
     dir2_hint_blocks = (uint32_t)std::min<int64_t>((2 * std::max<int64_t>(vocab_capacity, 8192) + 65536) / 32, 1 << 22);
@@ -495,16 +427,13 @@ hipError_t Tfidf::init(hipStream_t s, int64_t* bytes, int64_t sig_capacity, int6
 }
 
 void Tfidf::destroy() {
-    harvest_released(true);
-    for (PinBlock& b : pin_free) { (void)hipEventDestroy(b.ev); (void)hipHostFree(b.p); }
-    pin_free.clear();
+    keys.destroy();
     for (Bucket& b : buckets) { b.coo_w.release(bytes_device); b.coo_pc.release(bytes_device); b.sealed.release(bytes_device); }
     buckets.clear();
     pool.destroy(bytes_device);
-    DevBuf* all[] = {&slot_sig, &slot_ni, &slot_begin, &slot_cnt, &nw, &did, &wrow, &idf_tab, &d_id2ws, &bkt_tab, &bkt_ne, &bkt_D, &bkt_flags,
-                     &n_dense, &dir2, &seal_cntw, &seal_tiles, &q_w, &q_idf, &q_did, &qd_did, &qd_idf, &q_meta, &d_stage, &d_pairs};
+    DevBuf* all[] = {&slot_sig, &slot_ni, &slot_begin, &slot_cnt, &bkt_tab, &bkt_ne, &bkt_D, &bkt_flags,
+                     &n_dense, &dir2, &seal_cntw, &seal_tiles, &q_w, &q_idf, &q_did, &qd_did, &qd_idf, &q_meta, &d_stage};
     for (DevBuf* d : all) d->release(bytes_device);
-    h_stage.release();
     if (h_n_dense) { (void)hipHostFree(h_n_dense); h_n_dense = nullptr; }
 }
 
@@ -516,14 +445,6 @@ hipError_t Tfidf::ensure_slots(int64_t n) {
     return hipSuccess;
 }
 
-hipError_t Tfidf::ensure_wslots(int32_t n) {
-    TF_TRY(grow_zeroed(nw, (size_t)n * 4, stream, bytes_device));
-    TF_TRY(grow_filled(did, (size_t)n * 4, 0xFF, stream, bytes_device));
-    TF_TRY(grow_zeroed(wrow, (size_t)n * 4, stream, bytes_device));
-    TF_TRY(grow_zeroed(idf_tab, (size_t)n * 8, stream, bytes_device));
-    return hipSuccess;
-}
-
 hipError_t Tfidf::ensure_buckets(int n) {
     TF_TRY(grow_zeroed(bkt_tab, (size_t)n * sizeof(BucketDev), stream, bytes_device));
     TF_TRY(grow_zeroed(bkt_ne, (size_t)n * 4, stream, bytes_device));
@@ -532,257 +453,9 @@ hipError_t Tfidf::ensure_buckets(int n) {
     return hipSuccess;
 }
 
-void Tfidf::free_wslot(int32_t w) {
-    // insert w into the interval set, merging with its neighbours
-    int32_t start = w, len = 1;
-    auto next = ws_free.lower_bound(w);
-    if (next != ws_free.begin()) {
-        auto prev = std::prev(next);
-        if (prev->first + prev->second > w) return;                   // already free (cannot happen)
-        if (prev->first + prev->second == w) { start = prev->first; len += prev->second; ws_free.erase(prev); }
-    }
-    if (next != ws_free.end() && next->first == w + 1) { len += next->second; ws_free.erase(next); }
-    ws_free[start] = len;
-    ws_free_count += 1;
-}
-
-// the same for a run of consecutive keys [start, start + len): one interval operation for the whole run
-void Tfidf::free_wslot_run(int32_t start, int32_t len) {
-    if (len <= 0) return;
-    auto next = ws_free.lower_bound(start);
-    const bool clash_next = next != ws_free.end() && next->first < start + len;
-    const bool clash_prev = next != ws_free.begin() && std::prev(next)->first + std::prev(next)->second > start;
-    if (len == 1 || clash_next || clash_prev) {                          // (an overlap cannot happen; key by key it is at least ignored safely)
-        for (int32_t k = 0; k < len; ++k) free_wslot(start + k);
-        return;
-    }
-    int32_t s0 = start, l0 = len;
-    if (next != ws_free.begin()) {
-        auto prev = std::prev(next);
-        if (prev->first + prev->second == start) { s0 = prev->first; l0 += prev->second; ws_free.erase(prev); }
-    }
-    if (next != ws_free.end() && next->first == start + len) { l0 += next->second; ws_free.erase(next); }
-    ws_free[s0] = l0;
-    ws_free_count += len;
-}
-
-int32_t Tfidf::take_wslot() {
-    if (ws_free.empty()) return -1;
-    auto it = std::prev(ws_free.end());
-    const int32_t w = it->first + it->second - 1;
-    if (--it->second == 0) ws_free.erase(it);
-    ws_free_count -= 1;
-    return w;
-}
-
-hipError_t Tfidf::wslot_of(int32_t word_id, bool create, int32_t* out) {
-    *out = -1;
-    if (word_id <= 0) return hipSuccess;
-    if ((size_t)word_id < id2ws.size() && id2ws[word_id] >= 0) { *out = id2ws[word_id]; return hipSuccess; }
-    int32_t w = -1;
-    if (resv.n > 0 && resv.first_id > 0 && word_id >= resv.first_id && word_id < resv.first_id + resv.n) {
-        // a new word of the last device-quantised frame: its wslot was reserved when the frame was enqueued
-        w = ws_runs_at(resv.runs, word_id - resv.first_id);
-    } else {
-        // a new word of an earlier frame whose reservation is being checked by the device: the verdict decides whether it exists
-        if (std::find(held_ids.begin(), held_ids.end(), word_id) != held_ids.end()) { TF_TRY(flush_held()); harvest_released(true); }
-        for (size_t i = 0; i < releasing.size(); ++i) {
-            const ReleaseBatch& r = releasing[i];
-            if (std::find(r.ids.begin(), r.ids.end(), word_id) != r.ids.end()) { harvest_released(true); break; }
-        }
-        if ((size_t)word_id < id2ws.size() && id2ws[word_id] >= 0) { *out = id2ws[word_id]; return hipSuccess; }
-        if (!create) return hipSuccess;
-        if (word_id >= (1 << 28)) return hipErrorInvalidValue;        // the id -> wslot table is direct-indexed
-        harvest_released(false);
-        w = take_wslot();
-        if (w < 0) { w = n_wslots++; TF_TRY(ensure_wslots(n_wslots)); }
-    }
-    if ((size_t)word_id >= id2ws.size()) id2ws.resize((size_t)word_id + 1 + id2ws.size() / 2, -1);
-    id2ws[word_id] = w;
-    id2ws_dirty.push_back(word_id);
-    *out = w;
-    return hipSuccess;
-}
-
-// bring the device copy of id2ws up to date: the entries changed since the last call travel as (id, wslot) pairs
-hipError_t Tfidf::sync_id2ws() {
-    TF_TRY(grow_filled(d_id2ws, std::max<size_t>(id2ws.size(), 1) * 4, 0xFF, stream, bytes_device));
-    d_id2ws_n = (int64_t)(d_id2ws.cap / 4);
-    if (id2ws_dirty.empty()) return hipSuccess;
-    const size_t m = id2ws_dirty.size();
-    TF_TRY(h_stage.reserve(m * 8));
-    int32_t* st = h_stage.as<int32_t>();
-    for (size_t i = 0; i < m; ++i) { st[2 * i] = id2ws_dirty[i]; st[2 * i + 1] = id2ws[id2ws_dirty[i]]; }
-    TF_TRY(d_pairs.reserve(m * 8, 0, stream, bytes_device));
-    TF_TRY(hipMemcpyAsync(d_pairs.p, st, m * 8, hipMemcpyHostToDevice, stream));
-    scatter_pairs_kernel<<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(d_pairs.as<int32_t>(), (int)m, d_id2ws.as<int32_t>());
-    TF_TRY(hipGetLastError());
-    TF_TRY(hipStreamSynchronize(stream));                             // staging buffers are reused
-    id2ws_dirty.clear();
-    return hipSuccess;
-}
-
-void Tfidf::harvest_released(bool wait) {
-    for (size_t i = 0; i < releasing.size();) {
-        ReleaseBatch& r = releasing[i];
-        const hipError_t q = wait ? hipEventSynchronize(r.blk.ev) : hipEventQuery(r.blk.ev);
-        if (q != hipSuccess) { ++i; continue; }
-        // the verdicts of a batch are mostly "free" for long runs of consecutive keys (what a frame reserved and did not use): a run
-        // goes back into the interval set with ONE operation -- key by key a batch of 16 384 keys kept the host busy for ~0.2 ms, a
-        // pause of the enqueueing thread every ~40 frames
-        int32_t run_start = 0, run_len = 0;
-        for (size_t k = 0; k < r.ws.size(); ++k) {
-            if (r.ok[k] == 1) {
-                if (run_len > 0 && r.ws[k] == run_start + run_len) { run_len += 1; continue; }
-                free_wslot_run(run_start, run_len);
-                run_start = r.ws[k]; run_len = 1;
-                continue;
-            }
-            // still referenced, or the key of a vocabulary row.  A wslot reserved for a frame's new word: the word exists (the frame
-            // created it) and keeps it.
-            const int32_t id = k < r.ids.size() ? r.ids[k] : 0;
-            if (id > 0) {
-                if ((size_t)id >= id2ws.size()) id2ws.resize((size_t)id + 1 + id2ws.size() / 2, -1);
-                if (id2ws[id] < 0) { id2ws[id] = r.ws[k]; id2ws_dirty.push_back(id); }
-            } else if (r.ok[k] == 0 && r.recheck) {
-                // a key without a word: the word was removed from the dictionary while a frame in flight still matched it (its row is
-                // tombstoned, the references of that frame's signature remain).  It comes back when those references are gone.
-                ghost_ws.push_back(r.ws[k]);
-            }
-        }
-        free_wslot_run(run_start, run_len);
-        pin_free.push_back(r.blk);
-        releasing.erase(releasing.begin() + i);
-    }
-}
-
-// hand wslots back: a kernel checks each one (nw == 0) and reports through pinned memory; the host collects the verdicts of
-// finished batches later (harvest_released), so nothing is synchronised here and a wslot that is still referenced is never reused
-hipError_t Tfidf::release_wslots(const std::vector<int32_t>& ws, const std::vector<int32_t>* ids, bool recheck) {
-    if (ws.empty()) return hipSuccess;
-    const size_t m = ws.size();
-    ReleaseBatch r;
-    r.ws = ws;
-    r.recheck = recheck;
-    if (ids) r.ids = *ids;
-    const size_t need = m * 5 + 16;                                          // [m wslots][m verdicts]
-    for (size_t i = 0; i < pin_free.size(); ++i)
-        if (pin_free[i].cap >= need) { r.blk = pin_free[i]; pin_free.erase(pin_free.begin() + i); break; }
-    if (!r.blk.p) {
-        r.blk.cap = 8192;
-        while (r.blk.cap < need) r.blk.cap *= 2;
-        TF_TRY(hipHostMalloc(&r.blk.p, r.blk.cap, hipHostMallocDefault));
-        TF_TRY(hipEventCreateWithFlags(&r.blk.ev, hipEventDisableTiming));
-    }
-    int32_t* p_ws = (int32_t*)r.blk.p;
-    uint8_t* p_ok = (uint8_t*)(p_ws + m);
-    std::memcpy(p_ws, ws.data(), m * 4);
-    std::memset(p_ok, 0, m);
-    r.ok = p_ok;
-    wslot_release_kernel<<<(unsigned)((m + 255) / 256), 256, 0, stream>>>(p_ws, (int)m, nw.as<uint32_t>(), wrow.as<uint32_t>(), did.as<int32_t>(),
-                                                                           idf_tab.as<uint2>(), p_ok);
-    TF_TRY(hipGetLastError());
-    TF_TRY(hipEventRecord(r.blk.ev, stream));
-    releasing.push_back(r);
-    return hipSuccess;
-}
-
-hipError_t Tfidf::flush_held() {
-    if (held_ws.empty()) return hipSuccess;
-    std::vector<int32_t> ws, ids;
-    ws.swap(held_ws); ids.swap(held_ids);
-    if (!ghost_ws.empty() && (++flushes & 7u) == 0u) {                       // every 8th batch also asks about the keys that were still referenced
-        ws.insert(ws.end(), ghost_ws.begin(), ghost_ws.end());
-        ids.resize(ws.size(), 0);
-        ghost_ws.clear();
-    }
-    return release_wslots(ws, &ids, true);
-}
-
-hipError_t Tfidf::rows_take_keys(const int32_t* d_ws, int n, int64_t first_row) {
-    if (n <= 0) return hipSuccess;
-    wrow_set_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(d_ws, n, (long long)first_row, wrow.as<uint32_t>());
-    return hipGetLastError();
-}
-hipError_t Tfidf::rows_drop_keys(const int32_t* d_row_wslot, const int32_t* d_rows, int n) {
-    if (n <= 0) return hipSuccess;
-    wrow_clear_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(d_row_wslot, d_rows, n, wrow.as<uint32_t>());
-    return hipGetLastError();
-}
-// a word the device numbered and keyed (LCD_NEW_WORD_IDS_AUTO): its row says which postings key it holds
-void Tfidf::adopt_key(int32_t word_id, int32_t ws) {
-    if (word_id <= 0 || ws < 0) return;
-    if ((size_t)word_id >= id2ws.size()) id2ws.resize((size_t)word_id + 1 + id2ws.size() / 2, -1);
-    if (id2ws[word_id] < 0) { id2ws[word_id] = ws; id2ws_dirty.push_back(word_id); }
-}
-void Tfidf::forget_word(int32_t word_id, int32_t ws) {
-    if (word_id <= 0 || ws < 0 || (size_t)word_id >= id2ws.size() || id2ws[word_id] != ws) return;
-    id2ws[word_id] = -1;
-    id2ws_dirty.push_back(word_id);
-    held_ws.push_back(ws); held_ids.push_back(0);
-}
-hipError_t Tfidf::rows_unlog_keys(const int32_t* d_pairs, int n) {
-    if (n <= 0) return hipSuccess;
-    wrow_unlog_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(d_pairs, n, wrow.as<uint32_t>());
-    return hipGetLastError();
-}
-hipError_t Tfidf::rows_clear() {
-    return (wrow.p && n_wslots > 0) ? hipMemsetAsync(wrow.p, 0, (size_t)n_wslots * 4, stream) : hipSuccess;
-}
-
 hipError_t Tfidf::release_words(const int32_t* word_ids, int n) {
     TF_TRY(flush_retire());               // retirements ride with the next frame otherwise: the check below would still see their references
-    std::vector<int32_t> ws;
-    for (int i = 0; i < n; ++i) {
-        int32_t w = -1;
-        TF_TRY(wslot_of(word_ids[i], false, &w));
-        if (w < 0) continue;
-        id2ws[word_ids[i]] = -1;
-        id2ws_dirty.push_back(word_ids[i]);
-        ws.push_back(w);
-    }
-    return release_wslots(ws);
-}
-
-// Postings keys for the words the coming frame may create (at most n).  The previous frame's reservation is handed to the device
-// for checking: keys it did not use (nw == 0) are recycled, used ones become the permanent keys of those words.
-hipError_t Tfidf::reserve_new_words(int32_t first_id, int n, WsRuns* runs, bool may_flush) {
-    runs->n = 0;
-    // first_id == -1 (LCD_NEW_WORD_IDS_AUTO): the device numbers the words; the host learns id and key of each from its row when it catches up (adopt_key)
-    if ((first_id <= 0 && first_id != -1) || n <= 0) return hipSuccess;
-    if (first_id > 0 && (int64_t)first_id + n >= (1 << 28)) return hipErrorInvalidValue;
-    if (resv.n > 0) {
-        int32_t k = 0;
-        for (int i = 0; i < resv.runs.n; ++i) {
-            for (int32_t j = 0; j < resv.runs.len[i]; ++j, ++k) {
-                const int32_t id = resv.first_id > 0 ? resv.first_id + k : 0;   // (0: numbered on the device -- the check only decides whether the key is in use)
-                if (id > 0 && (size_t)id < id2ws.size() && id2ws[id] >= 0) continue;    // already the word's permanent key
-                held_ws.push_back(resv.runs.start[i] + j);
-                held_ids.push_back((id > 0 && (first_id <= 0 || id < first_id)) ? id : 0);   // ids the caller is re-using now name other words
-            }
-        }
-        resv.n = 0;
-        // one check launch per ~32 frames, not per frame (the frame tail that may have used these keys is already enqueued)
-        if (may_flush && held_ws.size() >= 16384) TF_TRY(flush_held());
-    }
-    harvest_released(false);
-    int left = n;
-    while (left > 0 && runs->n < 15 && !ws_free.empty()) {                    // recycled intervals first ...
-        auto it = std::prev(ws_free.end());
-        const int32_t take = std::min(it->second, left);
-        const int32_t start = it->first + it->second - take;
-        runs->start[runs->n] = start; runs->len[runs->n] = take; runs->n += 1;
-        if ((it->second -= take) == 0) ws_free.erase(it);
-        ws_free_count -= take;
-        left -= take;
-    }
-    if (left > 0) {                                                           // ... the rest fresh
-        runs->start[runs->n] = n_wslots; runs->len[runs->n] = left; runs->n += 1;
-        n_wslots += left;
-        TF_TRY(ensure_wslots(n_wslots));
-    }
-    resv.first_id = first_id; resv.n = n; resv.runs = *runs;
-    return hipSuccess;
+    return keys.release_words(word_ids, n);
 }
 
 hipError_t Tfidf::set_bucket(int b) {
@@ -843,7 +516,7 @@ hipError_t Tfidf::ensure_dir2(uint32_t blocks, uint32_t buckets_needed) {
 
 hipError_t Tfidf::seal_batch(const std::vector<int>& ids, bool bulk) {
     if (ids.empty()) return hipSuccess;
-    const uint32_t W = (uint32_t)n_wslots;
+    const uint32_t W = (uint32_t)keys.n_keys();
     TF_TRY(ensure_dir2((W + 31) / 32, (uint32_t)buckets.size() + 1));
     const int tiles = std::max(1, (int)((W + SEAL_TILE - 1) / SEAL_TILE));
     const size_t BATCH = 64;
@@ -880,7 +553,7 @@ hipError_t Tfidf::seal_batch(const std::vector<int>& ids, bool bulk) {
         const dim3 ge((unsigned)std::min<uint32_t>((max_e + SEAL_BLOCK - 1) / SEAL_BLOCK, 512), (unsigned)nb);
         const dim3 gw((unsigned)std::min<uint32_t>((W + SEAL_BLOCK - 1) / SEAL_BLOCK + 1, 512), (unsigned)nb);
         seal_count_kernel<<<ge, SEAL_BLOCK, 0, stream>>>(dj, jobs[0]);
-        seal_densify_kernel<<<gw, SEAL_BLOCK, 0, stream>>>(dj, jobs[0], did.as<int32_t>(), n_dense.as<uint32_t>());
+        seal_densify_kernel<<<gw, SEAL_BLOCK, 0, stream>>>(dj, jobs[0], keys.did.as<int32_t>(), n_dense.as<uint32_t>());
         TF_TRY(hipGetLastError());
         uint32_t D_alloc;
         if (bulk) {
@@ -915,11 +588,11 @@ hipError_t Tfidf::seal_batch(const std::vector<int>& ids, bool bulk) {
         }
         TF_TRY(upload_jobs());
         const dim3 gt((unsigned)tiles, (unsigned)nb);
-        seal_classify_kernel<<<ge, SEAL_BLOCK, 0, stream>>>(dj, jobs[0], did.as<int32_t>(), n_dense.as<uint32_t>(), bkt_D.as<uint32_t>(),
+        seal_classify_kernel<<<ge, SEAL_BLOCK, 0, stream>>>(dj, jobs[0], keys.did.as<int32_t>(), n_dense.as<uint32_t>(), bkt_D.as<uint32_t>(),
                                                            bkt_flags.as<uint32_t>(), h_n_dense);
         seal_tile_kernel<<<gt, SEAL_BLOCK, 0, stream>>>(dj, jobs[0]);
         seal_scan_kernel<<<gt, SEAL_BLOCK, 0, stream>>>(dj, jobs[0]);
-        seal_scatter_kernel<<<ge, SEAL_BLOCK, 0, stream>>>(dj, jobs[0], did.as<int32_t>(), bkt_D.as<uint32_t>());
+        seal_scatter_kernel<<<ge, SEAL_BLOCK, 0, stream>>>(dj, jobs[0], keys.did.as<int32_t>(), bkt_D.as<uint32_t>());
         TF_TRY(hipGetLastError());
         for (size_t j = 0; j < nb; ++j) {
             Bucket& k = buckets[ids[i0 + j]];
@@ -953,7 +626,7 @@ hipError_t Tfidf::flush_retire() {
         const int64_t slot = pending_retire.back();
         pending_retire.pop_back();
         retire_kernel<<<1, 256, 0, stream>>>((long long)slot, buckets[(size_t)(slot / TF_R)].coo_w.as<uint32_t>(), slot_begin.as<uint32_t>(),
-                                             slot_cnt.as<uint32_t>(), nw.as<uint32_t>(), slot_ni.as<uint32_t>(), slot_sig.as<int32_t>());
+                                             slot_cnt.as<uint32_t>(), keys.nw.as<uint32_t>(), slot_ni.as<uint32_t>(), slot_sig.as<int32_t>());
         TF_TRY(hipGetLastError());
     }
     return hipSuccess;
@@ -965,9 +638,9 @@ static hipError_t run_frame_words(Tfidf& t, const int32_t* d_src, int n, bool id
     if (shard_app && (resolve || defer || shard_app->q <= 0 || shard_app->q > 8192)) return hipErrorInvalidValue;
     const int H = next_pow2(std::max(2 * n, 128));
     size_t shmem = ((size_t)H * 2 + H / 64 + 8) * 4;
-    if (ids_given) TF_TRY(t.sync_id2ws());
+    if (ids_given) TF_TRY(t.keys.sync_id2ws());
     FwArgs a;
-    a.src = d_src; a.n = n; a.xlate = ids_given ? t.d_id2ws.as<int32_t>() : nullptr; a.xlate_n = ids_given ? t.d_id2ws_n : 0;
+    a.src = d_src; a.n = n; a.xlate = ids_given ? t.keys.xlate() : nullptr; a.xlate_n = ids_given ? t.keys.xlate_n() : 0;
     a.H = H; a.do_register = reg ? 1 : 0; a.want_q = 1;
     a.sig_id = sig_id; a.slot = (long long)slot; a.slot_local = (uint32_t)(slot % TF_R); a.ni = (uint32_t)ni; a.N = N;
     a.coo_w = nullptr; a.coo_pc = nullptr; a.ne_counter = nullptr;
@@ -982,13 +655,13 @@ static hipError_t run_frame_words(Tfidf& t, const int32_t* d_src, int n, bool id
     t.stamp += 1;
     if (t.stamp == 0) t.stamp = 1;
     a.stamp = t.stamp;
-    a.nw = t.nw.as<uint32_t>(); a.did = t.did.as<int32_t>();
+    a.nw = t.keys.nw.as<uint32_t>(); a.did = t.keys.did.as<int32_t>();
     a.slot_sig = t.slot_sig.as<int32_t>(); a.slot_ni = t.slot_ni.as<uint32_t>(); a.slot_begin = t.slot_begin.as<uint32_t>();
     a.slot_cnt = t.slot_cnt.as<uint32_t>();
     a.q_w = t.q_w.as<uint32_t>(); a.q_idf = t.q_idf.as<int32_t>(); a.q_did = t.q_did.as<int32_t>(); a.qd_did = t.qd_did.as<int32_t>();
-    a.qd_idf = t.qd_idf.as<int32_t>(); a.q_meta = t.q_meta.as<uint32_t>(); a.idf_tab = t.idf_tab.as<uint2>();
+    a.qd_idf = t.qd_idf.as<int32_t>(); a.q_meta = t.q_meta.as<uint32_t>(); a.idf_tab = t.keys.idf_tab.as<uint2>();
     a.new_ws = new_ws ? *new_ws : WsRuns();
-    a.wrow = t.wrow.as<uint32_t>();
+    a.wrow = t.keys.wrow.as<uint32_t>();
     a.row_wslot = nullptr;
     if (defer && !resolve) {                                            // registration alone, launched inside a later filter launch
         defer->a = a; defer->ret = ret; defer->shmem = shmem;
@@ -1056,7 +729,7 @@ hipError_t Tfidf::register_bulk(int n_sigs, const int32_t* sig_ids, const int64_
                                 int64_t total_ids, int max_n) {
     if (n_sigs <= 0) return hipSuccess;
     (void)total_ids;
-    TF_TRY(sync_id2ws());
+    TF_TRY(keys.sync_id2ws());
     const int64_t slot0 = n_slots;
     TF_TRY(ensure_slots(slot0 + n_sigs));
     // buckets touched by the call: the open one is topped up, the others are new; every one that ends up full is sealed
@@ -1081,8 +754,8 @@ hipError_t Tfidf::register_bulk(int n_sigs, const int32_t* sig_ids, const int64_
     const size_t shmem = ((size_t)H * 2 + H / 64 + 8) * 4;
     bulk_register_kernel<<<(unsigned)n_sigs, BR_BLOCK, shmem, stream>>>(d_ids, (const long long*)d_off.p, d_sig.as<int32_t>(),
                                                                          ni ? d_ni.as<int32_t>() : nullptr, (long long)slot0,
-                                                                         d_id2ws.as<int32_t>(), d_id2ws_n, bkt_tab.as<BucketDev>(),
-                                                                         bkt_ne.as<uint32_t>(), nw.as<uint32_t>(), slot_sig.as<int32_t>(),
+                                                                         keys.xlate(), keys.xlate_n(), bkt_tab.as<BucketDev>(),
+                                                                         bkt_ne.as<uint32_t>(), keys.nw.as<uint32_t>(), slot_sig.as<int32_t>(),
                                                                          slot_ni.as<uint32_t>(), slot_begin.as<uint32_t>(), slot_cnt.as<uint32_t>());
     TF_TRY(hipGetLastError());
     std::vector<int> full;
@@ -1118,7 +791,7 @@ hipError_t Tfidf::score_args(float* d_likelihood, long long* lfix, int block, Sc
     A.q_w = q_w.as<uint32_t>(); A.q_idf = q_idf.as<int32_t>(); A.q_did = q_did.as<int32_t>(); A.qd_did = qd_did.as<int32_t>();
     A.qd_idf = qd_idf.as<int32_t>(); A.q_meta = q_meta.as<uint32_t>();
     A.slot_ni = slot_ni.as<uint32_t>(); A.slot_begin = slot_begin.as<uint32_t>(); A.slot_cnt = slot_cnt.as<uint32_t>();
-    A.idf_tab = idf_tab.as<uint2>(); A.stamp = stamp;
+    A.idf_tab = keys.idf_tab.as<uint2>(); A.stamp = stamp;
     A.out_like = d_likelihood; A.out_fix = lfix;
     A.dir2 = dir2.as<uint32_t>(); A.dir2_stride = dir2_stride;
     A.n_closed_pad = (A.n_closed + 7) / 8 * 8;
@@ -1146,21 +819,12 @@ hipError_t Tfidf::launch_score(float* d_likelihood, long long* lfix) {
 hipError_t Tfidf::score_work(int64_t out[8]) {
     for (int i = 0; i < 8; ++i) out[i] = 0;
     if (n_slots == 0) return hipSuccess;
-    TF_TRY(flush_retire());
-    const bool has_open = !buckets.empty() && buckets.back().state == 0;
-    ScoreArgs A;
-    A.tab = bkt_tab.as<BucketDev>(); A.bkt_D = bkt_D.as<uint32_t>(); A.bkt_flags = bkt_flags.as<uint32_t>();
-    A.n_closed = (int)buckets.size() - (has_open ? 1 : 0);
-    A.n_open_slots = has_open ? buckets.back().n_slots : 0;
-    A.wcap = std::max(q_n_ub, 1);
-    A.q_w = q_w.as<uint32_t>(); A.q_idf = q_idf.as<int32_t>(); A.q_did = q_did.as<int32_t>(); A.qd_did = qd_did.as<int32_t>();
-    A.qd_idf = qd_idf.as<int32_t>(); A.q_meta = q_meta.as<uint32_t>();
-    A.slot_ni = slot_ni.as<uint32_t>(); A.slot_begin = slot_begin.as<uint32_t>(); A.slot_cnt = slot_cnt.as<uint32_t>();
-    A.idf_tab = idf_tab.as<uint2>(); A.stamp = stamp; A.out_like = nullptr; A.out_fix = nullptr;
+    ScoreArgs A; int grid = 0;                                         // (no outputs: score_work_kernel never reads them)
+    TF_TRY(score_args(nullptr, nullptr, 256, &A, &grid));
     DevBuf cnt;
     TF_TRY(cnt.reserve(64, 0, stream, bytes_device));
     TF_TRY(hipMemsetAsync(cnt.p, 0, 64, stream));
-    score_work_kernel<<<A.n_closed + 1, 256, 0, stream>>>(A, nw.as<uint32_t>(), (unsigned long long*)cnt.p);
+    score_work_kernel<<<A.n_closed + 1, 256, 0, stream>>>(A, keys.nw.as<uint32_t>(), (unsigned long long*)cnt.p);
     TF_TRY(hipGetLastError());
     TF_TRY(hipMemcpyAsync(out, cnt.p, 64, hipMemcpyDeviceToHost, stream));
     TF_TRY(hipStreamSynchronize(stream));
@@ -1201,29 +865,6 @@ hipError_t Tfidf::retire(int32_t sig_id) {
 }
 
 }  // namespace lcd
-
-// The interval set of recycled postings keys, as the engine keeps it (host code, no device needed: tests).  keys[0 .. n) with ok[i] != 0 are
-// freed -- by_runs: consecutive keys as ONE interval operation (Tfidf::free_wslot_run, what harvest_released does), else key by key --
-// then `take` keys are taken back; out receives the intervals as (start, length) pairs in ascending order.  Returns the number of pairs
-// (or -1 if out is too small); *count = free keys as the set counts them.
-extern "C" int lcd_debug_key_intervals(const int32_t* keys, const unsigned char* ok, int n, int by_runs, int take, int32_t* out, int cap, long long* count) {
-    lcd::Tfidf t;
-    int32_t run_start = 0, run_len = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!ok[i]) { if (by_runs) { t.free_wslot_run(run_start, run_len); run_len = 0; } continue; }
-        if (!by_runs) { t.free_wslot(keys[i]); continue; }
-        if (run_len > 0 && keys[i] == run_start + run_len) { run_len += 1; continue; }
-        t.free_wslot_run(run_start, run_len);
-        run_start = keys[i]; run_len = 1;
-    }
-    if (by_runs) t.free_wslot_run(run_start, run_len);
-    for (int i = 0; i < take; ++i) (void)t.take_wslot();
-    if ((int)t.ws_free.size() > cap) return -1;
-    int k = 0;
-    for (const auto& kv : t.ws_free) { out[2 * k] = kv.first; out[2 * k + 1] = kv.second; k += 1; }
-    if (count) *count = (long long)t.ws_free_count;
-    return k;
-}
 
 #ifdef LCD_SCORE_TIMING
 extern "C" int lcd_debug_score_timing(unsigned long long* out, int n_words) {
