@@ -71,7 +71,11 @@ typedef struct lcd_config {
     int32_t struct_size;       /* sizeof(lcd_config), for ABI evolution */
     int32_t device;            /* HIP device ordinal */
     int32_t dtype;             /* lcd_dtype */
-    int32_t dim;               /* columns: floats (LCD_F32) or bytes (LCD_U8) per descriptor */
+    int32_t dim;               /* columns: floats (LCD_F32) or bytes (LCD_U8) per descriptor.  LCD_U8 rows whose dim is no multiple of 4
+                                  (AKAZE: 61) are stored zero-padded on the device: every entry point that takes HOST rows serves such a
+                                  handle, the ones that take a DEVICE descriptor pointer (lcd_frame_dev, lcd_knn2_dev, lcd_shard_knn2_dev,
+                                  lcd_shard_frame_dev) and lcd_frame_host return LCD_ERR_UNSUPPORTED -- a [q x dim] buffer is not what the
+                                  kernels walk; use lcd_quantize / lcd_knn2 */
     int64_t vocab_capacity;    /* initial row capacity (grows on demand) */
     int64_t sig_capacity;      /* initial signature-slot capacity (grows on demand) */
     int32_t max_queries;       /* initial per-call query capacity (Kp/MaxFeatures; grows on demand) */
@@ -222,7 +226,8 @@ typedef struct lcd_hypothesis {
 typedef struct lcd_frame_args {
     int32_t struct_size;               /* sizeof(lcd_frame_args) */
     int32_t q;                         /* descriptors in the frame (1..8192) */
-    const void* d_descriptors;         /* [q x dim], 16-byte aligned (rows are read as 16-byte vectors) */
+    const void* d_descriptors;         /* [q x dim], 16-byte aligned (rows are read as 16-byte vectors).  A handle whose rows are padded
+                                          (lcd_config.dim): LCD_ERR_UNSUPPORTED, nothing is enqueued */
     int32_t flags;                     /* lcd_quantize_flags */
     float nndr_ratio;
     int32_t sig_id;                    /* != 0: register the frame as this signature (it must not exist yet) */
@@ -278,7 +283,8 @@ int lcd_frame_dev(lcd_engine* h, const lcd_frame_args* args);
 typedef struct lcd_frame_host_args {
     int32_t struct_size;               /* sizeof(lcd_frame_host_args) */
     int32_t q;                         /* descriptors in the frame (1..8192) */
-    const void* descriptors;           /* HOST [q x dim], row-major, as cv::Mat::data of a continuous matrix */
+    const void* descriptors;           /* HOST [q x dim], row-major, as cv::Mat::data of a continuous matrix.  A handle whose rows are
+                                          padded (lcd_config.dim): LCD_ERR_UNSUPPORTED (the mirror then takes the call-by-call path) */
     int32_t flags;                     /* lcd_quantize_flags */
     float nndr_ratio;
     int32_t sig_id;                    /* != 0: register the frame as this signature */
@@ -338,7 +344,8 @@ int lcd_bayes_update(lcd_engine* h, const int32_t* sig_ids, const float* adjuste
 /* the filter's current posterior for some signatures (host arrays; unknown / never considered signatures -> 0); sig id -1 = the
  * virtual place.  Synchronises. */
 int lcd_bayes_posterior(lcd_engine* h, const int32_t* sig_ids, int n, float* out);
-/* lcd_knn2 with device-resident queries and outputs (d_word_ids[q*2], d_dist[q*2]); enqueued, not synchronised */
+/* lcd_knn2 with device-resident queries [q x dim] and outputs (d_word_ids[q*2], d_dist[q*2]); enqueued, not synchronised.  A handle whose
+ * rows are padded (lcd_config.dim): LCD_ERR_UNSUPPORTED, nothing is enqueued. */
 int lcd_knn2_dev(lcd_engine* h, const void* d_queries, int q, int32_t* d_word_ids, float* d_dist);
 /* ---- vocabulary sharded by word-ID range over several engines/GPUs (one handle per rank).
  * Every rank holds a consecutive id range of the vocabulary and the references of those words; every rank registers
@@ -348,7 +355,9 @@ int lcd_knn2_dev(lcd_engine* h, const void* d_queries, int q, int32_t* d_word_id
  * order-free, so the result equals the single-GPU one bit for bit -- (5) lcd_finalize_dev.
  * (1) and (3) of a frame are one pair: the search also leaves the frame's same-frame distance matrix on the handle (it rides in the
  * filter's launch), and the frame call that follows it with the SAME d_descriptors pointer and q -- their content unchanged in between --
- * takes it from there; any other frame call computes the matrix itself. */
+ * takes it from there; any other frame call computes the matrix itself.
+ * d_descriptors is [q x dim] as for lcd_frame_dev; both calls return LCD_ERR_UNSUPPORTED on a handle whose rows are padded (lcd_config.dim),
+ * before anything is enqueued. */
 typedef struct lcd_shard_cand { uint64_t key; int32_t word; int32_t wslot; } lcd_shard_cand;
 int lcd_shard_knn2_dev(lcd_engine* h, const void* d_descriptors, int q, lcd_shard_cand* d_cand /* [q*2] */);
 int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int flags, float nndr_ratio, int32_t sig_id,

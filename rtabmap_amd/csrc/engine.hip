@@ -1014,7 +1014,9 @@ int lcd_adjust_likelihood_dev(lcd_engine* h, float* d_likelihood, int n, float v
 int lcd_knn2_dev(lcd_engine* h, const void* d_queries, int q, int32_t* d_word_ids, float* d_dist) {
     LCD_TRY
     LCD_CHECK_HANDLE(h);
-    LCD_DEV(h);
+    LCD_DEV_NODRAIN(h);
+    if (rows_padded(h)) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_knn2_dev: rows of this size are padded on the device (use lcd_knn2)");
+    { int rc = h->drain(); if (rc) return rc; }
     if (q <= 0 || !d_queries || !d_word_ids || !d_dist) return h->fail(LCD_ERR_INVALID, "lcd_knn2_dev: bad argument");
     if (((uintptr_t)d_queries & 15u) != 0) return h->fail(LCD_ERR_INVALID, "lcd_knn2_dev: d_queries must be 16-byte aligned");
     LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
@@ -1185,6 +1187,7 @@ int lcd_shard_knn2_dev(lcd_engine* h, const void* d_descriptors, int q, lcd_shar
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV_NODRAIN(h);
+    if (rows_padded(h)) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_shard_knn2_dev: rows of this size are padded on the device (use lcd_knn2)");
     { int rc = drain_keep_rows_lazy(h); if (rc) return rc; }
     if (q <= 0 || !d_descriptors || !d_cand) return h->fail(LCD_ERR_INVALID, "lcd_shard_knn2_dev: bad argument");
     if (((uintptr_t)d_descriptors & 15u) != 0) return h->fail(LCD_ERR_INVALID, "lcd_shard_knn2_dev: d_descriptors must be 16-byte aligned");
@@ -1232,6 +1235,7 @@ int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int fla
     LCD_TRY
     LCD_CHECK_HANDLE(h);
     LCD_DEV_NODRAIN(h);
+    if (rows_padded(h)) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_shard_frame_dev: rows of this size are padded on the device (use lcd_quantize)");
     { int rc = drain_keep_rows_lazy(h); if (rc) return rc; }
     const bool matrix_left = h->shard_sd_desc != nullptr && h->shard_sd_desc == d_descriptors && h->shard_sd_q == q;   // by this frame's search
     h->shard_sd_desc = nullptr;                                       // (one frame call per search: whatever happens below, it is used up)
@@ -1251,7 +1255,7 @@ int lcd_shard_frame_dev(lcd_engine* h, const void* d_descriptors, int q, int fla
     const bool cyclic = h->shard_block > 0 && h->shard_first > 0;
     // the frame's new words become rows of this rank's shard on the device (shard_append): they need postings keys and an owner whether or
     // not the frame is registered as a signature (a query-only frame: the single-GPU path reserves keys whenever frame_appends() holds)
-    const bool dev_append = h->shard_append && (flags & LCD_Q_INCREMENTAL) && first_new_word_id > 0 && h->row_bytes == h->dim * (h->dtype == LCD_F32 ? 4 : 1);
+    const bool dev_append = h->shard_append && (flags & LCD_Q_INCREMENTAL) && first_new_word_id > 0;
     if (cyclic && (sig_id != 0 || dev_append) && first_new_word_id > 0 && (flags & LCD_Q_INCREMENTAL) && first_new_word_id < h->shard_first)
         return h->fail(LCD_ERR_INVALID, "lcd_shard_frame_dev: first_new_word_id lies in front of shard_growth_first");
     const int have_index = total_live_rows >= 2 ? 1 : 0;

@@ -27,6 +27,10 @@ static inline hipError_t dreserve(lcd_engine* h, lcd::DevBuf& b, size_t bytes, s
     return b.reserve(bytes, keep, h->stream, &h->bytes_device);
 }
 
+// u8 rows whose `dim` is no multiple of 4 are stored zero-padded (row_bytes > dim): a caller's [q x dim] DEVICE buffer does not have the layout
+// the kernels walk (they stride by row_bytes), so every entry point that takes one refuses such a handle; host rows are padded as they are staged
+static inline bool rows_padded(const lcd_engine* h) { return (size_t)h->row_bytes != (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1); }
+
 // ---- VWDictionary::update()'s append branch on the device (see engine.h)
 static inline int64_t vocab_cap_rows(const lcd_engine* h) {
     int64_t c = (int64_t)(h->vocab.cap / (size_t)h->row_bytes);

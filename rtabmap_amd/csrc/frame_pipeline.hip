@@ -62,10 +62,11 @@ static int frame_score_s(lcd_engine* h, const lcd_frame_args& a) {
     return hypothesis_stage(h, a);
 }
 
-// (any descriptor type: rows that are not 64 floats are copied without the matrix-core filter's tables -- such handles are never pipelined)
+// (any descriptor type: rows that are not 64 floats are copied without the matrix-core filter's tables -- such handles are never pipelined;
+// rows are stored as they arrive: a handle whose rows are padded does not get here, frame_dev_body refuses it)
 static bool frame_appends(const lcd_engine* h, const lcd_frame_args& a) {
-    return a.append_new_words != 0 && (a.first_new_word_id > 0 || a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO) && (a.flags & LCD_Q_INCREMENTAL) != 0 &&
-           h->row_bytes == h->dim * (h->dtype == LCD_F32 ? 4 : 1);     // (rows are stored as they arrive: no padding to add on the device)
+    (void)h;
+    return a.append_new_words != 0 && (a.first_new_word_id > 0 || a.first_new_word_id == LCD_NEW_WORD_IDS_AUTO) && (a.flags & LCD_Q_INCREMENTAL) != 0;
 }
 
 // Who numbers the words this frame creates.  LCD_NEW_WORD_IDS_AUTO: the device, id = row + id_delta -- exact as long as every unreconciled appender is
@@ -505,6 +506,7 @@ static int frame_dev_body(lcd_engine* h, const lcd_frame_args* a) {
     const int q = a->q;
     if (q <= 0 || q > 8192 || !a->d_descriptors || !a->d_word_ids) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: bad argument");
     if (((uintptr_t)a->d_descriptors & 15u) != 0) return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: d_descriptors must be 16-byte aligned");
+    if (rows_padded(h)) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_dev: rows of this size are padded on the device (use lcd_quantize)");
     if ((a->d_hypothesis || a->d_adjusted || a->d_posterior || a->d_bayes) && !a->d_likelihood)
         return h->fail(LCD_ERR_INVALID, "lcd_frame_dev: the hypothesis needs d_likelihood");
     if ((a->d_posterior || a->d_bayes) && !h->bayes.configured) return h->fail(LCD_ERR_STATE, "lcd_frame_dev: lcd_bayes_configure first");
@@ -566,8 +568,7 @@ int lcd_frame_host(lcd_engine* h, const lcd_frame_host_args* a) {
     if (!a || a->struct_size != (int32_t)sizeof(lcd_frame_host_args)) return h->fail(LCD_ERR_INVALID, "lcd_frame_host: bad argument block");
     const int q = a->q;
     if (q <= 0 || q > 8192 || !a->descriptors || !a->word_ids) return h->fail(LCD_ERR_INVALID, "lcd_frame_host: bad argument");
-    const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-    if (src_row != (size_t)h->row_bytes) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_host: rows of this size are padded on the device (use lcd_quantize)");
+    if (rows_padded(h)) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_frame_host: rows of this size are padded on the device (use lcd_quantize)");
     const int64_t slots_after = h->tfidf.n_slots + (a->sig_id != 0 ? 1 : 0);
     if (a->likelihood && a->likelihood_capacity < slots_after) return h->fail(LCD_ERR_INVALID, "lcd_frame_host: likelihood buffer too small");
     // descriptors: host -> pinned staging -> device, on the engine's stream (the one synchronisation at the end frees the staging)

@@ -157,3 +157,62 @@ def min_word_visibility(sigs, query, live=None):
     best = np.zeros(uw.size)
     np.maximum.at(best, inv, rel)
     return float(best.min()) if best.size else 0.0
+
+
+# ---- descriptor shapes the engine picks different device code for (tests/test_gpu_descriptor_sizes.py)
+
+# (dtype, dim, the detector it stands for).  What each one selects: f32 x 128 the fixed-DIM float kernels and a row writer that makes 8 trips;
+# f32 x 256 the dynamic float kernels, 16 trips; f32 x 6 rows that are not 16-byte aligned, l2_ref_dyn's scalar tail, 6 dwords per row (10 of a
+# row's 16 lanes idle); u8 x 16 knn2_hamming_kernel<4>, 4 dwords; u8 x 64 knn2_hamming_kernel<16>, exactly one trip; u8 x 24 w32 == 6: the
+# dynamic Hamming scan; u8 x 61 rows padded to 64 bytes on the device
+DESCRIPTOR_SHAPES = [
+    ("f32", 128, "SIFT, extended SURF / KAZE"),
+    ("f32", 256, "SuperPoint"),
+    ("f32", 6, "no detector"),
+    ("u8", 16, "BRIEF-16"),
+    ("u8", 64, "BRISK, FREAK"),
+    ("u8", 24, "no detector"),
+    ("u8", 61, "AKAZE MLDB"),
+]
+
+
+def shape_id(shape):
+    return "%sx%d" % (shape[0], shape[1])
+
+
+def unit_rows(n, dim, seed):
+    """n unit-norm Gaussian float32 rows of ANY dimension (synth.vocab_surf shapes its rows in groups of four floats)."""
+    rng = np.random.default_rng(seed)
+    v = rng.standard_normal((n, dim)).astype(np.float32)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    return np.ascontiguousarray(v, dtype=np.float32)
+
+
+def rows_of(shape, n, seed):
+    """n fresh descriptors of a shape: unit-norm floats or uniform random bytes."""
+    if shape[0] == "f32":
+        return unit_rows(n, shape[1], seed)
+    return np.random.default_rng(seed).integers(0, 256, (n, shape[1]), dtype=np.uint8)
+
+
+def noisy(rows, rng, sigma=0.02, flip=0.02):
+    """Copies of `rows` a detector would produce at the same place again: Gaussian noise of `sigma` per component and renormalised (float), or
+    each bit flipped with probability `flip` (binary)."""
+    out = rows.copy()
+    if rows.dtype == np.uint8:
+        out ^= np.packbits(rng.random((rows.shape[0], rows.shape[1] * 8)) < flip, axis=1)
+        return np.ascontiguousarray(out)
+    out += rng.standard_normal(out.shape).astype(np.float32) * np.float32(sigma)
+    out /= np.linalg.norm(out, axis=1, keepdims=True)
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def queries_of(shape, vocab, q, seed, frac_known=0.8, sigma=0.03, flip=0.05):
+    """q descriptors: `frac_known` of them noisy copies of vocabulary rows (NNDR accepts), the others fresh (would-be new words) -- what
+    synth.queries_surf / queries_orb give at 64 floats / any byte count, for every shape."""
+    rng = np.random.default_rng(seed)
+    out = rows_of(shape, q, seed + 7919)
+    known = rng.random(q) < frac_known
+    src = rng.integers(0, vocab.shape[0], q)
+    out[known] = noisy(vocab[src[known]], rng, sigma, flip)
+    return np.ascontiguousarray(out)

@@ -7,18 +7,23 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import rows_of
 from rtabmap_amd import synth
 from test_gpu_frame_stream import _revisit, RTOL, ATOL
 
 pytestmark = pytest.mark.gpu
 
 
-def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="surf", knn_mode=None, options=None, clean_every_frame=False, auto_ids=False,
-            fresh_frac=0.3, min_words_in_a_frame=0):
-    import rtabmap_amd
-    from rtabmap_amd import capi
+def _oracle_stream(oracle, n_words, q, n_frames, seed, kind="surf", fresh_frac=0.3, shape=None):
+    """The oracle's half of an appending stream, before any engine exists: a base vocabulary, bulk signatures that reference every word, then
+    n_frames revisiting frames through Memory::update.  shape: (dtype, dim) of tests/helpers.py's table instead of `kind`'s 64 floats / 32 bytes.
+    Returns (base rows, their ids, bulk words [n_bulk x q], frames, the id of each frame's first new word, word ids, likelihoods)."""
     rng = np.random.default_rng(seed)
-    base = synth.vocab_surf(n_words, seed=seed + 1) if kind == "surf" else synth.vocab_orb(n_words, seed=seed + 1)
+    if shape is not None:
+        kind = "surf" if shape[0] == "f32" else "orb"
+        base = rows_of(shape, n_words, seed + 1)
+    else:
+        base = synth.vocab_surf(n_words, seed=seed + 1) if kind == "surf" else synth.vocab_orb(n_words, seed=seed + 1)
     n_bulk = max(40, (n_words + q - 1) // q + 2)
     words = synth.zipf_words(n_bulk, q, n_words, seed=seed + 2)
     words.reshape(-1)[-n_words:] = np.arange(1, n_words + 1, dtype=np.int32)       # every word referenced: cleanUnusedWords drops none
@@ -33,7 +38,7 @@ def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="su
     history = [base[rng.integers(0, n_words, q)] for _ in range(2)]
     frames, first_new, expected, likes = [], [], [], []
     for t in range(n_frames):
-        desc = _revisit(rng, kind, history, base, q, fresh_frac=fresh_frac)
+        desc = _revisit(rng, kind, history, base, q, fresh_frac=fresh_frac, shape=shape)
         history.append(desc)
         first_new.append(m.vwd.last_word_id + 1)
         sid, exp = m.update(desc)
@@ -43,9 +48,19 @@ def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="su
         live = np.array(m.signature_ids(), np.int32)
         likes.append(m.compute_likelihood(np.array(exp, np.int32), live)[1])
     assert not m.vwd.get_unused_word_ids()
+    return base, ids, words, frames, first_new, expected, likes
+
+
+def _stream(oracle, pipeline, n_words, q, n_frames, seed, sync_every=0, kind="surf", knn_mode=None, options=None, clean_every_frame=False, auto_ids=False,
+            fresh_frac=0.3, min_words_in_a_frame=0, shape=None):
+    """shape: (dtype, dim) of tests/helpers.py's table instead of `kind`'s 64 floats / 32 bytes."""
+    import rtabmap_amd
+    from rtabmap_amd import capi
+    base, ids, words, frames, first_new, expected, likes = _oracle_stream(oracle, n_words, q, n_frames, seed, kind, fresh_frac, shape)
+    n_bulk = words.shape[0]
     # (by the oracle's ids, before anything runs on the device: a caller that needs a frame with that many new words has one)
     assert max(len(set(w for w in exp if w >= first)) for exp, first in zip(expected, first_new)) >= min_words_in_a_frame
-    eng = rtabmap_amd.Engine("f32" if kind == "surf" else "u8", base.shape[1], sig_capacity=n_bulk + n_frames + 8, pipeline=pipeline, knn_mode=knn_mode)
+    eng = rtabmap_amd.Engine("f32" if base.dtype == np.float32 else "u8", base.shape[1], sig_capacity=n_bulk + n_frames + 8, pipeline=pipeline, knn_mode=knn_mode)
     for key, value in (options or {}).items():
         eng.set_option(key, value)
     eng.vocab_append(base, ids)

@@ -11,17 +11,23 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import unit_rows
 from rtabmap_amd import synth
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-4, 1e-7
 
 
-def _revisit(rng, kind, history, vocab_rows, q, fresh_frac):
+def _revisit(rng, kind, history, vocab_rows, q, fresh_frac, shape=None):
     """A frame that revisits an earlier frame: noisy copies of that frame's descriptors (so that words the earlier frame CREATED
-    are matched again) plus some fresh descriptors."""
+    are matched again) plus some fresh descriptors.  shape: (dtype, dim) of tests/helpers.py's table instead of 64-float SURF rows /
+    binary rows as wide as the vocabulary's (`kind` is then taken from it)."""
+    if shape is not None:
+        kind = "surf" if shape[0] == "f32" else "orb"
     if kind == "orb":
         fresh = rng.integers(0, 256, (q, vocab_rows.shape[1]), dtype=np.uint8)
+    elif shape is not None:
+        fresh = unit_rows(q, shape[1], seed=int(rng.integers(1 << 30)))
     else:
         fresh = synth.vocab_surf(q, seed=int(rng.integers(1 << 30)))
     if not history:
