@@ -52,19 +52,24 @@ enum lcd_quantize_flags {
     LCD_Q_NEW_WORDS_COMPARED = 2        /* Kp/NewWordsComparedTogether: also match words created earlier in the same call */
 };
 
-/* how the squared-L2 2-NN of 64-float descriptors is computed.  Every mode returns the SAME bits (the reference's distances and
- * tie-break): the matrix-core modes only rank candidates, an exact re-rank in the reference's arithmetic plus a completeness
- * certificate (exact redo when it fails) produces the result.  Other descriptor types always use the exact scan. */
+/* how the 2-NN is computed.  Every mode returns the SAME bits (the reference's distances and tie-break).
+ * Squared L2 of 64-float descriptors: the matrix-core modes only rank candidates, an exact re-rank in the reference's arithmetic plus a
+ * completeness certificate (exact redo when it fails) produces the result; float rows of any other length use the exact scan.
+ * Hamming (LCD_U8 handles): the exact vector-ALU scan unless the handle asks for LCD_KNN_HAMMING_MFMA, which computes the same integer
+ * distances on the i8 matrix cores (an integer dot product: no filter, no re-rank); the float modes mean LCD_KNN_DEFAULT there. */
 enum lcd_knn_mode {
     LCD_KNN_DEFAULT = 0,       /* = LCD_KNN_BF16X3 where it applies */
     LCD_KNN_EXACT_VALU = 1,    /* exact vector-ALU scan only */
     LCD_KNN_F32_MFMA = 2,      /* fp32 matrix-core filter (v_mfma_f32_32x32x2_f32) + exact re-rank */
     LCD_KNN_BF16X3 = 3,        /* bf16 matrix-core filter, three bf16 products per fp32 product + exact re-rank */
-    LCD_KNN_F16 = 4            /* fp16 matrix-core filter, ONE product per fp32 product (operands rounded to IEEE half: a third of the
+    LCD_KNN_F16 = 4,           /* fp16 matrix-core filter, ONE product per fp32 product (operands rounded to IEEE half: a third of the
                                   matrix work, an error bound of ~2^-10 (|q|^2 + |v|^2) instead of ~2^-14) + exact re-rank.  Made for
                                   unit-scale descriptors (SURF/SIFT are L2-normalised); queries whose certificate the wider bound
                                   cannot give -- and descriptors beyond half's range -- go to the exact scan, so the results stay the
                                   same bits; a vocabulary of near-duplicate words makes that the common case and this mode the slower one */
+    LCD_KNN_HAMMING_MFMA = 5   /* LCD_U8 handles, any row length: the Hamming 2-NN of the main vocabulary (256 rows or more) on the matrix cores
+                                  (v_mfma_i32_32x32x32_i8 over bits written as +-127 bytes), exact by construction.  Opt-in: LCD_KNN_DEFAULT on
+                                  a u8 handle stays the vector-ALU scan.  On an LCD_F32 handle it means LCD_KNN_DEFAULT */
 };
 
 typedef struct lcd_config {

@@ -28,8 +28,9 @@ SYMBOLS = [
 ]
 
 
-LCD_KNN_DEFAULT, LCD_KNN_EXACT_VALU, LCD_KNN_F32_MFMA, LCD_KNN_BF16X3, LCD_KNN_F16 = 0, 1, 2, 3, 4
-KNN_MODES = {None: 0, "default": 0, "valu": 1, "exact": 1, "mfma32": 2, "f32": 2, "bf16": 3, "bf16x3": 3, "f16": 4, "fp16": 4}
+LCD_KNN_DEFAULT, LCD_KNN_EXACT_VALU, LCD_KNN_F32_MFMA, LCD_KNN_BF16X3, LCD_KNN_F16, LCD_KNN_HAMMING_MFMA = 0, 1, 2, 3, 4, 5
+KNN_MODES = {None: 0, "default": 0, "valu": 1, "exact": 1, "mfma32": 2, "f32": 2, "bf16": 3, "bf16x3": 3, "f16": 4, "fp16": 4,
+             "hamming_mfma": 5}     # u8 handles: Hamming 2-NN on the i8 matrix cores; on an f32 handle the default
 
 
 class LcdConfig(C.Structure):

@@ -283,6 +283,7 @@ struct lcd_engine {
     int f16() const { return knn_mode == 3 ? 1 : 0; }
     int knn_mode = 2;                                   // f32 dim 64: 2 = bf16x3 MFMA filter + exact re-rank (default), 3 = fp16 one-product filter, 1 = f32 MFMA filter
                                                         // + exact re-rank, 0 = exact VALU scan only (lcd_config.knn_mode)
+    bool hamming_mfma = false;                          // u8 handles, LCD_KNN_HAMMING_MFMA: the main vocabulary's Hamming 2-NN runs on the i8 matrix cores (knn_hamming_mfma.hip)
     // ---- pipelined frames (lcd_config.pipeline): see FramePipeline
     int pipeline = 0;
     hipStream_t kst = nullptr;                          // the stream the 2-NN stage is enqueued on (== stream)

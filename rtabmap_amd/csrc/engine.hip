@@ -109,6 +109,25 @@ static void fill_redo(lcd_engine* h, RowparArgs* a, const void* vocab, const int
     if (cb) a->cb = *cb;
 }
 
+// The partial keys [n_blocks][2][qpad] of an exact search, into d_partial; *pm is what the merge launches read.  The main vocabulary of a u8 handle in
+// LCD_KNN_HAMMING_MFMA mode is searched on the matrix cores from 256 rows on (the threshold of the float matrix-core modes), everything else by the scan.
+static int scan_partial(lcd_engine* h, const void* d_queries, int q, const void* vocab, const int32_t* row_id, int64_t n_rows, bool main_vocab, KnnPlan* pm) {
+    const bool prof = main_vocab && h->prof_cap > 0 && h->prof_n < h->prof_cap;
+    const bool hmfma = main_vocab && h->hamming_mfma && h->dtype == LCD_U8 && n_rows >= 256;
+    const HammingMfmaPlan hp = hmfma ? knn_hamming_mfma_plan(q, (int)n_rows, h->row_bytes) : HammingMfmaPlan{};
+    *pm = hmfma ? knn_hamming_mfma_merge_plan(hp) : knn_plan(q, (int)n_rows, h->row_bytes);
+    LCD_HIP(h, dreserve(h, h->d_partial, hmfma ? knn_hamming_mfma_partial_bytes(hp) : knn_partial_bytes(*pm)));
+    if (prof) LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n], h->kst));
+    if (hmfma) LCD_HIP(h, launch_knn2_hamming_mfma(vocab, row_id, d_queries, hp, h->d_partial.as<uint64_t>(), h->kst));
+    else LCD_HIP(h, launch_knn2_partial(h->dtype, h->kdim, vocab, row_id, d_queries, *pm, h->d_partial.as<uint64_t>(), h->kst));
+    if (prof) {
+        LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n + 1], h->kst));
+        h->prof_n += 1;
+        h->prof_kernel = hmfma ? "knn2_hamming_mfma_kernel" : h->dtype == LCD_F32 ? "knn2_l2_kernel" : "knn2_hamming_kernel";
+    }
+    return LCD_OK;
+}
+
 // 2-NN of q device-resident queries against a row matrix -> o_{row,word,dist}[q*2].  `main_vocab` selects the resident
 // vocabulary (which has row norms and may use the MFMA filter); other matrices (findNN's not-indexed words) use the exact scan.
 int run_knn2_raw(lcd_engine* h, const void* d_queries, int q, const void* vocab, const int32_t* row_id, int64_t n_rows, bool main_vocab,
@@ -118,7 +137,6 @@ int run_knn2_raw(lcd_engine* h, const void* d_queries, int q, const void* vocab,
     if (packed) *packed = false;
     if (q == 0) return LCD_OK;
     const bool mfma = main_vocab && h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim) && n_rows >= 256;
-    const KnnPlan p = knn_plan(q, (int)n_rows, h->row_bytes);
     if (mfma && h->bf_family()) {
         MfmaPlan mp = knn_bf16_plan(q, (int)n_rows, cb != nullptr ? knn_selfdist_wgs(q) : 0);
         mp.filter_units = h->filter_units;
@@ -161,12 +179,10 @@ int run_knn2_raw(lcd_engine* h, const void* d_queries, int q, const void* vocab,
             if (pack && packed) *packed = true;
         }
     } else {
-        LCD_HIP(h, dreserve(h, h->d_partial, knn_partial_bytes(p)));
-        const bool prof = main_vocab && h->prof_cap > 0 && h->prof_n < h->prof_cap;
-        if (prof) LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n], h->kst));
-        LCD_HIP(h, launch_knn2_partial(h->dtype, h->kdim, vocab, row_id, d_queries, p, h->d_partial.as<uint64_t>(), h->kst));
-        if (prof) { LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n + 1], h->kst)); h->prof_n += 1; h->prof_kernel = h->dtype == LCD_F32 ? "knn2_l2_kernel" : "knn2_hamming_kernel"; }
-        LCD_HIP(h, launch_knn2_merge(h->dtype, p, h->d_partial.as<uint64_t>(), row_id, o_row, o_word, o_dist, h->kst));
+        KnnPlan pm;
+        const int rc = scan_partial(h, d_queries, q, vocab, row_id, n_rows, main_vocab, &pm);
+        if (rc) return rc;
+        LCD_HIP(h, launch_knn2_merge(h->dtype, pm, h->d_partial.as<uint64_t>(), row_id, o_row, o_word, o_dist, h->kst));
     }
     h->knn_launches += 1;
     if (mfma) h->last_fail_count = h->d_fail_count.p;
@@ -323,12 +339,9 @@ int prepare_resolve(lcd_engine* h, const void* d_desc, int q, int flags, float n
         LCD_HIP(h, dreserve(h, h->d_knn_row, (size_t)q * 2 * 4));
         LCD_HIP(h, dreserve(h, h->d_knn_word, (size_t)q * 2 * 4));
         LCD_HIP(h, dreserve(h, h->d_knn_dist, (size_t)q * 2 * 4));
-        const KnnPlan p = knn_plan(q, (int)knn_rows, h->row_bytes);
-        LCD_HIP(h, dreserve(h, h->d_partial, knn_partial_bytes(p)));
-        const bool prof = h->prof_cap > 0 && h->prof_n < h->prof_cap;
-        if (prof) LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n], h->kst));
-        LCD_HIP(h, launch_knn2_partial(h->dtype, h->kdim, h->vocab.p, h->row_id.as<int32_t>(), d_desc, p, h->d_partial.as<uint64_t>(), h->kst));
-        if (prof) { LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n + 1], h->kst)); h->prof_n += 1; h->prof_kernel = "knn2_hamming_kernel"; }
+        KnnPlan p;
+        rc = scan_partial(h, d_desc, q, h->vocab.p, h->row_id.as<int32_t>(), knn_rows, true, &p);
+        if (rc) return rc;
         LCD_HIP(h, launch_knn2_merge_selfdist_hamming(p, h->d_partial.as<uint64_t>(), h->row_id.as<int32_t>(), h->d_knn_row.as<int32_t>(),
                                                       h->d_knn_word.as<int32_t>(), h->d_knn_dist.as<float>(), d_desc, h->kdim, h->d_selfdist.as<float>(), ld,
                                                       have_index, h->d_bits.as<uint32_t>(), bw, h->kst));
@@ -377,13 +390,13 @@ int lcd_create(const lcd_config* cfg, lcd_engine** out) {
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(lcd_config)) return LCD_ERR_INVALID;
     if (cfg->dim <= 0 || cfg->dim > 4096 || (cfg->dtype != LCD_F32 && cfg->dtype != LCD_U8)) return LCD_ERR_INVALID;
-    if (cfg->knn_mode < LCD_KNN_DEFAULT || cfg->knn_mode > LCD_KNN_F16) return LCD_ERR_INVALID;
+    if (cfg->knn_mode < LCD_KNN_DEFAULT || cfg->knn_mode > LCD_KNN_HAMMING_MFMA) return LCD_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return LCD_ERR_HIP;
     if (hipSetDevice(cfg->device) != hipSuccess) return LCD_ERR_HIP;
     {   // the filter's launch plans fill THIS device's compute units (256 on MI355X; fewer on a partitioned part)
         int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) knn_set_compute_units(cus);
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) { knn_set_compute_units(cus); knn_hamming_mfma_set_compute_units(cus); }
     }
     lcd_engine* h = new (std::nothrow) lcd_engine();
     if (!h) return LCD_ERR_NOMEM;
@@ -410,6 +423,7 @@ int lcd_create(const lcd_config* cfg, lcd_engine** out) {
     if (e == hipSuccess) e = h->d_hyp_scratch.reserve(64, 0, h->stream, &h->bytes_device);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_fail_count.p, 0, 64, h->stream);
     h->knn_mode = cfg->knn_mode == LCD_KNN_EXACT_VALU ? 0 : cfg->knn_mode == LCD_KNN_F32_MFMA ? 1 : cfg->knn_mode == LCD_KNN_F16 ? 3 : 2;
+    h->hamming_mfma = cfg->knn_mode == LCD_KNN_HAMMING_MFMA && cfg->dtype == LCD_U8;   // (on an f32 handle the value means the default, above)
     h->kst = h->stream;
     if (cfg->pipeline < 0 || cfg->pipeline > 1) { delete h; return LCD_ERR_INVALID; }
     h->pipeline = cfg->pipeline;

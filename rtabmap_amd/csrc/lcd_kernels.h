@@ -32,6 +32,20 @@ hipError_t launch_knn2_merge_selfdist_hamming(const KnnPlan& p, const uint64_t* 
                                               float* out_dist, const void* queries, int dim_bytes, float* selfdist, int ld, int have_index, uint32_t* bits,
                                               int bw, hipStream_t s);
 
+// ---- Hamming 2-NN on the i8 matrix cores (knn_hamming_mfma.hip, LCD_KNN_HAMMING_MFMA): writes the partial keys launch_knn2_partial writes
+// for u8 rows, exactly; the merges above take them through knn_hamming_mfma_merge_plan().
+struct HammingMfmaPlan {
+    int q, qpad, n_rows, rows_per_block, n_blocks;
+    int w32;           // dwords per row
+    int group_q;       // queries per workgroup (grid.y = ceil(qpad / group_q))
+};
+HammingMfmaPlan knn_hamming_mfma_plan(int q, int n_rows, int dim_bytes);
+KnnPlan knn_hamming_mfma_merge_plan(const HammingMfmaPlan& p);   // n_blocks and qpad are what the merges read
+size_t knn_hamming_mfma_partial_bytes(const HammingMfmaPlan& p);
+void knn_hamming_mfma_set_compute_units(int cus);                // the device's compute units: the plan aims at two workgroups on each
+hipError_t launch_knn2_hamming_mfma(const void* vocab, const int32_t* row_id, const void* queries, const HammingMfmaPlan& p, uint64_t* partial,
+                                    hipStream_t s);
+
 // Optional by-product of the MFMA 2-NN: the candidate bit matrix of the addNewWords resolution (see launch_selfdist) from an
 // already computed same-frame distance matrix.  bits == nullptr: not wanted.
 struct CandBits {
