@@ -398,7 +398,8 @@ int lcd_profile_read_likelihood(lcd_engine* h, float* avg_ms, int* n_samples, co
  * pipelined frame hands the registration the vocabulary ROW of every matched word and the registration looks the postings key up (in the
  * round trip that fetches the retired signature's words); 0 = the decision loop gathers the keys itself.  "score_block": threads per workgroup of the scoring kernel
  * (256 / 512 / 1024).  "filter_units": compute units the bf16 filter plans its persistent workgroups for when the vocabulary has
- * more 256-word strips than that (-1 built-in, 0 never persistent).  "decision_straight": 1 (built-in: while the stream creates 16 words per frame or more; 2 = always; 0 = never) = the decision loop of a pipelined frame requests
+ * more 256-word strips than that (-1 built-in, 0 never persistent).  A value > 0 is also the number of compute units the matrix-core Hamming scan of a u8 handle
+ * (LCD_KNN_HAMMING_MFMA) plans its workgroups for (two on each; 0 and -1: the device's own count).  "decision_straight": 1 (built-in: while the stream creates 16 words per frame or more; 2 = always; 0 = never) = the decision loop of a pipelined frame requests
  * everything its first round trip reads unconditionally, in one straight line (faster while frames create words, slower once they only revisit: DESIGN.md 4d).  "next_word_id": one past the highest word id handed out so far (VWDictionary::_lastWordId + 1): where LCD_NEW_WORD_IDS_AUTO continues (never lowered: the handle
  * keeps the maximum of this and the ids of the rows it has seen).  "profile_skip": the number of launches of a pipelined handle that lcd_profile_begin lets pass before it brackets one (0; the first launches behind an idle
  * queue are not the steady state).  "profile_likelihood": 0 = lcd_profile_begin brackets only the

@@ -114,7 +114,7 @@ static void fill_redo(lcd_engine* h, RowparArgs* a, const void* vocab, const int
 static int scan_partial(lcd_engine* h, const void* d_queries, int q, const void* vocab, const int32_t* row_id, int64_t n_rows, bool main_vocab, KnnPlan* pm) {
     const bool prof = main_vocab && h->prof_cap > 0 && h->prof_n < h->prof_cap;
     const bool hmfma = main_vocab && h->hamming_mfma && h->dtype == LCD_U8 && n_rows >= 256;
-    const HammingMfmaPlan hp = hmfma ? knn_hamming_mfma_plan(q, (int)n_rows, h->row_bytes) : HammingMfmaPlan{};
+    const HammingMfmaPlan hp = hmfma ? knn_hamming_mfma_plan(q, (int)n_rows, h->row_bytes, h->filter_units > 0 ? h->filter_units : -1) : HammingMfmaPlan{};
     *pm = hmfma ? knn_hamming_mfma_merge_plan(hp) : knn_plan(q, (int)n_rows, h->row_bytes);
     LCD_HIP(h, dreserve(h, h->d_partial, hmfma ? knn_hamming_mfma_partial_bytes(hp) : knn_partial_bytes(*pm)));
     if (prof) LCD_HIP(h, hipEventRecord(h->prof_ev[2 * h->prof_n], h->kst));

@@ -250,7 +250,7 @@ int g_cus = 256;
 // ================================================================================================ host side
 bool knn_hamming_mfma_fixed(int w32) { return w32 == 2 || w32 == 4 || w32 == 8 || w32 == 16; }
 
-HammingMfmaPlan knn_hamming_mfma_plan(int q, int n_rows, int dim_bytes) {
+HammingMfmaPlan knn_hamming_mfma_plan(int q, int n_rows, int dim_bytes, int units) {
     HammingMfmaPlan p;
     p.q = q;
     p.qpad = (q + 63) / 64 * 64;
@@ -261,7 +261,8 @@ HammingMfmaPlan knn_hamming_mfma_plan(int q, int n_rows, int dim_bytes) {
     const int groups = (p.qpad + p.group_q - 1) / p.group_q;
     const int unit = fixed ? PLAN_UNIT : WAVES * 32;                // rows a workgroup takes in one step
     // two workgroups per compute unit (one wave of each on every SIMD: the products of one run beside the key updates of the other)
-    const int target = std::max(1, (2 * g_cus + groups - 1) / groups);
+    const int cus = units > 0 ? units : g_cus;                      // (tests: a fixed number of workgroups, whatever the device)
+    const int target = std::max(1, (int)((2 * (long long)cus + groups - 1) / groups));
     long long rpb = ((long long)n_rows + target - 1) / target;
     rpb = (rpb + unit - 1) / unit * unit;
     if (rpb < unit) rpb = unit;
@@ -295,3 +296,19 @@ hipError_t launch_knn2_hamming_mfma(const void* vocab, const int32_t* row_id, co
 }
 
 }  // namespace lcd
+
+// The launch plan of the matrix-core Hamming 2-NN for q queries over n_rows rows of dim_bytes (padded to whole dwords, as the handle pads its
+// rows), as scan_partial makes it for a handle whose "filter_units" is `units` (0, -1: the device's compute units) -- tests; no device needed:
+// out6[0] rows per workgroup, [1] workgroups along the rows (grid.x), [2] query groups (grid.y), [3] rows of a chunk of the chosen
+// instantiation (the runtime-K kernel: the 128 rows its four waves take in one step), [4] qpad, [5] bytes of the partial keys / 16.
+// -1: no such plan (arguments the handle does not admit, or partial keys beyond an int)
+extern "C" int lcd_debug_hamming_mfma_plan(int q, int n_rows, int dim_bytes, int units, int* out6) {
+    if (q <= 0 || n_rows <= 0 || dim_bytes <= 0 || dim_bytes > 4096 || !out6) return -1;
+    const lcd::HammingMfmaPlan p = lcd::knn_hamming_mfma_plan(q, n_rows, (dim_bytes + 3) / 4 * 4, units);
+    const size_t bytes = lcd::knn_hamming_mfma_partial_bytes(p);
+    if (bytes > 0x7FFFFFFFull) return -1;
+    out6[0] = p.rows_per_block; out6[1] = p.n_blocks; out6[2] = (p.qpad + p.group_q - 1) / p.group_q;
+    out6[3] = lcd::knn_hamming_mfma_fixed(p.w32) ? (p.w32 == 16 ? 32 : 64) : lcd::WAVES * 32;
+    out6[4] = p.qpad; out6[5] = (int)(bytes / 16);
+    return 0;
+}

@@ -39,7 +39,7 @@ struct HammingMfmaPlan {
     int w32;           // dwords per row
     int group_q;       // queries per workgroup (grid.y = ceil(qpad / group_q))
 };
-HammingMfmaPlan knn_hamming_mfma_plan(int q, int n_rows, int dim_bytes);
+HammingMfmaPlan knn_hamming_mfma_plan(int q, int n_rows, int dim_bytes, int units = -1);   // units > 0: plan for that many compute units (lcd_set_option "filter_units")
 KnnPlan knn_hamming_mfma_merge_plan(const HammingMfmaPlan& p);   // n_blocks and qpad are what the merges read
 size_t knn_hamming_mfma_partial_bytes(const HammingMfmaPlan& p);
 void knn_hamming_mfma_set_compute_units(int cus);                // the device's compute units: the plan aims at two workgroups on each
