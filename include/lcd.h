@@ -54,7 +54,16 @@ enum lcd_quantize_flags {
 
 /* how the 2-NN is computed.  Every mode returns the SAME bits (the reference's distances and tie-break).
  * Squared L2 of 64-float descriptors: the matrix-core modes only rank candidates, an exact re-rank in the reference's arithmetic plus a
- * completeness certificate (exact redo when it fails) produces the result; float rows of any other length use the exact scan.
+ * completeness certificate (exact redo when it fails) produces the result.
+ * Squared L2 of 128- and 256-float descriptors (SIFT, extended SURF, SuperPoint): a handle whose config WRITES LCD_KNN_BF16X3 or LCD_KNN_F16
+ * searches its main vocabulary (256 rows or more) with a stateless matrix-core filter of that arithmetic (knn_wide_filter_kernel: it reads the
+ * fp32 rows and converts them on the way, the handle keeps no operand or norm table for them), the same exact re-rank with the certificate and
+ * the same exact redo.  LCD_KNN_DEFAULT -- and LCD_KNN_EXACT_VALU, LCD_KNN_F32_MFMA, LCD_KNN_HAMMING_MFMA -- stay the exact scan on such a
+ * handle: the two arms have NOT yet been measured against the scan at vocabulary sizes (49 000 rows and more) -- profiles/wide_mfma_scan.txt holds
+ * the commands, the compiler's resource lines and what little was timed, DESIGN.md 4e the design -- so no speed-up is claimed, and a later change
+ * decides whether the default moves.  A search whose launch plan cannot be made (candidate records beyond 2^31 - 1 bytes: about 200 000 shares
+ * of 1 024 rows x 512 queries; more than 65 535 query blocks) silently uses the exact scan, same bits; lcd_profile_read names the kernel that ran.
+ * Float rows of any other length use the exact scan.
  * Hamming (LCD_U8 handles): the exact vector-ALU scan unless the handle asks for LCD_KNN_HAMMING_MFMA, which computes the same integer
  * distances on the i8 matrix cores (an integer dot product: no filter, no re-rank); the float modes mean LCD_KNN_DEFAULT there. */
 enum lcd_knn_mode {

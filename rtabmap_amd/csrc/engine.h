@@ -284,6 +284,9 @@ struct lcd_engine {
     int knn_mode = 2;                                   // f32 dim 64: 2 = bf16x3 MFMA filter + exact re-rank (default), 3 = fp16 one-product filter, 1 = f32 MFMA filter
                                                         // + exact re-rank, 0 = exact VALU scan only (lcd_config.knn_mode)
     bool hamming_mfma = false;                          // u8 handles, LCD_KNN_HAMMING_MFMA: the main vocabulary's Hamming 2-NN runs on the i8 matrix cores (knn_hamming_mfma.hip)
+    bool wide_mfma = false;                             // f32 x 128 / f32 x 256 handles whose caller wrote LCD_KNN_BF16X3 or LCD_KNN_F16: the main vocabulary's 2-NN runs the
+                                                        // stateless matrix-core filter + re-rank + redo (wide_filter_body.cuh); f16() picks the operands
+    lcd::DevBuf d_wide_norm;                            // its scratch word: the largest |row|^2 the filter multiplied (zeroed by every search)
     // ---- pipelined frames (lcd_config.pipeline): see FramePipeline
     int pipeline = 0;
     hipStream_t kst = nullptr;                          // the stream the 2-NN stage is enqueued on (== stream)

@@ -137,6 +137,10 @@ int run_knn2_raw(lcd_engine* h, const void* d_queries, int q, const void* vocab,
     if (packed) *packed = false;
     if (q == 0) return LCD_OK;
     const bool mfma = main_vocab && h->knn_mode != 0 && knn_mfma_supported(h->dtype, h->kdim) && n_rows >= 256;
+    // (a handle of 128- or 256-float rows whose caller wrote LCD_KNN_BF16X3 or LCD_KNN_F16; a search the plan cannot describe stays on the scan)
+    WidePlan wp;
+    const bool wide = !mfma && main_vocab && h->wide_mfma && n_rows >= 256 && n_rows <= 0x7fffffff &&
+                      knn_wide_mfma_plan(q, (int)n_rows, h->kdim, h->filter_units > 0 ? h->filter_units : -1, &wp);
     if (mfma && h->bf_family()) {
         MfmaPlan mp = knn_bf16_plan(q, (int)n_rows, cb != nullptr ? knn_selfdist_wgs(q) : 0);
         mp.filter_units = h->filter_units;
@@ -178,6 +182,19 @@ int run_knn2_raw(lcd_engine* h, const void* d_queries, int q, const void* vocab,
                                          h->d_fail_count.as<int32_t>(), h->d_partial3.p, o_row, o_word, o_dist, h->kst, cb, pack));
             if (pack && packed) *packed = true;
         }
+    } else if (wide) {
+        // rows of 128 / 256 floats, LCD_KNN_BF16X3 / LCD_KNN_F16 asked for: the stateless matrix-core filter, its re-rank and the exact redo.  cb,
+        // defer_redo and pack are not looked at, exactly as in the scan branch below (the callers' own launches follow)
+        LCD_HIP(h, dreserve(h, h->d_partial2, knn_wide_partial_bytes(wp)));
+        LCD_HIP(h, dreserve(h, h->d_fail_list, (size_t)q * 4));
+        LCD_HIP(h, dreserve(h, h->d_partial3, knn_rowpar_partial_bytes((int)n_rows, q)));
+        LCD_HIP(h, dreserve(h, h->d_wide_norm, 64));
+        const bool prof = h->prof_cap > 0 && h->prof_n < h->prof_cap;
+        LCD_HIP(h, launch_knn_wide(wp, h->f16(), vocab, row_id, d_queries, h->d_partial2.p, h->d_partial3.p, h->d_wide_norm.as<uint32_t>(), o_row, o_word,
+                                   o_dist, h->d_fail_list.as<int32_t>(), h->d_fail_count.as<int32_t>(), h->kst, prof ? h->prof_ev[2 * h->prof_n] : nullptr,
+                                   prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr, !h->fail_count_clean));
+        h->fail_count_clean = false;
+        if (prof) { h->prof_n += 1; h->prof_kernel = h->f16() ? "knn_wide_filter_kernel (fp16 operands)" : "knn_wide_filter_kernel"; }
     } else {
         KnnPlan pm;
         const int rc = scan_partial(h, d_queries, q, vocab, row_id, n_rows, main_vocab, &pm);
@@ -185,7 +202,7 @@ int run_knn2_raw(lcd_engine* h, const void* d_queries, int q, const void* vocab,
         LCD_HIP(h, launch_knn2_merge(h->dtype, pm, h->d_partial.as<uint64_t>(), row_id, o_row, o_word, o_dist, h->kst));
     }
     h->knn_launches += 1;
-    if (mfma) h->last_fail_count = h->d_fail_count.p;
+    if (mfma || wide) h->last_fail_count = h->d_fail_count.p;
     return LCD_OK;
 }
 
@@ -424,6 +441,8 @@ int lcd_create(const lcd_config* cfg, lcd_engine** out) {
     if (e == hipSuccess) e = hipMemsetAsync(h->d_fail_count.p, 0, 64, h->stream);
     h->knn_mode = cfg->knn_mode == LCD_KNN_EXACT_VALU ? 0 : cfg->knn_mode == LCD_KNN_F32_MFMA ? 1 : cfg->knn_mode == LCD_KNN_F16 ? 3 : 2;
     h->hamming_mfma = cfg->knn_mode == LCD_KNN_HAMMING_MFMA && cfg->dtype == LCD_U8;   // (on an f32 handle the value means the default, above)
+    // rows of 128 / 256 floats take the matrix-core path only when the caller WROTE one of its two modes (DEFAULT folds into knn_mode 2 above)
+    h->wide_mfma = (cfg->knn_mode == LCD_KNN_BF16X3 || cfg->knn_mode == LCD_KNN_F16) && knn_wide_mfma_supported(cfg->dtype, cfg->dim);
     h->kst = h->stream;
     if (cfg->pipeline < 0 || cfg->pipeline > 1) { delete h; return LCD_ERR_INVALID; }
     h->pipeline = cfg->pipeline;
@@ -462,7 +481,7 @@ void lcd_destroy(lcd_engine* h) {
                      &h->d_out_wslot, &h->d_n_new, &h->d_tmp_i32, &h->d_extra_rows, &h->d_extra_id, &h->d_extra_word,
                      &h->d_extra_dist, &h->d_extra_row, &h->d_like, &h->d_slots, &h->d_bits, &h->row_norm, &h->norm_max, &h->d_partial2,
                      &h->d_fail_list, &h->d_fail_count, &h->d_partial3, &h->row_norm_alt, &h->vocab_bf, &h->d_hyp_scratch, &h->d_adj_scratch,
-                     &h->d_shard_selfdist};
+                     &h->d_shard_selfdist, &h->d_wide_norm};
     for (DevBuf* d : all) d->release(&h->bytes_device);
     h->applog.release(&h->bytes_device);
     h->d_rmlog.release(&h->bytes_device);

@@ -31,6 +31,7 @@
 #include "frame_tail_body.cuh"
 #include "score_body.cuh"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace lcd {
@@ -477,6 +478,10 @@ __global__ __launch_bounds__(MF_BLOCK) void knn_mfma_rerank_kernel(const uint64_
                                                           norm_max_bits, out_row, out_word, out_dist, fail_list, fail_count, cb, nullptr, nullptr,
                                                           n_rows, nullptr, 0, f16);
 }
+
+// ------------------------------------------------------------------------------------------------ rows of 128 and 256 floats
+// (the stateless bf16x3 / fp16 filter, its re-rank and its redo: knn_wide_filter_kernel, knn_wide_rerank_kernel, knn_wide_rowpar_kernel)
+#include "wide_filter_body.cuh"
 
 // ------------------------------------------------------------------------------------------------ software-pipelined frames
 // Consecutive frames of a device-resident stream overlap INSIDE two launches instead of across streams: the 2-NN stage of frame t
@@ -930,6 +935,87 @@ hipError_t launch_knn_rowpar(int dim, const void* vocab, const int32_t* row_id, 
     return hipGetLastError();
 }
 
+// ---- rows of 128 and 256 floats (wide_filter_body.cuh)
+bool knn_wide_mfma_supported(int dtype, int dim) { return dtype == 0 && (dim == 128 || dim == 256); }
+
+// One workgroup (eight waves of up to 256 VGPRs: one per compute unit) per block of queries and compute unit; the rows are cut into equal shares
+// of at most WD_SHARE_TILES 32-row tiles (one record each), a workgroup takes one or several and walks each in strips of MF_STRIP_TILES.
+// units > 0: plan for that many compute units (lcd_set_option "filter_units").  false: no such plan.
+bool knn_wide_mfma_plan(int q, int n_rows, int dim, int units, WidePlan* out) {
+    if (!out || q <= 0 || n_rows <= 0 || !knn_wide_mfma_supported(0, dim)) return false;
+    WidePlan p;
+    p.q = q;
+    p.qpad = (int)(((long long)q + 63) / 64 * 64);
+    if (p.qpad <= 0) return false;
+    p.n_rows = n_rows;
+    p.dim = dim;
+    p.group_q = wide_group_q(dim);
+    p.n_qblocks = (p.qpad + p.group_q - 1) / p.group_q;
+    if (p.n_qblocks > 65535) return false;                              // grid.y
+    const int cus = units > 0 ? units : g_plan_cus;
+    const int target = std::max(1, cus / p.n_qblocks);
+    const int n_tiles = (int)(((long long)n_rows + 31) / 32);
+    // tiles per workgroup when every compute unit gets one; more than a share holds: every workgroup walks `rounds` equal shares
+    const int w = (n_tiles + target - 1) / target;
+    const int rounds = (w + WD_SHARE_TILES - 1) / WD_SHARE_TILES;
+    p.tiles_per_block = (int)(((long long)n_tiles + (long long)target * rounds - 1) / ((long long)target * rounds));
+    p.n_blocks = (n_tiles + p.tiles_per_block - 1) / p.tiles_per_block;
+    p.n_wgs = std::min(p.n_blocks, target);
+    if (knn_wide_partial_bytes(p) > 0x7FFFFFFFull) return false;
+    *out = p;
+    return true;
+}
+size_t knn_wide_partial_bytes(const WidePlan& p) {
+    const size_t nb = (size_t)(p.n_blocks > 0 ? p.n_blocks : 1);
+    return nb * BF_KEEP * p.qpad * sizeof(uint64_t) + nb * p.qpad * sizeof(uint32_t);
+}
+
+template <int DIM, int M>
+static hipError_t launch_wide_filter(const WidePlan& p, const float* vocab, const int32_t* row_id, const float* queries, uint64_t* pk, uint32_t* pl,
+                                     uint32_t* norm_max_bits, hipStream_t s) {
+    // (per launch, checked: <256, 0> needs more than the 64 KB a kernel gets unasked, and the attribute belongs to the current device)
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_wide_filter_kernel<DIM, M>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideShape<DIM, M>::LDS_BYTES);
+    if (attr != hipSuccess) return attr;
+    knn_wide_filter_kernel<DIM, M><<<dim3(p.n_wgs, p.n_qblocks), WD_BLOCK, WideShape<DIM, M>::LDS_BYTES, s>>>(vocab, row_id, p.n_rows, queries, p.q, p.qpad,
+                                                                                                             p.tiles_per_block, p.n_blocks, pk, pl, norm_max_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_knn_wide(const WidePlan& p, int f16, const void* vocab, const int32_t* row_id, const void* queries, void* partial, void* partial_redo,
+                           uint32_t* norm_max_bits, int32_t* out_row, int32_t* out_word, float* out_dist, int32_t* fail_list, int32_t* fail_count,
+                           hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, bool reset_count) {
+    if (p.q == 0) return hipSuccess;
+    if (!knn_wide_mfma_supported(0, p.dim) || p.n_blocks <= 0 || p.n_rows <= 0) return hipErrorInvalidValue;
+    uint64_t* pk = (uint64_t*)partial;
+    uint32_t* pl = (uint32_t*)(pk + (size_t)p.n_blocks * BF_KEEP * p.qpad);
+    const float* v = (const float*)vocab; const float* qq = (const float*)queries;
+    knn_wide_reset_kernel<<<1, 64, 0, s>>>(fail_count, reset_count ? 1 : 0, norm_max_bits);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (ev_begin) { e = hipEventRecord(ev_begin, s); if (e != hipSuccess) return e; }
+    if (p.dim == 128) e = f16 ? launch_wide_filter<128, 1>(p, v, row_id, qq, pk, pl, norm_max_bits, s) : launch_wide_filter<128, 0>(p, v, row_id, qq, pk, pl, norm_max_bits, s);
+    else e = f16 ? launch_wide_filter<256, 1>(p, v, row_id, qq, pk, pl, norm_max_bits, s) : launch_wide_filter<256, 0>(p, v, row_id, qq, pk, pl, norm_max_bits, s);
+    if (e != hipSuccess) return e;
+    if (ev_end) { e = hipEventRecord(ev_end, s); if (e != hipSuccess) return e; }
+    if (p.dim == 128)
+        knn_wide_rerank_kernel<128><<<p.q, MF_BLOCK, 0, s>>>(pk, pl, p.n_blocks, p.q, p.qpad, v, qq, row_id, p.n_rows, norm_max_bits, out_row, out_word, out_dist,
+                                                             fail_list, fail_count, f16);
+    else
+        knn_wide_rerank_kernel<256><<<p.q, MF_BLOCK, 0, s>>>(pk, pl, p.n_blocks, p.q, p.qpad, v, qq, row_id, p.n_rows, norm_max_bits, out_row, out_word, out_dist,
+                                                             fail_list, fail_count, f16);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the queries the certificate rejected are redone exactly (usually none: every workgroup leaves at once)
+    RowparArgs a;
+    a.enabled = 1; a.vocab = v; a.row_id = row_id; a.n_rows = p.n_rows; a.queries = qq;
+    a.fail_list = fail_list; a.partial = (unsigned long long*)partial_redo; a.out_row = out_row; a.out_word = out_word; a.out_dist = out_dist;
+    const int nb = (p.n_rows + MF_BLOCK - 1) / MF_BLOCK;
+    if (p.dim == 128) knn_wide_rowpar_kernel<128><<<nb, MF_BLOCK, 0, s>>>(a, fail_count);
+    else knn_wide_rowpar_kernel<256><<<nb, MF_BLOCK, 0, s>>>(a, fail_count);
+    return hipGetLastError();
+}
+
 // ---- software-pipelined frames (see frame_a_kernel / frame_b_kernel)
 int pipe_block_size() { return PIPE_BLOCK; }
 int pipe_b_block_size() { return PIPE_B_BLOCK; }
@@ -1082,6 +1168,21 @@ extern "C" int lcd_debug_frame_plan(int q, int n_rows, int new_words_compared, i
     const int tiles = new_words_compared ? lcd::knn_selfdist_wgs(q) : 0;
     const lcd::MfmaPlan p = lcd::knn_bf16_plan_pipelined(q, n_rows, tiles, -1);
     out[0] = p.tiles_per_block; out[1] = p.n_blocks; out[2] = lcd::bf16_persistent_px(p); out[3] = tiles; out[4] = (q + lcd::BF_QB - 1) / lcd::BF_QB;
+    return 0;
+}
+
+// The launch plan of the wide-row matrix-core filter for q queries over n_rows rows of dim floats (128 or 256), as run_knn2_raw makes it for a
+// handle whose "filter_units" is `units` (0, -1: the device's compute units) -- tests; no device needed:
+// out9[0] tiles (32 rows) per share, [1] shares (one record per share and query), [2] query blocks (grid.y), [3] queries per block, [4] qpad,
+// [5] bytes of the partial records / 4, [6] tiles per strip (the key's index bits), [7] strips per share, [8] workgroups along the rows
+// (grid.x; workgroup x takes shares x, x + [8], ...).
+// -1: no such plan (another row length, arguments the handle does not admit, or records beyond an int)
+extern "C" int lcd_debug_wide_mfma_plan(int q, int n_rows, int dim, int units, int* out9) {
+    lcd::WidePlan p;
+    if (!out9 || !lcd::knn_wide_mfma_plan(q, n_rows, dim, units, &p)) return -1;
+    out9[0] = p.tiles_per_block; out9[1] = p.n_blocks; out9[2] = p.n_qblocks; out9[3] = p.group_q; out9[4] = p.qpad;
+    out9[5] = (int)(lcd::knn_wide_partial_bytes(p) / 4); out9[6] = lcd::MF_STRIP_TILES;
+    out9[7] = (p.tiles_per_block + lcd::MF_STRIP_TILES - 1) / lcd::MF_STRIP_TILES; out9[8] = p.n_wgs;
     return 0;
 }
 

@@ -205,6 +205,26 @@ hipError_t launch_knn_bf16(int dim, const void* vocab, const void* vocab_bf, con
                            bool with_selfdist = false,     // true: extra workgroups of the filter launch fill cb->selfdist (queries x queries)
                            hipStream_t s_rerank = nullptr, hipEvent_t ev_bridge = nullptr);   // re-rank on its own stream behind ev_bridge
 
+// ---- the same filters for rows of 128 and 256 floats (wide_filter_body.cuh, a section of knn_mfma_kernels.hip): STATELESS -- the filter reads
+// the fp32 rows and row_id only (no operand table, no norm table), converts each 32-row tile once in LDS and collects the norm maximum the
+// certificate needs itself.  reset + filter + re-rank + exact redo on one stream; the answers are the exact scan's.
+struct WidePlan {
+    int q = 0, qpad = 0, n_rows = 0, dim = 0;
+    int group_q = 0;          // queries per workgroup
+    int n_qblocks = 0;        // grid.y
+    int tiles_per_block = 0;  // 32-row tiles per share of the rows (at most 32), walked in strips of at most 8 (the in-loop key's index bits)
+    int n_blocks = 0;         // shares: one record of two keys and a bound per (share, query)
+    int n_wgs = 0;            // workgroups along the rows (grid.x): workgroup x takes shares x, x + n_wgs, ...
+};
+bool knn_wide_mfma_supported(int dtype, int dim);                     // f32 x 128, f32 x 256 (knn_mfma_supported() stays 64-float only)
+bool knn_wide_mfma_plan(int q, int n_rows, int dim, int units, WidePlan* out);   // units > 0: that many compute units ("filter_units"); false: no such plan
+size_t knn_wide_partial_bytes(const WidePlan& p);
+// partial: knn_wide_partial_bytes(); partial_redo: knn_rowpar_partial_bytes(); norm_max_bits: one scratch word (zeroed here); ev_begin / ev_end
+// bracket the filter kernel alone
+hipError_t launch_knn_wide(const WidePlan& p, int f16, const void* vocab, const int32_t* row_id, const void* queries, void* partial, void* partial_redo,
+                           uint32_t* norm_max_bits, int32_t* out_row, int32_t* out_word, float* out_dist, int32_t* fail_list, int32_t* fail_count,
+                           hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr, bool reset_count = true);
+
 // Row gather used by lcd_vocab_rebuild: dst[i] = src[perm[i]] (rows of row_bytes bytes, multiple of 4), ids likewise.
 hipError_t launch_gather_rows(const void* src, const int32_t* src_id, const int32_t* perm, int n, int row_bytes,
                               void* dst, int32_t* dst_id, hipStream_t s);

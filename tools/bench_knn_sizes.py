@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """2-NN kernel time by vocabulary size (HIP events around the filter / scan launch, lcd_profile_*), 500 queries.
 Default: SURF rows at 49k words (headline), 125k (one GPU's shard of config 4) and 1M (config 4 on one GPU).
-  --dtype u8 --dim 32 --rows 20000,200000,1000000 --knn-mode valu,hamming_mfma    binary rows, the modes' launches alternated in one process"""
+  --dtype u8 --dim 32 --rows 20000,200000,1000000 --knn-mode valu,hamming_mfma    binary rows, the modes' launches alternated in one process
+  --dtype f32 --dim 128 --knn-mode valu,bf16,f16                                   SIFT-sized rows: the scan against the two matrix-core arms
+Every arm's line names the kernel lcd_profile_read reported for it."""
 import argparse
 import json
 import os
@@ -61,7 +63,8 @@ def main():
         for arm in arms:
             ms, ns, name = arm["eng"].profile_read()
             r = {"rows": n, "dtype": a.dtype, "dim": dim, "knn_mode": arm["mode"], "kernel": name, "filter_ms": ms, "knn2_call_ms": arm["wall"] / reps * 1e3,
-                 "table_gbps": n * (256 if a.dtype == "f32" else dim) / (ms * 1e-3) / 1e9, "fallback_queries": arm["eng"].stats()["knn_last_fallback_queries"]}
+                 "table_gbps": n * ((256 if dim == 64 else 4 * dim) if a.dtype == "f32" else dim) / (ms * 1e-3) / 1e9,     # (64 floats: the 256-byte operand rows; other float rows are read as they are)
+                 "fallback_queries": arm["eng"].stats()["knn_last_fallback_queries"], "max_err_ratio": arm["eng"].stats()["knn_max_err_ratio"]}
             if a.dtype == "f32":
                 r["algorithmic_tflops"] = 2.0 * q * n * dim / (ms * 1e-3) / 1e12
             else:
