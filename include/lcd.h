@@ -211,6 +211,28 @@ int lcd_word_nrefs(lcd_engine* h, int32_t word_id, int32_t* out_nw);
 int lcd_likelihood(lcd_engine* h, const int32_t* query_word_ids, int nq, const int32_t* sig_ids, int n_ids,
                    float N, float* out);
 
+/* Signature::compareTo, words branch (Signature.cpp:273-286), for Memory::computeLikelihood with Kp/TfIdfLikelihoodUsed=false
+ * (Memory.cpp:2179-2214) and Memory::rehearsal (:4245):
+ *   pairs  = sum over word ids w > 0 of min(occurrences of w in the query, occurrences of w in the signature)
+ *            (EpipolarGeometry::findPairs on the two multimaps pairs the k-th occurrence with the k-th, EpipolarGeometry.h:123-151)
+ *   out[k] = float(pairs) / float(max(vq, vs)),  vq / vs = entries with id > 0 of the query / of signature sig_ids[k]
+ *            (words.size() - invalidWordsCount); 0 when either is 0 (isBadSignature, Signature.cpp:277).
+ * Integers up to one IEEE float division: bit-exact against the reference, whatever the index layout.  vq counts every id > 0 of the
+ * query, also ids the index has never seen (valid words that pair with nothing).  Nothing is weighted or masked by idf.
+ * out[k] pairs with sig_ids[k]; unknown / retired ids and ids <= 0 give 0 (the reference's "*iter > 0" test).  out_pairs / out_valid
+ * (may be NULL): the integers behind out[k], pairs and vs.  nq <= 8192 (more: LCD_ERR_UNSUPPORTED, the handle stays usable); n_ids == 0
+ * returns LCD_OK, an empty index gives zeros.
+ * Two departures from the reference: ids <= 0 are "no word" on both sides (findPairs would admit a key 0, which RTAB-Map never
+ * issues); the global-descriptor branch of compareTo (Signature.cpp:257-272) is not implemented -- signatures are compared by their
+ * words alone.  Not available across sharded handles (the pairs would all-reduce, vs needs a second exchange) and not fused into the
+ * pipelined launches: stand-alone launches on the engine stream. */
+int lcd_similarity(lcd_engine* h, const int32_t* query_word_ids, int nq, const int32_t* sig_ids, int n_ids,
+                   float* out, int32_t* out_pairs, int32_t* out_valid);
+/* the same with the query's word ids in DEVICE memory and the dense result over signature slots (as d_likelihood of lcd_frame_dev;
+ * retired slots 0); enqueued, not synchronised; completes what a pipelined handle owes first.  capacity = floats available at d_out
+ * (smaller than the slots in use: LCD_ERR_INVALID). */
+int lcd_similarity_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, float* d_out, int64_t capacity);
+
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */
 int lcd_adjust_likelihood(lcd_engine* h, float* likelihood, int n, float virtual_place_ratio);

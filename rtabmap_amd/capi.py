@@ -23,7 +23,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -128,6 +128,8 @@ def load():
     L.lcd_sig_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.lcd_word_nrefs.argtypes = [vp, i32, C.POINTER(i32)]
     L.lcd_likelihood.argtypes = [vp, vp, C.c_int, vp, C.c_int, f32, vp]
+    L.lcd_similarity.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.lcd_similarity_dev.argtypes = [vp, vp, C.c_int, vp, i64]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -316,6 +318,26 @@ class Engine:
         out = np.zeros(s.shape[0], np.float32)
         self._ck(self.L.lcd_likelihood(self.h, _p(w), w.shape[0], _p(s), s.shape[0], float(N), _p(out)))
         return out
+
+    def similarity(self, query_word_ids, sig_ids, with_counts=False):
+        """lcd_similarity: Signature::compareTo's words branch of the query against sig_ids; with_counts: also (pairs, valid words)."""
+        w = np.ascontiguousarray(query_word_ids, dtype=np.int32)
+        s = np.ascontiguousarray(sig_ids, dtype=np.int32)
+        out = np.zeros(s.shape[0], np.float32)
+        pairs = np.zeros(s.shape[0], np.int32) if with_counts else None
+        valid = np.zeros(s.shape[0], np.int32) if with_counts else None
+        self._ck(self.L.lcd_similarity(self.h, _p(w), w.shape[0], _p(s), s.shape[0], _p(out), _p(pairs), _p(valid)))
+        return (out, pairs, valid) if with_counts else out
+
+    def similarity_dev(self, d_query_word_ids, d_out):
+        """lcd_similarity_dev on torch tensors of the engine's device: int32 word ids in, float32 similarity over the signature slots out
+        (d_out holds at least slot_count entries); enqueued on the engine stream, not synchronised."""
+        import torch
+        if d_query_word_ids.dtype != torch.int32 or d_out.dtype != torch.float32 or not (d_query_word_ids.is_cuda and d_out.is_cuda) or \
+                not (d_query_word_ids.is_contiguous() and d_out.is_contiguous()):
+            raise ValueError("similarity_dev: contiguous device tensors expected, int32 word ids and float32 output")
+        self._ck(self.L.lcd_similarity_dev(self.h, d_query_word_ids.data_ptr() if d_query_word_ids.numel() else None, int(d_query_word_ids.numel()),
+                                           d_out.data_ptr(), int(d_out.numel())))
 
     def adjust_likelihood_dev(self, d_ptr, n, ratio=0.0):
         self._ck(self.L.lcd_adjust_likelihood_dev(self.h, d_ptr, n, ratio))

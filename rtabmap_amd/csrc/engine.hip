@@ -1010,6 +1010,72 @@ int lcd_likelihood(lcd_engine* h, const int32_t* query_word_ids, int nq, const i
     LCD_CATCH(h)
 }
 
+// Signature::compareTo's words branch of the query against the listed signatures (similarity.hip): built as lcd_likelihood is
+int lcd_similarity(lcd_engine* h, const int32_t* query_word_ids, int nq, const int32_t* sig_ids, int n_ids, float* out, int32_t* out_pairs,
+                   int32_t* out_valid) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_similarity");
+    LCD_DEV(h);
+    if (nq < 0 || n_ids < 0 || (nq > 0 && !query_word_ids) || (n_ids > 0 && (!sig_ids || !out)))
+        return h->fail(LCD_ERR_INVALID, "lcd_similarity: null input");
+    if (n_ids == 0) return LCD_OK;
+    if (nq > TF_MAX_WORDS) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_similarity: more than 8192 query words");
+    Tfidf& t = h->tfidf;
+    if (t.n_slots == 0) {
+        std::memset(out, 0, (size_t)n_ids * 4);
+        if (out_pairs) std::memset(out_pairs, 0, (size_t)n_ids * 4);
+        if (out_valid) std::memset(out_valid, 0, (size_t)n_ids * 4);
+        return LCD_OK;
+    }
+    int rc = stage_word_ids(h, query_word_ids, nq, false);
+    if (rc) return rc;
+    const size_t ns = (size_t)t.n_slots, ni = (size_t)n_ids;
+    LCD_HIP(h, dreserve(h, h->d_like, (ns + ni) * 4));
+    LCD_HIP(h, dreserve(h, t.sim.d_int, 2 * (ns + ni) * 4));
+    float* d_sim = h->d_like.as<float>();
+    int32_t* d_pairs = t.sim.d_int.as<int32_t>();
+    int32_t* d_valid = d_pairs + ns;
+    LCD_HIP(h, t.sim.run(t, t.d_stage.as<int32_t>(), nq, d_sim, d_pairs, d_valid));
+    // gather the requested signatures
+    LCD_HIP(h, h->h_in.reserve(ni * 8));
+    int64_t* slots = h->h_in.as<int64_t>();
+    for (int i = 0; i < n_ids; ++i) { auto it = t.sig_slot.find(sig_ids[i]); slots[i] = it == t.sig_slot.end() ? -1 : it->second; }
+    LCD_HIP(h, dreserve(h, h->d_slots, ni * 8));
+    LCD_HIP(h, hipMemcpyAsync(h->d_slots.p, slots, ni * 8, hipMemcpyHostToDevice, h->stream));
+    int32_t* g_pairs = d_valid + ns;
+    int32_t* g_valid = g_pairs + ni;
+    LCD_HIP(h, launch_gather_f32(d_sim, h->d_slots.as<int64_t>(), n_ids, d_sim + ns, h->stream));
+    LCD_HIP(h, launch_gather_i32(d_pairs, h->d_slots.as<int64_t>(), n_ids, g_pairs, h->stream));
+    LCD_HIP(h, launch_gather_i32(d_valid, h->d_slots.as<int64_t>(), n_ids, g_valid, h->stream));
+    // one synchronisation for the three results (g_pairs and g_valid are adjacent)
+    LCD_HIP(h, h->h_out.reserve(3 * ni * 4));
+    char* pin = h->h_out.as<char>();
+    LCD_HIP(h, hipMemcpyAsync(pin, d_sim + ns, ni * 4, hipMemcpyDeviceToHost, h->stream));
+    LCD_HIP(h, hipMemcpyAsync(pin + ni * 4, g_pairs, 2 * ni * 4, hipMemcpyDeviceToHost, h->stream));
+    LCD_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(out, pin, ni * 4);
+    if (out_pairs) std::memcpy(out_pairs, pin + ni * 4, ni * 4);
+    if (out_valid) std::memcpy(out_valid, pin + 2 * ni * 4, ni * 4);
+    return LCD_OK;
+    LCD_CATCH(h)
+}
+
+int lcd_similarity_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, float* d_out, int64_t capacity) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_similarity_dev");
+    LCD_DEV(h);                                                      // completes what a pipelined handle owes
+    Tfidf& t = h->tfidf;
+    if (nq < 0 || (nq > 0 && !d_query_word_ids) || capacity < 0 || (t.n_slots > 0 && !d_out))
+        return h->fail(LCD_ERR_INVALID, "lcd_similarity_dev: bad argument");
+    if (nq > TF_MAX_WORDS) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_similarity_dev: more than 8192 query words");
+    if (capacity < t.n_slots) return h->fail(LCD_ERR_INVALID, "lcd_similarity_dev: output buffer smaller than the slots in use");
+    LCD_HIP(h, t.sim.run(t, d_query_word_ids, nq, d_out, nullptr, nullptr));
+    return LCD_OK;
+    LCD_CATCH(h)
+}
+
 // Rtabmap::adjustLikelihood on a device vector whose entry 0 is the virtual place, in place: the decision stage's two passes
 // (bayes.hip) with every entry taking part
 static int adjust_vector(lcd_engine* h, float* d_L, int n, float ratio) {

@@ -95,6 +95,7 @@ struct Bucket {
     DevBuf coo_w, coo_pc, sealed;
     size_t off_dirb = 0, off_spoff = 0, off_spent = 0;   // byte offsets inside `sealed` (dense rows at 0)
     uint32_t W = 0, D_alloc = 0;
+    bool nv_done = false;     // sealed: Similarity::slot_nv holds the valid-word counts of this bucket's slots (similarity.hip fills them on first use)
 };
 
 // VWDictionary::update()'s append branch (VWDictionary.cpp:571-609) on the device, run by the decision loop's workgroup right after the
@@ -263,6 +264,37 @@ hipError_t launch_frame_a(const PipeKnn* k, const QSplitArgs* qs, const TailLaun
 hipError_t launch_frame_b(const PipeKnn* k, const ScoreArgs* score, int score_wgs, hipStream_t s, hipEvent_t ev_begin = nullptr,
                           hipEvent_t ev_end = nullptr, const AppendRowsArgs* app = nullptr, const PipeOpts& opt = PipeOpts());
 
+// ---- pair similarity (similarity.hip, similarity_body.cuh): Signature::compareTo's words branch over the same index
+// the query reduction (one workgroup): word ids -> unique postings keys with their counts cq, the stamped per-key table, vq
+struct SimQueryArgs {
+    const int32_t* src; int n;                    // the query's word ids; <= 0 = no word
+    const int32_t* xlate; long long xlate_n;      // word id -> key (KeyPool::xlate)
+    int H; uint32_t stamp; const int32_t* did;
+    uint32_t* q_w; uint32_t* q_cnt; int32_t* q_did; int32_t* qd_did; uint32_t* qd_cnt;
+    uint32_t* q_meta;                             // [0] unique words, [1] dense words, [2] vq = entries with id > 0
+    uint2* tab;                                   // per key {stamp, cq}: what the open bucket's walk looks up (KeyPool::idf_tab under a fresh stamp)
+};
+struct SimArgs {
+    const BucketDev* tab; const uint32_t* bkt_D; const uint32_t* bkt_flags;
+    const uint32_t* dir2; uint32_t dir2_stride;
+    int n_closed, n_closed_pad, n_open_slots;     // as ScoreArgs
+    const uint32_t* q_w; const uint32_t* q_cnt; const int32_t* q_did; const int32_t* qd_did; const uint32_t* qd_cnt; const uint32_t* q_meta;
+    const uint32_t* slot_ni; const uint32_t* slot_nv; const uint32_t* slot_begin; const uint32_t* slot_cnt;
+    const uint2* sim_tab; uint32_t stamp;
+    float* out_sim; int32_t* out_pairs; int32_t* out_valid;   // dense over the slots, every slot written; the integers may be NULL
+};
+struct Tfidf;
+struct Similarity {
+    DevBuf slot_nv;                               // per slot of a SEALED bucket: its entries with id > 0 (the log's counts are released at sealing)
+    DevBuf q_w, q_cnt, q_did, qd_did, qd_cnt, q_meta;
+    DevBuf d_int;                                 // host-side calls: pairs and vs over the slots, and their gathered copies
+    int64_t launches = 0;
+    // out_sim[slot] (and the integers behind it) of the query d_ids[n] (word ids on the device) against every slot; enqueued on t.stream
+    hipError_t run(Tfidf& t, const int32_t* d_ids, int n, float* out_sim, int32_t* out_pairs, int32_t* out_valid);
+    void destroy(int64_t* bytes);
+};
+hipError_t launch_gather_i32(const int32_t* dense, const int64_t* slots, int n, int32_t* out, hipStream_t s);
+
 // recycled allocations of bucket-sized device buffers (a bucket is born and dies every 256 frames in steady state:
 // hipMalloc / hipFree there would synchronise the device)
 struct BufPool {
@@ -282,6 +314,7 @@ struct Tfidf {
     // per bucket
     DevBuf bkt_tab, bkt_ne, bkt_D, bkt_flags;
     std::vector<Bucket> buckets;
+    Similarity sim;                      // the pair similarity's own lists and the lazy per-slot valid-word counts
     int score_block = 512;               // threads per scoring workgroup (256 / 512 / 1024; lcd_set_option "score_block")
     int q_n_ub = 0;                      // word count of the last frame handed to frame_words (upper bound of its unique words)
     BufPool pool;

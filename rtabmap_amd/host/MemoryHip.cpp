@@ -25,9 +25,11 @@ struct Stage {
 }  // namespace
 
 MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
-    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _deviceFrames(true), _likeSig(0), _likeSortedValid(false) {
+    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
     ParametersMap::const_iterator it = parameters.find("Mem/STMSize");
     if (it != parameters.end()) _maxStMemSize = atoi(it->second.c_str());
+    it = parameters.find("Kp/TfIdfLikelihoodUsed");
+    if (it != parameters.end()) _tfIdfLikelihoodUsed = !(it->second == "false" || it->second == "0" || it->second == "False" || it->second == "FALSE");
     if (_maxStMemSize < 0) _maxStMemSize = 0;
     _workingMem.insert(kIdVirtual);             // Memory.cpp:592
     static const char* names[] = {"TimingMem/Pre_update/ms", "TimingMem/Joining_dictionary_update/ms", "TimingMem/Add_new_words/ms",
@@ -74,7 +76,7 @@ int MemoryHip::update(const Mat& descriptors, int nQuantized, std::vector<int>& 
     if (rows && nq == rows && _deviceFrames && _vwd->isIncremental()) {
         // quantisation + the signature's references + update()'s append + the likelihood of Rtabmap.cpp:2117, one device call
         fast = _vwd->addNewWordsAndScore(descriptors, id, (float)(_signatures.size() + 1), [this](int s) { return this->getNi(s); }, wordIds, _likeSlots);
-        if (fast && !_likeSlots.empty()) { _likeSig = id; _likeSortedValid = false; }
+        if (fast && !_likeSlots.empty() && _tfIdfLikelihoodUsed) { _likeSig = id; _likeSortedValid = false; }   // (the frame's values are TF-IDF)
     }
     if (rows && !fast) {
         if (nq > 0) {
@@ -263,10 +265,24 @@ std::vector<int> MemoryHip::signatureIds() const {
 
 std::map<int, float> MemoryHip::computeLikelihood(const std::list<int>& wordIds, const std::list<int>& ids) {
     Stage st(_vwd, "Memory::computeLikelihood");
+    if (!_tfIdfLikelihoodUsed) {                 // Memory.cpp:2179-2214
+        std::map<int, float> S = _vwd->computeSimilarity(wordIds, ids, [this](int s) { return this->getNi(s); });
+        _stats["Timing/Likelihood_computation/ms"] = st.ms();
+        return S;
+    }
     const float N = (float)_signatures.size();   // Memory.cpp:2248: every signature in memory, not only `ids`
     std::map<int, float> L = _vwd->computeLikelihood(wordIds, ids, N, [this](int s) { return this->getNi(s); });
     _stats["Timing/Likelihood_computation/ms"] = st.ms();
     return L;
+}
+
+float MemoryHip::compareTo(int sigA, int sigB) {
+    std::map<int, std::vector<int> >::const_iterator it = _signatures.find(sigA);
+    if (it == _signatures.end() || sigB <= 0 || !_signatures.count(sigB)) return 0.0f;
+    Stage st(_vwd, "Signature::compareTo");
+    const std::map<int, float> S = _vwd->computeSimilarity(std::list<int>(it->second.begin(), it->second.end()), std::list<int>(1, sigB),
+                                                           [this](int s) { return this->getNi(s); });
+    return S.empty() ? 0.0f : S.begin()->second;
 }
 
 // (signature id, likelihood) of every signature registered on the device, ascending id, from the frame's slot-indexed result

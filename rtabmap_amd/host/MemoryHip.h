@@ -2,12 +2,14 @@
 //
 // Mirrors (reference corelib/src/Memory.cpp): preUpdate :1004-1016 + cleanUnusedWords :6899-6920, the quantisation glue
 // of createSignature :5941-6059 (features not sent to quantisation get ids -1,-2,.. and still count in ni),
-// getNi :4955-4968, disableWordsRef :6877-6897 (WM -> LTM transfer) and computeLikelihood :2177-2292 (TF-IDF branch).
+// getNi :4955-4968, disableWordsRef :6877-6897 (WM -> LTM transfer) and computeLikelihood :2177-2292 (both branches: TF-IDF, and with
+// Kp/TfIdfLikelihoodUsed=false Signature::compareTo's words branch).
 // For the Bayes filter it also keeps what BayesFilter asks a Memory: the short-term / working memory
 // split (addSignatureToStm :1146-1230, the transfer loop of update() :1112-1135, moveSignatureToWMFromSTM :1442), neighbour and
 // loop-closure links between signatures, and getNeighborsId :1703-1893 restricted to the arguments BayesFilter passes
 // (BayesFilter.cpp:329: maxCheckedInDatabase = 0, loop closures stay on the margin of the node they leave from).
-// Everything else of Memory (poses, database, sensors, rehearsal) is out of scope.
+// The similarity half of Memory::rehearsal (:4218-4262, the compareTo of :4245) is available as compareTo(); rehearsalMerge and
+// everything else of Memory (poses, database, sensors) is out of scope.
 #pragma once
 #include <list>
 #include <map>
@@ -49,6 +51,14 @@ public:
     // changed in between (same N, same references) -- otherwise, and for any other signature, it runs lcd_likelihood as before.
     // setDeviceFrames(false) gives the call-by-call path of rounds 1-4 back (lcd_quantize, lcd_sig_add, lcd_likelihood: five
     // synchronisations per frame).  Results are the same (tests run both).
+    // Kp/TfIdfLikelihoodUsed (Parameters.h: true).  false: every computeLikelihood overload answers with Signature::compareTo's words
+    // branch (Memory.cpp:2179-2214 -> lcd_similarity); the likelihood a device frame brought back is TF-IDF and is not used then.
+    // The global-descriptor branch of compareTo (Signature.cpp:257-272) is not implemented.
+    void setTfIdfLikelihoodUsed(bool on) { _tfIdfLikelihoodUsed = on; _likeSig = 0; }
+    bool tfIdfLikelihoodUsed() const { return _tfIdfLikelihoodUsed; }
+    // sigA->compareTo(*sigB) (Signature.cpp:250-288, words branch) for two signatures in memory, as Memory::rehearsal compares the new
+    // signature with the one before it (Memory.cpp:4245); 0 when either is missing or sigB <= 0
+    float compareTo(int sigA, int sigB);
     void setDeviceFrames(bool on) { _deviceFrames = on; _likeSig = 0; }
     bool deviceFrames() const { return _deviceFrames; }
     // the same answer into a caller-owned map: entries whose keys are already there are overwritten in place (Rtabmap asks for nearly the
@@ -100,6 +110,7 @@ private:
     std::map<int, std::map<int, LinkType> > _links; // Signature::getLinks(): id -> (other id -> type)
     // the likelihood update() brought back with the frame: by device slot, for signature _likeSig (0: none / stale)
     bool _deviceFrames;
+    bool _tfIdfLikelihoodUsed;                      // Kp/TfIdfLikelihoodUsed
     int _likeSig;
     std::vector<float> _likeSlots;
     std::vector<std::pair<int, float> > _likeSorted;   // (signature id, value) ascending id, built on demand from _likeSlots

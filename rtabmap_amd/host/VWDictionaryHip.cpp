@@ -686,6 +686,28 @@ std::map<int, float> VWDictionaryHip::computeLikelihood(const std::list<int>& wo
     return likelihood;
 }
 
+// Memory::computeLikelihood, similarity branch (Memory.cpp:2179-2214): sim = signature->compareTo(*sB) for every id > 0
+std::map<int, float> VWDictionaryHip::computeSimilarity(const std::list<int>& wordIds, const std::list<int>& ids, const std::function<int(int)>& getNi) {
+    std::map<int, float> likelihood;
+    if (ids.empty()) { fprintf(stderr, "[WARN] ids list is empty\n"); return likelihood; }   // :2190-2194
+    for (std::list<int>::const_iterator i = ids.begin(); i != ids.end(); ++i) likelihood.insert(likelihood.end(), std::pair<int, float>(*i, 0.0f));
+    if (!_engine) return likelihood;
+    if (!flushReferences(getNi)) { logError("%s", _lastError.c_str()); return likelihood; }
+    // every id > 0 is a valid word of the query (words.size() - invalidWordsCount, Signature.cpp:280), whether or not anything else holds it
+    std::vector<int32_t> q(wordIds.begin(), wordIds.end());
+    std::vector<int32_t> sig;
+    for (std::map<int, float>::iterator i = likelihood.begin(); i != likelihood.end(); ++i) sig.push_back(i->first);
+    std::vector<float> out(sig.size(), 0.0f);
+    if (lcd_similarity(_engine, q.data(), (int)q.size(), sig.data(), (int)sig.size(), out.data(), 0, 0) != LCD_OK) {
+        _lastError = lcd_last_error(_engine);
+        logError("%s", _lastError.c_str());
+        return likelihood;
+    }
+    size_t k = 0;
+    for (std::map<int, float>::iterator i = likelihood.begin(); i != likelihood.end(); ++i, ++k) i->second = i->first > 0 ? out[k] : 0.0f;   // "if(*iter > 0)" (:2199)
+    return likelihood;
+}
+
 // ---------------------------------------------------------------------------------------------- exportDictionary :1619-1696
 void VWDictionaryHip::exportDictionary(const char* fileNameReferences, const char* fileNameDescriptors) const {
     if (_visualWords.empty()) { fprintf(stderr, "[WARN] Dictionary is empty, cannot export it!\n"); return; }

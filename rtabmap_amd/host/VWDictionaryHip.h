@@ -9,7 +9,8 @@
 //     update()        -> lcd_vocab_append | lcd_vocab_remove + lcd_vocab_rebuild      (VWDictionary.cpp:475-701)
 //     addNewWords()   -> lcd_quantize (2-NN + same-frame words + NNDR on the device)  (VWDictionary.cpp:913-1229)
 //     findNN()        -> lcd_find_nn                                                  (VWDictionary.cpp:1273-1552)
-// and Memory::computeLikelihood's TF-IDF branch (Memory.cpp:2215-2291) -> lcd_likelihood through computeLikelihood().
+// and Memory::computeLikelihood's TF-IDF branch (Memory.cpp:2215-2291) -> lcd_likelihood through computeLikelihood(); its other branch
+// (Kp/TfIdfLikelihoodUsed=false, :2179-2214) -> lcd_similarity through computeSimilarity().
 // No search or scoring arithmetic is done on the host: if the engine cannot be created every call fails loudly.
 #pragma once
 #include <cstdlib>
@@ -130,6 +131,11 @@ public:
     // wordIds: the keys of signature->getWords(); N = Memory::getSignatures().size(); getNi = Memory::getNi.
     std::map<int, float> computeLikelihood(const std::list<int>& wordIds, const std::list<int>& ids, float N,
                                            const std::function<int(int)>& getNi);
+
+    // ---- Memory::computeLikelihood(signature, ids) with Kp/TfIdfLikelihoodUsed=false (Memory.cpp:2179-2214): Signature::compareTo's words
+    // branch (Signature.cpp:273-286) of the signature given by its word ids against every id of `ids` -> lcd_similarity.  Ids <= 0 (the
+    // virtual place) and unknown signatures map to 0.  wordIds: the keys of signature->getWords(), ids <= 0 = features without a word.
+    std::map<int, float> computeSimilarity(const std::list<int>& wordIds, const std::list<int>& ids, const std::function<int(int)>& getNi);
 
     // ---- Memory::update's quantisation AND Memory::computeLikelihood of the new signature in ONE device call (lcd_frame_host, ABI v5):
     // addNewWords(descriptors, signatureId) with the bookkeeping of :1162-1219 -- plus, on the device, the signature's references (no

@@ -147,6 +147,10 @@ double hmem_time_loop(void* h, const void* descs, int n_frames, int rows, int co
 }
 
 void hmem_set_device_frames(void* h, int on) { ((MemoryHip*)h)->setDeviceFrames(on != 0); }
+// Kp/TfIdfLikelihoodUsed: 0 = every computeLikelihood answers with Signature::compareTo's words branch (Memory.cpp:2179-2214)
+void hmem_set_tfidf_likelihood_used(void* h, int on) { ((MemoryHip*)h)->setTfIdfLikelihoodUsed(on != 0); }
+// sigA->compareTo(*sigB) for two signatures in memory (the comparison of Memory::rehearsal, Memory.cpp:4245)
+float hmem_compare_to(void* h, int a, int b) { return ((MemoryHip*)h)->compareTo(a, b); }
 // mean milliseconds a device-resident update() spent inside lcd_frame_host so far (-1: none ran)
 double hmem_fast_frame_device_ms(void* h) {
     long long ns = 0, calls = 0;

@@ -61,6 +61,10 @@ def lib():
         L.hmem_time_loop_modes.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
         L.hmem_set_device_frames.argtypes = [vp, ci]
         L.hmem_set_device_frames.restype = None
+        L.hmem_set_tfidf_likelihood_used.argtypes = [vp, ci]
+        L.hmem_set_tfidf_likelihood_used.restype = None
+        L.hmem_compare_to.argtypes = [vp, ci, ci]
+        L.hmem_compare_to.restype = C.c_float
         L.hmem_fast_frame_device_ms.argtypes = [vp]
         L.hmem_fast_frame_device_ms.restype = C.c_double
         L.hmem_add_signatures_bulk.argtypes = [vp, vp, ci, ci, ci]
@@ -275,6 +279,15 @@ class MemoryHip:
         """MemoryHip::setDeviceFrames: update() as ONE device call (lcd_frame_host) that also brings the likelihood back (default), or the
         call-by-call path (lcd_quantize / lcd_sig_add / lcd_likelihood)."""
         lib().hmem_set_device_frames(self.h, int(bool(on)))
+
+    def set_tfidf_likelihood_used(self, on):
+        """Kp/TfIdfLikelihoodUsed.  False: compute_likelihood / compute_likelihood_of answer with Signature::compareTo's words branch
+        (Memory.cpp:2179-2214, lcd_similarity) instead of TF-IDF."""
+        lib().hmem_set_tfidf_likelihood_used(self.h, int(bool(on)))
+
+    def compare_to(self, sig_a, sig_b):
+        """sigA->compareTo(*sigB), words branch, for two signatures in memory (what Memory::rehearsal compares, Memory.cpp:4245)"""
+        return float(lib().hmem_compare_to(self.h, int(sig_a), int(sig_b)))
 
     def add_signatures_bulk(self, words, first_id=1):
         """n signatures (rows of `words`) through Memory::addSignature in C++, then ONE bulk registration on the device"""
