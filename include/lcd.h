@@ -222,16 +222,63 @@ int lcd_likelihood(lcd_engine* h, const int32_t* query_word_ids, int nq, const i
  * out[k] pairs with sig_ids[k]; unknown / retired ids and ids <= 0 give 0 (the reference's "*iter > 0" test).  out_pairs / out_valid
  * (may be NULL): the integers behind out[k], pairs and vs.  nq <= 8192 (more: LCD_ERR_UNSUPPORTED, the handle stays usable); n_ids == 0
  * returns LCD_OK, an empty index gives zeros.
- * Two departures from the reference: ids <= 0 are "no word" on both sides (findPairs would admit a key 0, which RTAB-Map never
- * issues); the global-descriptor branch of compareTo (Signature.cpp:257-272) is not implemented -- signatures are compared by their
- * words alone.  Not available across sharded handles (the pairs would all-reduce, vs needs a second exchange) and not fused into the
- * pipelined launches: stand-alone launches on the engine stream. */
+ * One departure from the reference: ids <= 0 are "no word" on both sides (findPairs would admit a key 0, which RTAB-Map never
+ * issues).  This entry compares signatures by their words alone; lcd_compare_to below adds compareTo's global-descriptor branch and is
+ * the whole of Signature::compareTo.  Not available across sharded handles (the pairs would all-reduce, vs needs a second exchange) and
+ * not fused into the pipelined launches: stand-alone launches on the engine stream. */
 int lcd_similarity(lcd_engine* h, const int32_t* query_word_ids, int nq, const int32_t* sig_ids, int n_ids,
                    float* out, int32_t* out_pairs, int32_t* out_valid);
 /* the same with the query's word ids in DEVICE memory and the dense result over signature slots (as d_likelihood of lcd_frame_dev;
  * retired slots 0); enqueued, not synchronised; completes what a pipelined handle owes first.  capacity = floats available at d_out
  * (smaller than the slots in use: LCD_ERR_INVALID). */
 int lcd_similarity_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, float* d_out, int64_t capacity);
+
+/* ---- Signature::compareTo complete: the global-descriptor branch (Signature.cpp:257-272) in front of the words branch.
+ * A signature may carry up to LCD_GLOBAL_MAX_CHANNELS global descriptors (SensorData::globalDescriptors(), what Mem/GlobalDescriptorStrategy
+ * produces: GlobalDescriptor(type, 1 x dim CV_32F), e.g. a NetVLAD vector of 4096 floats).  A CHANNEL is the index in that vector.  For every
+ * channel on which the query AND the signature hold a descriptor of type 1
+ *     dotProd = (a . b + 1.0f) / 2.0f;  similarity += dotProd;  totalDescs += 1          (ascending channel index)
+ * and, when totalDescs > 0, out = similarity / float(totalDescs); otherwise out is exactly what lcd_similarity returns.
+ * Arithmetic -- defined by the ENGINE: cv::Mat::dot is OpenCV's and its float summation order is not part of the reference tree, so
+ * there is nothing to be bit-exact against.  Products and sums are fp32 with fused multiply-add; the summation order of a . b is a
+ * function of the channel's dim and of nothing else (not of the slot, the number of signatures, the launch or the entry point, and
+ * a . b == b . a); the three statements above are the reference's, in its order.
+ * Not reproduced: UASSERT(dotProd >= 0) -- rows that are not unit vectors are answered as computed, negative values included; the
+ * UASSERT of equal globalDescriptors().size() -- a channel one side never set simply counts as "not type 1".
+ * Storage: a channel's dim (1 .. LCD_GLOBAL_MAX_DIM) is fixed by the first type-1 row stored on it, for the life of the handle.  Nothing
+ * is allocated before that row; then the channel holds one fp32 row per signature slot on the device (counted in
+ * lcd_stats.bytes_device).  lcd_sig_remove leaves the row where it is: the retired signature scores 0 like every retired one.
+ * Not available across sharded handles and not fused into the pipelined launches, as lcd_similarity. */
+#define LCD_GLOBAL_MAX_CHANNELS 4
+#define LCD_GLOBAL_MAX_DIM 16384
+typedef struct lcd_global_desc {
+    int32_t type;              /* GlobalDescriptor::type(); only 1 takes part, anything else is stored as "absent" (data may be NULL) */
+    int32_t dim;               /* floats in data (1 x dim CV_32F) */
+    const float* data;
+} lcd_global_desc;
+/* descs[i] is channel i of signature sig_id; the call REPLACES all of the signature's channels (channels >= n become absent).  data on
+ * the HOST, copied before the call returns.  Errors, after each of which nothing was stored and the handle stays usable: unknown or retired
+ * sig_id LCD_ERR_STATE; n > LCD_GLOBAL_MAX_CHANNELS or dim > LCD_GLOBAL_MAX_DIM LCD_ERR_UNSUPPORTED; on a type-1 entry dim <= 0, a dim
+ * other than the channel's, or data == NULL LCD_ERR_INVALID.  Completes what a pipelined handle owes first, so the signature of a frame in
+ * flight has its slot. */
+int lcd_sig_set_globals(lcd_engine* h, int32_t sig_id, const lcd_global_desc* descs, int n);
+/* the same with data in DEVICE memory (the extractor's output, left where it is); enqueued on the engine stream, not synchronised */
+int lcd_sig_set_globals_dev(lcd_engine* h, int32_t sig_id, const lcd_global_desc* descs, int n);
+/* one type-1 row for each of n_sigs signatures on ONE channel (a database replay); rows on the HOST, [n_sigs x dim]; the signatures' other
+ * channels are left as they are.  A repeated sig id is LCD_ERR_INVALID; otherwise the errors of lcd_sig_set_globals. */
+int lcd_sig_set_global_bulk(lcd_engine* h, int channel, int n_sigs, const int32_t* sig_ids, const float* rows, int dim);
+/* SensorData::clearGlobalDescriptors() (Memory.cpp:3124): every channel of the signature becomes absent */
+int lcd_sig_clear_globals(lcd_engine* h, int32_t sig_id);
+/* this->compareTo(s) for the query (its word ids and its global descriptors, both on the HOST) against the signatures sig_ids[n_ids].
+ * The query's descriptors obey the rules of lcd_sig_set_globals; a query channel on which the handle never stored a row matches nothing.
+ * out[k] pairs with sig_ids[k]; ids <= 0, unknown and retired ids give 0.  out_n_global (may be NULL): totalDescs per id.  n_globals == 0
+ * returns lcd_similarity's bits; n_ids == 0 returns LCD_OK. */
+int lcd_compare_to(lcd_engine* h, const int32_t* query_word_ids, int nq, const lcd_global_desc* query_globals, int n_globals,
+                   const int32_t* sig_ids, int n_ids, float* out, int32_t* out_n_global);
+/* the same with the word ids and the descriptors' data in DEVICE memory and the dense result over the signature slots, as
+ * lcd_similarity_dev: enqueued, not synchronised (query_globals itself, the array of structs, is host memory read during the call) */
+int lcd_compare_to_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, const lcd_global_desc* query_globals, int n_globals,
+                       float* d_out, int64_t capacity);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

@@ -14,6 +14,7 @@ from . import build as _build
 LCD_OK = 0
 LCD_F32, LCD_U8 = 0, 1
 LCD_Q_INCREMENTAL, LCD_Q_NEW_WORDS_COMPARED = 1, 2
+LCD_GLOBAL_MAX_CHANNELS, LCD_GLOBAL_MAX_DIM = 4, 16384      # global descriptors per signature, floats per descriptor (include/lcd.h)
 LCD_NEW_WORD_IDS_AUTO = -1      # lcd_frame_args.first_new_word_id: the device numbers the frame's new words (include/lcd.h)
 STATUS = {0: "LCD_OK", 1: "LCD_ERR_INVALID", 2: "LCD_ERR_HIP", 3: "LCD_ERR_NOMEM", 4: "LCD_ERR_STATE", 5: "LCD_ERR_UNSUPPORTED"}
 
@@ -23,7 +24,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -71,6 +72,10 @@ class LcdStats(C.Structure):
                 ("frame_calls", C.c_int64), ("frame_host_ns", C.c_int64),
                 ("bytes_device", C.c_int64), ("knn_last_fallback_queries", C.c_int64), ("knn_max_err_ratio", C.c_double),
                 ("clean_divergent_refs", C.c_int64)]
+
+
+class LcdGlobalDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("dim", C.c_int32), ("data", C.c_void_p)]
 
 
 class LcdError(RuntimeError):
@@ -130,6 +135,12 @@ def load():
     L.lcd_likelihood.argtypes = [vp, vp, C.c_int, vp, C.c_int, f32, vp]
     L.lcd_similarity.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     L.lcd_similarity_dev.argtypes = [vp, vp, C.c_int, vp, i64]
+    L.lcd_sig_set_globals.argtypes = [vp, i32, vp, C.c_int]
+    L.lcd_sig_set_globals_dev.argtypes = [vp, i32, vp, C.c_int]
+    L.lcd_sig_set_global_bulk.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int]
+    L.lcd_sig_clear_globals.argtypes = [vp, i32]
+    L.lcd_compare_to.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.lcd_compare_to_dev.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, i64]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -338,6 +349,82 @@ class Engine:
             raise ValueError("similarity_dev: contiguous device tensors expected, int32 word ids and float32 output")
         self._ck(self.L.lcd_similarity_dev(self.h, d_query_word_ids.data_ptr() if d_query_word_ids.numel() else None, int(d_query_word_ids.numel()),
                                            d_out.data_ptr(), int(d_out.numel())))
+
+    # ---- global descriptors: Signature::compareTo's other branch
+    @staticmethod
+    def _globals_host(descs):
+        """[(type, row or None), ...] or plain rows (type 1) -> (lcd_global_desc array, count, the arrays kept alive)"""
+        descs = list(descs or [])
+        arr = (LcdGlobalDesc * max(len(descs), 1))()
+        keep = []
+        for i, d in enumerate(descs):
+            typ, row = d if isinstance(d, tuple) else (1, d)
+            if row is None:
+                arr[i] = LcdGlobalDesc(int(typ), 0, None)
+                continue
+            row = np.ascontiguousarray(row, dtype=np.float32).reshape(-1)
+            keep.append(row)
+            arr[i] = LcdGlobalDesc(int(typ), row.shape[0], row.ctypes.data if row.shape[0] else None)
+        return arr, len(descs), keep
+
+    @staticmethod
+    def _globals_dev(descs):
+        """the same for torch tensors of the engine's device"""
+        import torch
+        descs = list(descs or [])
+        arr = (LcdGlobalDesc * max(len(descs), 1))()
+        for i, d in enumerate(descs):
+            typ, row = d if isinstance(d, tuple) else (1, d)
+            if row is None:
+                arr[i] = LcdGlobalDesc(int(typ), 0, None)
+                continue
+            if row.dtype != torch.float32 or not row.is_cuda or not row.is_contiguous():
+                raise ValueError("global descriptors: contiguous float32 device tensors expected")
+            arr[i] = LcdGlobalDesc(int(typ), int(row.numel()), row.data_ptr() if row.numel() else None)
+        return arr, len(descs)
+
+    def sig_set_globals(self, sig_id, descs):
+        """lcd_sig_set_globals: descs[i] is channel i, a float row (type 1) or (type, row or None); replaces all of the signature's channels"""
+        arr, n, keep = self._globals_host(descs)
+        self._ck(self.L.lcd_sig_set_globals(self.h, int(sig_id), C.addressof(arr), n))
+
+    def sig_set_globals_dev(self, sig_id, descs):
+        """lcd_sig_set_globals_dev: the rows are torch tensors on the engine's device; enqueued on the engine stream, not synchronised"""
+        arr, n = self._globals_dev(descs)
+        self._ck(self.L.lcd_sig_set_globals_dev(self.h, int(sig_id), C.addressof(arr), n))
+
+    def sig_set_global_bulk(self, channel, sig_ids, rows):
+        """lcd_sig_set_global_bulk: rows[k] becomes the type-1 descriptor of sig_ids[k] on one channel"""
+        s = np.ascontiguousarray(sig_ids, dtype=np.int32)
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim != 2 or r.shape[0] != s.shape[0]:
+            raise ValueError("sig_set_global_bulk: rows must be [len(sig_ids), dim]")
+        self._ck(self.L.lcd_sig_set_global_bulk(self.h, int(channel), s.shape[0], _p(s), _p(r), r.shape[1]))
+
+    def sig_clear_globals(self, sig_id):
+        self._ck(self.L.lcd_sig_clear_globals(self.h, int(sig_id)))
+
+    def compare_to(self, query_word_ids, query_globals, sig_ids, with_counts=False):
+        """lcd_compare_to: Signature::compareTo of the query (word ids, global descriptors as in sig_set_globals) against sig_ids;
+        with_counts: also totalDescs, the number of global descriptors that took part, per id"""
+        w = np.ascontiguousarray(query_word_ids, dtype=np.int32)
+        s = np.ascontiguousarray(sig_ids, dtype=np.int32)
+        arr, n, keep = self._globals_host(query_globals)
+        out = np.zeros(s.shape[0], np.float32)
+        cnt = np.zeros(s.shape[0], np.int32) if with_counts else None
+        self._ck(self.L.lcd_compare_to(self.h, _p(w), w.shape[0], C.addressof(arr), n, _p(s), s.shape[0], _p(out), _p(cnt)))
+        return (out, cnt) if with_counts else out
+
+    def compare_to_dev(self, d_query_word_ids, query_globals, d_out):
+        """lcd_compare_to_dev on torch tensors of the engine's device: int32 word ids and float32 descriptor rows in, float32 result over the
+        signature slots out (d_out holds at least slot_count entries); enqueued on the engine stream, not synchronised."""
+        import torch
+        if d_query_word_ids.dtype != torch.int32 or d_out.dtype != torch.float32 or not (d_query_word_ids.is_cuda and d_out.is_cuda) or \
+                not (d_query_word_ids.is_contiguous() and d_out.is_contiguous()):
+            raise ValueError("compare_to_dev: contiguous device tensors expected, int32 word ids and float32 output")
+        arr, n = self._globals_dev(query_globals)
+        self._ck(self.L.lcd_compare_to_dev(self.h, d_query_word_ids.data_ptr() if d_query_word_ids.numel() else None, int(d_query_word_ids.numel()),
+                                           C.addressof(arr), n, d_out.data_ptr(), int(d_out.numel())))
 
     def adjust_likelihood_dev(self, d_ptr, n, ratio=0.0):
         self._ck(self.L.lcd_adjust_likelihood_dev(self.h, d_ptr, n, ratio))

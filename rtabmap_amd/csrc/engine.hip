@@ -1076,6 +1076,191 @@ int lcd_similarity_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, f
     LCD_CATCH(h)
 }
 
+// ---- global descriptors (global_similarity.hip): Signature::compareTo's other branch
+// the rules every entry applies to an array of descriptors before anything is stored or launched; a query (sig == false) may name a channel
+// the handle has never stored a row on (it matches nothing)
+static int check_globals(lcd_engine* h, const char* who, const lcd_global_desc* d, int n) {
+    if (n < 0 || (n > 0 && !d)) return h->fail(LCD_ERR_INVALID, std::string(who) + ": null input");
+    if (n > GLOBAL_MAX_CHANNELS) return h->fail(LCD_ERR_UNSUPPORTED, std::string(who) + ": more than 4 global descriptors");
+    for (int i = 0; i < n; ++i) {
+        if (d[i].type != 1) continue;
+        if (d[i].dim > GLOBAL_MAX_DIM) return h->fail(LCD_ERR_UNSUPPORTED, std::string(who) + ": a global descriptor of more than 16384 floats");
+        if (d[i].dim <= 0 || !d[i].data) return h->fail(LCD_ERR_INVALID, std::string(who) + ": a type-1 global descriptor without data");
+        const int have = h->tfidf.glob.ch[i].dim;
+        if (have && have != d[i].dim) return h->fail(LCD_ERR_INVALID, std::string(who) + ": the channel holds rows of another length");
+    }
+    return LCD_OK;
+}
+
+static int set_globals(lcd_engine* h, const char* who, int32_t sig_id, const lcd_global_desc* descs, int n, bool on_device) {
+    int rc = check_globals(h, who, descs, n);
+    if (rc) return rc;
+    Tfidf& t = h->tfidf;
+    auto it = t.sig_slot.find(sig_id);
+    if (it == t.sig_slot.end()) return h->fail(LCD_ERR_STATE, std::string(who) + ": unknown signature");
+    const int64_t slot = it->second;
+    const int64_t hint = (int64_t)(t.slot_sig.cap / 4);
+    size_t off[GLOBAL_MAX_CHANNELS], total = 0;
+    for (int c = 0; c < n; ++c) {
+        if (descs[c].type != 1) continue;
+        LCD_HIP(h, t.glob.ensure(t, c, descs[c].dim, slot + 1, hint));
+        off[c] = total; total += (size_t)descs[c].dim * 4;
+    }
+    if (!on_device && total) {                                        // the rows in one pinned block, one copy
+        LCD_HIP(h, h->h_in.reserve(total));
+        for (int c = 0; c < n; ++c) if (descs[c].type == 1) std::memcpy(h->h_in.as<char>() + off[c], descs[c].data, (size_t)descs[c].dim * 4);
+        LCD_HIP(h, dreserve(h, t.glob.stage, total));
+        LCD_HIP(h, hipMemcpyAsync(t.glob.stage.p, h->h_in.p, total, hipMemcpyHostToDevice, h->stream));
+    }
+    for (int c = 0; c < GLOBAL_MAX_CHANNELS; ++c) {
+        if (c < n && descs[c].type == 1)
+            LCD_HIP(h, t.glob.store(t, c, on_device ? descs[c].data : (const float*)(t.glob.stage.as<char>() + off[c]), 1, nullptr, slot));
+        else
+            LCD_HIP(h, t.glob.clear(t, c, slot));
+    }
+    if (!on_device) LCD_HIP(h, hipStreamSynchronize(h->stream));      // h_in is reused by the next call
+    return LCD_OK;
+}
+
+int lcd_sig_set_globals(lcd_engine* h, int32_t sig_id, const lcd_global_desc* descs, int n) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    LCD_DEV(h);
+    return set_globals(h, "lcd_sig_set_globals", sig_id, descs, n, false);
+    LCD_CATCH(h)
+}
+
+int lcd_sig_set_globals_dev(lcd_engine* h, int32_t sig_id, const lcd_global_desc* descs, int n) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    LCD_DEV(h);
+    return set_globals(h, "lcd_sig_set_globals_dev", sig_id, descs, n, true);
+    LCD_CATCH(h)
+}
+
+int lcd_sig_set_global_bulk(lcd_engine* h, int channel, int n_sigs, const int32_t* sig_ids, const float* rows, int dim) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    LCD_DEV(h);
+    if (channel < 0 || n_sigs < 0 || (n_sigs > 0 && (!sig_ids || !rows))) return h->fail(LCD_ERR_INVALID, "lcd_sig_set_global_bulk: bad argument");
+    if (channel >= GLOBAL_MAX_CHANNELS) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_sig_set_global_bulk: more than 4 global descriptors");
+    if (dim > GLOBAL_MAX_DIM) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_sig_set_global_bulk: a global descriptor of more than 16384 floats");
+    if (dim <= 0) return h->fail(LCD_ERR_INVALID, "lcd_sig_set_global_bulk: dim <= 0");
+    Tfidf& t = h->tfidf;
+    if (t.glob.ch[channel].dim && t.glob.ch[channel].dim != dim) return h->fail(LCD_ERR_INVALID, "lcd_sig_set_global_bulk: the channel holds rows of another length");
+    if (n_sigs == 0) return LCD_OK;
+    {
+        std::vector<int32_t> sorted(sig_ids, sig_ids + n_sigs);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return h->fail(LCD_ERR_INVALID, "lcd_sig_set_global_bulk: repeated signature id");
+    }
+    std::vector<int64_t> slots((size_t)n_sigs);
+    int64_t top = 0;
+    for (int i = 0; i < n_sigs; ++i) {
+        auto it = t.sig_slot.find(sig_ids[i]);
+        if (it == t.sig_slot.end()) return h->fail(LCD_ERR_STATE, "lcd_sig_set_global_bulk: unknown signature");
+        slots[(size_t)i] = it->second;
+        top = std::max(top, it->second + 1);
+    }
+    LCD_HIP(h, t.glob.ensure(t, channel, dim, top, (int64_t)(t.slot_sig.cap / 4)));
+    const size_t bytes = (size_t)n_sigs * (size_t)dim * 4;
+    LCD_HIP(h, h->h_in.reserve((size_t)n_sigs * 8));
+    std::memcpy(h->h_in.p, slots.data(), (size_t)n_sigs * 8);
+    LCD_HIP(h, dreserve(h, h->d_slots, (size_t)n_sigs * 8));
+    LCD_HIP(h, hipMemcpyAsync(h->d_slots.p, h->h_in.p, (size_t)n_sigs * 8, hipMemcpyHostToDevice, h->stream));
+    LCD_HIP(h, dreserve(h, t.glob.stage, bytes));
+    LCD_HIP(h, hipMemcpyAsync(t.glob.stage.p, rows, bytes, hipMemcpyHostToDevice, h->stream));   // caller-owned source: synchronised below
+    LCD_HIP(h, t.glob.store(t, channel, t.glob.stage.as<float>(), n_sigs, h->d_slots.as<int64_t>(), 0));
+    LCD_HIP(h, hipStreamSynchronize(h->stream));
+    return LCD_OK;
+    LCD_CATCH(h)
+}
+
+int lcd_sig_clear_globals(lcd_engine* h, int32_t sig_id) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    LCD_DEV(h);
+    Tfidf& t = h->tfidf;
+    auto it = t.sig_slot.find(sig_id);
+    if (it == t.sig_slot.end()) return h->fail(LCD_ERR_STATE, "lcd_sig_clear_globals: unknown signature");
+    for (int c = 0; c < GLOBAL_MAX_CHANNELS; ++c) LCD_HIP(h, t.glob.clear(t, c, it->second));
+    return LCD_OK;
+    LCD_CATCH(h)
+}
+
+static GlobalQuery global_query(const lcd_global_desc* d, int n, bool on_device) {
+    GlobalQuery q;
+    q.n = n; q.on_device = on_device;
+    for (int c = 0; c < n; ++c) { q.type[c] = d[c].type; q.dim[c] = d[c].dim; q.data[c] = d[c].data; }
+    return q;
+}
+
+// Signature::compareTo: the words branch over every slot (similarity.hip), then the global descriptors replace it where a channel matches
+int lcd_compare_to(lcd_engine* h, const int32_t* query_word_ids, int nq, const lcd_global_desc* query_globals, int n_globals,
+                   const int32_t* sig_ids, int n_ids, float* out, int32_t* out_n_global) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_compare_to");
+    LCD_DEV(h);
+    if (nq < 0 || n_ids < 0 || (nq > 0 && !query_word_ids) || (n_ids > 0 && (!sig_ids || !out)))
+        return h->fail(LCD_ERR_INVALID, "lcd_compare_to: null input");
+    int rc = check_globals(h, "lcd_compare_to", query_globals, n_globals);
+    if (rc) return rc;
+    if (nq > TF_MAX_WORDS) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_compare_to: more than 8192 query words");
+    if (n_ids == 0) return LCD_OK;
+    Tfidf& t = h->tfidf;
+    const size_t ns = (size_t)t.n_slots, ni = (size_t)n_ids;
+    if (ns == 0) {
+        std::memset(out, 0, ni * 4);
+        if (out_n_global) std::memset(out_n_global, 0, ni * 4);
+        return LCD_OK;
+    }
+    rc = stage_word_ids(h, query_word_ids, nq, false);
+    if (rc) return rc;
+    LCD_HIP(h, dreserve(h, h->d_like, (ns + ni) * 4));
+    LCD_HIP(h, dreserve(h, t.sim.d_int, ni * 4));
+    float* d_sim = h->d_like.as<float>();
+    LCD_HIP(h, t.sim.run(t, t.d_stage.as<int32_t>(), nq, d_sim, nullptr, nullptr));
+    LCD_HIP(h, t.glob.run(t, global_query(query_globals, n_globals, false), d_sim));
+    LCD_HIP(h, h->h_in.reserve(ni * 8));
+    int64_t* slots = h->h_in.as<int64_t>();
+    for (int i = 0; i < n_ids; ++i) { auto it = t.sig_slot.find(sig_ids[i]); slots[i] = it == t.sig_slot.end() ? -1 : it->second; }
+    LCD_HIP(h, dreserve(h, h->d_slots, ni * 8));
+    LCD_HIP(h, hipMemcpyAsync(h->d_slots.p, slots, ni * 8, hipMemcpyHostToDevice, h->stream));
+    LCD_HIP(h, launch_gather_f32(d_sim, h->d_slots.as<int64_t>(), n_ids, d_sim + ns, h->stream));
+    const bool counted = t.glob.any();                               // (a handle that never stored a row: totalDescs is 0 everywhere)
+    if (counted) LCD_HIP(h, launch_gather_i32(t.glob.acc_cnt.as<int32_t>(), h->d_slots.as<int64_t>(), n_ids, t.sim.d_int.as<int32_t>(), h->stream));
+    LCD_HIP(h, h->h_out.reserve(2 * ni * 4));
+    char* pin = h->h_out.as<char>();
+    LCD_HIP(h, hipMemcpyAsync(pin, d_sim + ns, ni * 4, hipMemcpyDeviceToHost, h->stream));
+    if (counted) LCD_HIP(h, hipMemcpyAsync(pin + ni * 4, t.sim.d_int.p, ni * 4, hipMemcpyDeviceToHost, h->stream));
+    else std::memset(pin + ni * 4, 0, ni * 4);
+    LCD_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(out, pin, ni * 4);
+    if (out_n_global) std::memcpy(out_n_global, pin + ni * 4, ni * 4);
+    return LCD_OK;
+    LCD_CATCH(h)
+}
+
+int lcd_compare_to_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, const lcd_global_desc* query_globals, int n_globals,
+                       float* d_out, int64_t capacity) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_compare_to_dev");
+    LCD_DEV(h);                                                      // completes what a pipelined handle owes
+    Tfidf& t = h->tfidf;
+    if (nq < 0 || (nq > 0 && !d_query_word_ids) || capacity < 0 || (t.n_slots > 0 && !d_out))
+        return h->fail(LCD_ERR_INVALID, "lcd_compare_to_dev: bad argument");
+    int rc = check_globals(h, "lcd_compare_to_dev", query_globals, n_globals);
+    if (rc) return rc;
+    if (nq > TF_MAX_WORDS) return h->fail(LCD_ERR_UNSUPPORTED, "lcd_compare_to_dev: more than 8192 query words");
+    if (capacity < t.n_slots) return h->fail(LCD_ERR_INVALID, "lcd_compare_to_dev: output buffer smaller than the slots in use");
+    LCD_HIP(h, t.sim.run(t, d_query_word_ids, nq, d_out, nullptr, nullptr));
+    LCD_HIP(h, t.glob.run(t, global_query(query_globals, n_globals, true), d_out));
+    return LCD_OK;
+    LCD_CATCH(h)
+}
+
 // Rtabmap::adjustLikelihood on a device vector whose entry 0 is the virtual place, in place: the decision stage's two passes
 // (bayes.hip) with every entry taking part
 static int adjust_vector(lcd_engine* h, float* d_L, int n, float ratio) {

@@ -295,6 +295,43 @@ struct Similarity {
 };
 hipError_t launch_gather_i32(const int32_t* dense, const int64_t* slots, int n, int32_t* out, hipStream_t s);
 
+// ---- global descriptors (global_similarity.hip): Signature::compareTo's global-descriptor branch (Signature.cpp:257-272).  A channel is the
+// index in SensorData::globalDescriptors(); it holds one dense fp32 row per signature slot and a presence flag per slot (set only when a
+// type-1 row was stored).  Nothing is allocated before the first row of a channel arrives; slots are never reused, a retired slot keeps its
+// row and scores 0 through slot_sig.
+constexpr int GLOBAL_MAX_CHANNELS = 4;            // LCD_GLOBAL_MAX_CHANNELS
+constexpr int GLOBAL_MAX_DIM = 16384;             // LCD_GLOBAL_MAX_DIM: a query row fits 64 KB of LDS
+struct GlobalQuery {                              // the query's descriptors, data on the DEVICE (dim floats each, unpadded) or on the host
+    int n = 0;
+    int type[GLOBAL_MAX_CHANNELS] = {0, 0, 0, 0};
+    int dim[GLOBAL_MAX_CHANNELS] = {0, 0, 0, 0};
+    const float* data[GLOBAL_MAX_CHANNELS] = {nullptr, nullptr, nullptr, nullptr};
+    bool on_device = false;
+};
+struct GlobalRows {
+    struct Channel {
+        DevBuf rows;                              // [cap_slots x stride] fp32, stride = dim rounded up to 4 floats, the tail of a stored row zero
+        DevBuf present;                           // [cap_slots] uint32: 1 = a type-1 row is stored for the slot
+        int dim = 0, stride = 0;                  // fixed by the first row stored on the channel, for the life of the handle
+        int64_t cap_slots = 0;
+    };
+    Channel ch[GLOBAL_MAX_CHANNELS];
+    DevBuf q_rows;                                // the query's rows, zero-padded to the channels' strides, one behind the other
+    DevBuf acc_sum, acc_cnt;                      // per slot: `similarity` and `totalDescs` of compareTo's loop
+    DevBuf stage;                                 // rows of host-side calls on their way to the matrix
+    int n_cus = 0;
+    bool any() const { for (const Channel& c : ch) if (c.dim) return true; return false; }
+    // channel c holds rows of `dim` floats for slots [0, slots): allocates on first use (sized for slots_hint), grows keeping what is stored
+    hipError_t ensure(Tfidf& t, int c, int dim, int64_t slots, int64_t slots_hint);
+    // n rows [n x dim] on the device -> the slots d_slots[n] (or the single slot slot0 when d_slots == NULL) of channel c, flags set
+    hipError_t store(Tfidf& t, int c, const float* d_src, int n, const int64_t* d_slots, int64_t slot0);
+    hipError_t clear(Tfidf& t, int c, int64_t slot);                  // the slot's flag of channel c becomes 0 (the row stays)
+    // out[slot] holds the words-branch value of every slot on entry (Similarity::run); slots with a matching channel receive
+    // sum / totalDescs, out_cnt (acc_cnt, dense over the slots) the totalDescs of every slot.  Enqueued on t.stream.
+    hipError_t run(Tfidf& t, const GlobalQuery& q, float* out);
+    void destroy(int64_t* bytes);
+};
+
 // recycled allocations of bucket-sized device buffers (a bucket is born and dies every 256 frames in steady state:
 // hipMalloc / hipFree there would synchronise the device)
 struct BufPool {
@@ -315,6 +352,7 @@ struct Tfidf {
     DevBuf bkt_tab, bkt_ne, bkt_D, bkt_flags;
     std::vector<Bucket> buckets;
     Similarity sim;                      // the pair similarity's own lists and the lazy per-slot valid-word counts
+    GlobalRows glob;                     // the signatures' global descriptors (compareTo's other branch); empty until a row is stored
     int score_block = 512;               // threads per scoring workgroup (256 / 512 / 1024; lcd_set_option "score_block")
     int q_n_ub = 0;                      // word count of the last frame handed to frame_words (upper bound of its unique words)
     BufPool pool;

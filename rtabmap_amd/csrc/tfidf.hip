@@ -429,6 +429,7 @@ hipError_t Tfidf::init(hipStream_t s, int64_t* bytes, int64_t sig_capacity, int6
 void Tfidf::destroy() {
     keys.destroy();
     sim.destroy(bytes_device);
+    glob.destroy(bytes_device);
     for (Bucket& b : buckets) { b.coo_w.release(bytes_device); b.coo_pc.release(bytes_device); b.sealed.release(bytes_device); }
     buckets.clear();
     pool.destroy(bytes_device);

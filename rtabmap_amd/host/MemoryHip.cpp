@@ -253,6 +253,8 @@ void MemoryHip::forget(int signatureId) {
     _vwd->removeAllWordRefs(keys, signatureId);
     _dbNi[signatureId] = (int)it->second.size();
     _signatures.erase(it);
+    _globals.erase(signatureId);                // (its device rows stay behind in a retired slot, which scores 0)
+    _globalsDirty.erase(signatureId);
     _stMem.erase(signatureId);                  // the links stay (they are in the database): getNeighborsId stops at the missing node
     _workingMem.erase(signatureId);
 }
@@ -265,8 +267,8 @@ std::vector<int> MemoryHip::signatureIds() const {
 
 std::map<int, float> MemoryHip::computeLikelihood(const std::list<int>& wordIds, const std::list<int>& ids) {
     Stage st(_vwd, "Memory::computeLikelihood");
-    if (!_tfIdfLikelihoodUsed) {                 // Memory.cpp:2179-2214
-        std::map<int, float> S = _vwd->computeSimilarity(wordIds, ids, [this](int s) { return this->getNi(s); });
+    if (!_tfIdfLikelihoodUsed) {                 // Memory.cpp:2179-2214 (no signature, no global descriptors: the words branch)
+        std::map<int, float> S = this->similarityOf(0, wordIds, ids);
         _stats["Timing/Likelihood_computation/ms"] = st.ms();
         return S;
     }
@@ -280,9 +282,67 @@ float MemoryHip::compareTo(int sigA, int sigB) {
     std::map<int, std::vector<int> >::const_iterator it = _signatures.find(sigA);
     if (it == _signatures.end() || sigB <= 0 || !_signatures.count(sigB)) return 0.0f;
     Stage st(_vwd, "Signature::compareTo");
-    const std::map<int, float> S = _vwd->computeSimilarity(std::list<int>(it->second.begin(), it->second.end()), std::list<int>(1, sigB),
-                                                           [this](int s) { return this->getNi(s); });
+    const std::map<int, float> S = this->similarityOf(sigA, std::list<int>(it->second.begin(), it->second.end()), std::list<int>(1, sigB));
     return S.empty() ? 0.0f : S.begin()->second;
+}
+
+// ---- global descriptors
+bool MemoryHip::setGlobalDescriptors(int signatureId, const std::vector<GlobalDescriptor>& descriptors) {
+    if (!_signatures.count(signatureId) || descriptors.size() > (size_t)LCD_GLOBAL_MAX_CHANNELS) return false;
+    for (size_t c = 0; c < descriptors.size(); ++c) if (descriptors[c].data.size() > (size_t)LCD_GLOBAL_MAX_DIM) return false;
+    _globals[signatureId] = descriptors;
+    _globalsDirty.insert(signatureId);
+    return true;
+}
+
+void MemoryHip::clearGlobalDescriptors(int signatureId) {
+    if (_globals.erase(signatureId)) _globalsDirty.insert(signatureId);
+}
+
+const std::vector<MemoryHip::GlobalDescriptor>& MemoryHip::globalDescriptors(int signatureId) const {
+    static const std::vector<GlobalDescriptor> none;
+    std::map<int, std::vector<GlobalDescriptor> >::const_iterator it = _globals.find(signatureId);
+    return it == _globals.end() ? none : it->second;
+}
+
+static std::vector<lcd_global_desc> asLcd(const std::vector<MemoryHip::GlobalDescriptor>& g) {
+    std::vector<lcd_global_desc> d(g.size());
+    for (size_t c = 0; c < g.size(); ++c) {
+        d[c].type = g[c].data.empty() ? 0 : g[c].type;          // (an empty cv::Mat cannot be compared: absent)
+        d[c].dim = (int32_t)g[c].data.size();
+        d[c].data = g[c].data.empty() ? 0 : g[c].data.data();
+    }
+    return d;
+}
+
+bool MemoryHip::flushGlobals() {
+    if (_globals.empty() && _globalsDirty.empty()) return this->flushReferences();
+    // a signature whose references changed gets a new slot from flushReferences: its rows follow it there
+    const std::set<int>& moved = _vwd->dirtySignatures();
+    for (std::set<int>::const_iterator s = moved.begin(); s != moved.end(); ++s) if (_globals.count(*s)) _globalsDirty.insert(*s);
+    if (!this->flushReferences()) return false;
+    for (std::set<int>::iterator s = _globalsDirty.begin(); s != _globalsDirty.end();) {
+        if (!_vwd->isOnDevice(*s)) { if (_globals.count(*s)) ++s; else s = _globalsDirty.erase(s); continue; }   // no slot yet: later
+        std::map<int, std::vector<GlobalDescriptor> >::const_iterator g = _globals.find(*s);
+        const std::vector<lcd_global_desc> d = g == _globals.end() ? std::vector<lcd_global_desc>() : asLcd(g->second);
+        const int rc = d.empty() ? lcd_sig_clear_globals(_vwd->engine(), *s) : lcd_sig_set_globals(_vwd->engine(), *s, d.data(), (int)d.size());
+        if (rc != LCD_OK) { fprintf(stderr, "[ERROR] global descriptors of signature %d: %s\n", *s, lcd_last_error(_vwd->engine())); return false; }
+        s = _globalsDirty.erase(s);
+    }
+    return true;
+}
+
+// this->compareTo(s) of the query (signature querySig's descriptors, if it is in memory and has any) against every id of `ids`
+std::map<int, float> MemoryHip::similarityOf(int querySig, const std::list<int>& wordIds, const std::list<int>& ids) {
+    std::vector<lcd_global_desc> d;
+    std::map<int, std::vector<GlobalDescriptor> >::const_iterator g = _globals.find(querySig);
+    if (g != _globals.end()) d = asLcd(g->second);
+    if (_vwd->engine() && !ids.empty() && !this->flushGlobals()) {
+        std::map<int, float> zeros;
+        for (std::list<int>::const_iterator i = ids.begin(); i != ids.end(); ++i) zeros[*i] = 0.0f;
+        return zeros;
+    }
+    return _vwd->computeSimilarity(wordIds, ids, [this](int s) { return this->getNi(s); }, d.empty() ? 0 : d.data(), (int)d.size());
 }
 
 // (signature id, likelihood) of every signature registered on the device, ascending id, from the frame's slot-indexed result
@@ -329,6 +389,12 @@ std::map<int, float> MemoryHip::computeLikelihood(int signatureId, const std::li
         if (sorted) for (std::list<int>::const_iterator i = ids.begin(); i != ids.end(); ++i) likelihood.insert(likelihood.end(), std::pair<int, float>(*i, lookupSorted(v, cursor, *i)));
         else for (std::list<int>::const_iterator i = ids.begin(); i != ids.end(); ++i) likelihood[*i] = lookupSorted(v, cursor, *i);
         return likelihood;
+    }
+    if (!_tfIdfLikelihoodUsed) {                 // Memory.cpp:2179-2214: sim = signature->compareTo(*sB)
+        Stage st(_vwd, "Memory::computeLikelihood");
+        std::map<int, float> S = this->similarityOf(signatureId, std::list<int>(it->second.begin(), it->second.end()), ids);
+        _stats["Timing/Likelihood_computation/ms"] = st.ms();
+        return S;
     }
     return computeLikelihood(std::list<int>(it->second.begin(), it->second.end()), ids);
 }

@@ -3,7 +3,7 @@
 // Mirrors (reference corelib/src/Memory.cpp): preUpdate :1004-1016 + cleanUnusedWords :6899-6920, the quantisation glue
 // of createSignature :5941-6059 (features not sent to quantisation get ids -1,-2,.. and still count in ni),
 // getNi :4955-4968, disableWordsRef :6877-6897 (WM -> LTM transfer) and computeLikelihood :2177-2292 (both branches: TF-IDF, and with
-// Kp/TfIdfLikelihoodUsed=false Signature::compareTo's words branch).
+// Kp/TfIdfLikelihoodUsed=false Signature::compareTo, global descriptors and words).
 // For the Bayes filter it also keeps what BayesFilter asks a Memory: the short-term / working memory
 // split (addSignatureToStm :1146-1230, the transfer loop of update() :1112-1135, moveSignatureToWMFromSTM :1442), neighbour and
 // loop-closure links between signatures, and getNeighborsId :1703-1893 restricted to the arguments BayesFilter passes
@@ -53,12 +53,23 @@ public:
     // synchronisations per frame).  Results are the same (tests run both).
     // Kp/TfIdfLikelihoodUsed (Parameters.h: true).  false: every computeLikelihood overload answers with Signature::compareTo's words
     // branch (Memory.cpp:2179-2214 -> lcd_similarity); the likelihood a device frame brought back is TF-IDF and is not used then.
-    // The global-descriptor branch of compareTo (Signature.cpp:257-272) is not implemented.
+    // computeLikelihood(signatureId, ids) and compareTo() answer the whole of Signature::compareTo (Signature.cpp:250-288): when the query
+    // signature carries global descriptors (setGlobalDescriptors) they go to lcd_compare_to, which scores by them wherever a channel matches
+    // and by the words elsewhere.  computeLikelihood(wordIds, ids) has no signature, hence no descriptors: words only.
     void setTfIdfLikelihoodUsed(bool on) { _tfIdfLikelihoodUsed = on; _likeSig = 0; }
     bool tfIdfLikelihoodUsed() const { return _tfIdfLikelihoodUsed; }
-    // sigA->compareTo(*sigB) (Signature.cpp:250-288, words branch) for two signatures in memory, as Memory::rehearsal compares the new
+    // sigA->compareTo(*sigB) (Signature.cpp:250-288) for two signatures in memory, as Memory::rehearsal compares the new
     // signature with the one before it (Memory.cpp:4245); 0 when either is missing or sigB <= 0
     float compareTo(int sigA, int sigB);
+    // SensorData::setGlobalDescriptors / globalDescriptors() / clearGlobalDescriptors of a signature in memory: the host copy is kept here, as
+    // SensorData keeps it, and reaches the device (lcd_sig_set_globals) before the next comparison that needs it.  descriptors[i] is channel i;
+    // only type 1 takes part (GlobalDescriptor.h: 1 x dim CV_32F).  false: no such signature, more than LCD_GLOBAL_MAX_CHANNELS entries or a row of
+    // more than LCD_GLOBAL_MAX_DIM floats.  forget() drops them with the signature (Memory.cpp:3124 clears them where a node leaves the working memory's
+    // comparisons).  A signature without a single valid word is not registered on the device and cannot hold rows there: it scores 0.
+    struct GlobalDescriptor { int type; std::vector<float> data; };
+    bool setGlobalDescriptors(int signatureId, const std::vector<GlobalDescriptor>& descriptors);
+    void clearGlobalDescriptors(int signatureId);
+    const std::vector<GlobalDescriptor>& globalDescriptors(int signatureId) const;
     void setDeviceFrames(bool on) { _deviceFrames = on; _likeSig = 0; }
     bool deviceFrames() const { return _deviceFrames; }
     // the same answer into a caller-owned map: entries whose keys are already there are overwritten in place (Rtabmap asks for nearly the
@@ -111,6 +122,10 @@ private:
     // the likelihood update() brought back with the frame: by device slot, for signature _likeSig (0: none / stale)
     bool _deviceFrames;
     bool _tfIdfLikelihoodUsed;                      // Kp/TfIdfLikelihoodUsed
+    std::map<int, std::vector<GlobalDescriptor> > _globals;   // SensorData::globalDescriptors() per signature in memory
+    std::set<int> _globalsDirty;                    // ... whose device rows are not what _globals says
+    bool flushGlobals();                            // references first (a re-registered signature has a new slot), then the rows
+    std::map<int, float> similarityOf(int querySig, const std::list<int>& wordIds, const std::list<int>& ids);
     int _likeSig;
     std::vector<float> _likeSlots;
     std::vector<std::pair<int, float> > _likeSorted;   // (signature id, value) ascending id, built on demand from _likeSlots

@@ -687,7 +687,8 @@ std::map<int, float> VWDictionaryHip::computeLikelihood(const std::list<int>& wo
 }
 
 // Memory::computeLikelihood, similarity branch (Memory.cpp:2179-2214): sim = signature->compareTo(*sB) for every id > 0
-std::map<int, float> VWDictionaryHip::computeSimilarity(const std::list<int>& wordIds, const std::list<int>& ids, const std::function<int(int)>& getNi) {
+std::map<int, float> VWDictionaryHip::computeSimilarity(const std::list<int>& wordIds, const std::list<int>& ids, const std::function<int(int)>& getNi,
+                                                        const lcd_global_desc* globals, int nGlobals) {
     std::map<int, float> likelihood;
     if (ids.empty()) { fprintf(stderr, "[WARN] ids list is empty\n"); return likelihood; }   // :2190-2194
     for (std::list<int>::const_iterator i = ids.begin(); i != ids.end(); ++i) likelihood.insert(likelihood.end(), std::pair<int, float>(*i, 0.0f));
@@ -698,7 +699,9 @@ std::map<int, float> VWDictionaryHip::computeSimilarity(const std::list<int>& wo
     std::vector<int32_t> sig;
     for (std::map<int, float>::iterator i = likelihood.begin(); i != likelihood.end(); ++i) sig.push_back(i->first);
     std::vector<float> out(sig.size(), 0.0f);
-    if (lcd_similarity(_engine, q.data(), (int)q.size(), sig.data(), (int)sig.size(), out.data(), 0, 0) != LCD_OK) {
+    const int rc = nGlobals > 0 ? lcd_compare_to(_engine, q.data(), (int)q.size(), globals, nGlobals, sig.data(), (int)sig.size(), out.data(), 0)
+                                : lcd_similarity(_engine, q.data(), (int)q.size(), sig.data(), (int)sig.size(), out.data(), 0, 0);
+    if (rc != LCD_OK) {
         _lastError = lcd_last_error(_engine);
         logError("%s", _lastError.c_str());
         return likelihood;

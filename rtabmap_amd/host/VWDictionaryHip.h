@@ -10,7 +10,7 @@
 //     addNewWords()   -> lcd_quantize (2-NN + same-frame words + NNDR on the device)  (VWDictionary.cpp:913-1229)
 //     findNN()        -> lcd_find_nn                                                  (VWDictionary.cpp:1273-1552)
 // and Memory::computeLikelihood's TF-IDF branch (Memory.cpp:2215-2291) -> lcd_likelihood through computeLikelihood(); its other branch
-// (Kp/TfIdfLikelihoodUsed=false, :2179-2214) -> lcd_similarity through computeSimilarity().
+// (Kp/TfIdfLikelihoodUsed=false, :2179-2214) -> lcd_similarity / lcd_compare_to through computeSimilarity().
 // No search or scoring arithmetic is done on the host: if the engine cannot be created every call fails loudly.
 #pragma once
 #include <cstdlib>
@@ -135,7 +135,14 @@ public:
     // ---- Memory::computeLikelihood(signature, ids) with Kp/TfIdfLikelihoodUsed=false (Memory.cpp:2179-2214): Signature::compareTo's words
     // branch (Signature.cpp:273-286) of the signature given by its word ids against every id of `ids` -> lcd_similarity.  Ids <= 0 (the
     // virtual place) and unknown signatures map to 0.  wordIds: the keys of signature->getWords(), ids <= 0 = features without a word.
-    std::map<int, float> computeSimilarity(const std::list<int>& wordIds, const std::list<int>& ids, const std::function<int(int)>& getNi);
+    // globals / nGlobals: the query signature's global descriptors (SensorData::globalDescriptors()); with any, the whole of compareTo
+    // (Signature.cpp:250-288) is answered -> lcd_compare_to
+    std::map<int, float> computeSimilarity(const std::list<int>& wordIds, const std::list<int>& ids, const std::function<int(int)>& getNi,
+                                           const lcd_global_desc* globals = 0, int nGlobals = 0);
+    // what MemoryHip needs to keep the signatures' global descriptors on the device: a signature whose references changed is registered
+    // again by flushReferences (a new slot, without rows); only a registered signature can hold rows
+    const std::set<int>& dirtySignatures() const { return _dirtySigs; }
+    bool isOnDevice(int signatureId) const { return _deviceSigs.count(signatureId) != 0; }
 
     // ---- Memory::update's quantisation AND Memory::computeLikelihood of the new signature in ONE device call (lcd_frame_host, ABI v5):
     // addNewWords(descriptors, signatureId) with the bookkeeping of :1162-1219 -- plus, on the device, the signature's references (no

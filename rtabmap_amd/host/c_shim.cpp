@@ -151,6 +151,20 @@ void hmem_set_device_frames(void* h, int on) { ((MemoryHip*)h)->setDeviceFrames(
 void hmem_set_tfidf_likelihood_used(void* h, int on) { ((MemoryHip*)h)->setTfIdfLikelihoodUsed(on != 0); }
 // sigA->compareTo(*sigB) for two signatures in memory (the comparison of Memory::rehearsal, Memory.cpp:4245)
 float hmem_compare_to(void* h, int a, int b) { return ((MemoryHip*)h)->compareTo(a, b); }
+// SensorData::setGlobalDescriptors of a signature in memory: n descriptors, types[i] / dims[i], their floats one behind the other in `data`
+// (1: stored, 0: refused -- MemoryHip::setGlobalDescriptors); n == 0 is clearGlobalDescriptors
+int hmem_set_global_descriptors(void* h, int sigId, int n, const int* types, const int* dims, const float* data) {
+    if (n <= 0) { ((MemoryHip*)h)->clearGlobalDescriptors(sigId); return 1; }
+    std::vector<MemoryHip::GlobalDescriptor> g((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        g[(size_t)i].type = types[i];
+        if (dims[i] > 0) g[(size_t)i].data.assign(data, data + dims[i]);
+        data += dims[i] > 0 ? dims[i] : 0;
+    }
+    return ((MemoryHip*)h)->setGlobalDescriptors(sigId, g) ? 1 : 0;
+}
+// globalDescriptors().size() of a signature in memory (0: none, or no such signature)
+int hmem_num_global_descriptors(void* h, int sigId) { return (int)((MemoryHip*)h)->globalDescriptors(sigId).size(); }
 // mean milliseconds a device-resident update() spent inside lcd_frame_host so far (-1: none ran)
 double hmem_fast_frame_device_ms(void* h) {
     long long ns = 0, calls = 0;

@@ -65,6 +65,8 @@ def lib():
         L.hmem_set_tfidf_likelihood_used.restype = None
         L.hmem_compare_to.argtypes = [vp, ci, ci]
         L.hmem_compare_to.restype = C.c_float
+        L.hmem_set_global_descriptors.argtypes = [vp, ci, ci, vp, vp, vp]
+        L.hmem_num_global_descriptors.argtypes = [vp, ci]
         L.hmem_fast_frame_device_ms.argtypes = [vp]
         L.hmem_fast_frame_device_ms.restype = C.c_double
         L.hmem_add_signatures_bulk.argtypes = [vp, vp, ci, ci, ci]
@@ -286,8 +288,24 @@ class MemoryHip:
         lib().hmem_set_tfidf_likelihood_used(self.h, int(bool(on)))
 
     def compare_to(self, sig_a, sig_b):
-        """sigA->compareTo(*sigB), words branch, for two signatures in memory (what Memory::rehearsal compares, Memory.cpp:4245)"""
+        """sigA->compareTo(*sigB) for two signatures in memory (what Memory::rehearsal compares, Memory.cpp:4245): by their global
+        descriptors where both carry one of type 1 on the same channel, by their words otherwise"""
         return float(lib().hmem_compare_to(self.h, int(sig_a), int(sig_b)))
+
+    def set_global_descriptors(self, sig_id, descs):
+        """SensorData::setGlobalDescriptors of a signature in memory: descs[i] is channel i, a float row (type 1) or (type, row or None);
+        an empty list clears them.  False: refused (no such signature, too many or too long)."""
+        types, dims, rows = [], [], []
+        for d in descs:
+            typ, row = d if isinstance(d, tuple) else (1, d)
+            row = np.zeros(0, np.float32) if row is None else np.ascontiguousarray(row, dtype=np.float32).reshape(-1)
+            types.append(int(typ)); dims.append(row.shape[0]); rows.append(row)
+        t, m = np.asarray(types, np.int32), np.asarray(dims, np.int32)
+        data = np.concatenate(rows) if rows else np.zeros(0, np.float32)
+        return bool(lib().hmem_set_global_descriptors(self.h, int(sig_id), len(types), _p(t), _p(m), _p(data)))
+
+    def num_global_descriptors(self, sig_id):
+        return int(lib().hmem_num_global_descriptors(self.h, int(sig_id)))
 
     def add_signatures_bulk(self, words, first_id=1):
         """n signatures (rows of `words`) through Memory::addSignature in C++, then ONE bulk registration on the device"""
