@@ -292,6 +292,8 @@ struct lcd_engine {
     hipStream_t kst = nullptr;                          // the stream the 2-NN stage is enqueued on (== stream)
     FramePipeline pipe;
     const void* last_fail_count = nullptr;              // certificate counters of the latest pipelined frame (lcd_get_stats)
+    // tests (lcd_debug_last_frame_knn): where the latest frame's 2-NN stage left its rows, words and distances ([q x 2] each)
+    const void* dbg_knn_row = nullptr; const void* dbg_knn_word = nullptr; const void* dbg_knn_dist = nullptr; int dbg_knn_q = 0;
     // ---- VWDictionary::update()'s append branch on the device (lcd_frame_args.append_new_words): see AppendLog
     AppendLog applog;
     int64_t vocab_capacity_cfg = 0;                     // lcd_config.vocab_capacity: every per-row buffer is sized for it

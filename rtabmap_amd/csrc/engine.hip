@@ -384,6 +384,7 @@ int prepare_resolve(lcd_engine* h, const void* d_desc, int q, int flags, float n
     r->out_word = d_out_word;
     r->out_n_new = h->d_n_new.as<int32_t>();
     r->knn_row = h->d_knn_row.as<int32_t>();
+    h->dbg_knn_row = h->d_knn_row.p; h->dbg_knn_word = h->d_knn_word.p; h->dbg_knn_dist = h->d_knn_dist.p; h->dbg_knn_q = q;
     r->row_wslot = h->row_wslot.as<int32_t>();
     r->out_wslot = d_out_wslot;
     r->new_ws = WsRuns();

@@ -230,6 +230,7 @@ static int build_knn(lcd_engine* h, FramePipeline::InFlight& f, PipeKnn* kp, con
     if (!sc.fail_count_clean) LCD_HIP(h, hipMemsetAsync(sc.d_fail_count.p, 0, 8, h->stream));
     sc.fail_count_clean = true;                                      // the frame's decision loop (a later launch A) resets the counters
     h->last_fail_count = sc.d_fail_count.p;
+    h->dbg_knn_row = k.out_row; h->dbg_knn_word = k.out_word; h->dbg_knn_dist = k.out_dist; h->dbg_knn_q = q;
     // ---- the decision loop's arguments (launched one call later), the redo of rejected queries riding with it
     ResolveArgs& r = f.r;
     r = ResolveArgs();
@@ -552,6 +553,30 @@ int lcd_debug_host_profile(const lcd_engine* h, int64_t* out9) {
     if (!h || !out9) return LCD_ERR_INVALID;
     for (int i = 0; i < 9; ++i) out9[i] = h->host_prof[i];
     return LCD_OK;
+}
+
+// The 2-NN stage of the LATEST frame as it stands on the device: rows, words and distances, [q x 2] each (capacity in queries; any of the three may be NULL),
+// *out_q = its descriptor count.  Nothing is drained: behind lcd_synchronize these are the frame's final neighbours (exact redo included); on a pipelined
+// handle right behind lcd_frame_dev they are the neighbours of the frame BEFORE the one just passed in (its launch B has run, its decision loop has not), and
+// out_rejected = the queries its certificate sent to the exact redo (the decision loop resets that counter: 0 on a plain handle).  Tests; not part of lcd.h.
+int lcd_debug_last_frame_knn(lcd_engine* h, int32_t* out_row, int32_t* out_word, float* out_dist, int capacity, int* out_q, int* out_rejected) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    LCD_DEV_NODRAIN(h);
+    if (!out_q) return LCD_ERR_INVALID;
+    *out_q = h->dbg_knn_q;
+    if (out_rejected) *out_rejected = 0;
+    if (h->dbg_knn_q <= 0 || !h->dbg_knn_row) return LCD_OK;
+    if (capacity < h->dbg_knn_q) return h->fail(LCD_ERR_INVALID, "lcd_debug_last_frame_knn: capacity below the frame's descriptor count");
+    LCD_HIP(h, hipStreamSynchronize(h->stream));
+    if (h->kst && h->kst != h->stream) LCD_HIP(h, hipStreamSynchronize(h->kst));
+    const size_t bytes = (size_t)h->dbg_knn_q * 2 * 4;
+    if (out_row) LCD_HIP(h, hipMemcpy(out_row, h->dbg_knn_row, bytes, hipMemcpyDeviceToHost));
+    if (out_word) LCD_HIP(h, hipMemcpy(out_word, h->dbg_knn_word, bytes, hipMemcpyDeviceToHost));
+    if (out_dist) LCD_HIP(h, hipMemcpy(out_dist, h->dbg_knn_dist, bytes, hipMemcpyDeviceToHost));
+    if (out_rejected && h->last_fail_count) LCD_HIP(h, hipMemcpy(out_rejected, h->last_fail_count, 4, hipMemcpyDeviceToHost));
+    return LCD_OK;
+    LCD_CATCH(h)
 }
 
 int lcd_slot_count(const lcd_engine* h, int64_t* n_slots) {

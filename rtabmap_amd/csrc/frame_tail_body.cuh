@@ -479,6 +479,17 @@ __device__ __forceinline__ void frame_tail_body(uint32_t* ft_dyn_smem, const Res
     FT_STAMP(3);
 }
 
+// p, a pointer to global memory that is uniform over the wave, as a scalar register pair of its own: the value is no longer a part of the
+// multi-register kernel-argument load it came from, so what is kept alive (or spilled, to a lane) across a long body is this one pair, and the
+// accesses through it are still global ones.  frame_resolve_part takes the pointers it uses up to its last stores this way, which keeps
+// launch A free of a private segment (tests/test_pipeline_scratch.py; profiles/launch_b_scratch.txt 5).
+template <class T>
+__device__ __forceinline__ T* scalar_global(T* p) {
+    auto g = (__attribute__((address_space(1))) T*)p;
+    asm volatile("" : "+s"(g));
+    return (T*)g;
+}
+
 // The same tail split in two for the pipelined handle (frame_a_kernel): the decision loop of frame t - 1 and the retirement +
 // registration of frame t - 2 run as two workgroups of the SAME launch (12.9 us + 9.2 us at 256 threads used to be one 22 us chain,
 // longer than the 20 us filter it was meant to hide behind).  The word slots travel through global memory (out_wslot), new words as
@@ -486,6 +497,9 @@ __device__ __forceinline__ void frame_tail_body(uint32_t* ft_dyn_smem, const Res
 template <int NT>
 __device__ __forceinline__ void frame_resolve_part(uint32_t* ft_dyn_smem, const ResolveArgs& r, int wb, int n_wb) {
     if (wb > 0) { rowpar_body<64, NT>(r.rp, wb - 1, n_wb - 1, r.fail_count); return; }
+    int32_t* const out_word = scalar_global(r.out_word); int32_t* const out_n_new = scalar_global(r.out_n_new); int32_t* const out_wslot = scalar_global(r.out_wslot);
+    const int32_t* const knn_row = scalar_global(r.knn_row); const int32_t* const row_wslot = scalar_global(r.row_wslot);
+    const uint2* const cand_list = scalar_global(r.cand_list); const int32_t* const cand_cnt = scalar_global(r.cand_cnt);
     constexpr int KPT = 1024 / NT;
     const bool fast = r.q <= KPT * NT;
     const bool helpers = r.rp.enabled && n_wb > 1;
@@ -505,10 +519,10 @@ __device__ __forceinline__ void frame_resolve_part(uint32_t* ft_dyn_smem, const 
     FT_STAMP(0);
     const uint32_t* fmask;
     if (fast) fmask = resolve_body_fast<NT, KPT>(ft_dyn_smem, nullptr, r.q, r.flags, r.nndr, r.have_index, r.knn_word, r.knn_dist, r.selfdist,
-                                                 r.ld, r.cand_bits, r.bw, r.out_word, r.out_n_new, r.knn_row, r.row_wslot, r.out_wslot, r.new_ws,
-                                                 r.cand_list, r.cand_cnt, &n_in_early, cnt_in, helpers ? r.fail_count : nullptr, r.slots_are_rows != 0, r.straight != 0);
-    else { asm volatile("" : "+v"(n_in_early)); fmask = resolve_body<NT>(ft_dyn_smem, r.q, r.flags, r.nndr, r.have_index, r.knn_word, r.knn_dist, r.selfdist, r.ld, r.cand_bits, r.bw, r.out_word,
-                                  r.out_n_new, r.knn_row, r.row_wslot, r.out_wslot, r.new_ws, r.slots_are_rows != 0); }   // (both paths leave n_in_early awaited: the
+                                                 r.ld, r.cand_bits, r.bw, out_word, out_n_new, knn_row, row_wslot, out_wslot, r.new_ws,
+                                                 cand_list, cand_cnt, &n_in_early, cnt_in, helpers ? r.fail_count : nullptr, r.slots_are_rows != 0, r.straight != 0);
+    else { asm volatile("" : "+v"(n_in_early)); fmask = resolve_body<NT>(ft_dyn_smem, r.q, r.flags, r.nndr, r.have_index, r.knn_word, r.knn_dist, r.selfdist, r.ld, r.cand_bits, r.bw, out_word,
+                                  out_n_new, knn_row, row_wslot, out_wslot, r.new_ws, r.slots_are_rows != 0); }   // (both paths leave n_in_early awaited: the
                                                                         // compiler's wait in front of its use would otherwise cover the loop's stores)
     if (threadIdx.x == 0 && r.fail_count) { r.fail_count[0] = 0; r.fail_count[1] = 0; r.fail_count[3] = 0; }
     if (r.ap.enabled && r.ap.defer_rows) append_publish<NT>(r.ap, r.q, fmask, ft_dyn_smem + 2 * ((r.q + 63) / 64 * 2), n_in_early);

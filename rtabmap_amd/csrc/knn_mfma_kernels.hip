@@ -1097,6 +1097,7 @@ hipError_t launch_frame_a(const PipeKnn* kp, const QSplitArgs* qsp, const TailLa
 }
 
 
+static long long g_b_routes[8];                                        // see lcd_debug_launch_b_routes
 hipError_t launch_frame_b(const PipeKnn* k, const ScoreArgs* score, int score_wgs, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
                           const AppendRowsArgs* app, const PipeOpts& opt) {
     RerankArgs rk{};
@@ -1118,7 +1119,7 @@ hipError_t launch_frame_b(const PipeKnn* k, const ScoreArgs* score, int score_wg
     if (n_rerank + score_wgs + n_app == 0) return hipSuccess;
     // frames that append their words on the device: 40 KB of dynamic LDS stage 160 pending rows per re-rank workgroup (three workgroups
     // of launch B share a compute unit: 3 x (40 + 10) KB of its 160 KB); the workgroups that write appended rows stage them there too
-    const uint32_t dyn = ((k && k->n_hi) || n_app) ? PIPE_B_STAGE_ROWS * 256u + 512u : 0u;   // + the workgroup's two queries
+    const uint32_t dyn = ((k && k->n_hi) || n_app) ? PIPE_B_STAGE_ROWS * 256u : 0u;   // (the workgroup's two queries lie in the body's static LDS)
     rk.stage_rows = (dyn && k && k->n_hi) ? (int)PIPE_B_STAGE_ROWS : 0;
     ar.ap.lds_bytes = (int)(PIPE_B_STAGE_ROWS * 256u);
     if (k && n_app) { rk.pend_desc = ar.ap.descriptors; rk.pend_list = ar.ap.list_out; rk.pend_first_id = ar.ap.first_id; }   // k's pending rows ARE the rows being written
@@ -1142,6 +1143,11 @@ hipError_t launch_frame_b(const PipeKnn* k, const ScoreArgs* score, int score_wg
     const int n_wr = (!writers && n_app == 0 && k && app && app->ap.enabled && app->ap.defer_rows && k->n_hi && k->plan.q > 0 && rk.stage_rows >= 4 && !rk.cross &&
                       (opt.row_writer_wgs > 0 || shadow)) ? (opt.row_writer_wgs > 0 ? opt.row_writer_wgs : 16) : 0;
     if (shadow && n_wr == 0) return hipErrorInvalidValue;
+    if (k && n_rerank > 0) {                                         // (tests: lcd_debug_launch_b_routes)
+        g_b_routes[0] += 1; g_b_routes[1] += shadow ? 1 : 0; g_b_routes[2] += n_wr > 0 ? 1 : 0; g_b_routes[3] += rk.cross ? 1 : 0;
+        g_b_routes[4] += (rk.pend_list && !shadow && !rk.cross && rk.stage_rows >= 4) ? 1 : 0;
+        g_b_routes[5] += (!writers && n_app == 0 && n_wr == 0 && rk.pend_list) ? 1 : 0; g_b_routes[6] = n_wr; g_b_routes[7] = n_rerank;
+    }
     const bool split = n_app > 0 && score && score->n_closed >= (opt.append_split_buckets >= 0 ? opt.append_split_buckets : APPEND_SPLIT_BUCKETS);   // (see frame_b_kernel)
     if (split || n_app == 0) {
         if (n_rerank + score_wgs > 0) {
@@ -1159,6 +1165,17 @@ hipError_t launch_frame_b(const PipeKnn* k, const ScoreArgs* score, int score_wg
 }
 
 }  // namespace lcd
+
+// Which routes the launches B of this process were given through the re-rank role since the last reset (tests; host-side counts of what each launch was
+// set up for -- whether rows were pending at all is the device's to know --, nothing is read from the device): out8[0] launches with re-rank workgroups, of which [1] with shadow scores (the new words of the frame before as candidates of one row each),
+// [2] with row-writer workgroups of the re-rank role, [3] with the pending rows' distances from the cross-frame tiles, [4] with the pending rows staged and
+// scanned by every re-rank workgroup, [5] with the rows written by the re-rank workgroups themselves; [6] writer workgroups and [7] re-rank workgroups (two
+// queries each, padded to a multiple of eight) of the latest such launch.
+extern "C" int lcd_debug_launch_b_routes(long long* out8, int reset) {
+    if (out8) for (int i = 0; i < 8; ++i) out8[i] = lcd::g_b_routes[i];
+    if (reset) for (int i = 0; i < 8; ++i) lcd::g_b_routes[i] = 0;
+    return 0;
+}
 
 // The launch plan of a pipelined frame's filter for a vocabulary of n_rows and q descriptors, as the engine makes it (tests; no device
 // needed): out[0] tiles per workgroup, [1] strips, [2] persistent workgroups per block of 512 queries (0: one workgroup per strip),

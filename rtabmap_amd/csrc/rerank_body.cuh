@@ -136,16 +136,24 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     const int32_t pend_id0 = pend_first_id > 0 ? pend_first_id : n_lo0 - pend_first_id;   // word id of the first pending row
     // with shadow rows the pending scan only has to cover vocabulary rows the filter's plan did not reach ([p_lo, n_lo0): rare)
     const int p_hi_s = sh_q > 0 ? min(p_hi, n_lo0) : p_hi;
+    // the pinned row-count mirror of the frame whose rows this launch writes, when its decision loop left it to this launch (AppendArgs::mirror_later):
+    // one thread of the launch, at the END of its workgroup's body (a store to host memory in front of a load would hold that load for its acknowledgement)
+    auto store_mirror = [&]() {
+        const AppendArgs& ap = wr.ap;
+        if (ap.mirror_later && ap.host_mirror && wr_on && wr_index == 0 && threadIdx.x == 0)
+            __hip_atomic_store(ap.host_mirror, ((unsigned long long)ap.tag << 32) | (unsigned long long)(uint32_t)p_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    };
+    // a writer workgroup without rows to write leaves here, in front of every request (a request nobody waits for would be waited for at the mirror's store)
+    if (rows_only && (!wr_on || stage == nullptr || stage_rows < 4 || pend_list == nullptr || p_hi - n_lo0 <= wr_index)) { store_mirror(); return; }
     __shared__ uint32_t s_plist[NT];                                   // the first entries of pend_list (one per thread: read with the keys)
-    const uint32_t plreg = pend_list ? pend_list[threadIdx.x] : 0u;    // (the list buffer holds at least NT entries)
+    uint32_t plreg = 0u, shreg = 0u;                                   // (requested behind the keys; the writers request theirs below)
     auto plist_at = [&](int j) -> uint32_t { return j < NT ? s_plist[j] : pend_list[j]; };
     constexpr int SH_MW_MAX = 128;                                     // mask words of a frame of 4 096 descriptors
     __shared__ uint32_t s_shmask[2 * SH_MW_MAX + 1];
     const int sh_mw = sh_q > 0 ? (sh_q + 63) / 64 * 2 : 0;
-    const uint32_t shreg = (sh_q > 0 && (int)threadIdx.x < 2 * sh_mw + 1) ? sh_mask[threadIdx.x] : 0u;
     auto sh_isword = [&](uint32_t j) -> bool { return (s_shmask[j >> 5] >> (j & 31)) & 1u; };
     auto sh_rank = [&](uint32_t j) -> int { return (int)(s_shmask[sh_mw + (j >> 5)] + (uint32_t)__popc(s_shmask[j >> 5] & ((1u << (j & 31)) - 1u))); };
-    const int hf = HALVES == 2 ? (int)threadIdx.x / MF_BLOCK : 0;
+    const int hf = HALVES == 2 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / MF_BLOCK) : 0;   // (uniform over the wave: the query index and all that follows from it stay scalar)
     const int tid = HALVES == 2 ? (int)threadIdx.x % MF_BLOCK : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // The pending rows are the same for every query: with a staging area they come in by LDS-DMA -- no registers, requested in front of pass 2,
     // a whole chunk in one round trip that runs under the two passes -- instead of four rows per 16-lane group and trip
@@ -204,19 +212,11 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
         }
         append_norm_max(ap, nmax);
     };
-    // the pinned row-count mirror of the frame whose rows this launch writes, when its decision loop left it to this launch (AppendArgs::mirror_later):
-    // one thread of the launch, at the END of its workgroup's body (a store to host memory in front of a load would hold that load for its acknowledgement)
-    auto store_mirror = [&]() {
-        const AppendArgs& ap = wr.ap;
-        if (ap.mirror_later && ap.host_mirror && wr_on && wr_index == 0 && threadIdx.x == 0)
-            __hip_atomic_store(ap.host_mirror, ((unsigned long long)ap.tag << 32) | (unsigned long long)(uint32_t)p_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    };
 
     // ---- rows-only exit: a writer workgroup of the re-rank role stages its rows (wr_index + wr_n m, m < n_mine) and writes them
     if (rows_only) {                                                 // (uniform over the workgroup)
         const int n_new = p_hi - n_lo0;
-        if (!wr_on || stage == nullptr || stage_rows < 4 || pend_list == nullptr || n_new <= wr_index) { store_mirror(); return; }
-        s_plist[threadIdx.x] = plreg;
+        s_plist[threadIdx.x] = pend_list[threadIdx.x];
         lds_barrier();
         const int wv = (int)threadIdx.x >> 6, ln = (int)threadIdx.x & 63;       // (wave of the WORKGROUP: both halves stage rows together)
         const int n_mine = (n_new - wr_index + wr_n - 1) / wr_n;
@@ -278,10 +278,17 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     int32_t (&s_word)[RR_MAX_CAND] = s_word_all[hf];
     float (&s_err)[MF_WAVES] = s_err_all[hf];
     uint64_t (&s_pend)[MF_WAVES][2] = s_pend_all[hf];
+    // the query slice of every lane (chunk lane & 15) is needed up to the last exact distance: it lives in LDS, not in four registers held across the whole body
+    __shared__ float4 s_q_all[HALVES][16];
+    const float4* const s_q = s_q_all[hf];
 
     // ---- up-front requests.  Everything that does not depend on other loads is requested here (the kernel is a chain of round trips): the
-    // first two keys and the first bound of every thread, the query slice, the vocabulary norm bound and -- for the candidate bits -- the
-    // thread's two entries of the query's row of the same-frame distance matrix.
+    // first three keys and the first bound of every thread, the query slice, the vocabulary norm bound, -- for the candidate bits -- the
+    // thread's two entries of the query's row of the same-frame distance matrix, the shadow scores and, LAST, the thread's list and mask entries:
+    // requested in front of the keys (where they used to be) they are waited for before the first key's address is formed -- a round trip of
+    // their own at the head of every re-rank workgroup.
+    // Register budget (frame_b_kernel<false>: 80, no scratch -- tests/test_pipeline_scratch.py): the query slice goes to LDS as soon as its norm
+    // is taken, the waves' bounds stay in LDS until the certificate, and the half / query index is scalar.
     RR_STAMP(0);
     const uint64_t kreg0 = tid < n_keys ? key_at(tid) : KEY_NONE;
     const uint64_t kreg1 = tid + MF_BLOCK < n_keys ? key_at(tid + MF_BLOCK) : KEY_NONE;
@@ -296,6 +303,8 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     }
     float2 xsh = make_float2(__int_as_float(0x7f800000), __int_as_float(0x7f800000));   // the query's scores against descriptors 2 tid, 2 tid + 1 of the frame before
     if (sh_q > 0 && 2 * tid < sh_ld) xsh = *reinterpret_cast<const float2*>(sh_x + (size_t)qi * sh_ld + 2 * tid);
+    if (pend_list) plreg = pend_list[threadIdx.x];                     // (the list buffer holds at least NT entries)
+    if (sh_q > 0 && (int)threadIdx.x < 2 * sh_mw + 1) shreg = sh_mask[threadIdx.x];
     float qn = fmaf(q4.w, q4.w, fmaf(q4.z, q4.z, fmaf(q4.y, q4.y, q4.x * q4.x)));
 #pragma unroll
     for (int m = 8; m >= 1; m >>= 1) qn += __shfl_xor(qn, m, 64);
@@ -346,16 +355,15 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
                                              (__attribute__((address_space(3))) void*)(xd + hf * XD_MAX + j0 + wave * 64), 4, 0, 0);
         }
     }
-    if (staged && lane < 16 && wave == 0) reinterpret_cast<float4*>(stage + (size_t)stage_rows * DIM)[hf * 16 + lane] = q4;   // the query, for every lane
+    if (lane < 16 && wave == 0) s_q_all[hf][lane] = q4;                // the query, for every lane
     lds_barrier();                                                     // (LDS traffic only: __syncthreads() would also wait for the rows just requested)
     RR_STAMP(1);
-    a0 = s_a0[0]; a1 = s_a1[0]; bound = s_bound[0];
+    a0 = s_a0[0]; a1 = s_a1[0];                                        // (the waves' bounds stay in LDS until the certificate reads them)
 #pragma unroll
     for (int wi = 1; wi < MF_WAVES; ++wi) {
         const uint32_t o0 = s_a0[wi], o1 = s_a1[wi];
         a1 = min(max(a0, o0), min(a1, o1));
         a0 = min(a0, o0);
-        bound = min(bound, s_bound[wi]);
     }
     const float eps = BF16 ? (f16 ? eps_f16(DIM, qn, vn_max) : eps_bf16(DIM, qn, vn_max)) : eps_for(DIM, qn, vn_max);
     const float tau = __uint_as_float(a1);
@@ -427,7 +435,7 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
             const uint32_t row = cand_row(i);
             const bool sh = sh_q > 0 && (uint32_t)key >= SHADOW_ROW_BASE;
             const bool in_range = sh ? (GS == 1 || (i & 3) == 0) : (GS == 1 || row < row_limit);
-            const float t = l2_term4(v4, q4);
+            const float t = l2_term4(v4, s_q[lane & 15]);
             float res = 0.0f;
 #pragma unroll
             for (int j = 0; j < 16; ++j) res = __fadd_rn(res, __shfl(t, (lane & 48) + j, 64));
@@ -479,11 +487,10 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
                 // ONE LANE PER ROW: the sixteen 4-float terms are formed and added by the same lane in the reference's order (dist.h:150-177),
                 // the row's chunks from LDS, the query's as a broadcast read -- no cross-lane traffic (sixteen lanes per row gathered the
                 // terms with sixteen ds_bpermute per row: at ~150 pending rows per query that was the whole cost of the scan)
-                const float4* sq = reinterpret_cast<const float4*>(stage + (size_t)stage_rows * DIM) + hf * 16;
                 for (int r = tid; r < n_chunk; r += MF_BLOCK) {
                     float res = 0.0f;
 #pragma unroll 4
-                    for (int c = 0; c < 16; ++c) res = __fadd_rn(res, l2_term4(*staged_chunk(stage, r, c), sq[c]));
+                    for (int c = 0; c < 16; ++c) res = __fadd_rn(res, l2_term4(*staged_chunk(stage, r, c), s_q[c]));
                     top2_push(pb, ps, ((uint64_t)__float_as_uint(res) << 32) | (uint32_t)(c0 + r));
                 }
                 if (wr_on && sh_q == 0 && c0 + stage_rows < p_hi) write_rows(c0, n_chunk);   // (more than one chunk: the staging area is about to be reused;
@@ -500,7 +507,7 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
 #pragma unroll
             for (int u = 0; u < PU; ++u) {                             // sixteen lanes per row
                 const int r0 = base + u * (MF_BLOCK / 16) + (tid >> 4);
-                const float t = l2_term4(v4[u], q4);
+                const float t = l2_term4(v4[u], s_q[lane & 15]);
                 float res = 0.0f;
 #pragma unroll
                 for (int j = 0; j < 16; ++j) res = __fadd_rn(res, __shfl(t, (lane & 48) + j, 64));
@@ -560,6 +567,8 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     // trip each time (three of them in the first version of this block: 3.6 us of an 8 us chain, measured with in-kernel stamps).
     if (tid == 0 && valid) {
         err_ratio = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
+        static_assert(MF_WAVES == 4, "the four waves' partial results");
+        bound = min(min(s_bound[0], s_bound[1]), min(s_bound[2], s_bound[3]));
         const uint64_t win[2] = {best, second};
         const int sl[2] = {sbest, ssecond};
         int32_t wout[2] = {0, 0};

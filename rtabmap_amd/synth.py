@@ -33,6 +33,19 @@ def queries_surf(vocab, q, seed=500, frac_known=0.7, sigma=0.05):
     return np.ascontiguousarray(out, dtype=np.float32)
 
 
+def revisit_surf(rng, history, q, fresh_frac=0.3, sigma=0.02):
+    """A frame that revisits one of the earlier frames in `history` ([n x 64] arrays): noisy unit-norm copies of q of its descriptors (so that the
+    words that frame CREATED are matched again), a fraction fresh_frac of them replaced by fresh SURF-like draws (they become words)."""
+    fresh = vocab_surf(q, seed=int(rng.integers(1 << 30)))
+    src = history[int(rng.integers(len(history)))]
+    out = src[rng.integers(0, src.shape[0], q)].copy()
+    out += rng.standard_normal(out.shape).astype(np.float32) * np.float32(sigma)
+    out /= np.linalg.norm(out, axis=1, keepdims=True)
+    m = rng.random(q) < fresh_frac
+    out[m] = fresh[m]
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
 def vocab_orb(n, seed=200000, nbytes=32):
     rng = np.random.default_rng(seed)
     return rng.integers(0, 256, (n, nbytes), dtype=np.uint8)
