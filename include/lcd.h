@@ -104,7 +104,9 @@ typedef struct lcd_config {
                                   handle, which completes the owed stages first; lcd_synchronize to wait for them): keep
                                   lcd_pipeline_depth() + 1 sets of buffers and rotate.  lcd_sig_remove, lcd_record_event and
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
-                                  place in the call order.  Results are identical with and without. */
+                                  place in the call order.  Results are identical with and without.  The one exception to "any other
+                                  call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev touch no engine state and complete
+                                  nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
 
@@ -279,6 +281,63 @@ int lcd_compare_to(lcd_engine* h, const int32_t* query_word_ids, int nq, const l
  * lcd_similarity_dev: enqueued, not synchronised (query_globals itself, the array of structs, is host memory read during the call) */
 int lcd_compare_to_dev(lcd_engine* h, const int32_t* d_query_word_ids, int nq, const lcd_global_desc* query_globals, int n_globals,
                        float* d_out, int64_t capacity);
+
+/* ---- two-frame descriptor matching, stateless: the verification step behind the loop-closure hypothesis (RegistrationVis.cpp:1383-1504,
+ * Rtabmap::process and every proximity candidate).  n_pairs frame pairs per call; the rows of all pairs are concatenated, pair p owns the
+ * from-rows [from_offsets[p], from_offsets[p+1]) and the to-rows [to_offsets[p], to_offsets[p+1]).  The call needs no handle per pair and
+ * reads and writes NOTHING of the handle's vocabulary, index, Bayes filter or word numbering ("next_word_id"); it only borrows the
+ * handle's dtype, dim, device and stream.
+ *
+ * LCD_MATCH_DICTIONARY (Vis/CorNNType 0-4, :1482-1503: the temporary two-frame VWDictionary).  For each pair the outputs are exactly what
+ *   1. lcd_quantize(from, flags, nndr_ratio) on an empty vocabulary, new words numbered 1, 2, ... in descriptor order (++_lastWordId from 0),
+ *   2. lcd_vocab_append of those words in ascending id (update()),
+ *   3. lcd_quantize(to, flags, nndr_ratio), its new words continuing the numbering,
+ * return on a fresh handle of the same dtype and dim: the indexed search of step 3 takes part only if step 1 made at least 2 words
+ * (VWDictionary.cpp:1015); with LCD_Q_NEW_WORDS_COMPARED from-rows match each other (out_from_word_ids repeats ids), without it every
+ * from-row is a word; a pair without to-rows gives only the from ids, a pair without from-rows runs `to` against nothing.
+ * from_word_ids != NULL (orignalWordsFromIds): step 1 is addWord(id, row) per from-row (:1488-1496, VWDictionary::addWord :1554) --
+ * out_from_word_ids echoes the ids, the vocabulary rows are in ascending id (the distance tie-break), the to-frame's new words are numbered
+ * from max(id) + 1.  The ids must be > 0 and distinct within a pair: lcd_match_pairs checks it (LCD_ERR_INVALID); lcd_match_pairs_dev cannot
+ * see them and leaves it to the caller (other ids give ids that mean nothing, never an access out of bounds).
+ * flags without LCD_Q_INCREMENTAL: LCD_ERR_INVALID (a fixed dictionary without indexed words returns an empty list, :926).
+ *
+ * LCD_MATCH_CROSS_CHECK (Vis/CorNNType 5, :1451-1453: cv::BFMatcher(NORM_HAMMING | NORM_L2SQR, crossCheck = true).match(to, from)).  OpenCV's
+ * source is not part of the reference tree, so the rule is defined by the ENGINE.  With D[i][j] the exact distance of to-row i and from-row j
+ * (the bits lcd_knn2 returns):
+ *     nn(i)   = argmin over j of D[i][j], the lowest j on ties;
+ *     back(j) = the i with the smallest D[i][j] among { i : nn(i) == j }, the lowest i on ties;
+ *     out_to_match[i] = nn(i) if back(nn(i)) == i, else -1;      out_to_dist[i] = D[i][nn(i)] for EVERY to-row, -1.0f when `from` is empty.
+ * A from-row is kept by the closest of the to-rows that chose it (cv::batchDistance's cross-check as best known); this is NOT the symmetric
+ * mutual nearest neighbour: a from-row's own nearest to-row is never computed.
+ * The reference's id bookkeeping behind the match (:1465-1477) is the host mirror's (VWDictionaryHip::matchFrames).
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on one side of a pair or
+ * n_pairs > 65535 LCD_ERR_UNSUPPORTED; offsets that do not start at 0 or decrease, a NULL pointer where the mode needs an input or output (rows or an output of zero rows may be NULL),
+ * an unknown mode or a wrong struct_size LCD_ERR_INVALID; lcd_match_pairs_dev on a handle whose rows are padded (lcd_config.dim)
+ * LCD_ERR_UNSUPPORTED (lcd_match_pairs serves it).  Not offered across sharded handles.
+ * Pipelined handles: see lcd_config.pipeline -- this is the one call that does NOT complete what the handle owes.  It runs on scratch of its
+ * own (counted in lcd_stats.bytes_device), two launches per group of pairs; a batch whose distance blocks exceed the larger of 256 MiB and
+ * the largest single pair runs in consecutive groups ("pair_match_budget" of lcd_set_option moves the 256 MiB, results never depend on it). */
+enum lcd_match_mode { LCD_MATCH_DICTIONARY = 0, LCD_MATCH_CROSS_CHECK = 1 };
+typedef struct lcd_match_args {
+    int32_t struct_size;            /* sizeof(lcd_match_args) */
+    int32_t mode;                   /* lcd_match_mode */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t flags;                  /* lcd_quantize_flags, dictionary mode only */
+    float   nndr_ratio;             /* Vis/CorNNDR, dictionary mode only */
+    int32_t reserved;
+    const void* from; const void* to;                          /* rows of all pairs, concatenated, the handle's dtype and dim (device entry: 16-byte aligned) */
+    const int64_t* from_offsets; const int64_t* to_offsets;    /* HOST, [n_pairs + 1] row offsets, non-decreasing, [0] == 0 */
+    const int32_t* from_word_ids;   /* may be NULL; dictionary mode: orignalWordsFromIds, one per from-row */
+    int32_t* out_from_word_ids;     /* dictionary mode, one per from-row */
+    int32_t* out_to_word_ids;       /* dictionary mode, one per to-row */
+    int32_t* out_to_match;          /* cross-check mode, one per to-row: from-row index WITHIN its pair, -1 = none */
+    float*   out_to_dist;           /* cross-check mode, may be NULL: distance to nn(i), written whether or not the match is kept */
+} lcd_match_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_match_pairs(lcd_engine* h, const lcd_match_args* a);
+/* from, to, from_word_ids and out_* in DEVICE memory, the offsets on the HOST (read during the call); enqueued on the engine stream, not synchronised */
+int lcd_match_pairs_dev(lcd_engine* h, const lcd_match_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */
@@ -487,6 +546,7 @@ int lcd_profile_read_likelihood(lcd_engine* h, float* avg_ms, int* n_samples, co
  * "append_from_rerank": 1 (built-in) = those rows are written by the re-rank workgroups of launch B, 0 = by eight row-writer
  * workgroups.  "cross_frame_tiles": 1 = launch A also computes a frame's distances to the frame before it and the re-rank reads
  * the distances of the rows that frame appended from there instead of staging the rows (0 / -1 = built-in: staged).
+ * "pair_match_budget": bytes of distance blocks lcd_match_pairs gives one group of pairs (0 = built-in, 256 MiB; a single pair always fits; tests).
  * Unknown keys / values -> LCD_ERR_INVALID.
  * The two keys that DO change what a call means (sharded handles only, identical on every rank): "shard_growth_first" = F and
  * "shard_growth_block" = B > 0 make lcd_shard_frame_dev give the words frames create (ids >= F) to rank ((id - F) / B) % world instead of

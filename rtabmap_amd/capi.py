@@ -15,6 +15,7 @@ LCD_OK = 0
 LCD_F32, LCD_U8 = 0, 1
 LCD_Q_INCREMENTAL, LCD_Q_NEW_WORDS_COMPARED = 1, 2
 LCD_GLOBAL_MAX_CHANNELS, LCD_GLOBAL_MAX_DIM = 4, 16384      # global descriptors per signature, floats per descriptor (include/lcd.h)
+LCD_MATCH_DICTIONARY, LCD_MATCH_CROSS_CHECK = 0, 1          # lcd_match_args.mode (include/lcd.h)
 LCD_NEW_WORD_IDS_AUTO = -1      # lcd_frame_args.first_new_word_id: the device numbers the frame's new words (include/lcd.h)
 STATUS = {0: "LCD_OK", 1: "LCD_ERR_INVALID", 2: "LCD_ERR_HIP", 3: "LCD_ERR_NOMEM", 4: "LCD_ERR_STATE", 5: "LCD_ERR_UNSUPPORTED"}
 
@@ -24,7 +25,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -76,6 +77,16 @@ class LcdStats(C.Structure):
 
 class LcdGlobalDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("dim", C.c_int32), ("data", C.c_void_p)]
+
+
+class LcdMatchArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("n_pairs", C.c_int32), ("flags", C.c_int32), ("nndr_ratio", C.c_float),
+                ("reserved", C.c_int32), ("from_rows", C.c_void_p), ("to_rows", C.c_void_p), ("from_offsets", C.c_void_p),
+                ("to_offsets", C.c_void_p), ("from_word_ids", C.c_void_p), ("out_from_word_ids", C.c_void_p),
+                ("out_to_word_ids", C.c_void_p), ("out_to_match", C.c_void_p), ("out_to_dist", C.c_void_p)]
+
+
+MATCH_MODES = {"dictionary": LCD_MATCH_DICTIONARY, "cross_check": LCD_MATCH_CROSS_CHECK}
 
 
 class LcdError(RuntimeError):
@@ -141,6 +152,8 @@ def load():
     L.lcd_sig_clear_globals.argtypes = [vp, i32]
     L.lcd_compare_to.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
     L.lcd_compare_to_dev.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, i64]
+    L.lcd_match_pairs.argtypes = [vp, C.POINTER(LcdMatchArgs)]
+    L.lcd_match_pairs_dev.argtypes = [vp, C.POINTER(LcdMatchArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -349,6 +362,58 @@ class Engine:
             raise ValueError("similarity_dev: contiguous device tensors expected, int32 word ids and float32 output")
         self._ck(self.L.lcd_similarity_dev(self.h, d_query_word_ids.data_ptr() if d_query_word_ids.numel() else None, int(d_query_word_ids.numel()),
                                            d_out.data_ptr(), int(d_out.numel())))
+
+    # ---- two-frame descriptor matching (stateless: nothing of the handle is read or written)
+    def _match_args(self, mode, n_pairs, from_offsets, to_offsets, new_words_compared, nndr):
+        mode = MATCH_MODES[mode] if isinstance(mode, str) else int(mode)
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64)
+        if fo.shape != (n_pairs + 1,) or to.shape != (n_pairs + 1,):
+            raise ValueError("match_pairs: offsets are [n_pairs + 1]")
+        flags = LCD_Q_INCREMENTAL | (LCD_Q_NEW_WORDS_COMPARED if new_words_compared else 0)
+        a = LcdMatchArgs(C.sizeof(LcdMatchArgs), mode, n_pairs, flags if mode == LCD_MATCH_DICTIONARY else 0, nndr, 0)
+        a.from_offsets, a.to_offsets = fo.ctypes.data, to.ctypes.data
+        return a, mode, fo, to
+
+    def match_pairs(self, from_rows, to_rows, from_offsets, to_offsets, mode="dictionary", new_words_compared=True, nndr=0.8,
+                    from_word_ids=None):
+        """lcd_match_pairs over host arrays: pair p is from_rows[from_offsets[p]:from_offsets[p+1]] against to_rows[to_offsets[p]:...].
+        "dictionary" -> (from_word_ids, to_word_ids); "cross_check" -> (match per to-row: from-row index within the pair or -1, distance)."""
+        f, t = self._rows(from_rows), self._rows(to_rows)
+        a, mode, fo, to = self._match_args(mode, len(from_offsets) - 1, from_offsets, to_offsets, new_words_compared, nndr)
+        if int(fo[-1]) != f.shape[0] or int(to[-1]) != t.shape[0]:
+            raise ValueError("match_pairs: the last offset is the number of rows")
+        ids = None if from_word_ids is None else np.ascontiguousarray(from_word_ids, dtype=np.int32)
+        if ids is not None and ids.shape != (f.shape[0],):
+            raise ValueError("match_pairs: one word id per from-row")
+        a.from_rows, a.to_rows, a.from_word_ids = _p(f), _p(t), _p(ids)
+        nf, nt = f.shape[0], t.shape[0]
+        if mode == LCD_MATCH_DICTIONARY:
+            o1, o2 = np.zeros(max(nf, 1), np.int32), np.zeros(max(nt, 1), np.int32)
+            a.out_from_word_ids, a.out_to_word_ids = _p(o1), _p(o2)
+        else:
+            o1, o2 = np.zeros(max(nt, 1), np.int32), np.zeros(max(nt, 1), np.float32)
+            a.out_to_match, a.out_to_dist = _p(o1), _p(o2)
+        self._ck(self.L.lcd_match_pairs(self.h, C.byref(a)))
+        return (o1[:nf], o2[:nt]) if mode == LCD_MATCH_DICTIONARY else (o1[:nt], o2[:nt])
+
+    def match_pair(self, from_rows, to_rows, mode="dictionary", **kw):
+        """one pair: match_pairs with the offsets [0, n]"""
+        return self.match_pairs(from_rows, to_rows, [0, len(from_rows)], [0, len(to_rows)], mode, **kw)
+
+    def match_pairs_dev(self, d_from, d_to, from_offsets, to_offsets, d_out_a, d_out_b, mode="dictionary", new_words_compared=True,
+                        nndr=0.8, d_from_word_ids=None):
+        """lcd_match_pairs_dev on torch tensors of the engine's device (rows of the handle's dtype, int32 ids; offsets stay on the host):
+        "dictionary" writes d_out_a = from word ids, d_out_b = to word ids (int32); "cross_check" d_out_a = match per to-row (int32),
+        d_out_b = distance per to-row (float32) or None.  Enqueued on the engine stream, not synchronised."""
+        a, mode, fo, to = self._match_args(mode, len(from_offsets) - 1, from_offsets, to_offsets, new_words_compared, nndr)
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        a.from_rows, a.to_rows, a.from_word_ids = ptr(d_from), ptr(d_to), ptr(d_from_word_ids)
+        if mode == LCD_MATCH_DICTIONARY:
+            a.out_from_word_ids, a.out_to_word_ids = ptr(d_out_a), ptr(d_out_b)
+        else:
+            a.out_to_match, a.out_to_dist = ptr(d_out_a), ptr(d_out_b)
+        self._ck(self.L.lcd_match_pairs_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

@@ -486,6 +486,7 @@ void lcd_destroy(lcd_engine* h) {
     for (DevBuf* d : all) d->release(&h->bytes_device);
     h->applog.release(&h->bytes_device);
     h->d_rmlog.release(&h->bytes_device);
+    h->pairs.release(&h->bytes_device);
     h->h_in.release(); h->h_out.release(); h->h_out2.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1740,6 +1741,8 @@ int lcd_set_option(lcd_engine* h, const char* key, int64_t value) {
     if (!std::strcmp(key, "profile_skip") && value >= 0 && value <= (1 << 20)) { h->prof_skip = (int)value; return LCD_OK; }
     if (!std::strcmp(key, "decision_straight") && value >= -1 && value <= 2) { h->popt.decision_straight = value >= 0 ? (int)value : PipeOpts().decision_straight; return LCD_OK; }
     if (!std::strcmp(key, "slots_from_rows") && value >= -1 && value <= 2) { h->popt.slots_from_rows = value >= 0 ? (int)value : PipeOpts().slots_from_rows; return LCD_OK; }
+    // tests: the distance-block bytes lcd_match_pairs gives one group of pairs (0: built-in); a single pair always fits
+    if (!std::strcmp(key, "pair_match_budget") && value >= 0 && value <= (1ll << 40)) { h->pairs.budget_bytes = value; return LCD_OK; }
     if (!std::strcmp(key, "row_writer_wgs") && value >= -1 && value <= 256) { h->popt.row_writer_wgs = value >= 0 ? (int)value : PipeOpts().row_writer_wgs; return LCD_OK; }
     return h->fail(LCD_ERR_INVALID, "lcd_set_option: unknown key or value");
     LCD_CATCH(h)

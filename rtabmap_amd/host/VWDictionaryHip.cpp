@@ -464,6 +464,62 @@ std::list<int> VWDictionaryHip::addNewWords(const Mat& descriptorsIn, int signat
     return wordIds;
 }
 
+// ---------------------------------------------------------------------------------------------- matchFrames  RegistrationVis.cpp:1383-1504
+void VWDictionaryHip::crossCheckWordIds(int rowsFrom, const std::vector<int>& originalFromIds, const int32_t* match, int rowsTo,
+                                        std::list<int>& fromWordIds, std::list<int>& toWordIds) {
+    std::vector<int> fromWordIdsV((size_t)rowsFrom);
+    for (int i = 0; i < rowsFrom; ++i) {                                             // :1391-1401
+        const int id = originalFromIds.empty() ? i + 1 : originalFromIds[(size_t)i];
+        fromWordIds.push_back(id);
+        fromWordIdsV[(size_t)i] = id;
+    }
+    const int last = fromWordIds.empty() ? 0 : fromWordIds.back();                   // (the reference reads back() of an empty list here)
+    for (int i = 0; i < rowsTo; ++i) {                                               // :1465-1477
+        const int toId = match[i] >= 0 && match[i] < rowsFrom ? fromWordIdsV[(size_t)match[i]] : 0;
+        toWordIds.push_back(toId == 0 ? last + i + 1 : toId);
+    }
+}
+
+bool VWDictionaryHip::matchFrames(const Mat& descriptorsFrom, const Mat& descriptorsTo, int nnType, float nndr, const std::vector<int>& originalFromIds,
+                                  std::list<int>& fromWordIds, std::list<int>& toWordIds) const {
+    fromWordIds.clear(); toWordIds.clear();
+    const Mat& any = descriptorsFrom.rows ? descriptorsFrom : descriptorsTo;
+    if (descriptorsFrom.rows == 0 && descriptorsTo.rows == 0) return true;
+    if (nnType < 0 || nnType > 5) { _lastError = "matchFrames: Vis/CorNNType 6 and 7 (Python matcher, GMS) are not offered"; return false; }
+    if (descriptorsFrom.rows && descriptorsTo.rows && (descriptorsFrom.cols != descriptorsTo.cols || descriptorsFrom.type() != descriptorsTo.type())) {
+        _lastError = "matchFrames: the two frames' descriptors differ in size or type"; return false;
+    }
+    if (!originalFromIds.empty() && (int)originalFromIds.size() != descriptorsFrom.rows) { _lastError = "matchFrames: one original id per from-row"; return false; }
+    if (!ensureEngine(any.type(), any.cols)) return false;
+    const int64_t fromOffsets[2] = {0, descriptorsFrom.rows}, toOffsets[2] = {0, descriptorsTo.rows};
+    std::vector<int32_t> outFrom((size_t)descriptorsFrom.rows + 1), outTo((size_t)descriptorsTo.rows + 1);
+    std::vector<int32_t> ids(originalFromIds.begin(), originalFromIds.end());
+    lcd_match_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.struct_size = (int32_t)sizeof(a);
+    a.n_pairs = 1;
+    a.from = descriptorsFrom.data.data(); a.to = descriptorsTo.data.data();
+    a.from_offsets = fromOffsets; a.to_offsets = toOffsets;
+    if (nnType == 5) {
+        a.mode = LCD_MATCH_CROSS_CHECK;
+        a.out_to_match = outTo.data();
+    } else {
+        a.mode = LCD_MATCH_DICTIONARY;
+        a.flags = LCD_Q_INCREMENTAL | (_newWordsComparedTogether ? LCD_Q_NEW_WORDS_COMPARED : 0);
+        a.nndr_ratio = nndr;
+        a.from_word_ids = ids.empty() ? nullptr : ids.data();
+        a.out_from_word_ids = outFrom.data(); a.out_to_word_ids = outTo.data();
+    }
+    if (lcd_match_pairs(_engine, &a) != LCD_OK) { _lastError = lcd_last_error(_engine); logError("%s", _lastError.c_str()); return false; }
+    if (nnType == 5) {
+        crossCheckWordIds(descriptorsFrom.rows, originalFromIds, outTo.data(), descriptorsTo.rows, fromWordIds, toWordIds);
+    } else {
+        fromWordIds.assign(outFrom.begin(), outFrom.begin() + descriptorsFrom.rows);
+        toWordIds.assign(outTo.begin(), outTo.begin() + descriptorsTo.rows);
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------- addNewWords + computeLikelihood, one device call
 bool VWDictionaryHip::addNewWordsAndScore(const Mat& descriptorsIn, int signatureId, float N, const std::function<int(int)>& getNi,
                                           std::list<int>& wordIds, std::vector<float>& likelihoodBySlot) {

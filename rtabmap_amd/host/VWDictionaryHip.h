@@ -160,6 +160,18 @@ public:
     // what is left of a caller's update() time is the mirror's own std::map bookkeeping
     void fastFrameStats(long long* deviceCallNs, long long* calls) const { *deviceCallNs = _fastDeviceNs; *calls = _fastCalls; }
 
+    // ---- RegistrationVis.cpp:1383-1504: the descriptors of two frames matched into word ids, over THIS dictionary's long-lived engine
+    // handle and without touching the dictionary (lcd_match_pairs: no temporary VWDictionary, no handle per pair, nothing drained).
+    // nnType = Vis/CorNNType: 0-4 the temporary two-frame dictionary (:1482-1503; this dictionary's Kp/NewWordsComparedTogether, `nndr` =
+    // Vis/CorNNDR), 5 brute force with cross-check (:1451-1477, the engine's rule, include/lcd.h) with the reference's id bookkeeping:
+    // from ids i + 1 or originalFromIds[i]; a matched to-row takes its from-row's id, an unmatched one fromWordIds.back() + i + 1.
+    // originalFromIds: empty, or one id per from-row (orignalWordsFromIds).  false (lastError): no engine, or the device refused the call.
+    bool matchFrames(const Mat& descriptorsFrom, const Mat& descriptorsTo, int nnType, float nndr, const std::vector<int>& originalFromIds,
+                     std::list<int>& fromWordIds, std::list<int>& toWordIds) const;
+    // the bookkeeping of :1391-1477 alone (plain host code): `match` = lcd_match_args.out_to_match of the pair
+    static void crossCheckWordIds(int rowsFrom, const std::vector<int>& originalFromIds, const int32_t* match, int rowsTo,
+                                  std::list<int>& fromWordIds, std::list<int>& toWordIds);
+
     // send the references added / removed since the last call to the device's inverted index (computeLikelihood does it itself)
     bool flushReferences(const std::function<int(int)>& getNi);
     // the same for a memory that has just been loaded (Memory::loadDataFromDb, Memory.cpp:447-480): every signature that is not on the

@@ -1,5 +1,6 @@
 // c_shim.cpp -- flat C entry points over VWDictionaryHip / MemoryHip so that the Python parity tests can drive the C++
 // host mirror exactly as they drive the oracle (same call sequence, same argument meaning).  Not part of lcd.h.
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 
@@ -41,6 +42,17 @@ int hvwd_find_nn(void* h, const void* desc, int rows, int cols, int type, int* o
     return rows;
 }
 void hvwd_update(void* h) { ((VWDictionaryHip*)h)->update(); }
+// VWDictionaryHip::matchFrames: outFrom[rowsFrom], outTo[rowsTo]; origIds NULL or one per from-row; 1 = done, 0 = failed (hvwd_last_error)
+int hvwd_match_frames(void* h, const void* from, int rowsFrom, const void* to, int rowsTo, int cols, int type, int nnType, float nndr,
+                      const int* origIds, int* outFrom, int* outTo) {
+    std::list<int> f, t;
+    const std::vector<int> orig = origIds ? std::vector<int>(origIds, origIds + rowsFrom) : std::vector<int>();
+    if (!((VWDictionaryHip*)h)->matchFrames(make_mat(from, rowsFrom, cols, type), make_mat(to, rowsTo, cols, type), nnType, nndr, orig, f, t)) return 0;
+    if ((int)f.size() != rowsFrom || (int)t.size() != rowsTo) return 0;
+    std::copy(f.begin(), f.end(), outFrom);
+    std::copy(t.begin(), t.end(), outTo);
+    return 1;
+}
 void hvwd_add_word(void* h, int id, const void* desc, int cols, int type) {
     ((VWDictionaryHip*)h)->addWord(new VisualWord(id, make_mat(desc, 1, cols, type)));
 }
@@ -81,6 +93,14 @@ int hvwd_index_ids(void* h, int* out, int cap) {
     return (int)v.size();
 }
 int hvwd_export_text(void* h, const char* refs, const char* desc) { ((VWDictionaryHip*)h)->exportDictionary(refs, desc); return 0; }
+
+// the id bookkeeping of Vis/CorNNType 5 alone (no engine involved): match[rowsTo] as lcd_match_args.out_to_match
+void hvwd_cross_check_word_ids(int rowsFrom, const int* origIds, const int* match, int rowsTo, int* outFrom, int* outTo) {
+    std::list<int> f, t;
+    VWDictionaryHip::crossCheckWordIds(rowsFrom, origIds ? std::vector<int>(origIds, origIds + rowsFrom) : std::vector<int>(), match, rowsTo, f, t);
+    std::copy(f.begin(), f.end(), outFrom);
+    std::copy(t.begin(), t.end(), outTo);
+}
 
 void* hmem_create(int strategy, int incremental, float nndr, int together, const char* dictPath, int device) {
     return new MemoryHip(make_params(strategy, incremental, nndr, together, dictPath), device);

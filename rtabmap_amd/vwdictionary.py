@@ -39,6 +39,9 @@ def lib():
         L.hvwd_add_new_words.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci]
         L.hvwd_find_nn.argtypes = [vp, vp, ci, ci, ci, vp]
         L.hvwd_update.argtypes = [vp]
+        L.hvwd_match_frames.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, C.c_float, vp, vp, vp]
+        L.hvwd_cross_check_word_ids.argtypes = [ci, vp, vp, ci, vp, vp]
+        L.hvwd_cross_check_word_ids.restype = None
         L.hvwd_add_word.argtypes = [vp, ci, vp, ci, ci]
         L.hvwd_add_word_ref.argtypes = [vp, ci, ci]
         L.hvwd_remove_all_word_ref.argtypes = [vp, ci, ci]
@@ -145,6 +148,18 @@ class VWDictionaryHip:
         out = np.zeros(desc.shape[0], np.int32)
         lib().hvwd_find_nn(self.h, _p(desc), desc.shape[0], desc.shape[1], _type_of(desc), _p(out))
         return out.tolist()
+
+    def match_frames(self, desc_from, desc_to, nn_type=1, nndr=0.8, original_from_ids=None):
+        """VWDictionaryHip::matchFrames (RegistrationVis.cpp:1383-1504): (fromWordIds, toWordIds) of a frame pair over this dictionary's
+        long-lived engine handle; the dictionary itself is untouched.  nn_type = Vis/CorNNType (0-4 temporary dictionary, 5 cross-check)."""
+        f, t = np.ascontiguousarray(desc_from), np.ascontiguousarray(desc_to)
+        ids = None if original_from_ids is None else np.ascontiguousarray(original_from_ids, dtype=np.int32)
+        of, ot = np.zeros(max(f.shape[0], 1), np.int32), np.zeros(max(t.shape[0], 1), np.int32)
+        ok = lib().hvwd_match_frames(self.h, _p(f), f.shape[0], _p(t), t.shape[0], f.shape[1], _type_of(f), nn_type, nndr,
+                                     None if ids is None else _p(ids), _p(of), _p(ot))
+        if not ok:
+            raise RuntimeError("matchFrames: " + self.last_error())
+        return of[: f.shape[0]].tolist(), ot[: t.shape[0]].tolist()
 
     def update(self):
         lib().hvwd_update(self.h)
