@@ -105,8 +105,8 @@ typedef struct lcd_config {
                                   lcd_pipeline_depth() + 1 sets of buffers and rotate.  lcd_sig_remove, lcd_record_event and
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
-                                  call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev touch no engine state and complete
-                                  nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
+                                  call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev and lcd_match_guided / lcd_match_guided_dev
+                                  touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
 
@@ -338,6 +338,71 @@ typedef struct lcd_match_args {
 int lcd_match_pairs(lcd_engine* h, const lcd_match_args* a);
 /* from, to, from_word_ids and out_* in DEVICE memory, the offsets on the HOST (read during the call); enqueued on the engine stream, not synchronised */
 int lcd_match_pairs_dev(lcd_engine* h, const lcd_match_args* a);
+
+/* ---- guided two-frame matching, stateless: what the verification runs whenever the caller has a guess transform (RegistrationVis.cpp:1078-1365,
+ * Vis/CorGuessWinSize > 0: proximity detection with an odometry guess, the local loop closures in time, odometry refining, the graph's
+ * re-registration).  The from-frame's 3-D points have been projected into the to-image; a descriptor is compared only with the descriptors
+ * whose keypoints lie within `radius` pixels of the projection.  Stateless exactly as lcd_match_pairs: any number of pairs per call, nothing
+ * of the handle's vocabulary, index, Bayes filter or numbering is read or written, a pipelined handle is not drained.
+ *
+ * The projection stays with the CALLER (cv::Rodrigues, cv::projectPoints, the in-bounds / z > 0 / duplicate filter and the multi-camera x
+ * offset, :1032-1070: OpenCV is not part of the reference tree).  Per pair the caller passes what that block produces: `corners`
+ * (cornersProjected, [n_corners x 2] fp32, the to-image's stitched coordinates), `corner_from_row` (projectedIndexToDescIndex: the from-row
+ * of each corner WITHIN the pair; it need not be monotone nor cover every from-row), `to_points` (cv::KeyPoint::convert(kptsTo), [nt x 2]
+ * fp32), the descriptor rows laid out as for lcd_match_args, and radius = (float)Vis/CorGuessWinSize.  Pair p owns the corners
+ * [corner_offsets[p], corner_offsets[p+1]).  The descriptor of corner c is from[corner_from_row[c]].
+ *
+ * The rule.  A QUERY is a corner (LCD_GUIDED_PROJECTED_TO_FRAME, Vis/CorGuessMatchToProjection = false, the default, :1222-1364) or a to-row
+ * (LCD_GUIDED_FRAME_TO_PROJECTED, :1080-1221); the TARGETS are the other side.
+ *   1. Window: W(q) = { t : d2(q, t) < radius * radius }, d2 = rtflann's L2_Simple (dist.h:74-91) in fp32 without fused multiply-add:
+ *      fl(fl(dx * dx) + fl(dy * dy)), radius * radius one fp32 product; the comparison is strict (result_set.h:477); a NaN coordinate is in
+ *      no window.  The reference searches a kd-tree with 32 checks (:1085-1094, :1228-1235), best-bin-first: it may return a subset, in
+ *      traversal order.  The engine's window is the EXACT set -- the same decision as "Vis/CorNNType 0-4 all mean the exact search".
+ *   2. Decision.  |W| = 0: no match.  |W| = 1: that target, WITHOUT a descriptor comparison (:1150-1153, :1303-1306).  |W| >= 2: d1 <= d2 are
+ *      the two smallest exact descriptor distances over W (the bits lcd_knn2 returns: squared L2, or Hamming over every byte) and the
+ *      LOWEST TARGET INDEX WINS TIES -- the reference's order among equal distances is the kd-tree's traversal order, so this is defined by
+ *      the ENGINE.  LCD_GUIDED_RATIO (Vis/CorNNType 0-4): matched iff d1 < nndr_ratio * d2, the product rounded to fp32, the comparison
+ *      strict (:1144, :1297 -- not VWDictionary's <=: d1 == d2 == 0 is no match).  LCD_GUIDED_NEAREST (type 5): the nearest target, always
+ *      (a crossCheck matcher with one query row keeps its only chooser).
+ *   3. Projected-to-frame only: out_to_owner[t] = the lowest corner index whose decision is to-row t, or -1 -- addedWordsTo's first-come
+ *      rule (:1319-1331): a later corner loses even when it is closer.  The reference's isFinite(kptsFrom3D) test (:1260) is the caller's,
+ *      who passes only such corners.
+ * Outputs, one per query (corners, or to-rows): out_count = |W| (info.projectedIDs lists the corners with count > 0); out_match = the target
+ * index WITHIN the pair (a to-row, or a corner) or -1, before the first-come rule; out_dist (may be NULL) = d1, d2, both -1.0f for |W| <= 1.
+ * The id bookkeeping behind the match is the host mirror's (VWDictionaryHip::matchFramesGuided).
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows or corners on one side of a
+ * pair, n_pairs > 65535, a handle of a sharded vocabulary (lcd_set_option "shard_*"; not offered by lcd_shard.h either), or
+ * lcd_match_guided_dev on a handle whose rows are padded: LCD_ERR_UNSUPPORTED; offsets that do not start at 0 or decrease, a radius that is
+ * not finite or <= 0, a wrong struct_size / direction / nn_type, a NULL pointer where rows, corners or outputs exist: LCD_ERR_INVALID;
+ * lcd_match_guided also refuses a corner_from_row outside [0, nf) with LCD_ERR_INVALID.  lcd_match_guided_dev cannot see them: there such a
+ * corner is treated as NO CANDIDATE -- as a query it gets count 0 and match -1, as a target it is in no window -- and its from-row is never
+ * dereferenced.  n_pairs == 0 returns LCD_OK.
+ * One kernel launch and one fill per call whatever the batch; scratch is O(rows) (the job table and, for the host entry, the staged rows). */
+enum lcd_guided_direction { LCD_GUIDED_PROJECTED_TO_FRAME = 0, LCD_GUIDED_FRAME_TO_PROJECTED = 1 };
+enum lcd_guided_nn_type { LCD_GUIDED_RATIO = 0, LCD_GUIDED_NEAREST = 1 };
+typedef struct lcd_guided_args {
+    int32_t struct_size;            /* sizeof(lcd_guided_args) */
+    int32_t direction;              /* lcd_guided_direction */
+    int32_t nn_type;                /* lcd_guided_nn_type */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    float   radius;                 /* (float)Vis/CorGuessWinSize, pixels; finite and > 0 */
+    float   nndr_ratio;             /* Vis/CorNNDR, LCD_GUIDED_RATIO only */
+    const void* from; const void* to;                          /* rows of all pairs, concatenated, the handle's dtype and dim (device entry: 16-byte aligned) */
+    const float* corners;           /* [n_corners x 2], all pairs concatenated */
+    const int32_t* corner_from_row; /* one per corner: from-row within its pair */
+    const float* to_points;         /* [n_to x 2], one per to-row */
+    const int64_t* from_offsets; const int64_t* to_offsets; const int64_t* corner_offsets;   /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    int32_t* out_count;             /* one per query: |W| */
+    int32_t* out_match;             /* one per query: target index within the pair, -1 = none */
+    float*   out_dist;              /* may be NULL; [2] per query: d1, d2 */
+    int32_t* out_to_owner;          /* projected-to-frame only, one per to-row: lowest corner index within the pair that chose it, -1 = none */
+} lcd_guided_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_match_guided(lcd_engine* h, const lcd_guided_args* a);
+/* rows, corners, corner_from_row, to_points and out_* in DEVICE memory (points 8-byte aligned), the offsets on the HOST (read during the
+ * call); enqueued on the engine stream, not synchronised */
+int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

@@ -16,6 +16,8 @@ LCD_F32, LCD_U8 = 0, 1
 LCD_Q_INCREMENTAL, LCD_Q_NEW_WORDS_COMPARED = 1, 2
 LCD_GLOBAL_MAX_CHANNELS, LCD_GLOBAL_MAX_DIM = 4, 16384      # global descriptors per signature, floats per descriptor (include/lcd.h)
 LCD_MATCH_DICTIONARY, LCD_MATCH_CROSS_CHECK = 0, 1          # lcd_match_args.mode (include/lcd.h)
+LCD_GUIDED_PROJECTED_TO_FRAME, LCD_GUIDED_FRAME_TO_PROJECTED = 0, 1   # lcd_guided_args.direction (include/lcd.h)
+LCD_GUIDED_RATIO, LCD_GUIDED_NEAREST = 0, 1                          # lcd_guided_args.nn_type
 LCD_NEW_WORD_IDS_AUTO = -1      # lcd_frame_args.first_new_word_id: the device numbers the frame's new words (include/lcd.h)
 STATUS = {0: "LCD_OK", 1: "LCD_ERR_INVALID", 2: "LCD_ERR_HIP", 3: "LCD_ERR_NOMEM", 4: "LCD_ERR_STATE", 5: "LCD_ERR_UNSUPPORTED"}
 
@@ -25,7 +27,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -87,6 +89,18 @@ class LcdMatchArgs(C.Structure):
 
 
 MATCH_MODES = {"dictionary": LCD_MATCH_DICTIONARY, "cross_check": LCD_MATCH_CROSS_CHECK}
+
+
+class LcdGuidedArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("direction", C.c_int32), ("nn_type", C.c_int32), ("n_pairs", C.c_int32), ("radius", C.c_float),
+                ("nndr_ratio", C.c_float), ("from_rows", C.c_void_p), ("to_rows", C.c_void_p), ("corners", C.c_void_p),
+                ("corner_from_row", C.c_void_p), ("to_points", C.c_void_p), ("from_offsets", C.c_void_p), ("to_offsets", C.c_void_p),
+                ("corner_offsets", C.c_void_p), ("out_count", C.c_void_p), ("out_match", C.c_void_p), ("out_dist", C.c_void_p),
+                ("out_to_owner", C.c_void_p)]
+
+
+GUIDED_DIRECTIONS = {"projected_to_frame": LCD_GUIDED_PROJECTED_TO_FRAME, "frame_to_projected": LCD_GUIDED_FRAME_TO_PROJECTED}
+GUIDED_NN_TYPES = {"ratio": LCD_GUIDED_RATIO, "nearest": LCD_GUIDED_NEAREST}
 
 
 class LcdError(RuntimeError):
@@ -154,6 +168,8 @@ def load():
     L.lcd_compare_to_dev.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, i64]
     L.lcd_match_pairs.argtypes = [vp, C.POINTER(LcdMatchArgs)]
     L.lcd_match_pairs_dev.argtypes = [vp, C.POINTER(LcdMatchArgs)]
+    L.lcd_match_guided.argtypes = [vp, C.POINTER(LcdGuidedArgs)]
+    L.lcd_match_guided_dev.argtypes = [vp, C.POINTER(LcdGuidedArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -414,6 +430,52 @@ class Engine:
         else:
             a.out_to_match, a.out_to_dist = ptr(d_out_a), ptr(d_out_b)
         self._ck(self.L.lcd_match_pairs_dev(self.h, C.byref(a)))
+
+    # ---- guided two-frame matching (stateless; the projection is the caller's)
+    def _guided_args(self, from_offsets, to_offsets, corner_offsets, radius, nndr, nn_type, direction):
+        offs = [np.ascontiguousarray(o, dtype=np.int64) for o in (from_offsets, to_offsets, corner_offsets)]
+        n_pairs = offs[0].shape[0] - 1
+        if n_pairs < 0 or any(o.shape != (n_pairs + 1,) for o in offs):
+            raise ValueError("match_guided: offsets are [n_pairs + 1]")
+        direction = GUIDED_DIRECTIONS[direction] if isinstance(direction, str) else int(direction)
+        nn_type = GUIDED_NN_TYPES[nn_type] if isinstance(nn_type, str) else int(nn_type)
+        a = LcdGuidedArgs(C.sizeof(LcdGuidedArgs), direction, nn_type, n_pairs, radius, nndr)
+        a.from_offsets, a.to_offsets, a.corner_offsets = (o.ctypes.data for o in offs)
+        return a, direction, offs
+
+    def match_guided(self, from_rows, to_rows, corners, corner_from_row, to_points, from_offsets, to_offsets, corner_offsets, radius=40.0,
+                     nndr=0.8, nn_type="ratio", direction="projected_to_frame", with_dist=True):
+        """lcd_match_guided over host arrays (include/lcd.h has the rule): pair p owns from_rows[from_offsets[p]:from_offsets[p+1]], the
+        to-rows and to_points [to_offsets[p]:...] and the corners / corner_from_row [corner_offsets[p]:...].
+        -> (count, match, dist [n_queries x 2] or None, to_owner or None); queries are the corners ("projected_to_frame", which also
+        gives to_owner per to-row) or the to-rows ("frame_to_projected")."""
+        f, t = self._rows(from_rows), self._rows(to_rows)
+        c = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 2)
+        r = np.ascontiguousarray(corner_from_row, dtype=np.int32).reshape(-1)
+        pts = np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
+        a, direction, (fo, to, co) = self._guided_args(from_offsets, to_offsets, corner_offsets, radius, nndr, nn_type, direction)
+        if int(fo[-1]) != f.shape[0] or int(to[-1]) != t.shape[0] or pts.shape[0] != t.shape[0] or int(co[-1]) != c.shape[0] or r.shape[0] != c.shape[0]:
+            raise ValueError("match_guided: the last offset is the number of rows / corners, one point per to-row, one from-row per corner")
+        p2f = direction == LCD_GUIDED_PROJECTED_TO_FRAME
+        nq, nt = (c.shape[0] if p2f else t.shape[0]), t.shape[0]
+        count, match = np.zeros(max(nq, 1), np.int32), np.zeros(max(nq, 1), np.int32)
+        dist = np.zeros((max(nq, 1), 2), np.float32) if with_dist else None
+        owner = np.zeros(max(nt, 1), np.int32) if p2f else None
+        a.from_rows, a.to_rows, a.corners, a.corner_from_row, a.to_points = _p(f), _p(t), _p(c), _p(r), _p(pts)
+        a.out_count, a.out_match, a.out_dist, a.out_to_owner = _p(count), _p(match), _p(dist), _p(owner)
+        self._ck(self.L.lcd_match_guided(self.h, C.byref(a)))
+        return count[:nq], match[:nq], (dist[:nq] if with_dist else None), (owner[:nt] if p2f else None)
+
+    def match_guided_dev(self, d_from, d_to, d_corners, d_corner_from_row, d_to_points, from_offsets, to_offsets, corner_offsets, d_count,
+                         d_match, d_dist, d_to_owner, radius=40.0, nndr=0.8, nn_type="ratio", direction="projected_to_frame"):
+        """lcd_match_guided_dev on torch tensors of the engine's device (rows of the handle's dtype, float32 points, int32 corner_from_row and
+        outputs; the offsets stay on the host); d_dist may be None, d_to_owner is written in "projected_to_frame" only.  Enqueued on the
+        engine stream, not synchronised."""
+        a, direction, _ = self._guided_args(from_offsets, to_offsets, corner_offsets, radius, nndr, nn_type, direction)
+        ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()
+        a.from_rows, a.to_rows, a.corners, a.corner_from_row, a.to_points = ptr(d_from), ptr(d_to), ptr(d_corners), ptr(d_corner_from_row), ptr(d_to_points)
+        a.out_count, a.out_match, a.out_dist, a.out_to_owner = ptr(d_count), ptr(d_match), ptr(d_dist), ptr(d_to_owner)
+        self._ck(self.L.lcd_match_guided_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

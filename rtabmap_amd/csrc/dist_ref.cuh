@@ -1,6 +1,6 @@
 // dist_ref.cuh -- the reference's two distance functions, bit for bit (squared L2: rtflann L2 functor, dist.h:150-177, every product and sum
 // individually rounded; Hamming: popcount(a ^ b), dist.h:555-579); shared by the exact scans and the same-frame distance kernels
-// (knn2_kernels.hip) and the pair matcher's distance blocks (pair_match.hip).
+// (knn2_kernels.hip), the pair matcher's distance blocks (pair_match.hip) and the guided matcher's candidates (guided_match.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

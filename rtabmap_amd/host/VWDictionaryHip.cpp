@@ -520,6 +520,75 @@ bool VWDictionaryHip::matchFrames(const Mat& descriptorsFrom, const Mat& descrip
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------- matchFramesGuided  RegistrationVis.cpp:1078-1365
+void VWDictionaryHip::guidedWordIds(int rowsFrom, const std::vector<int>& originalFromIds, const std::vector<int>& projectedIndexToDescIndex,
+                                    const int32_t* toCorner, int rowsTo, const int32_t* cornerCount, std::list<int>& fromWordIds,
+                                    std::list<int>& toWordIds, std::list<int>* projectedIds) {
+    const bool orig = !originalFromIds.empty();
+    const int nCorners = (int)projectedIndexToDescIndex.size();
+    auto idOf = [&](int row) { return orig ? originalFromIds[(size_t)row] : row; };               // :1158, :1308 (the row index itself, not + 1)
+    int newToId = rowsFrom;                                                                        // :1104, :1349
+    if (orig) {                                                                                    // fromSignature.getWords().rbegin()->first + 1
+        newToId = 0;
+        for (int i = 0; i < rowsFrom && i < (int)originalFromIds.size(); ++i) newToId = std::max(newToId, originalFromIds[(size_t)i]);
+        newToId += 1;
+    }
+    for (int i = 0; i < rowsFrom; ++i) fromWordIds.push_back(orig && i >= (int)originalFromIds.size() ? i : idOf(i));
+    for (int i = 0; i < rowsTo; ++i) {
+        const int c = toCorner ? toCorner[i] : -1;
+        const int row = c >= 0 && c < nCorners ? projectedIndexToDescIndex[(size_t)c] : -1;
+        if (row >= 0 && row < rowsFrom && (!orig || row < (int)originalFromIds.size())) toWordIds.push_back(idOf(row));
+        else toWordIds.push_back(newToId++);                                                       // gen fake ids (:1189, :1354)
+    }
+    if (projectedIds && cornerCount)
+        for (int c = 0; c < nCorners; ++c) {
+            const int row = projectedIndexToDescIndex[(size_t)c];
+            if (cornerCount[c] > 0 && row >= 0 && row < rowsFrom && (!orig || row < (int)originalFromIds.size())) projectedIds->push_back(idOf(row));
+        }
+}
+
+bool VWDictionaryHip::matchFramesGuided(const Mat& descriptorsFrom, const Mat& descriptorsTo, const std::vector<float>& cornersProjected,
+                                        const std::vector<int>& projectedIndexToDescIndex, const std::vector<float>& pointsTo, int winSize, int nnType,
+                                        float nndr, bool matchToProjection, const std::vector<int>& originalFromIds, std::list<int>& fromWordIds,
+                                        std::list<int>& toWordIds, std::list<int>* projectedIds) const {
+    fromWordIds.clear(); toWordIds.clear();
+    if (projectedIds) projectedIds->clear();
+    const int nCorners = (int)projectedIndexToDescIndex.size();
+    if (nnType < 0 || nnType > 5) { _lastError = "matchFramesGuided: Vis/CorNNType 6 and 7 (Python matcher, GMS) are not offered"; return false; }
+    if (descriptorsFrom.rows && descriptorsTo.rows && (descriptorsFrom.cols != descriptorsTo.cols || descriptorsFrom.type() != descriptorsTo.type())) {
+        _lastError = "matchFramesGuided: the two frames' descriptors differ in size or type"; return false;
+    }
+    if (!originalFromIds.empty() && (int)originalFromIds.size() != descriptorsFrom.rows) { _lastError = "matchFramesGuided: one original id per from-row"; return false; }
+    if ((int)cornersProjected.size() != 2 * nCorners || (int)pointsTo.size() != 2 * descriptorsTo.rows) {
+        _lastError = "matchFramesGuided: two coordinates per corner and per to-row"; return false;
+    }
+    std::vector<int32_t> count, match, owner((size_t)descriptorsTo.rows + 1, -1);
+    const bool any = descriptorsFrom.rows || descriptorsTo.rows;
+    if (any) {
+        const Mat& first = descriptorsFrom.rows ? descriptorsFrom : descriptorsTo;
+        if (!ensureEngine(first.type(), first.cols)) return false;
+        const int nQueries = matchToProjection ? descriptorsTo.rows : nCorners;
+        count.assign((size_t)nQueries + 1, 0); match.assign((size_t)nQueries + 1, -1);
+        const int64_t fromOffsets[2] = {0, descriptorsFrom.rows}, toOffsets[2] = {0, descriptorsTo.rows}, cornerOffsets[2] = {0, nCorners};
+        std::vector<int32_t> rows(projectedIndexToDescIndex.begin(), projectedIndexToDescIndex.end());
+        lcd_guided_args a;
+        std::memset(&a, 0, sizeof(a));
+        a.struct_size = (int32_t)sizeof(a);
+        a.direction = matchToProjection ? LCD_GUIDED_FRAME_TO_PROJECTED : LCD_GUIDED_PROJECTED_TO_FRAME;
+        a.nn_type = nnType == 5 ? LCD_GUIDED_NEAREST : LCD_GUIDED_RATIO;
+        a.n_pairs = 1;
+        a.radius = (float)winSize; a.nndr_ratio = nndr;
+        a.from = descriptorsFrom.data.data(); a.to = descriptorsTo.data.data();
+        a.corners = cornersProjected.data(); a.corner_from_row = rows.data(); a.to_points = pointsTo.data();
+        a.from_offsets = fromOffsets; a.to_offsets = toOffsets; a.corner_offsets = cornerOffsets;
+        a.out_count = count.data(); a.out_match = match.data(); a.out_to_owner = owner.data();
+        if (lcd_match_guided(_engine, &a) != LCD_OK) { _lastError = lcd_last_error(_engine); logError("%s", _lastError.c_str()); return false; }
+    }
+    guidedWordIds(descriptorsFrom.rows, originalFromIds, projectedIndexToDescIndex, matchToProjection ? match.data() : owner.data(), descriptorsTo.rows,
+                  matchToProjection || count.empty() ? nullptr : count.data(), fromWordIds, toWordIds, projectedIds);
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------- addNewWords + computeLikelihood, one device call
 bool VWDictionaryHip::addNewWordsAndScore(const Mat& descriptorsIn, int signatureId, float N, const std::function<int(int)>& getNi,
                                           std::list<int>& wordIds, std::vector<float>& likelihoodBySlot) {

@@ -172,6 +172,25 @@ public:
     static void crossCheckWordIds(int rowsFrom, const std::vector<int>& originalFromIds, const int32_t* match, int rowsTo,
                                   std::list<int>& fromWordIds, std::list<int>& toWordIds);
 
+    // ---- RegistrationVis.cpp:1078-1365: the same two frames matched under a guess transform (Vis/CorGuessWinSize > 0), again over this
+    // dictionary's long-lived handle and without touching the dictionary (lcd_match_guided, include/lcd.h has the rule).  The projection is
+    // the caller's: cornersProjected ([n x 2], the to-image's coordinates), projectedIndexToDescIndex (the from-row of each corner), pointsTo
+    // ([descriptorsTo.rows x 2], cv::KeyPoint::convert(kptsTo)); winSize = Vis/CorGuessWinSize, nnType = Vis/CorNNType (0-4 NNDR with `nndr`
+    // = Vis/CorNNDR, 5 the nearest), matchToProjection = Vis/CorGuessMatchToProjection.  fromWordIds: one id per from-row, originalFromIds[i]
+    // or i; toWordIds: one per to-row (guidedWordIds); projectedIds (may be NULL): the ids info.projectedIDs receives (:1255-1258,
+    // projected-to-frame only).  false (lastError): no engine, a from-row index out of range, or the device refused the call.
+    bool matchFramesGuided(const Mat& descriptorsFrom, const Mat& descriptorsTo, const std::vector<float>& cornersProjected,
+                           const std::vector<int>& projectedIndexToDescIndex, const std::vector<float>& pointsTo, int winSize, int nnType, float nndr,
+                           bool matchToProjection, const std::vector<int>& originalFromIds, std::list<int>& fromWordIds, std::list<int>& toWordIds,
+                           std::list<int>* projectedIds = nullptr) const;
+    // the id bookkeeping of :1104-1199 / :1253-1363 alone (plain host code).  toCorner[i] = the corner whose from-row gives to-row i its id:
+    // lcd_guided_args.out_to_owner (projected-to-frame: no two to-rows share an id) or out_match (frame-to-projected: several to-rows may
+    // share one, :1160-1164); -1 or out of range: a fake id newToId++, in to-row order, from max(originalFromIds) + 1 or rowsFrom (:1104,
+    // :1349).  cornerCount (may be NULL) = out_count of the corners: those with a count > 0 give projectedIds, in corner order.
+    static void guidedWordIds(int rowsFrom, const std::vector<int>& originalFromIds, const std::vector<int>& projectedIndexToDescIndex,
+                              const int32_t* toCorner, int rowsTo, const int32_t* cornerCount, std::list<int>& fromWordIds,
+                              std::list<int>& toWordIds, std::list<int>* projectedIds);
+
     // send the references added / removed since the last call to the device's inverted index (computeLikelihood does it itself)
     bool flushReferences(const std::function<int(int)>& getNi);
     // the same for a memory that has just been loaded (Memory::loadDataFromDb, Memory.cpp:447-480): every signature that is not on the

@@ -102,6 +102,37 @@ void hvwd_cross_check_word_ids(int rowsFrom, const int* origIds, const int* matc
     std::copy(t.begin(), t.end(), outTo);
 }
 
+// VWDictionaryHip::matchFramesGuided: corners[2 nCorners], cornerRows[nCorners], pointsTo[2 rowsTo]; outFrom[rowsFrom], outTo[rowsTo],
+// outProjected[nCorners] (may be NULL) with *nProjected entries written; 1 = done, 0 = failed (hvwd_last_error)
+int hvwd_match_frames_guided(void* h, const void* from, int rowsFrom, const void* to, int rowsTo, int cols, int type, const float* corners,
+                             const int* cornerRows, int nCorners, const float* pointsTo, int winSize, int nnType, float nndr, int matchToProjection,
+                             const int* origIds, int* outFrom, int* outTo, int* outProjected, int* nProjected) {
+    std::list<int> f, t, p;
+    const std::vector<int> orig = origIds ? std::vector<int>(origIds, origIds + rowsFrom) : std::vector<int>();
+    if (!((VWDictionaryHip*)h)->matchFramesGuided(make_mat(from, rowsFrom, cols, type), make_mat(to, rowsTo, cols, type),
+                                                  std::vector<float>(corners, corners + 2 * (size_t)nCorners), std::vector<int>(cornerRows, cornerRows + nCorners),
+                                                  std::vector<float>(pointsTo, pointsTo + 2 * (size_t)rowsTo), winSize, nnType, nndr, matchToProjection != 0,
+                                                  orig, f, t, &p)) return 0;
+    if ((int)f.size() != rowsFrom || (int)t.size() != rowsTo || (int)p.size() > nCorners) return 0;
+    std::copy(f.begin(), f.end(), outFrom);
+    std::copy(t.begin(), t.end(), outTo);
+    if (outProjected) std::copy(p.begin(), p.end(), outProjected);
+    if (nProjected) *nProjected = (int)p.size();
+    return 1;
+}
+// the id bookkeeping of the guided match alone (no engine involved): toCorner[rowsTo] = lcd_guided_args.out_to_owner / out_match,
+// cornerCount NULL or [nCorners]; returns the number of projected ids written
+int hvwd_guided_word_ids(int rowsFrom, const int* origIds, const int* cornerRows, int nCorners, const int* toCorner, int rowsTo, const int* cornerCount,
+                         int* outFrom, int* outTo, int* outProjected) {
+    std::list<int> f, t, p;
+    VWDictionaryHip::guidedWordIds(rowsFrom, origIds ? std::vector<int>(origIds, origIds + rowsFrom) : std::vector<int>(),
+                                   std::vector<int>(cornerRows, cornerRows + nCorners), toCorner, rowsTo, cornerCount, f, t, &p);
+    std::copy(f.begin(), f.end(), outFrom);
+    std::copy(t.begin(), t.end(), outTo);
+    if (outProjected) std::copy(p.begin(), p.end(), outProjected);
+    return (int)p.size();
+}
+
 void* hmem_create(int strategy, int incremental, float nndr, int together, const char* dictPath, int device) {
     return new MemoryHip(make_params(strategy, incremental, nndr, together, dictPath), device);
 }

@@ -42,6 +42,8 @@ def lib():
         L.hvwd_match_frames.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, C.c_float, vp, vp, vp]
         L.hvwd_cross_check_word_ids.argtypes = [ci, vp, vp, ci, vp, vp]
         L.hvwd_cross_check_word_ids.restype = None
+        L.hvwd_match_frames_guided.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci, C.c_float, ci, vp, vp, vp, vp, vp]
+        L.hvwd_guided_word_ids.argtypes = [ci, vp, vp, ci, vp, ci, vp, vp, vp, vp]
         L.hvwd_add_word.argtypes = [vp, ci, vp, ci, ci]
         L.hvwd_add_word_ref.argtypes = [vp, ci, ci]
         L.hvwd_remove_all_word_ref.argtypes = [vp, ci, ci]
@@ -160,6 +162,26 @@ class VWDictionaryHip:
         if not ok:
             raise RuntimeError("matchFrames: " + self.last_error())
         return of[: f.shape[0]].tolist(), ot[: t.shape[0]].tolist()
+
+    def match_frames_guided(self, desc_from, desc_to, corners, corner_from_row, points_to, win_size=40, nn_type=1, nndr=0.8,
+                            match_to_projection=False, original_from_ids=None):
+        """VWDictionaryHip::matchFramesGuided (RegistrationVis.cpp:1078-1365): (fromWordIds, toWordIds, projectedIds) of a frame pair under a
+        guess, over this dictionary's long-lived engine handle; the projection (corners, corner_from_row) is the caller's."""
+        f, t = np.ascontiguousarray(desc_from), np.ascontiguousarray(desc_to)
+        c = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 2)
+        r = np.ascontiguousarray(corner_from_row, dtype=np.int32).reshape(-1)
+        p = np.ascontiguousarray(points_to, dtype=np.float32).reshape(-1, 2)
+        if r.shape[0] != c.shape[0] or p.shape[0] != t.shape[0]:
+            raise ValueError("match_frames_guided: one from-row per corner, one point per to-row")
+        ids = None if original_from_ids is None else np.ascontiguousarray(original_from_ids, dtype=np.int32)
+        of, ot, op = np.zeros(max(f.shape[0], 1), np.int32), np.zeros(max(t.shape[0], 1), np.int32), np.zeros(max(c.shape[0], 1), np.int32)
+        n = C.c_int(0)
+        ok = lib().hvwd_match_frames_guided(self.h, _p(f), f.shape[0], _p(t), t.shape[0], f.shape[1], _type_of(f), _p(c), _p(r), c.shape[0], _p(p),
+                                            int(win_size), nn_type, nndr, int(bool(match_to_projection)), None if ids is None else _p(ids),
+                                            _p(of), _p(ot), _p(op), C.cast(C.byref(n), C.c_void_p))
+        if not ok:
+            raise RuntimeError("matchFramesGuided: " + self.last_error())
+        return of[: f.shape[0]].tolist(), ot[: t.shape[0]].tolist(), op[: n.value].tolist()
 
     def update(self):
         lib().hvwd_update(self.h)
