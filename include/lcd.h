@@ -105,7 +105,8 @@ typedef struct lcd_config {
                                   lcd_pipeline_depth() + 1 sets of buffers and rotate.  lcd_sig_remove, lcd_record_event and
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
-                                  call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev and lcd_match_guided / lcd_match_guided_dev
+                                  call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
+                                  lcd_select_features / lcd_expand_word_ids with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -403,6 +404,97 @@ int lcd_match_guided(lcd_engine* h, const lcd_guided_args* a);
 /* rows, corners, corner_from_row, to_points and out_* in DEVICE memory (points 8-byte aligned), the offsets on the HOST (read during the
  * call); enqueued on the engine stream, not synchronised */
 int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a);
+
+/* ---- keypoint limiting and the -1, -2, ... word ids, stateless: the quantisation glue of Memory::createSignature (Memory.cpp:5941-6059) for a
+ * caller whose extractor leaves responses, positions and descriptors in device memory.  SELECTION (:5951-6023, Feature2D::limitKeypoints,
+ * Features2d.cpp:293-516) picks the features that are quantised; EXPANSION (:6029-6059) puts the word ids back onto all features and numbers
+ * the ones without a word -1, -2, ...  Stateless exactly as lcd_match_pairs: the calls borrow the handle's dtype, dim, device and stream,
+ * read and write nothing of its vocabulary, index, Bayes filter or numbering, do not complete what a pipelined handle owes, and keep their
+ * job table in the scratch lcd_match_pairs uses (counted in lcd_stats.bytes_device).  A call serves any number of frames: frame f owns the
+ * features [offsets[f], offsets[f+1]) of every array; an index is a position WITHIN its frame.
+ *
+ * The selection rule.
+ *   Key.  The key of feature i is (bits(response[i]) & 0x7FFFFFFF, i), compared lexicographically; "stronger" = the larger key.  This is the
+ *      reverse iteration of the reference's std::multimap<float, int> over fabs(response) (:362-371, :453-463): equivalent keys are inserted at
+ *      the upper bound, so among equal responses the HIGHER index comes first; -0.0 equals 0.0, denormals keep their order.  A NaN response
+ *      breaks the reference's ordering: lcd_select_features refuses it (LCD_ERR_INVALID), lcd_select_features_dev orders it by the same masked
+ *      bits, above +inf -- the ENGINE's definition.
+ *   A frame of n features is CUT when max_features > 0 and n > max_features; a frame that is not cut selects everything, in its own order,
+ *      whatever the order, the grid and the points (the whole-frame early exit, :297, :414, :481): out_index = 0, 1, ..., n - 1.
+ *   LCD_SELECT_KEEP_ORDER (the inlier mask of :412-516 compacted as :5999-6019 compacts it): out_index is quantizedToRawIndices, the selected
+ *      features in ASCENDING index.  1 x 1 grid: exactly the max_features strongest.  Larger grid (Kp/GridRows, Kp/GridCols; :479-516):
+ *      rowSize = height / grid_rows, colSize = width / grid_cols, perCell = max_features / (grid_rows * grid_cols), all integer divisions;
+ *      the cell of feature i is (int(y) / rowSize, int(x) / colSize), the conversion and the division both truncating toward zero (so a
+ *      coordinate in (-rowSize, 0) still belongs to row 0); a cell keeps its perCell strongest features when it holds more than perCell AND
+ *      perCell > 0, otherwise all of them -- with perCell == 0 the inner call's maxKeypoints > 0 test fails and the whole cell stays (the
+ *      reference's behaviour, restated and not repaired).  The number selected can therefore exceed max_features, or stay below it.
+ *      A keypoint whose cell lies outside the grid (the remainder strip when the image size does not divide; a coordinate at or below -rowSize /
+ *      -colSize) fails an assertion in the reference: lcd_select_features returns LCD_ERR_INVALID; lcd_select_features_dev selects such a
+ *      feature NEVER and counts it in no cell -- the ENGINE's definition; the conversion saturates (NaN -> 0) and nothing is indexed out of
+ *      range.  A cut frame with height <= grid_rows or width <= grid_cols: LCD_ERR_INVALID from both entries (the reference's second assertion).
+ *   LCD_SELECT_BY_RESPONSE (the compacting variant the extractors call, :356-400): a cut frame gives its max_features strongest in DESCENDING
+ *      key order -- the order matters, addNewWords numbers new words in row order.  With a grid above 1 x 1: LCD_ERR_INVALID (no such variant).
+ * Outputs.  Frame f writes the first out_count[f] entries of ITS OWN region of each output (the inputs' offsets): out_index (the rest of the
+ * region reads -1), out_rows and out_aux (the rest is unspecified).  Its selected rows start at out_rows + offsets[f] * row bytes, ready to be
+ * lcd_frame_args.d_descriptors where that address is 16-byte aligned.  With a 1 x 1 grid the host knows the count without a read-back
+ * (min(n, max_features), or n); a larger grid's count is data-dependent: out_count is where the caller gets q.  Outputs must not overlap inputs.
+ *
+ * Expansion, per frame of n features: (1) every feature starts without a word; (2) for j < count[f] (clamped to [0, n]):
+ * all[index[j]] = resolve(word_ids[j]), where an id > 0 stands, a code -(k+1) becomes first_new_word_id[f] + k when that array is given
+ * and its entry is > 0, and otherwise -- and for id 0, the fixed dictionary's "no entry", where the reference's shorter list would shift every
+ * later position -- means "no word" (the ENGINE's definition); the index entries of a frame are distinct; (3) in feature order every feature
+ * without a word receives -1, -2, ... (:6040-6047).  count[f] == 0 gives the all-negative list of the _badSignRatio branch (:6051-6059).
+ * An index entry outside [0, n): lcd_expand_word_ids returns LCD_ERR_INVALID, lcd_expand_word_ids_dev skips it without dereferencing.
+ * In the device entry count, index, word_ids and first_new_word_id are device memory: first_new_word_id can be filled by the frames'
+ * d_first_new_word_id outputs (LCD_NEW_WORD_IDS_AUTO) and nothing is read back.  On a pipelined handle the call is enqueued where it lands:
+ * frame t's d_word_ids are final behind the lcd_frame_dev call of frame t + lcd_pipeline_depth(), or behind lcd_synchronize -- expand then.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 16384 features in a frame (its 64-bit
+ * keys are sorted in one workgroup's LDS: 128 KiB), n_frames > 65535, grid_rows * grid_cols > 1024, a handle of a sharded vocabulary, or a
+ * device entry with rows on a handle whose rows are padded (lcd_config.dim; the host entry serves it): LCD_ERR_UNSUPPORTED; offsets that do not
+ * start at 0 or decrease, a NULL pointer where an input or output is needed, an unknown order, a wrong struct_size, a grid dimension < 1,
+ * aux_bytes that is negative, above 64 or no multiple of 4: LCD_ERR_INVALID.  n_frames == 0 returns LCD_OK.
+ * One kernel launch per call whatever the batch (one workgroup per frame), no private segment. */
+enum lcd_select_order { LCD_SELECT_KEEP_ORDER = 0, LCD_SELECT_BY_RESPONSE = 1 };
+typedef struct lcd_select_args {
+    int32_t struct_size;            /* sizeof(lcd_select_args) */
+    int32_t n_frames;               /* >= 0; 0 returns LCD_OK */
+    int32_t order;                  /* lcd_select_order */
+    int32_t max_features;           /* Kp/MaxFeatures; <= 0: nothing is cut */
+    int32_t grid_rows, grid_cols;   /* Kp/GridRows, Kp/GridCols, >= 1 */
+    int32_t aux_bytes;              /* bytes of the caller's per-feature payload (the cv::KeyPoint, the 3-D point): a multiple of 4, 0..64 */
+    int32_t reserved;
+    const int64_t* offsets;         /* HOST, [n_frames + 1], non-decreasing, [0] == 0 */
+    const int32_t* image_size;      /* HOST, [n_frames x 2]: width, height; may be NULL with a 1 x 1 grid */
+    const float* response;          /* [N] cv::KeyPoint::response */
+    const float* points;            /* [N x 2] cv::KeyPoint::pt (x, y); may be NULL with a 1 x 1 grid */
+    const void* rows;               /* may be NULL: [N x dim] of the handle's dtype */
+    const void* aux;                /* may be NULL (aux_bytes == 0): [N x aux_bytes] */
+    int32_t* out_count;             /* [n_frames] */
+    int32_t* out_index;             /* [N] */
+    void* out_rows;                 /* [N x dim], needed with rows */
+    void* out_aux;                  /* [N x aux_bytes], needed with aux */
+} lcd_select_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_select_features(lcd_engine* h, const lcd_select_args* a);
+/* response, points, rows, aux and out_* in DEVICE memory (4-byte aligned; rows and aux are copied as 16-byte vectors where their addresses and
+ * sizes allow), offsets and image_size on the HOST (read during the call); enqueued on the engine stream, not synchronised */
+int lcd_select_features_dev(lcd_engine* h, const lcd_select_args* a);
+
+typedef struct lcd_expand_args {
+    int32_t struct_size;            /* sizeof(lcd_expand_args) */
+    int32_t n_frames;               /* >= 0; 0 returns LCD_OK */
+    const int64_t* offsets;         /* HOST, [n_frames + 1], non-decreasing, [0] == 0 */
+    const int32_t* count;           /* [n_frames]: the selected features of each frame (lcd_select_args.out_count) */
+    const int32_t* index;           /* [N]: frame f's selected features at offsets[f], count[f] of them valid (lcd_select_args.out_index) */
+    const int32_t* word_ids;        /* [N]: frame f's ids at offsets[f], count[f] of them valid, as lcd_quantize / lcd_frame_dev write them */
+    const int32_t* first_new_word_id;   /* may be NULL; [n_frames] */
+    int32_t* out_word_ids;          /* [N]: one id per feature */
+} lcd_expand_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_expand_word_ids(lcd_engine* h, const lcd_expand_args* a);
+/* count, index, word_ids, first_new_word_id and out_word_ids in DEVICE memory, the offsets on the HOST; enqueued on the engine stream, not synchronised */
+int lcd_expand_word_ids_dev(lcd_engine* h, const lcd_expand_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

@@ -18,6 +18,7 @@ LCD_GLOBAL_MAX_CHANNELS, LCD_GLOBAL_MAX_DIM = 4, 16384      # global descriptors
 LCD_MATCH_DICTIONARY, LCD_MATCH_CROSS_CHECK = 0, 1          # lcd_match_args.mode (include/lcd.h)
 LCD_GUIDED_PROJECTED_TO_FRAME, LCD_GUIDED_FRAME_TO_PROJECTED = 0, 1   # lcd_guided_args.direction (include/lcd.h)
 LCD_GUIDED_RATIO, LCD_GUIDED_NEAREST = 0, 1                          # lcd_guided_args.nn_type
+LCD_SELECT_KEEP_ORDER, LCD_SELECT_BY_RESPONSE = 0, 1                 # lcd_select_args.order
 LCD_NEW_WORD_IDS_AUTO = -1      # lcd_frame_args.first_new_word_id: the device numbers the frame's new words (include/lcd.h)
 STATUS = {0: "LCD_OK", 1: "LCD_ERR_INVALID", 2: "LCD_ERR_HIP", 3: "LCD_ERR_NOMEM", 4: "LCD_ERR_STATE", 5: "LCD_ERR_UNSUPPORTED"}
 
@@ -27,7 +28,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -103,6 +104,21 @@ GUIDED_DIRECTIONS = {"projected_to_frame": LCD_GUIDED_PROJECTED_TO_FRAME, "frame
 GUIDED_NN_TYPES = {"ratio": LCD_GUIDED_RATIO, "nearest": LCD_GUIDED_NEAREST}
 
 
+class LcdSelectArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("order", C.c_int32), ("max_features", C.c_int32), ("grid_rows", C.c_int32),
+                ("grid_cols", C.c_int32), ("aux_bytes", C.c_int32), ("reserved", C.c_int32), ("offsets", C.c_void_p), ("image_size", C.c_void_p),
+                ("response", C.c_void_p), ("points", C.c_void_p), ("rows", C.c_void_p), ("aux", C.c_void_p), ("out_count", C.c_void_p),
+                ("out_index", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p)]
+
+
+class LcdExpandArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("offsets", C.c_void_p), ("count", C.c_void_p), ("index", C.c_void_p),
+                ("word_ids", C.c_void_p), ("first_new_word_id", C.c_void_p), ("out_word_ids", C.c_void_p)]
+
+
+SELECT_ORDERS = {"keep_order": LCD_SELECT_KEEP_ORDER, "by_response": LCD_SELECT_BY_RESPONSE}
+
+
 class LcdError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__("%s: %s" % (STATUS.get(status, status), msg))
@@ -170,6 +186,10 @@ def load():
     L.lcd_match_pairs_dev.argtypes = [vp, C.POINTER(LcdMatchArgs)]
     L.lcd_match_guided.argtypes = [vp, C.POINTER(LcdGuidedArgs)]
     L.lcd_match_guided_dev.argtypes = [vp, C.POINTER(LcdGuidedArgs)]
+    L.lcd_select_features.argtypes = [vp, C.POINTER(LcdSelectArgs)]
+    L.lcd_select_features_dev.argtypes = [vp, C.POINTER(LcdSelectArgs)]
+    L.lcd_expand_word_ids.argtypes = [vp, C.POINTER(LcdExpandArgs)]
+    L.lcd_expand_word_ids_dev.argtypes = [vp, C.POINTER(LcdExpandArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -476,6 +496,74 @@ class Engine:
         a.from_rows, a.to_rows, a.corners, a.corner_from_row, a.to_points = ptr(d_from), ptr(d_to), ptr(d_corners), ptr(d_corner_from_row), ptr(d_to_points)
         a.out_count, a.out_match, a.out_dist, a.out_to_owner = ptr(d_count), ptr(d_match), ptr(d_dist), ptr(d_to_owner)
         self._ck(self.L.lcd_match_guided_dev(self.h, C.byref(a)))
+
+    # ---- keypoint limiting and the -1, -2, ... word ids (stateless; include/lcd.h has the rule)
+    def _select_args(self, offsets, max_features, order, grid, image_size, aux_bytes):
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n_frames = off.shape[0] - 1
+        if n_frames < 0:
+            raise ValueError("select_features: offsets are [n_frames + 1]")
+        order = SELECT_ORDERS[order] if isinstance(order, str) else int(order)
+        size = None if image_size is None else np.ascontiguousarray(image_size, dtype=np.int32).reshape(-1, 2)
+        if size is not None and size.shape[0] != n_frames:
+            raise ValueError("select_features: one (width, height) per frame")
+        a = LcdSelectArgs(C.sizeof(LcdSelectArgs), n_frames, order, int(max_features), int(grid[0]), int(grid[1]), int(aux_bytes), 0)
+        a.offsets, a.image_size = off.ctypes.data, (None if size is None else size.ctypes.data)
+        return a, off, size
+
+    def select_features(self, response, offsets, max_features, order="keep_order", grid=(1, 1), image_size=None, points=None, rows=None, aux=None):
+        """lcd_select_features over host arrays: frame f owns the features [offsets[f], offsets[f+1]); aux is a [N x aux_bytes] uint8 payload.
+        -> (count [n_frames], index [N], rows or None, aux or None); only the first count[f] entries of a frame's region are meaningful."""
+        r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
+        p = None if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        d = None if rows is None else self._rows(rows)
+        x = None if aux is None else np.ascontiguousarray(aux, dtype=np.uint8).reshape(r.shape[0], -1)
+        a, off, _size = self._select_args(offsets, max_features, order, grid, image_size, 0 if x is None else x.shape[1])
+        n = r.shape[0]
+        if int(off[-1]) != n or (p is not None and p.shape[0] != n) or (d is not None and d.shape[0] != n):
+            raise ValueError("select_features: the last offset is the number of features; one point and one row per feature")
+        count, index = np.zeros(max(a.n_frames, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        out_rows = None if d is None else np.zeros((max(n, 1), self.dim), self.np_dtype)
+        out_aux = None if x is None else np.zeros((max(n, 1), x.shape[1]), np.uint8)
+        a.response, a.points, a.rows, a.aux = _p(r), _p(p), _p(d), _p(x)
+        a.out_count, a.out_index, a.out_rows, a.out_aux = _p(count), _p(index), _p(out_rows), _p(out_aux)
+        self._ck(self.L.lcd_select_features(self.h, C.byref(a)))
+        return count[:a.n_frames], index[:n], (None if d is None else out_rows[:n]), (None if x is None else out_aux[:n])
+
+    def select_features_dev(self, d_response, offsets, max_features, d_count, d_index, order="keep_order", grid=(1, 1), image_size=None,
+                            d_points=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_rows=None, d_out_aux=None):
+        """lcd_select_features_dev on torch tensors of the engine's device (float32 responses and points, rows of the handle's dtype, int32
+        outputs; offsets and image sizes stay on the host).  Enqueued on the engine stream, not synchronised."""
+        a, _off, _size = self._select_args(offsets, max_features, order, grid, image_size, aux_bytes)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        a.response, a.points, a.rows, a.aux = ptr(d_response), ptr(d_points), ptr(d_rows), ptr(d_aux)
+        a.out_count, a.out_index, a.out_rows, a.out_aux = ptr(d_count), ptr(d_index), ptr(d_out_rows), ptr(d_out_aux)
+        self._ck(self.L.lcd_select_features_dev(self.h, C.byref(a)))
+
+    def expand_word_ids(self, offsets, count, index, word_ids, first_new_word_id=None):
+        """lcd_expand_word_ids over host arrays -> one id per feature [N]"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        i = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(word_ids, dtype=np.int32).reshape(-1)
+        f = None if first_new_word_id is None else np.ascontiguousarray(first_new_word_id, dtype=np.int32).reshape(-1)
+        n_frames, n = off.shape[0] - 1, int(off[-1])
+        if n_frames < 0 or c.shape[0] != n_frames or i.shape[0] != n or w.shape[0] != n or (f is not None and f.shape[0] != n_frames):
+            raise ValueError("expand_word_ids: count and first ids per frame, index and ids per feature")
+        out = np.zeros(max(n, 1), np.int32)
+        a = LcdExpandArgs(C.sizeof(LcdExpandArgs), n_frames)
+        a.offsets, a.count, a.index, a.word_ids, a.first_new_word_id, a.out_word_ids = off.ctypes.data, _p(c), _p(i), _p(w), _p(f), _p(out)
+        self._ck(self.L.lcd_expand_word_ids(self.h, C.byref(a)))
+        return out[:n]
+
+    def expand_word_ids_dev(self, offsets, d_count, d_index, d_word_ids, d_out_word_ids, d_first_new_word_id=None):
+        """lcd_expand_word_ids_dev on int32 torch tensors of the engine's device (the offsets stay on the host); enqueued, not synchronised"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        a = LcdExpandArgs(C.sizeof(LcdExpandArgs), off.shape[0] - 1)
+        a.offsets = off.ctypes.data
+        a.count, a.index, a.word_ids, a.first_new_word_id, a.out_word_ids = ptr(d_count), ptr(d_index), ptr(d_word_ids), ptr(d_first_new_word_id), ptr(d_out_word_ids)
+        self._ck(self.L.lcd_expand_word_ids_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

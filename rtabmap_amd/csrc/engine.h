@@ -252,8 +252,9 @@ struct FramePipeline {
     void submit(InFlight&& f) { f.set = next_set(); f.stage = Stage::Filter; inflight.push_back(std::move(f)); frame_seq += 1; }
 };
 
-// Scratch of lcd_match_pairs / lcd_match_pairs_dev (pair_match.hip) and lcd_match_guided / lcd_match_guided_dev (guided_match.hip: the job
-// table, the staged rows and results), the calls that neither read nor write engine state and therefore
+// Scratch of lcd_match_pairs / lcd_match_pairs_dev (pair_match.hip), lcd_match_guided / lcd_match_guided_dev (guided_match.hip: the job
+// table, the staged rows and results) and lcd_select_features / lcd_expand_word_ids with their _dev forms (feature_select.hip: the same),
+// the calls that neither read nor write engine state and therefore
 // do not complete what a pipelined handle owes: everything they write on the device lives here and nowhere else, so they can be enqueued
 // between the stages of frames in flight.  The buffers only grow, and a growth frees the old allocation after the engine stream has
 // drained (DevBuf::reserve): work of an earlier call that is still enqueued keeps what it reads.  The job tables of a call reach the
@@ -352,7 +353,7 @@ struct lcd_engine {
     lcd::Bayes bayes;                                   // Bayes filter over the signature slots (bayes.h)
     lcd::DevBuf d_adj_scratch;                          // adjusted likelihood when the caller wants the posterior but not that vector
     lcd::DevBuf d_hyp_scratch;                          // hypothesis record when the caller only wants the adjusted vector
-    PairScratch pairs;                                  // lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip)
+    PairScratch pairs;                                  // lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip), lcd_select_features (feature_select.hip)
 
     // ---- inverted index / TF-IDF
     lcd::Tfidf tfidf;

@@ -1,0 +1,516 @@
+// feature_select.hip -- lcd_select_features / lcd_expand_word_ids and their _dev forms: the quantisation glue of Memory::createSignature
+// (reference Memory.cpp:5941-6059) for a caller whose extractor leaves responses, positions and descriptors in device memory.  The selection
+// is Feature2D::limitKeypoints (Features2d.cpp:293-516) by the rule include/lcd.h writes down, the expansion puts the word ids back onto all
+// features and numbers the ones without a word -1, -2, ... (:6029-6059).  Any number of frames per call, one launch each:
+//   feature_select_kernel: one workgroup per frame.  A frame that is not cut writes the identity.  A cut frame builds one 64-bit key per
+//     feature in LDS -- cell || the complement of (masked response bits || index) -- and sorts them ascending (bitonic, padded to a power of
+//     two with all-ones keys, three steps of the network per round trip through LDS): the cells follow each other, the strongest feature
+//     of a cell first.  A feature's rank within its cell is its position minus the position where its cell starts; "selected" is
+//     rank < limit.  BY_RESPONSE writes the sorted prefix; KEEP_ORDER sets one bit per selected feature and compacts the bits in feature
+//     order with a ballot scan.  Rows and the caller's payload are gathered behind the index list with 16-byte copies where addresses and
+//     sizes allow, 4-byte copies otherwise.
+//   expand_word_ids_kernel: one workgroup per frame; the resolved ids are scattered into an LDS image of the frame, then a ballot scan over
+//     "has no word" in feature order hands out -1, -2, ...
+// Nothing of the engine is read or written: the job table is PairScratch's (engine.h), as for lcd_match_pairs and lcd_match_guided.
+#include "engine_impl.h"
+
+#include <cmath>
+#include <vector>
+
+static_assert(sizeof(lcd_select_args) == 112, "lcd_select_args: the layout include/lcd.h documents (LP64)");
+static_assert(sizeof(lcd_expand_args) == 56, "lcd_expand_args: the layout include/lcd.h documents (LP64)");
+
+namespace lcd {
+namespace {
+
+constexpr int MAX_FEATURES = 16384;          // features in one frame: 128 KiB of 64-bit keys (144 KiB with their padding) in one workgroup's LDS
+constexpr int MAX_CELLS = 1024;
+constexpr int IDX_BITS = 14;                 // an index within a frame
+constexpr int STRENGTH_BITS = 31 + IDX_BITS; // masked response bits || index
+constexpr uint64_t STRENGTH_MASK = (1ull << STRENGTH_BITS) - 1;
+constexpr int SMALL_BLOCK = 256, BIG_BLOCK = 1024;
+constexpr int SMALL_FRAME = 2048;            // the largest frame a call of 256-thread workgroups serves
+constexpr int MAX_WAVES = BIG_BLOCK / 64;
+
+struct FrameJob {
+    int64_t first;                           // the frame's first feature in every array
+    int32_t n;
+    int32_t row_size, col_size;              // pixels per grid cell (1 where the frame is not cut)
+    int32_t pad;
+};
+
+struct SelectArgs {
+    const FrameJob* jobs;
+    int order, max_features, grid_rows, grid_cols;
+    int p_max;                               // keys the LDS carve holds (a power of two >= every cut frame)
+    int row_bytes, row_vec, aux_bytes, aux_vec;   // *_vec: 16 or 4, the widest copy the addresses and sizes allow
+    const float* response; const float2* points; const void* rows; const void* aux;
+    int32_t* out_count; int32_t* out_index; void* out_rows; void* out_aux;
+};
+
+struct ExpandArgs {
+    const FrameJob* jobs;
+    const int32_t* count; const int32_t* index; const int32_t* word_ids; const int32_t* first_new_word_id;
+    int32_t* out_word_ids;
+};
+
+extern __shared__ __attribute__((aligned(16))) unsigned char fs_smem[];
+
+// exclusive rank of this thread's flag among the workgroup's flags in thread order, and their total (two barriers; wsum: one int per wave)
+__device__ __forceinline__ int block_rank(bool flag, int* wsum, int& total) {
+    const unsigned long long m = __ballot(flag);
+    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const int wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) wsum[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < n_waves; ++w) {
+        const int v = wsum[w];
+        if (w < wave) before += v;
+        all += v;
+    }
+    __syncthreads();
+    total = all;
+    return before + in_wave;
+}
+
+// Where key i lies in LDS: one spare slot behind every eight keys.  The network's threads walk the keys with strides of 8, 64, 512, .. keys
+// between neighbouring lanes; unpadded, those land on the same banks (64 banks of 4 bytes: 32 keys) up to sixteen lanes deep.
+__host__ __device__ __forceinline__ int padded(int i) { return i + (i >> 3); }
+
+// M consecutive steps of a bitonic network's level k in one round trip through LDS: the strides j, j/2, .., j >> (M - 1).  A thread takes the
+// 2^M keys that differ only in those M index bits (they meet nobody else during these steps), orders them in registers and puts them back.
+template <int M>
+__device__ __forceinline__ void bitonic_pass(uint64_t* keys, int p2, int k, int j) {
+    const int j_lo = j >> (M - 1);
+    for (int g = threadIdx.x; g < (p2 >> M); g += blockDim.x) {
+        const int base = ((g & ~(j_lo - 1)) << M) | (g & (j_lo - 1));
+        const bool ascending = (base & k) == 0;                        // the same for the 2^M keys: their indices differ below bit k
+        uint64_t e[1 << M];
+#pragma unroll
+        for (int a = 0; a < (1 << M); ++a) e[a] = keys[padded(base + a * j_lo)];
+#pragma unroll
+        for (int b = M - 1; b >= 0; --b) {
+#pragma unroll
+            for (int a = 0; a < (1 << M); ++a) {
+                if ((a >> b) & 1) continue;
+                const uint64_t x = e[a], y = e[a | (1 << b)];
+                const bool swap = (x > y) == ascending;
+                e[a] = swap ? y : x;
+                e[a | (1 << b)] = swap ? x : y;
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < (1 << M); ++a) keys[padded(base + a * j_lo)] = e[a];
+    }
+}
+
+// dst row j = src row idx[j], j < count, `bytes` per row in pieces of V
+template <typename V>
+__device__ __forceinline__ void gather_rows(const void* src, void* dst, const int32_t* idx, int64_t first, int count, int bytes) {
+    const int per = bytes / (int)sizeof(V);
+    const V* s = reinterpret_cast<const V*>(src) + first * per;
+    V* d = reinterpret_cast<V*>(dst) + first * per;
+    const int total = count * per;                                    // at most 16384 x 128
+    for (int e = threadIdx.x; e < total; e += blockDim.x) {
+        const int j = e / per, c = e - j * per;
+        d[(size_t)j * per + c] = s[(size_t)idx[j] * per + c];
+    }
+}
+
+__global__ __launch_bounds__(BIG_BLOCK) void feature_select_kernel(SelectArgs a) {
+    const FrameJob J = a.jobs[blockIdx.x];
+    const int n = J.n, tid = threadIdx.x, T = blockDim.x;
+    const int n_cells = a.grid_rows * a.grid_cols;
+    uint64_t* keys = reinterpret_cast<uint64_t*>(fs_smem);
+    uint32_t* sel = reinterpret_cast<uint32_t*>(fs_smem + (size_t)padded(a.p_max) * 8);   // one bit per feature
+    int32_t* cell_start = reinterpret_cast<int32_t*>(sel + a.p_max / 32);             // [n_cells + 1]: the last entry is "outside the grid"
+    int* wsum = cell_start + n_cells + 1;
+    int32_t* out_index = a.out_index + J.first;
+    const bool cut = a.max_features > 0 && n > a.max_features;
+    int count = n;
+
+    if (!cut) {
+        for (int i = tid; i < n; i += T) out_index[i] = i;             // the reference does not sort what it does not cut
+    } else {
+        int p2 = 2;
+        while (p2 < n) p2 <<= 1;                                       // <= p_max
+        const bool grid = n_cells > 1;
+        for (int i = tid; i < p2; i += T) {
+            uint64_t key = ~0ull;                                      // padding sorts last
+            if (i < n) {
+                uint32_t cell = 0;
+                if (grid) {
+                    const float2 p = a.points[J.first + i];
+                    const int cr = __float2int_rz(p.y) / J.row_size, cc = __float2int_rz(p.x) / J.col_size;   // int(y) / rowSize: both truncate toward zero
+                    const bool inside = cr >= 0 && cr < a.grid_rows && cc >= 0 && cc < a.grid_cols;
+                    cell = inside ? (uint32_t)(cr * a.grid_cols + cc) : (uint32_t)n_cells;
+                }
+                const uint64_t strength = ((uint64_t)(__float_as_uint(a.response[J.first + i]) & 0x7fffffffu) << IDX_BITS) | (uint32_t)i;
+                key = ((uint64_t)cell << STRENGTH_BITS) | (STRENGTH_MASK - strength);
+            }
+            keys[padded(i)] = key;
+        }
+        for (int w = tid; w < (n + 31) / 32; w += T) sel[w] = 0u;
+        __syncthreads();
+        for (int k = 2; k <= p2; k <<= 1) {                            // the strides k/2 .. 1 of level k, three to a round trip through LDS
+            int j = k >> 1;
+            for (; j >= 4; j >>= 3) { bitonic_pass<3>(keys, p2, k, j); __syncthreads(); }
+            if (j == 2) bitonic_pass<2>(keys, p2, k, 2);
+            else if (j == 1) bitonic_pass<1>(keys, p2, k, 1);
+            if (j) __syncthreads();
+        }
+        for (int p = tid; p < n; p += T) {
+            const int c = (int)(keys[padded(p)] >> STRENGTH_BITS);
+            if (p == 0 || (int)(keys[padded(p - 1)] >> STRENGTH_BITS) != c) cell_start[c] = p;
+        }
+        __syncthreads();
+        const int limit = grid ? a.max_features / n_cells : a.max_features;          // perCell == 0: the whole cell stays
+        const bool by_response = a.order == LCD_SELECT_BY_RESPONSE;
+        for (int p = tid; p < n; p += T) {
+            const uint64_t key = keys[padded(p)];
+            const int c = (int)(key >> STRENGTH_BITS);
+            const int i = (int)((STRENGTH_MASK - (key & STRENGTH_MASK)) & ((1u << IDX_BITS) - 1));
+            const bool chosen = c < n_cells && (limit <= 0 || p - cell_start[c] < limit);
+            if (!chosen) continue;
+            if (by_response) out_index[p] = i;                                        // (1 x 1 grid: the position is the rank)
+            else atomicOr(&sel[i >> 5], 1u << (i & 31));
+        }
+        __syncthreads();
+        if (by_response) {
+            count = a.max_features;
+        } else {
+            count = 0;
+            for (int base = 0; base < n; base += T) {
+                const int i = base + tid;
+                const bool flag = i < n && ((sel[i >> 5] >> (i & 31)) & 1u);
+                int total;
+                const int pos = count + block_rank(flag, wsum, total);
+                if (flag) out_index[pos] = i;
+                count += total;
+            }
+        }
+        for (int i = count + tid; i < n; i += T) out_index[i] = -1;
+    }
+    if (tid == 0) a.out_count[blockIdx.x] = count;
+    if (!a.rows && !a.aux) return;
+    __syncthreads();                                                   // the index list is read back by the threads that gather
+    if (a.rows) {
+        if (a.row_vec == 16) gather_rows<uint4>(a.rows, a.out_rows, out_index, J.first, count, a.row_bytes);
+        else gather_rows<uint32_t>(a.rows, a.out_rows, out_index, J.first, count, a.row_bytes);
+    }
+    if (a.aux) {
+        if (a.aux_vec == 16) gather_rows<uint4>(a.aux, a.out_aux, out_index, J.first, count, a.aux_bytes);
+        else gather_rows<uint32_t>(a.aux, a.out_aux, out_index, J.first, count, a.aux_bytes);
+    }
+}
+
+__global__ __launch_bounds__(BIG_BLOCK) void expand_word_ids_kernel(ExpandArgs a, int n_max) {
+    const FrameJob J = a.jobs[blockIdx.x];
+    const int n = J.n, tid = threadIdx.x, T = blockDim.x;
+    int32_t* all = reinterpret_cast<int32_t*>(fs_smem);                // the frame's resolved ids, 0 = no word
+    int* wsum = all + n_max;
+    const int count = min(max(a.count[blockIdx.x], 0), n);
+    const int32_t first_id = a.first_new_word_id ? a.first_new_word_id[blockIdx.x] : 0;
+    for (int i = tid; i < n; i += T) all[i] = 0;
+    __syncthreads();
+    for (int j = tid; j < count; j += T) {
+        const int32_t i = a.index[J.first + j];
+        if (i < 0 || i >= n) continue;                                 // (the host entry refuses it)
+        const int32_t w = a.word_ids[J.first + j];
+        int32_t id = w;
+        if (w < 0) id = first_id > 0 ? (int32_t)((uint32_t)first_id + (uint32_t)(-(w + 1))) : 0;   // the code -(k+1): first + k
+        if (id > 0) all[i] = id;
+    }
+    __syncthreads();
+    int negatives = 0;
+    for (int base = 0; base < n; base += T) {
+        const int i = base + tid;
+        const int32_t id = i < n ? all[i] : 1;
+        int total;
+        const int rank = negatives + block_rank(id <= 0, wsum, total);
+        if (i < n) a.out_word_ids[J.first + i] = id > 0 ? id : -(rank + 1);
+        negatives += total;
+    }
+}
+
+inline size_t select_lds(int p_max, int n_cells) { return ((size_t)padded(p_max) * 8 + (size_t)p_max / 8 + (size_t)(n_cells + 1) * 4 + MAX_WAVES * 4 + 15) & ~(size_t)15; }
+inline size_t expand_lds(int n_max) { return ((size_t)n_max * 4 + MAX_WAVES * 4 + 15) & ~(size_t)15; }
+
+// the largest frames need more than the default 64 KiB of dynamic LDS
+void allow_large_lds() {
+    static const bool once = [] {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&feature_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)select_lds(MAX_FEATURES, MAX_CELLS)) != hipSuccess) (void)hipGetLastError();
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&expand_word_ids_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)expand_lds(MAX_FEATURES)) != hipSuccess) (void)hipGetLastError();
+        return true;
+    }();
+    (void)once;
+}
+
+}  // namespace
+}  // namespace lcd
+
+using namespace lcd;
+
+namespace {
+
+inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// offsets, the limits every entry shares; *n_max: the largest frame
+int check_frames(lcd_engine* h, const char* who, int32_t n_frames, const int64_t* off, int* n_max) {
+    auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
+    if (n_frames < 0) return bad(LCD_ERR_INVALID, "negative n_frames");
+    if (n_frames > 65535) return bad(LCD_ERR_UNSUPPORTED, "more than 65535 frames per call");
+    if (h->shard_append || h->shard_first || h->shard_block) return bad(LCD_ERR_UNSUPPORTED, "not offered on the handles of a sharded vocabulary");
+    *n_max = 0;
+    if (n_frames == 0) return LCD_OK;
+    if (!off || off[0] != 0) return bad(LCD_ERR_INVALID, "offsets missing or not starting at 0");
+    for (int f = 0; f < n_frames; ++f) if (off[f + 1] < off[f]) return bad(LCD_ERR_INVALID, "decreasing offsets");
+    for (int f = 0; f < n_frames; ++f) {
+        if (off[f + 1] - off[f] > MAX_FEATURES) return bad(LCD_ERR_UNSUPPORTED, "more than 16384 features in a frame");
+        *n_max = std::max(*n_max, (int)(off[f + 1] - off[f]));
+    }
+    return LCD_OK;
+}
+
+// the job table reaches the device through a pinned slot whose last copy has run (PairScratch)
+int upload_jobs(lcd_engine* h, const std::vector<FrameJob>& jobs, const FrameJob** d_jobs) {
+    PairScratch& S = h->pairs;
+    hipStream_t st = h->stream;
+    const size_t job_bytes = jobs.size() * sizeof(FrameJob);
+    LCD_HIP(h, dreserve(h, S.d_table, job_bytes + 64));
+    const int slot = S.next_slot; S.next_slot ^= 1;
+    if (!S.table_read[slot]) LCD_HIP(h, hipEventCreateWithFlags(&S.table_read[slot], hipEventDisableTiming));
+    else LCD_HIP(h, hipEventSynchronize(S.table_read[slot]));
+    LCD_HIP(h, S.h_table[slot].reserve(job_bytes + 64));
+    std::memcpy(S.h_table[slot].p, jobs.data(), job_bytes);
+    LCD_HIP(h, hipMemcpyAsync(S.d_table.p, S.h_table[slot].p, job_bytes, hipMemcpyHostToDevice, st));
+    LCD_HIP(h, hipEventRecord(S.table_read[slot], st));
+    *d_jobs = S.d_table.as<FrameJob>();
+    return LCD_OK;
+}
+
+// int(v) as the device converts it: toward zero, saturating, NaN -> 0
+inline int to_int_rz(float v) {
+    if (std::isnan(v)) return 0;
+    if (v >= 2147483648.0f) return 2147483647;
+    if (v <= -2147483648.0f) return -2147483647 - 1;
+    return (int)v;
+}
+
+int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
+    const char* who = on_device ? "lcd_select_features_dev" : "lcd_select_features";
+    auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
+    // ---- everything that can be refused is refused before anything is enqueued or written
+    if (!a || a->struct_size != (int32_t)sizeof(lcd_select_args)) return bad(LCD_ERR_INVALID, "null arguments or wrong struct_size");
+    if (a->order != LCD_SELECT_KEEP_ORDER && a->order != LCD_SELECT_BY_RESPONSE) return bad(LCD_ERR_INVALID, "unknown order");
+    if (a->grid_rows < 1 || a->grid_cols < 1) return bad(LCD_ERR_INVALID, "grid_rows and grid_cols are >= 1");
+    if ((int64_t)a->grid_rows * a->grid_cols > MAX_CELLS) return bad(LCD_ERR_UNSUPPORTED, "more than 1024 grid cells");
+    const bool grid = a->grid_rows * a->grid_cols > 1;
+    if (grid && a->order == LCD_SELECT_BY_RESPONSE) return bad(LCD_ERR_INVALID, "LCD_SELECT_BY_RESPONSE has no grid variant");
+    if (a->aux_bytes < 0 || a->aux_bytes > 64 || a->aux_bytes % 4) return bad(LCD_ERR_INVALID, "aux_bytes is a multiple of 4, 0..64");
+    int n_max = 0;
+    if (int rc = check_frames(h, who, a->n_frames, a->offsets, &n_max)) return rc;
+    const bool with_rows = a->rows != nullptr, with_aux = a->aux != nullptr && a->aux_bytes > 0;
+    if (on_device && with_rows && rows_padded(h)) return bad(LCD_ERR_UNSUPPORTED, "the handle's rows are padded: a [n x dim] device buffer is not what the kernel walks");
+    if (a->n_frames == 0) return LCD_OK;
+    const int nf = a->n_frames;
+    const int64_t* off = a->offsets;
+    const int64_t N = off[nf];
+    if (!a->out_count) return bad(LCD_ERR_INVALID, "null out_count");
+    if (N > 0 && (!a->response || !a->out_index)) return bad(LCD_ERR_INVALID, "null response or out_index");
+    if (N > 0 && ((with_rows && !a->out_rows) || (with_aux && !a->out_aux))) return bad(LCD_ERR_INVALID, "rows or aux without an output");
+    if (N > 0 && grid && (!a->points || !a->image_size)) return bad(LCD_ERR_INVALID, "a grid needs points and image sizes");
+    std::vector<FrameJob> jobs((size_t)nf);
+    int cut_max = 0;
+    for (int f = 0; f < nf; ++f) {
+        FrameJob& J = jobs[(size_t)f];
+        J.first = off[f]; J.n = (int32_t)(off[f + 1] - off[f]); J.row_size = J.col_size = 1; J.pad = 0;
+        if (!(a->max_features > 0 && J.n > a->max_features)) continue;
+        cut_max = std::max(cut_max, (int)J.n);
+        if (!grid) continue;
+        const int32_t width = a->image_size[2 * f], height = a->image_size[2 * f + 1];
+        if (height <= a->grid_rows || width <= a->grid_cols) return bad(LCD_ERR_INVALID, "the image is not larger than the grid");
+        J.row_size = height / a->grid_rows; J.col_size = width / a->grid_cols;
+    }
+    if (!on_device) {
+        for (int64_t i = 0; i < N; ++i) if (std::isnan(a->response[i])) return bad(LCD_ERR_INVALID, "a NaN response has no place in the order");
+        if (grid)
+            for (int f = 0; f < nf; ++f) {
+                const FrameJob& J = jobs[(size_t)f];
+                if (!(a->max_features > 0 && J.n > a->max_features)) continue;
+                for (int64_t i = off[f]; i < off[f + 1]; ++i) {
+                    const int cr = to_int_rz(a->points[2 * i + 1]) / J.row_size, cc = to_int_rz(a->points[2 * i]) / J.col_size;
+                    if (cr < 0 || cr >= a->grid_rows || cc < 0 || cc >= a->grid_cols) return bad(LCD_ERR_INVALID, "a keypoint outside the grid");
+                }
+            }
+    }
+    PairScratch& S = h->pairs;
+    hipStream_t st = h->stream;
+
+    SelectArgs g;
+    g.order = a->order; g.max_features = a->max_features; g.grid_rows = a->grid_rows; g.grid_cols = a->grid_cols;
+    g.p_max = 64;
+    while (g.p_max < cut_max) g.p_max <<= 1;
+    g.row_bytes = h->row_bytes; g.aux_bytes = a->aux_bytes;
+    g.response = a->response; g.points = (const float2*)a->points; g.rows = with_rows ? a->rows : nullptr; g.aux = with_aux ? a->aux : nullptr;
+    g.out_count = a->out_count; g.out_index = a->out_index; g.out_rows = a->out_rows; g.out_aux = a->out_aux;
+
+    // ---- host entry: everything to the device, results back at the end (one synchronisation)
+    size_t o_count = 0, o_index = 0, o_rows = 0, o_aux = 0, out_bytes = 0;
+    if (!on_device) {
+        const size_t i_resp = 0, i_pts = i_resp + up256((size_t)N * 4), i_rows = i_pts + up256(grid ? (size_t)N * 8 : 0),
+                     i_aux = i_rows + up256(with_rows ? (size_t)N * h->row_bytes : 0), in_bytes = i_aux + up256(with_aux ? (size_t)N * a->aux_bytes : 0);
+        o_count = 0; o_index = o_count + up256((size_t)nf * 4); o_rows = o_index + up256((size_t)N * 4);
+        o_aux = o_rows + up256(with_rows ? (size_t)N * h->row_bytes : 0); out_bytes = o_aux + up256(with_aux ? (size_t)N * a->aux_bytes : 0);
+        LCD_HIP(h, S.h_in.reserve(in_bytes + 256));
+        LCD_HIP(h, S.h_out.reserve(out_bytes + 256));
+        LCD_HIP(h, dreserve(h, S.d_in, in_bytes + 256));
+        LCD_HIP(h, dreserve(h, S.d_out, out_bytes + 256));
+        char* hp = S.h_in.as<char>();
+        if (N) std::memcpy(hp + i_resp, a->response, (size_t)N * 4);
+        if (N && grid) std::memcpy(hp + i_pts, a->points, (size_t)N * 8);
+        if (N && with_rows) {
+            const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
+            if (src_row == (size_t)h->row_bytes) std::memcpy(hp + i_rows, a->rows, (size_t)N * src_row);
+            else {
+                std::memset(hp + i_rows, 0, (size_t)N * h->row_bytes);
+                for (int64_t i = 0; i < N; ++i) std::memcpy(hp + i_rows + (size_t)i * h->row_bytes, (const char*)a->rows + (size_t)i * src_row, src_row);
+            }
+        }
+        if (N && with_aux) std::memcpy(hp + i_aux, a->aux, (size_t)N * a->aux_bytes);
+        if (in_bytes) LCD_HIP(h, hipMemcpyAsync(S.d_in.p, hp, in_bytes, hipMemcpyHostToDevice, st));
+        const char* dp = S.d_in.as<char>();
+        char* dq = S.d_out.as<char>();
+        g.response = (const float*)(dp + i_resp); g.points = grid ? (const float2*)(dp + i_pts) : nullptr;
+        g.rows = with_rows ? dp + i_rows : nullptr; g.aux = with_aux ? dp + i_aux : nullptr;
+        g.out_count = (int32_t*)(dq + o_count); g.out_index = (int32_t*)(dq + o_index); g.out_rows = dq + o_rows; g.out_aux = dq + o_aux;
+    }
+    g.row_vec = g.rows && g.row_bytes % 16 == 0 && aligned16(g.rows) && aligned16(g.out_rows) ? 16 : 4;
+    g.aux_vec = g.aux && g.aux_bytes % 16 == 0 && aligned16(g.aux) && aligned16(g.out_aux) ? 16 : 4;
+
+    if (int rc = upload_jobs(h, jobs, &g.jobs)) return rc;
+    allow_large_lds();
+    const int block = n_max > SMALL_FRAME ? BIG_BLOCK : SMALL_BLOCK;
+    feature_select_kernel<<<dim3((unsigned)nf), dim3((unsigned)block), select_lds(g.p_max, a->grid_rows * a->grid_cols), st>>>(g);
+    LCD_HIP(h, hipGetLastError());
+    if (on_device) return LCD_OK;
+    LCD_HIP(h, hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    LCD_HIP(h, hipStreamSynchronize(st));
+    const char* ho = S.h_out.as<char>();
+    std::memcpy(a->out_count, ho + o_count, (size_t)nf * 4);
+    if (N) std::memcpy(a->out_index, ho + o_index, (size_t)N * 4);
+    for (int f = 0; f < nf && (with_rows || with_aux); ++f) {          // only what the frame wrote: the rest of its region stays as it was
+        const size_t cnt = (size_t)a->out_count[f], first = (size_t)off[f];
+        if (with_rows) {
+            const size_t dst_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
+            if (dst_row == (size_t)h->row_bytes) std::memcpy((char*)a->out_rows + first * dst_row, ho + o_rows + first * dst_row, cnt * dst_row);
+            else for (size_t j = first; j < first + cnt; ++j) std::memcpy((char*)a->out_rows + j * dst_row, ho + o_rows + j * h->row_bytes, dst_row);
+        }
+        if (with_aux) std::memcpy((char*)a->out_aux + first * a->aux_bytes, ho + o_aux + first * a->aux_bytes, cnt * a->aux_bytes);
+    }
+    return LCD_OK;
+}
+
+int expand_word_ids(lcd_engine* h, const lcd_expand_args* a, bool on_device) {
+    const char* who = on_device ? "lcd_expand_word_ids_dev" : "lcd_expand_word_ids";
+    auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
+    if (!a || a->struct_size != (int32_t)sizeof(lcd_expand_args)) return bad(LCD_ERR_INVALID, "null arguments or wrong struct_size");
+    int n_max = 0;
+    if (int rc = check_frames(h, who, a->n_frames, a->offsets, &n_max)) return rc;
+    if (a->n_frames == 0) return LCD_OK;
+    const int nf = a->n_frames;
+    const int64_t* off = a->offsets;
+    const int64_t N = off[nf];
+    if (!a->count) return bad(LCD_ERR_INVALID, "null count");
+    if (N > 0 && (!a->index || !a->word_ids || !a->out_word_ids)) return bad(LCD_ERR_INVALID, "null index, word_ids or out_word_ids");
+    if (!on_device)
+        for (int f = 0; f < nf; ++f) {
+            const int64_t n = off[f + 1] - off[f];
+            if (a->count[f] < 0 || a->count[f] > n) return bad(LCD_ERR_INVALID, "count outside its frame");
+            for (int64_t j = off[f]; j < off[f] + a->count[f]; ++j)
+                if (a->index[j] < 0 || a->index[j] >= n) return bad(LCD_ERR_INVALID, "an index entry outside its frame");
+        }
+    if (N == 0) return LCD_OK;
+    PairScratch& S = h->pairs;
+    hipStream_t st = h->stream;
+    std::vector<FrameJob> jobs((size_t)nf);
+    for (int f = 0; f < nf; ++f) jobs[(size_t)f] = FrameJob{off[f], (int32_t)(off[f + 1] - off[f]), 1, 1, 0};
+
+    ExpandArgs g;
+    g.count = a->count; g.index = a->index; g.word_ids = a->word_ids; g.first_new_word_id = a->first_new_word_id; g.out_word_ids = a->out_word_ids;
+    size_t out_off = 0;
+    if (!on_device) {
+        const size_t i_count = 0, i_index = i_count + up256((size_t)nf * 4), i_words = i_index + up256((size_t)N * 4),
+                     i_first = i_words + up256((size_t)N * 4), in_bytes = i_first + up256(a->first_new_word_id ? (size_t)nf * 4 : 0);
+        LCD_HIP(h, S.h_in.reserve(in_bytes + 256));
+        LCD_HIP(h, S.h_out.reserve((size_t)N * 4 + 256));
+        LCD_HIP(h, dreserve(h, S.d_in, in_bytes + 256));
+        LCD_HIP(h, dreserve(h, S.d_out, (size_t)N * 4 + 256));
+        char* hp = S.h_in.as<char>();
+        std::memcpy(hp + i_count, a->count, (size_t)nf * 4);
+        std::memcpy(hp + i_index, a->index, (size_t)N * 4);
+        std::memcpy(hp + i_words, a->word_ids, (size_t)N * 4);
+        if (a->first_new_word_id) std::memcpy(hp + i_first, a->first_new_word_id, (size_t)nf * 4);
+        LCD_HIP(h, hipMemcpyAsync(S.d_in.p, hp, in_bytes, hipMemcpyHostToDevice, st));
+        const char* dp = S.d_in.as<char>();
+        g.count = (const int32_t*)(dp + i_count); g.index = (const int32_t*)(dp + i_index); g.word_ids = (const int32_t*)(dp + i_words);
+        g.first_new_word_id = a->first_new_word_id ? (const int32_t*)(dp + i_first) : nullptr;
+        g.out_word_ids = (int32_t*)(S.d_out.as<char>() + out_off);
+    }
+    if (int rc = upload_jobs(h, jobs, &g.jobs)) return rc;
+    allow_large_lds();
+    const int block = n_max > SMALL_FRAME ? BIG_BLOCK : SMALL_BLOCK;
+    expand_word_ids_kernel<<<dim3((unsigned)nf), dim3((unsigned)block), expand_lds(n_max), st>>>(g, n_max);
+    LCD_HIP(h, hipGetLastError());
+    if (on_device) return LCD_OK;
+    LCD_HIP(h, hipMemcpyAsync(S.h_out.p, S.d_out.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    LCD_HIP(h, hipStreamSynchronize(st));
+    std::memcpy(a->out_word_ids, S.h_out.p, (size_t)N * 4);
+    return LCD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lcd_select_features(lcd_engine* h, const lcd_select_args* a) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_select_features");
+    LCD_DEV_NODRAIN(h);
+    return select_features(h, a, false);
+    LCD_CATCH(h)
+}
+
+int lcd_select_features_dev(lcd_engine* h, const lcd_select_args* a) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_select_features");
+    LCD_DEV_NODRAIN(h);
+    return select_features(h, a, true);
+    LCD_CATCH(h)
+}
+
+int lcd_expand_word_ids(lcd_engine* h, const lcd_expand_args* a) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_expand_word_ids");
+    LCD_DEV_NODRAIN(h);
+    return expand_word_ids(h, a, false);
+    LCD_CATCH(h)
+}
+
+int lcd_expand_word_ids_dev(lcd_engine* h, const lcd_expand_args* a) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, "lcd_expand_word_ids");
+    LCD_DEV_NODRAIN(h);
+    return expand_word_ids(h, a, true);
+    LCD_CATCH(h)
+}
+
+}  // extern "C"

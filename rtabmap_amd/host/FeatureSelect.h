@@ -1,0 +1,28 @@
+// FeatureSelect.h -- Feature2D::limitKeypoints (reference Features2d.cpp:293-516, without Kp/SSC) and the -1, -2, ... word ids of
+// Memory::createSignature (Memory.cpp:6029-6059) as plain host code: the rule include/lcd.h writes down for lcd_select_features and
+// lcd_expand_word_ids, for small frames and for a process without a device.  No engine is involved.
+#pragma once
+#include <vector>
+
+namespace rtabmap_amd {
+
+class FeatureSelect {
+public:
+    // The inlier mask (:412-516).  response[n]; points[2 n] (x, y), may be NULL with a 1 x 1 grid.  "Stronger" is the larger
+    // (bits(response) & 0x7FFFFFFF, index): among equal responses the higher index, as the reverse walk of the reference's multimap.
+    // false -- inliers untouched -- where the reference asserts or its order is undefined: a NaN response, a cut frame whose image is not
+    // larger than the grid, a keypoint whose cell is outside the grid.
+    static bool limitKeypoints(const float* response, const float* points, int n, int maxKeypoints, int imageWidth, int imageHeight, int gridRows,
+                               int gridCols, std::vector<bool>& inliers);
+    // The compacting form (:293-410): kept = the indices in output order -- the maxKeypoints strongest first when the frame is cut, the
+    // frame's own order otherwise.  false on a NaN response.
+    static bool limitKeypoints(const float* response, int n, int maxKeypoints, std::vector<int>& kept);
+    // :6029-6059.  index[count], wordIds[count]: feature index[j] has id wordIds[j]; an id > 0 stands, a code -(k+1) becomes firstNewWordId + k
+    // when firstNewWordId > 0, anything else is "no word"; the features without a word are numbered -1, -2, ... in feature order.
+    // false -- all untouched -- on a count or an index outside [0, n].
+    static bool expandWordIds(int n, const int* index, const int* wordIds, int count, int firstNewWordId, std::vector<int>& all);
+    // int(v) as the device converts it: toward zero, saturating, NaN -> 0 (the reference's cast is undefined there)
+    static int toInt(float v);
+};
+
+}  // namespace rtabmap_amd

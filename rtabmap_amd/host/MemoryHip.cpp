@@ -2,6 +2,7 @@
 #include "MemoryHip.h"
 
 #include "DbLoaderHip.h"
+#include "FeatureSelect.h"
 
 #include <algorithm>
 #include <chrono>
@@ -25,12 +26,15 @@ struct Stage {
 }  // namespace
 
 MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
-    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
+    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _maxFeatures(500), _gridRows(1), _gridCols(1), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
     ParametersMap::const_iterator it = parameters.find("Mem/STMSize");
     if (it != parameters.end()) _maxStMemSize = atoi(it->second.c_str());
     it = parameters.find("Kp/TfIdfLikelihoodUsed");
     if (it != parameters.end()) _tfIdfLikelihoodUsed = !(it->second == "false" || it->second == "0" || it->second == "False" || it->second == "FALSE");
     if (_maxStMemSize < 0) _maxStMemSize = 0;
+    if ((it = parameters.find("Kp/MaxFeatures")) != parameters.end()) _maxFeatures = atoi(it->second.c_str());
+    if ((it = parameters.find("Kp/GridRows")) != parameters.end()) _gridRows = atoi(it->second.c_str());
+    if ((it = parameters.find("Kp/GridCols")) != parameters.end()) _gridCols = atoi(it->second.c_str());
     _workingMem.insert(kIdVirtual);             // Memory.cpp:592
     static const char* names[] = {"TimingMem/Pre_update/ms", "TimingMem/Joining_dictionary_update/ms", "TimingMem/Add_new_words/ms",
                                   "Timing/Likelihood_computation/ms", "Timing/Forgetting/ms", "Keypoint/Dictionary_size/words",
@@ -96,6 +100,94 @@ int MemoryHip::update(const Mat& descriptors, int nQuantized, std::vector<int>& 
         }
     }
     _stats["TimingMem/Add_new_words/ms"] = quant.ms();          // (on the device-frame path this also holds the frame's likelihood: one call)
+    _stats["Keypoint/Current_frame/words"] = (float)wordIds.size();
+    _stats["Keypoint/Dictionary_size/words"] = (float)_vwd->getVisualWords().size();
+    _stats["Keypoint/Indexed_words/words"] = (float)_vwd->getIndexedWordsCount();
+    _signatures[id] = std::vector<int>(wordIds.begin(), wordIds.end());
+    outIds.assign(wordIds.begin(), wordIds.end());
+    this->addSignatureToStm(id);
+    return id;
+}
+
+// Memory.cpp:6026-6049 for a signature whose quantised descriptors are a selection: addNewWords, then the ids back onto all features
+bool MemoryHip::quantizeSelected(const Mat& forQuantization, const std::vector<int>* rawIndex, int rows, int id, std::list<int>& wordIds) {
+    std::list<int> quantized;
+    if (forQuantization.rows) quantized = _vwd->addNewWords(forQuantization, id);
+    const std::vector<int32_t> ids(quantized.begin(), quantized.end());
+    const int32_t count = (int32_t)ids.size();
+    std::vector<int32_t> index((size_t)count);
+    for (int32_t j = 0; j < count; ++j) index[(size_t)j] = rawIndex ? (*rawIndex)[(size_t)j] : j;
+    std::vector<int> all;
+    lcd_engine* eng = _vwd->engine();
+    if (eng && rows > 0) {
+        // the arrays of a frame share its offsets: count entries of index / ids are valid, rows are written
+        std::vector<int32_t> idx((size_t)rows, -1), wid((size_t)rows, 0), out((size_t)rows, 0);
+        std::copy(index.begin(), index.end(), idx.begin());
+        std::copy(ids.begin(), ids.end(), wid.begin());
+        const int64_t offsets[2] = {0, rows};
+        lcd_expand_args e;
+        e.struct_size = (int32_t)sizeof(e); e.n_frames = 1; e.offsets = offsets; e.count = &count; e.index = idx.data(); e.word_ids = wid.data();
+        e.first_new_word_id = 0; e.out_word_ids = out.data();
+        if (lcd_expand_word_ids(eng, &e) != LCD_OK) { _selectError = lcd_last_error(eng); return false; }
+        all.assign(out.begin(), out.end());
+    } else if (!FeatureSelect::expandWordIds(rows, index.data(), ids.data(), count, 0, all)) {
+        _selectError = "expandWordIds: an index outside the frame";
+        return false;
+    }
+    wordIds.assign(all.begin(), all.end());
+    return true;
+}
+
+int MemoryHip::update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
+                      std::vector<int>& outIds) {
+    const int rows = descriptors.rows;
+    const bool grid = _gridRows > 1 || _gridCols > 1;
+    _selectError.clear();
+    if (!(_maxFeatures > 0 && rows > _maxFeatures)) return this->update(descriptors, -1, outIds);     // :5954: nothing to select
+    if ((int)responses.size() != rows || (grid && (int)points.size() != 2 * rows)) { _selectError = "one response (and one point) per descriptor"; return 0; }
+    // ---- the selection (:5951-6023)
+    std::vector<int> rawIndex;
+    Mat forQuantization;
+    lcd_engine* eng = _vwd->engine();
+    if (eng) {
+        const int64_t offsets[2] = {0, rows};
+        const int32_t size[2] = {imageWidth, imageHeight};
+        int32_t count = 0;
+        std::vector<int32_t> index((size_t)rows);
+        std::vector<unsigned char> selected(descriptors.data.size());
+        lcd_select_args s;
+        s.struct_size = (int32_t)sizeof(s); s.n_frames = 1; s.order = LCD_SELECT_KEEP_ORDER; s.max_features = _maxFeatures;
+        s.grid_rows = _gridRows < 1 ? 1 : _gridRows; s.grid_cols = _gridCols < 1 ? 1 : _gridCols; s.aux_bytes = 0; s.reserved = 0;
+        s.offsets = offsets; s.image_size = size; s.response = responses.data(); s.points = grid ? points.data() : 0;
+        s.rows = descriptors.data.data(); s.aux = 0; s.out_count = &count; s.out_index = index.data(); s.out_rows = selected.data(); s.out_aux = 0;
+        if (lcd_select_features(eng, &s) != LCD_OK) { _selectError = lcd_last_error(eng); return 0; }
+        rawIndex.assign(index.begin(), index.begin() + count);
+        forQuantization = Mat(count, descriptors.cols, descriptors.type(), selected.data());
+    } else {
+        std::vector<bool> inliers;
+        if (!FeatureSelect::limitKeypoints(responses.data(), grid ? points.data() : 0, rows, _maxFeatures, imageWidth, imageHeight,
+                                           _gridRows < 1 ? 1 : _gridRows, _gridCols < 1 ? 1 : _gridCols, inliers)) {
+            _selectError = "limitKeypoints: a NaN response, a keypoint outside the grid or an image not larger than the grid";
+            return 0;
+        }
+        for (int k = 0; k < rows; ++k) if (inliers[(size_t)k]) rawIndex.push_back(k);
+        forQuantization = Mat((int)rawIndex.size(), descriptors.cols, descriptors.type());
+        for (size_t j = 0; j < rawIndex.size(); ++j)
+            std::copy(descriptors.ptr(rawIndex[j]), descriptors.ptr(rawIndex[j]) + descriptors.rowBytes(), forQuantization.data.begin() + j * descriptors.rowBytes());
+    }
+    // ---- the frame, as update(descriptors, nQuantized, ..) runs one whose descriptors are not all quantised
+    Stage whole(_vwd, "Memory::update");
+    {
+        Stage st(_vwd, "Memory::preUpdate");
+        this->preUpdate();
+        _stats["TimingMem/Pre_update/ms"] = st.ms();
+    }
+    Stage quant(_vwd, "VWDictionary::addNewWords");
+    const int id = ++_idCount;
+    _likeSig = 0;
+    std::list<int> wordIds;
+    if (!this->quantizeSelected(forQuantization, &rawIndex, rows, id, wordIds)) return 0;
+    _stats["TimingMem/Add_new_words/ms"] = quant.ms();
     _stats["Keypoint/Current_frame/words"] = (float)wordIds.size();
     _stats["Keypoint/Dictionary_size/words"] = (float)_vwd->getVisualWords().size();
     _stats["Keypoint/Indexed_words/words"] = (float)_vwd->getIndexedWordsCount();

@@ -30,6 +30,18 @@ public:
     // Memory::update -> createSignature: quantise rows [0, nQuantized) of `descriptors` (all if < 0); returns the new
     // signature id, wordIds receives one id per descriptor (unquantised ones -1,-2,..)
     int update(const Mat& descriptors, int nQuantized, std::vector<int>& wordIds);
+    // The same with the reference's own selection (Memory.cpp:5951-6049) instead of a prefix: Kp/MaxFeatures (500), Kp/GridRows and Kp/GridCols
+    // (1) of the ParametersMap decide, by Feature2D::limitKeypoints' inlier mask, which descriptors are quantised -- ONE lcd_select_features call
+    // in front of the frame -- and the ids go back onto all features, the others numbered -1, -2, ..., with ONE lcd_expand_word_ids call behind
+    // it (without an engine: FeatureSelect's host code).  responses: one per descriptor (cv::KeyPoint::response); points: x, y per descriptor
+    // (needed with a grid above 1 x 1, like the image size, which is the caller's pick among the camera models, :5958-5992).  Returns the
+    // signature id, 0 when the selection is refused (lastSelectError(): a NaN response, a keypoint outside the grid, sizes that do not match).
+    int update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
+               std::vector<int>& wordIds);
+    int getMaxFeatures() const { return _maxFeatures; }
+    int getGridRows() const { return _gridRows; }
+    int getGridCols() const { return _gridCols; }
+    const std::string& lastSelectError() const { return _selectError; }
     // a signature given directly by its word ids (database replay, Memory.cpp:447-480)
     int addSignature(const std::vector<int>& wordIds, int id = 0);
     // Memory::loadDataFromDb (Memory.cpp:392-480) from a RTAB-Map database file: the nodes of the last saved state (or all of them) become
@@ -118,6 +130,10 @@ private:
     void addSignatureToStm(int id);
     std::set<int> _stMem, _workingMem;
     int _maxStMemSize;                              // Mem/STMSize (Parameters.h: 10)
+    int _maxFeatures, _gridRows, _gridCols;         // Kp/MaxFeatures (500), Kp/GridRows (1), Kp/GridCols (1)
+    std::string _selectError;
+    // quantises `forQuantization` as signature `id` the call-by-call way; rawIndex (may be NULL): its rows' places among the `rows` features
+    bool quantizeSelected(const Mat& forQuantization, const std::vector<int>* rawIndex, int rows, int id, std::list<int>& wordIds);
     std::map<int, std::map<int, LinkType> > _links; // Signature::getLinks(): id -> (other id -> type)
     // the likelihood update() brought back with the frame: by device slot, for signature _likeSig (0: none / stale)
     bool _deviceFrames;

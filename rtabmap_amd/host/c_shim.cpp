@@ -6,6 +6,7 @@
 
 #include "BayesFilterHip.h"
 #include "DbLoaderHip.h"
+#include "FeatureSelect.h"
 #include "MemoryHip.h"
 #include "RtabmapHip.h"
 
@@ -140,6 +141,46 @@ void* hmem_create_stm(int strategy, int incremental, float nndr, int together, c
     ParametersMap p = make_params(strategy, incremental, nndr, together, dictPath);
     p["Mem/STMSize"] = std::to_string(stmSize);
     return new MemoryHip(p, device);
+}
+// a memory that selects its own features: Kp/MaxFeatures, Kp/GridRows, Kp/GridCols (MemoryHip::update with responses and points)
+void* hmem_create_select(int strategy, int incremental, float nndr, int together, int device, int stmSize, int maxFeatures, int gridRows, int gridCols) {
+    ParametersMap p = make_params(strategy, incremental, nndr, together, "");
+    p["Mem/STMSize"] = std::to_string(stmSize);
+    p["Kp/MaxFeatures"] = std::to_string(maxFeatures);
+    p["Kp/GridRows"] = std::to_string(gridRows);
+    p["Kp/GridCols"] = std::to_string(gridCols);
+    return new MemoryHip(p, device);
+}
+// responses[rows], points[2 rows] (may be NULL with a 1 x 1 grid); returns the signature id, 0 = refused (hmem_select_error)
+int hmem_update_select(void* h, const void* desc, int rows, int cols, int type, const float* responses, const float* points, int imageWidth,
+                       int imageHeight, int* outIds) {
+    std::vector<int> ids;
+    const int id = ((MemoryHip*)h)->update(make_mat(desc, rows, cols, type), std::vector<float>(responses, responses + rows),
+                                           points ? std::vector<float>(points, points + 2 * (size_t)rows) : std::vector<float>(), imageWidth, imageHeight, ids);
+    for (size_t i = 0; i < ids.size(); ++i) outIds[i] = ids[i];
+    return id;
+}
+const char* hmem_select_error(void* h) { return ((MemoryHip*)h)->lastSelectError().c_str(); }
+// FeatureSelect's three functions (no engine involved).  1 = done, 0 = refused
+int hfs_limit_keypoints(const float* response, const float* points, int n, int maxKeypoints, int imageWidth, int imageHeight, int gridRows, int gridCols,
+                        unsigned char* outInliers) {
+    std::vector<bool> inliers;
+    if (!FeatureSelect::limitKeypoints(response, points, n, maxKeypoints, imageWidth, imageHeight, gridRows, gridCols, inliers)) return 0;
+    for (size_t i = 0; i < inliers.size(); ++i) outInliers[i] = inliers[i] ? 1 : 0;
+    return 1;
+}
+// returns the number of indices written to outKept[n], -1 = refused
+int hfs_limit_keypoints_compact(const float* response, int n, int maxKeypoints, int* outKept) {
+    std::vector<int> kept;
+    if (!FeatureSelect::limitKeypoints(response, n, maxKeypoints, kept)) return -1;
+    std::copy(kept.begin(), kept.end(), outKept);
+    return (int)kept.size();
+}
+int hfs_expand_word_ids(int n, const int* index, const int* wordIds, int count, int firstNewWordId, int* out) {
+    std::vector<int> all;
+    if (!FeatureSelect::expandWordIds(n, index, wordIds, count, firstNewWordId, all)) return 0;
+    std::copy(all.begin(), all.end(), out);
+    return 1;
 }
 void hmem_destroy(void* h) { delete (MemoryHip*)h; }
 void* hmem_vwd(void* h) { return ((MemoryHip*)h)->getVWDictionary(); }

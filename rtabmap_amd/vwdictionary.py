@@ -61,6 +61,14 @@ def lib():
         L.hmem_create.argtypes = [ci, ci, cf, ci, C.c_char_p, ci]
         L.hmem_create_stm.restype = vp
         L.hmem_create_stm.argtypes = [ci, ci, cf, ci, C.c_char_p, ci, ci]
+        L.hmem_create_select.restype = vp
+        L.hmem_create_select.argtypes = [ci, ci, cf, ci, ci, ci, ci, ci, ci]
+        L.hmem_update_select.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp]
+        L.hmem_select_error.argtypes = [vp]
+        L.hmem_select_error.restype = C.c_char_p
+        L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
+        L.hfs_limit_keypoints_compact.argtypes = [vp, ci, ci, vp]
+        L.hfs_expand_word_ids.argtypes = [ci, vp, vp, ci, ci, vp]
         L.hmem_time_loop.argtypes = [vp, vp, ci, ci, ci, ci, ci]
         L.hmem_time_loop.restype = C.c_double
         L.hmem_time_loop_modes.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -115,6 +123,38 @@ def lib():
         L.hmem_load_error.restype = C.c_char_p
         _lib = L
     return _lib
+
+
+# ---- FeatureSelect (rtabmap_amd/host/FeatureSelect.h): the selection and expansion rule of include/lcd.h as plain host code, no engine
+def limit_keypoints(response, points=None, max_keypoints=0, image_size=(0, 0), grid_rows=1, grid_cols=1):
+    """Feature2D::limitKeypoints' inlier mask -> bool array, or None where the host mirror refuses (NaN response, keypoint outside the grid,
+    image not larger than the grid)."""
+    r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
+    p = None if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    if p is not None and p.shape[0] != r.shape[0]:
+        raise ValueError("limit_keypoints: one point per response")
+    out = np.zeros(max(r.shape[0], 1), np.uint8)
+    ok = lib().hfs_limit_keypoints(_p(r), _p(p), r.shape[0], int(max_keypoints), int(image_size[0]), int(image_size[1]), int(grid_rows), int(grid_cols), _p(out))
+    return out[:r.shape[0]].astype(bool) if ok else None
+
+
+def limit_keypoints_compact(response, max_keypoints=0):
+    """the compacting form -> the kept indices in output order, or None on a NaN response"""
+    r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
+    out = np.zeros(max(r.shape[0], 1), np.int32)
+    n = lib().hfs_limit_keypoints_compact(_p(r), r.shape[0], int(max_keypoints), _p(out))
+    return None if n < 0 else out[:n].copy()
+
+
+def expand_word_ids(n, index, word_ids, first_new_word_id=0):
+    """Memory.cpp:6029-6059 -> one id per feature, or None on an index outside [0, n)"""
+    i = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+    w = np.ascontiguousarray(word_ids, dtype=np.int32).reshape(-1)
+    if i.shape != w.shape:
+        raise ValueError("expand_word_ids: one id per index")
+    out = np.zeros(max(int(n), 1), np.int32)
+    ok = lib().hfs_expand_word_ids(int(n), _p(i), _p(w), i.shape[0], int(first_new_word_id), _p(out))
+    return out[:int(n)].copy() if ok else None
 
 
 class VWDictionaryHip:
@@ -242,10 +282,16 @@ class VWDictionaryHip:
 
 class MemoryHip:
     def __init__(self, strategy=kNNBruteForceHIP, incremental=True, nndr=0.8, new_words_compared_together=True,
-                 dictionary_path="", device=0, stm_size=10, _handle=None, _owner=None):
+                 dictionary_path="", device=0, stm_size=10, _handle=None, _owner=None, max_features=None, grid_rows=1, grid_cols=1):
         self._owner = _owner                    # a RtabmapHip owns its memory
-        self.h = _handle if _handle is not None else lib().hmem_create_stm(
-            strategy, int(incremental), float(nndr), int(new_words_compared_together), dictionary_path.encode(), device, int(stm_size))
+        if _handle is not None:
+            self.h = _handle
+        elif max_features is not None:          # Kp/MaxFeatures, Kp/GridRows, Kp/GridCols: update_select() honours them
+            self.h = lib().hmem_create_select(strategy, int(incremental), float(nndr), int(new_words_compared_together), device, int(stm_size),
+                                              int(max_features), int(grid_rows), int(grid_cols))
+        else:
+            self.h = lib().hmem_create_stm(
+                strategy, int(incremental), float(nndr), int(new_words_compared_together), dictionary_path.encode(), device, int(stm_size))
         self.vwd = VWDictionaryHip(_handle=lib().hmem_vwd(self.h), _owner=self)
 
     def close(self):
@@ -265,6 +311,22 @@ class MemoryHip:
         out = np.zeros(max(rows, 1), np.int32)
         sid = lib().hmem_update(self.h, _p(desc), rows, desc.shape[1], _type_of(desc), -1 if nq is None else nq, _p(out))
         return sid, out[:rows].tolist()
+
+    def update_select(self, desc, responses, points=None, image_size=(0, 0)):
+        """MemoryHip::update with the reference's own selection (Kp/MaxFeatures, Kp/GridRows, Kp/GridCols) -> (signature id, one id per
+        descriptor); id 0: refused (select_error())"""
+        desc = np.ascontiguousarray(desc)
+        rows = desc.shape[0]
+        r = np.ascontiguousarray(responses, dtype=np.float32).reshape(-1)
+        p = None if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        if r.shape[0] != rows or (p is not None and p.shape[0] != rows):
+            raise ValueError("update_select: one response (and one point) per descriptor")
+        out = np.zeros(max(rows, 1), np.int32)
+        sid = lib().hmem_update_select(self.h, _p(desc), rows, desc.shape[1], _type_of(desc), _p(r), _p(p), int(image_size[0]), int(image_size[1]), _p(out))
+        return sid, out[:rows].tolist()
+
+    def select_error(self):
+        return lib().hmem_select_error(self.h).decode()
 
     def add_signature(self, word_ids, sig_id=0):
         a = np.ascontiguousarray(word_ids, dtype=np.int32)
