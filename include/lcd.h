@@ -512,7 +512,8 @@ int lcd_adjust_likelihood_dev(lcd_engine* h, float* d_likelihood, int n, float v
  * against every live signature -> optionally Rtabmap::adjustLikelihood (Rtabmap.cpp:5691) and the best candidate.
  * New words are NOT added to the vocabulary here (that is VWDictionary::update() of the next frame: lcd_vocab_append). */
 typedef struct lcd_hypothesis {
-    int32_t sig_id;            /* signature with the highest likelihood among the considered ones (0: none is positive) */
+    int32_t sig_id;            /* signature with the highest likelihood among the considered ones (0: none is positive);
+                                  of equal likelihoods the one in the higher slot */
     int32_t slot;              /* its slot (-1: none) */
     float likelihood;          /* its raw likelihood */
     float adjusted;            /* its value after adjustLikelihood (1.0 when it is not above mean + stddev) */
