@@ -427,7 +427,7 @@ __device__ __forceinline__ void knn_bf16_filter_body(float* s_dyn, int bid, cons
 // only the strip (8 tiles + augmentation entries = 66 KB) and TWO workgroups share a compute unit.
 constexpr size_t BF_LDS_BYTES_Q = (size_t)MF_STRIP_TILES * BF_TILE_F * 4 + (size_t)MF_STRIP_TILES * 64 * 4;
 
-__device__ __forceinline__ void qsplit_item(const QSplitArgs& qs, int t, const float4& a, const float4& b) {
+__device__ __forceinline__ void qsplit_item(const QSplitArgs& qs, int t, const float4& a, const float4& b, uint32_t nm_seen) {
     const int qi = t >> 3, h = (t >> 2) & 1, sx = t & 3;
     uint4 hi, lo;
     op_split2_rt(qs.f16, -2.0f * a.x, -2.0f * a.y, hi.x, lo.x);
@@ -457,11 +457,12 @@ __device__ __forceinline__ void qsplit_item(const QSplitArgs& qs, int t, const f
             if (t == 0) { qs.shadow_norm[2 * (size_t)qs.qpad] = __int_as_float(0x7f800000); qs.shadow_norm[2 * (size_t)qs.qpad + 1] = 1.0f; }   // the sentinel
         }
         // the filter's error bound is made from the largest |row|^2 the filter may have multiplied: these rows are among them from the next launch on
-        // (a running maximum: raising it early only widens the bound); one atomic per wave
+        // (a running maximum: raising it early only widens the bound); one atomic per wave that holds something above what the maximum was seen
+        // to be (nm_seen, running_max_seen): the frames of a stream have norms alike, so after the first ones hardly any wave does
         float nm = qi < qs.nq ? part : 0.0f;
 #pragma unroll
         for (int m = 32; m >= 8; m >>= 1) nm = fmaxf(nm, __shfl_xor(nm, m, 64));
-        if (qs.norm_max_bits && (threadIdx.x & 63) == 0 && nm > 0.0f) atomicMax(qs.norm_max_bits, __float_as_uint(nm));
+        if (qs.norm_max_bits && (threadIdx.x & 63) == 0 && nm > 0.0f && __float_as_uint(nm) > nm_seen) atomicMax(qs.norm_max_bits, __float_as_uint(nm));
     }
 }
 // One item = eight floats of one query.  A thread's items are READ first and written afterwards: loads and stores share one in-order
@@ -469,6 +470,7 @@ __device__ __forceinline__ void qsplit_item(const QSplitArgs& qs, int t, const f
 // the eight two-trip workgroups took 17 us, the longest chain of launch A).  Frames of up to 1 024 descriptors get one item per thread.
 __device__ __forceinline__ void qsplit_body(const QSplitArgs& qs, int wg) {
     const int n_items = qs.qpad * 8, stride = qs.n_wgs * (int)blockDim.x;   // (qpad * 8 is a multiple of 64: a wave's lanes take part together)
+    const uint32_t nm_seen = qs.shadow_bf ? running_max_seen(qs.norm_max_bits) : 0u;
     for (int t0 = wg * (int)blockDim.x + (int)threadIdx.x; t0 < n_items; t0 += 2 * stride) {
         const int t1 = t0 + stride;
         const bool two = t1 < n_items;
@@ -476,8 +478,8 @@ __device__ __forceinline__ void qsplit_body(const QSplitArgs& qs, int wg) {
         const float4* s0 = reinterpret_cast<const float4*>(qs.queries + (size_t)min(t0 >> 3, qs.nq - 1) * 64 + 32 * ((t0 >> 2) & 1) + 8 * (t0 & 3));   // padding repeats the last query
         const float4* s1 = reinterpret_cast<const float4*>(qs.queries + (size_t)min(tt >> 3, qs.nq - 1) * 64 + 32 * ((tt >> 2) & 1) + 8 * (tt & 3));
         const float4 a0 = s0[0], b0 = s0[1], a1 = s1[0], b1 = s1[1];
-        qsplit_item(qs, t0, a0, b0);
-        if (two) qsplit_item(qs, t1, a1, b1);
+        qsplit_item(qs, t0, a0, b0, nm_seen);
+        if (two) qsplit_item(qs, t1, a1, b1, nm_seen);
     }
 }
 

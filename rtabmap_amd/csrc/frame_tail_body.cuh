@@ -274,10 +274,18 @@ __device__ __forceinline__ void append_write_ids(const AppendArgs& ap, const WsR
     ap.row_wslot[row] = key;
     if (key >= 0 && ap.wrow) ap.wrow[key] = (uint32_t)row + 1u;         // the key now belongs to a row: the batched check of superseded
 }                                                                       // reservations must not hand it out again
-__device__ __forceinline__ void append_norm_max(const AppendArgs& ap, float norm_max) {
+// A running maximum kept in memory -- the bits of a non-negative float, raised with atomicMax and by nothing else while the kernels that raise it
+// run -- as the scalar cache has it: an older value at worst, never above the current one.  Who holds nothing above it has nothing to add, so the
+// atomic (device scope, every wave of a launch on ONE address) is left to the few that do.  Requested where it is called (the head of a body), waited
+// for at its first use; NULL reads as 0 (everything is above it).
+__device__ __forceinline__ uint32_t running_max_seen(const uint32_t* p) {
+    return p ? *(const __attribute__((address_space(4))) uint32_t*)p : 0u;
+}
+// seen: running_max_seen(ap.norm_max_bits) of the caller's head, or 0 (a single-workgroup chain: the read would be a round trip of its own)
+__device__ __forceinline__ void append_norm_max(const AppendArgs& ap, float norm_max, uint32_t seen = 0u) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) norm_max = fmaxf(norm_max, __shfl_xor(norm_max, m, 64));
-    if ((threadIdx.x & 63) == 0 && norm_max > 0.0f) atomicMax(ap.norm_max_bits, __float_as_uint(norm_max));
+    if ((threadIdx.x & 63) == 0 && norm_max > 0.0f && __float_as_uint(norm_max) > seen) atomicMax(ap.norm_max_bits, __float_as_uint(norm_max));
 }
 
 // Deferred append, first half (the decision loop's workgroup, launch A): which descriptors became words, and how many rows there are now.
@@ -306,6 +314,7 @@ __device__ __forceinline__ void append_publish(const AppendArgs& ap, int q, cons
 template <int NT>
 __device__ __forceinline__ void append_rows_body(const AppendRowsArgs& A, int wg, float* stage, int stage_rows) {
     const AppendArgs& ap = A.ap;
+    const uint32_t nm_seen = ap.is_f32_64 ? running_max_seen(ap.norm_max_bits) : 0u;
     const int n_in = ap.cnt_in[0], n_new = ap.log_slot[0];
     const int per = (n_new + A.n_wgs - 1) / A.n_wgs;
     const int k_lo = min(wg * per, n_new), k_hi = min(k_lo + per, n_new);
@@ -339,7 +348,7 @@ __device__ __forceinline__ void append_rows_body(const AppendRowsArgs& A, int wg
             if (c == 0) append_write_ids(ap, A.new_ws, row, k);
         }
     }
-    if (ap.is_f32_64) append_norm_max(ap, norm_max);
+    if (ap.is_f32_64) append_norm_max(ap, norm_max, nm_seen);
     // (AppendArgs::mirror_later: the decision loop left the pinned mirror to this launch)
     if (ap.mirror_later && ap.host_mirror && wg == 0 && threadIdx.x == 0)
         __hip_atomic_store(ap.host_mirror, ((unsigned long long)ap.tag << 32) | (unsigned long long)(uint32_t)(n_in + n_new), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

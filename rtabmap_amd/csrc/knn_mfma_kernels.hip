@@ -563,9 +563,16 @@ __global__ __launch_bounds__(PIPE_BLOCK) void frame_a_kernel_p(FilterArgs f, int
 }
 #ifdef LCD_B_TIMING   // timing experiment only: start / end of every workgroup of launch B (100 MHz)
 __device__ unsigned long long g_b_timing[2 * 4096];
+__device__ unsigned g_b_role[4096];                                    // 0 re-rank, 1 row writer, 2 sealed bucket, 3 open bucket (tools/launch_b_tail.py)
+#define B_ROLE(r) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_b_role[blockIdx.x] = (r); } while (0)
+#ifdef LCD_RR_ACKSTAMP   // the end stamp waits for every wave's requests to be acknowledged (rerank_body.cuh)
+#define B_STAMP(i) do { if (i) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); if (threadIdx.x == 0 && blockIdx.x < 4096) g_b_timing[2 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
 #define B_STAMP(i) do { __builtin_amdgcn_s_barrier(); if (threadIdx.x == 0 && blockIdx.x < 4096) g_b_timing[2 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#endif
 #else
 #define B_STAMP(i) do { } while (0)
+#define B_ROLE(r) do { } while (0)
 #endif
 constexpr int PIPE_B_BLOCK = 512;   // workgroup size of launch B: eight waves per sealed bucket, two queries per re-rank workgroup
 constexpr uint32_t PIPE_B_STAGE_ROWS = 160;   // pending rows a re-rank workgroup stages in LDS at a time
@@ -592,6 +599,7 @@ __global__ __launch_bounds__(PIPE_B_BLOCK, 6) void frame_b_kernel(RerankArgs k, 
         return;
     }
     if (bid < n_rerank_wgs || rows_only) {                               // (a multiple of 8: see launch_frame_b)
+        B_ROLE(rows_only ? 1u : 0u);
         // consecutive query pairs on one XCD: eight queries share a 128-byte line of the block-major candidate records
         const int pair = rows_only ? 0 : (bid & 7) * (n_rerank_wgs >> 3) + (bid >> 3);
         if (2 * pair >= k.nq) return;
@@ -606,6 +614,7 @@ __global__ __launch_bounds__(PIPE_B_BLOCK, 6) void frame_b_kernel(RerankArgs k, 
         return;
     }
     const int g = bid - n_rerank_wgs;
+    B_ROLE(g < A.n_closed_pad ? 2u : 3u);
     if (g < A.n_closed_pad) {                                            // consecutive buckets on one XCD: they share directory lines
         const int b = (g & 7) * (A.n_closed_pad >> 3) + (g >> 3);
         if (b < A.n_closed) score_sealed_body<PIPE_B_BLOCK>(A, b);
@@ -665,6 +674,14 @@ extern "C" int lcd_debug_a_timing(unsigned long long* out, int n_words) {
 extern "C" int lcd_debug_rr_timing(unsigned long long* out, int n_words) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(lcd::g_rr_timing), (size_t)n_words * 8);
+}
+extern "C" int lcd_debug_rr_tail(unsigned long long* out, int n_words) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(lcd::g_rr_tail), (size_t)n_words * 8);
+}
+extern "C" int lcd_debug_b_role(unsigned* out, int n_words) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(lcd::g_b_role), (size_t)n_words * 4);
 }
 extern "C" int lcd_debug_b_timing(unsigned long long* out, int n_words) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;

@@ -50,8 +50,22 @@ constexpr int RR_MAX_CAND = 128;
 #ifdef LCD_B_TIMING   // timing experiment only: phases of the re-rank workgroups of launch B (100 MHz), without extra barriers
 __device__ unsigned long long g_rr_timing[8 * 512];
 #define RR_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 512) g_rr_timing[8 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+// the tail behind the barrier, per workgroup (tools/launch_b_tail.py): [0] bit row and list stored, [1] candidate rows, [2] list entries, [3] XCD.
+// LCD_RR_ACKSTAMP: the stamps behind stores (7, tail 0, the end of the workgroup) first wait for every request of their wave to be acknowledged --
+// what a phase COSTS in round trips, where the plain stamps say when its stores were issued
+__device__ unsigned long long g_rr_tail[4 * 512];
+#define RR_TAIL(i, v) do { if (threadIdx.x == 0 && blockIdx.x < 512) g_rr_tail[4 * blockIdx.x + (i)] = (v); } while (0)
+#define RR_XCD() ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (3 << 11)))   /* hardware register XCC_ID, bits [3:0] */
+#ifdef LCD_RR_ACKSTAMP
+#define RR_ACK() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#else
+#define RR_ACK() do { } while (0)
+#endif
 #else
 #define RR_STAMP(i) do { } while (0)
+#define RR_TAIL(i, v) do { } while (0)
+#define RR_XCD() 0ull
+#define RR_ACK() do { } while (0)
 #endif
 // the reference's term of four floats (dist.h:158-166): ((d0 d0 + d1 d1) + d2 d2) + d3 d3, every difference, product and sum rounded on its own
 __device__ __forceinline__ float l2_term4(const float4& v, const float4& q) {
@@ -129,9 +143,20 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     constexpr int NT = HALVES * MF_BLOCK;                              // threads of the workgroup
     // (both counters through the scalar cache, requested together: as two vector loads the compiler made each uniform right behind its request --
     // two round trips in a row at the head of every re-rank workgroup, round 6's ISA)
+    // err_seen: fail_count[2], the running maximum of the error ratio, as some earlier moment saw it (the scalar cache may hold an older line).  It only
+    // ever rises, so a stale value is never above the current one: a query whose ratio does not exceed it has nothing to add, and only the others
+    // issue the atomic -- a handful in the first frames of a stream, then almost none (it was one device-scope atomic per query, ~500 per launch on
+    // one address, in front of the result stores in the one in-order counter)
     int n_lo0 = 0, p_hi_ld = 0;
-    if (pend_lo && pend_hi) asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(n_lo0), "=&s"(p_hi_ld) : "s"(pend_lo), "s"(pend_hi) : "memory");
-    else { if (pend_lo) n_lo0 = pend_lo[0]; if (pend_hi) p_hi_ld = pend_hi[0]; }
+    uint32_t err_seen = 0u;
+    if (pend_lo && pend_hi)
+        asm volatile("s_load_dword %0, %3, 0x0\n\ts_load_dword %1, %4, 0x0\n\ts_load_dword %2, %5, 0x8\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(n_lo0), "=&s"(p_hi_ld), "=&s"(err_seen) : "s"(pend_lo), "s"(pend_hi), "s"(fail_count) : "memory");
+    else {
+        if (pend_lo) n_lo0 = pend_lo[0];
+        if (pend_hi) p_hi_ld = pend_hi[0];
+        asm volatile("s_load_dword %0, %1, 0x8\n\ts_waitcnt lgkmcnt(0)" : "=s"(err_seen) : "s"(fail_count) : "memory");
+    }
     const int p_lo = pend_lo ? min(n_lo0, pend_cap) : 0, p_hi = p_hi_ld;
     const int32_t pend_id0 = pend_first_id > 0 ? pend_first_id : n_lo0 - pend_first_id;   // word id of the first pending row
     // with shadow rows the pending scan only has to cover vocabulary rows the filter's plan did not reach ([p_lo, n_lo0): rare)
@@ -216,6 +241,7 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     // ---- rows-only exit: a writer workgroup of the re-rank role stages its rows (wr_index + wr_n m, m < n_mine) and writes them
     if (rows_only) {                                                 // (uniform over the workgroup)
         const int n_new = p_hi - n_lo0;
+        const uint32_t nm_seen = running_max_seen(wr.ap.norm_max_bits);   // (frame_tail_body.cuh: sixteen writers x eight waves would each raise it)
         s_plist[threadIdx.x] = pend_list[threadIdx.x];
         lds_barrier();
         const int wv = (int)threadIdx.x >> 6, ln = (int)threadIdx.x & 63;       // (wave of the WORKGROUP: both halves stage rows together)
@@ -228,6 +254,7 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
                 stage_four_rows(stage, i, ln, n_chunk, [&](int rl) -> const float* { return pend_desc + (size_t)plist_at(wr_index + wr_n * (m0 + rl)) * DIM; });
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
+            if (m0 == 0) { RR_STAMP(6); RR_TAIL(3, RR_XCD()); }
             {   // write_rows(own = true) over this chunk, staged row m being new word wr_index + wr_n (m0 + m).  A copy, not a call: as a call with a
                 // first-row argument it costs frame_b_kernel<false> two more s_waitcnt (profiles/refactor_rerank_body_isa.txt)
                 const AppendArgs& ap = wr.ap;
@@ -245,10 +272,12 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
                         if (key >= 0 && ap.wrow) ap.wrow[key] = (uint32_t)row + 1u;
                     }
                 }
-                append_norm_max(ap, nmax);
+                append_norm_max(ap, nmax, nm_seen);
             }
         }
         store_mirror();
+        RR_ACK();
+        RR_STAMP(7);
         return;
     }
     const bool valid = qi_first + hf < nq;                           // the odd query out: its half walks the last query again, writes nothing
@@ -524,9 +553,11 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     RR_STAMP(6);
     asm volatile("" : "+v"(dreg0), "+v"(dreg1));                       // (requested at the top, long since here: no wait for them behind the stores below)
 
-    // ---- top-2 and winner slots: the two best (distance, row) keys; ties go to the lower ROW (result_set.h:151-171), so the comparison key carries the row
+    // ---- top-2: the two best (distance, row) keys; ties go to the lower ROW (result_set.h:151-171), so the comparison key carries the row
     uint64_t best = KEY_NONE, second = KEY_NONE;
     int sbest = -1, ssecond = -1;
+    __shared__ int s_below_all[HALVES];                               // (the candidate bits' count of set bits below qi, CandBits::list)
+    int& s_below = s_below_all[hf];
     if (wave == 0) {
         if (!overflow)
             for (int i = lane; i < n_cand; i += 64) {
@@ -542,7 +573,16 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
 #pragma unroll
             for (int wi = 0; wi < MF_WAVES; ++wi) { top2_push(best, second, s_pend[wi][0]); top2_push(best, second, s_pend[wi][1]); }
         }
-        // which candidate slots won (for their word ids; a pending row that won has no slot: -1)
+        // the second neighbour's distance is all the candidate bits need: it is handed over HERE, and the other waves write their part of the bit
+        // row and list while this one looks for the winners' slots, checks the certificate and stores the results (they used to wait for all of that)
+        if (lane == 0) {
+            s_thr = (cb.have_index && second != KEY_NONE) ? __uint_as_float((uint32_t)(second >> 32)) : __int_as_float(0x7f800000);
+            s_below = 0;
+        }
+    }
+    if (cb.bits) lds_barrier();                                        // (uniform; LDS traffic only: no store is outstanding here)
+    // ---- winner slots: which candidate slots won (for their word ids; a pending row that won has no slot: -1)
+    if (wave == 0) {
         if (!overflow)
             for (int i = lane; i < n_cand; i += 64) {
                 if (s_exact[i] == KEY_NONE) continue;
@@ -559,24 +599,22 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
         RR_STAMP(5);
 #endif
     }
-    if (tid == 0) s_thr = (cb.have_index && second != KEY_NONE) ? __uint_as_float((uint32_t)(second >> 32)) : __int_as_float(0x7f800000);
 
-    // ---- results and certificate.  The tail of the chain: thread 0 writes the query's results.  Everything that READS memory comes first -- the
-    // word ids of winners that have no candidate slot, the certificate's operands -- and the stores last: the wait counter is one in-order counter
-    // for loads and stores, so a load (or the reload of a spilled register) behind a store waits for the store's acknowledgement, a full round
-    // trip each time (three of them in the first version of this block: 3.6 us of an 8 us chain, measured with in-kernel stamps).
-    if (tid == 0 && valid) {
+    // ---- results and certificate.  The tail of the chain: lane j < 2 of wave 0 holds the query's j-th neighbour (both reductions leave their results
+    // in every lane) and writes it -- one store instruction per result array, and ONE round trip for the word ids of winners that have no candidate
+    // slot.  Everything that READS memory comes first -- those word ids, the certificate's operands -- and the stores last: the wait counter is one
+    // in-order counter for loads and stores, so a load (or the reload of a spilled register) behind a store waits for the store's acknowledgement, a
+    // full round trip each time (three of them in the first version of this block: 3.6 us of an 8 us chain, measured with in-kernel stamps).
+    if (tid < 2 && valid) {
         err_ratio = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
         static_assert(MF_WAVES == 4, "the four waves' partial results");
         bound = min(min(s_bound[0], s_bound[1]), min(s_bound[2], s_bound[3]));
-        const uint64_t win[2] = {best, second};
-        const int sl[2] = {sbest, ssecond};
-        int32_t wout[2] = {0, 0};
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (win[j] == KEY_NONE) continue;
-            const int32_t rw = (int32_t)(uint32_t)win[j];
-            wout[j] = sl[j] >= 0 ? s_word[sl[j]] : ((pend_list && rw >= n_lo0) ? pend_id0 + (rw - n_lo0) : row_id[rw]);
+        const uint64_t win = tid == 0 ? best : second;
+        const int sl = tid == 0 ? sbest : ssecond;
+        int32_t wout = 0;
+        if (win != KEY_NONE) {
+            const int32_t rw = (int32_t)(uint32_t)win;
+            wout = sl >= 0 ? s_word[sl] : ((pend_list && rw >= n_lo0) ? pend_id0 + (rw - n_lo0) : row_id[rw]);
         }
         // certificate: every row the filter dropped is strictly farther than the exact second neighbour
         bool ok = !overflow;
@@ -592,27 +630,22 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
         if (f16 && !(qn < 1.0e8f && vn_max < 1.0e8f)) ok = false;
         const bool report = err_ratio > 0.0f && eps > 0.0f;
         int reject = ok ? 0 : 1;
-        asm volatile("" : "+v"(wout[0]), "+v"(wout[1]), "+v"(reject) :: "memory");   // every load of this thread has arrived: stores only from here
+        asm volatile("" : "+v"(wout), "+v"(reject) :: "memory");   // every load of this thread has arrived: stores only from here
         ok = reject == 0;
-        if (report) atomicMax(reinterpret_cast<uint32_t*>(fail_count) + 2, __float_as_uint(err_ratio));   // fail_count[2]: max |score - distance| / eps (diagnostics)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            out_row[2 * qi + j] = win[j] == KEY_NONE ? -1 : (int32_t)(uint32_t)win[j];
-            out_word[2 * qi + j] = wout[j];
-            out_dist[2 * qi + j] = win[j] == KEY_NONE ? -1.0f : __uint_as_float((uint32_t)(win[j] >> 32));
-        }
-        if (!ok) fail_list[atomicAdd(fail_count, 1)] = qi;
+        if (tid == 0 && report && __float_as_uint(err_ratio) > err_seen)         // fail_count[2]: max |score - distance| / eps (diagnostics; err_seen above)
+            atomicMax(reinterpret_cast<uint32_t*>(fail_count) + 2, __float_as_uint(err_ratio));
+        out_row[2 * qi + tid] = win == KEY_NONE ? -1 : (int32_t)(uint32_t)win;
+        out_word[2 * qi + tid] = wout;
+        out_dist[2 * qi + tid] = win == KEY_NONE ? -1.0f : __uint_as_float((uint32_t)(win >> 32));
+        if (tid == 0 && !ok) fail_list[atomicAdd(fail_count, 1)] = qi;
     }
+    RR_ACK();
     RR_STAMP(7);
 
     // ---- candidate bits: the query's row of the candidate bit matrix (uniform branch)
-    if (cb.bits) {
-        __shared__ int s_below_all[HALVES];                           // + the compact list of the set bits below qi (CandBits::list)
-        int& s_below = s_below_all[hf];
-        if (tid == 0) s_below = 0;
-        // LDS-only barriers from here on: thread 0 has just stored the query's results, and __syncthreads() would hold the whole
-        // workgroup until those stores are acknowledged -- a memory round trip per barrier, twice, at the end of a latency chain
-        lds_barrier();
+    if (cb.bits) {                                                     // + the compact list of the set bits below qi (CandBits::list)
+        // LDS-only barriers from the threshold's hand-over on: wave 0 has just stored the query's results, and __syncthreads() would hold the
+        // whole workgroup until those stores are acknowledged -- a memory round trip at the end of a latency chain
         const float thr2 = s_thr;
         for (int base = wave * 64; base < cb.ld; base += MF_BLOCK) {
             const int r = base + lane;
@@ -629,7 +662,10 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
             lds_barrier();
             if (tid == 0 && valid) cb.cnt[qi] = s_below;
         }
+        RR_TAIL(1, (unsigned long long)n_cand); RR_TAIL(2, (unsigned long long)s_below); RR_TAIL(3, RR_XCD());
     }
+    RR_ACK();
+    RR_TAIL(0, __builtin_amdgcn_s_memrealtime());
 
     // ---- row writes and mirror
     if (n_own > 0 && use_cross) {                                      // (every wave has waited for its requests; the rows came with wave 0's, ...)

@@ -265,6 +265,7 @@ __global__ __launch_bounds__(MF_BLOCK) void knn_wide_rerank_kernel(const uint64_
         }
     }
     const float vn_max = __uint_as_float(norm_max_bits[0]);
+    const uint32_t err_seen = running_max_seen(reinterpret_cast<const uint32_t*>(fail_count) + 2);   // (as knn_mfma_rerank_body: the atomic below is for a ratio above it)
 
     // ---- pass 1: tau and the bound on dropped rows
     uint32_t a0 = INF, a1 = INF, bound = INF;
@@ -361,7 +362,7 @@ __global__ __launch_bounds__(MF_BLOCK) void knn_wide_rerank_kernel(const uint64_
             if (!(err_ratio < 0.5f)) ok = false;
             // fp16 operands hold magnitudes up to 65504: descriptors far outside that (the filter multiplies -2 q) go to the exact redo
             if (f16 && !(qn < 1.0e8f && vn_max < 1.0e8f)) ok = false;
-            if (err_ratio > 0.0f && eps > 0.0f && err_ratio < __int_as_float(0x7f800000))
+            if (err_ratio > 0.0f && eps > 0.0f && err_ratio < __int_as_float(0x7f800000) && __float_as_uint(err_ratio) > err_seen)
                 atomicMax(reinterpret_cast<uint32_t*>(fail_count) + 2, __float_as_uint(err_ratio));   // fail_count[2]: max |score - distance| / eps
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
