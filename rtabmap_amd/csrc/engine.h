@@ -16,6 +16,7 @@
 #include "lcd_kernels.h"
 #include "bayes.h"
 #include "tfidf.h"
+#include "stateless_scratch.h"
 
 // Host mirror of the vocabulary's row order (the tie-break contract): key = word id the row was appended with, live = not tombstoned.
 // While the keys are ascending (the usual case: word ids only grow) a word's row is found by binary search; only a vocabulary with
@@ -252,34 +253,6 @@ struct FramePipeline {
     void submit(InFlight&& f) { f.set = next_set(); f.stage = Stage::Filter; inflight.push_back(std::move(f)); frame_seq += 1; }
 };
 
-// Scratch of lcd_match_pairs / lcd_match_pairs_dev (pair_match.hip), lcd_match_guided / lcd_match_guided_dev (guided_match.hip: the job
-// table, the staged rows and results) and lcd_select_features / lcd_expand_word_ids with their _dev forms (feature_select.hip: the same),
-// the calls that neither read nor write engine state and therefore
-// do not complete what a pipelined handle owes: everything they write on the device lives here and nowhere else, so they can be enqueued
-// between the stages of frames in flight.  The buffers only grow, and a growth frees the old allocation after the engine stream has
-// drained (DevBuf::reserve): work of an earlier call that is still enqueued keeps what it reads.  The job tables of a call reach the
-// device through one of two pinned slots; a slot is written again only after the copy that last read it has run (its event).
-struct PairScratch {
-    lcd::DevBuf d_dist;                                 // the distance blocks of one group of pairs (to x from; from x from and to x to when new words are compared)
-    lcd::DevBuf d_small;                                // per pair: the to-rows' 2-NN among the from-words, word ranks, candidate bit rows / the cross-check keys
-    lcd::DevBuf d_table;                                // the group's pair and tile jobs
-    lcd::DevBuf d_ones;                                 // one all-ones candidate bit row (a search without index: every earlier new word is a candidate)
-    bool ones_filled = false;
-    lcd::DevBuf d_in, d_out;                            // host entry: the rows and ids as staged on the device / the results before they go back
-    lcd::PinBuf h_in, h_out;
-    lcd::PinBuf h_table[2];
-    hipEvent_t table_read[2] = {nullptr, nullptr};      // recorded behind the copy out of the slot
-    int next_slot = 0;
-    int64_t budget_bytes = 0;                           // lcd_set_option("pair_match_budget"): distance-block bytes per group (0: built-in, 256 MiB)
-    void release(int64_t* bytes_device) {
-        lcd::DevBuf* all[] = {&d_dist, &d_small, &d_table, &d_ones, &d_in, &d_out};
-        for (lcd::DevBuf* d : all) d->release(bytes_device);
-        h_in.release(); h_out.release();
-        for (int i = 0; i < 2; ++i) { h_table[i].release(); if (table_read[i]) (void)hipEventDestroy(table_read[i]); table_read[i] = nullptr; }
-        ones_filled = false;
-    }
-};
-
 struct lcd_engine {
     int device = 0;
     int dtype = 0;
@@ -353,7 +326,7 @@ struct lcd_engine {
     lcd::Bayes bayes;                                   // Bayes filter over the signature slots (bayes.h)
     lcd::DevBuf d_adj_scratch;                          // adjusted likelihood when the caller wants the posterior but not that vector
     lcd::DevBuf d_hyp_scratch;                          // hypothesis record when the caller only wants the adjusted vector
-    PairScratch pairs;                                  // lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip), lcd_select_features (feature_select.hip)
+    StatelessScratch pairs;                             // lcd_match_pairs, lcd_match_guided, lcd_select_features, lcd_expand_word_ids (stateless_scratch.h)
 
     // ---- inverted index / TF-IDF
     lcd::Tfidf tfidf;

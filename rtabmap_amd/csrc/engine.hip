@@ -87,13 +87,7 @@ int upload_rows(lcd_engine* h, const void* rows, int n, DevBuf& dst) {
     LCD_HIP(h, dreserve(h, dst, std::max<size_t>(bytes, 4)));
     if (n == 0) return LCD_OK;
     LCD_HIP(h, h->h_in.reserve(bytes));
-    const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-    if (src_row == (size_t)h->row_bytes) {
-        std::memcpy(h->h_in.p, rows, bytes);
-    } else {
-        std::memset(h->h_in.p, 0, bytes);
-        for (int i = 0; i < n; ++i) std::memcpy((char*)h->h_in.p + (size_t)i * h->row_bytes, (const char*)rows + (size_t)i * src_row, src_row);
-    }
+    pack_rows(h->h_in.p, rows, n, host_row_bytes(h), (size_t)h->row_bytes);
     LCD_HIP(h, hipMemcpyAsync(dst.p, h->h_in.p, bytes, hipMemcpyHostToDevice, h->stream));
     // the staging buffer is reused by the next call: the copy must have left it
     LCD_HIP(h, hipStreamSynchronize(h->stream));

@@ -29,7 +29,20 @@ static inline hipError_t dreserve(lcd_engine* h, lcd::DevBuf& b, size_t bytes, s
 
 // u8 rows whose `dim` is no multiple of 4 are stored zero-padded (row_bytes > dim): a caller's [q x dim] DEVICE buffer does not have the layout
 // the kernels walk (they stride by row_bytes), so every entry point that takes one refuses such a handle; host rows are padded as they are staged
-static inline bool rows_padded(const lcd_engine* h) { return (size_t)h->row_bytes != (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1); }
+static inline size_t host_row_bytes(const lcd_engine* h) { return (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1); }
+static inline bool rows_padded(const lcd_engine* h) { return (size_t)h->row_bytes != host_row_bytes(h); }
+
+// The body of a stateless entry point and of its _dev form (pair_match.hip, guided_match.hip, feature_select.hip): nothing is drained, the
+// roctx range carries the base name for both
+template <typename Args>
+static inline int stateless_entry(lcd_engine* h, const char* name, int (*call)(lcd_engine*, const Args*, bool), const Args* a, bool on_device) {
+    LCD_TRY
+    LCD_CHECK_HANDLE(h);
+    lcd_engine::Range range__(h, name);
+    LCD_DEV_NODRAIN(h);
+    return call(h, a, on_device);
+    LCD_CATCH(h)
+}
 
 // ---- VWDictionary::update()'s append branch on the device (see engine.h)
 static inline int64_t vocab_cap_rows(const lcd_engine* h) {

@@ -11,7 +11,7 @@
 //     sizes allow, 4-byte copies otherwise.
 //   expand_word_ids_kernel: one workgroup per frame; the resolved ids are scattered into an LDS image of the frame, then a ballot scan over
 //     "has no word" in feature order hands out -1, -2, ...
-// Nothing of the engine is read or written: the job table is PairScratch's (engine.h), as for lcd_match_pairs and lcd_match_guided.
+// Nothing of the engine is read or written: the job table and the host entries' staging are StatelessScratch's (stateless_scratch.h), as for lcd_match_pairs and lcd_match_guided.
 #include "engine_impl.h"
 
 #include <cmath>
@@ -256,7 +256,6 @@ using namespace lcd;
 
 namespace {
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // offsets, the limits every entry shares; *n_max: the largest frame
@@ -273,23 +272,6 @@ int check_frames(lcd_engine* h, const char* who, int32_t n_frames, const int64_t
         if (off[f + 1] - off[f] > MAX_FEATURES) return bad(LCD_ERR_UNSUPPORTED, "more than 16384 features in a frame");
         *n_max = std::max(*n_max, (int)(off[f + 1] - off[f]));
     }
-    return LCD_OK;
-}
-
-// the job table reaches the device through a pinned slot whose last copy has run (PairScratch)
-int upload_jobs(lcd_engine* h, const std::vector<FrameJob>& jobs, const FrameJob** d_jobs) {
-    PairScratch& S = h->pairs;
-    hipStream_t st = h->stream;
-    const size_t job_bytes = jobs.size() * sizeof(FrameJob);
-    LCD_HIP(h, dreserve(h, S.d_table, job_bytes + 64));
-    const int slot = S.next_slot; S.next_slot ^= 1;
-    if (!S.table_read[slot]) LCD_HIP(h, hipEventCreateWithFlags(&S.table_read[slot], hipEventDisableTiming));
-    else LCD_HIP(h, hipEventSynchronize(S.table_read[slot]));
-    LCD_HIP(h, S.h_table[slot].reserve(job_bytes + 64));
-    std::memcpy(S.h_table[slot].p, jobs.data(), job_bytes);
-    LCD_HIP(h, hipMemcpyAsync(S.d_table.p, S.h_table[slot].p, job_bytes, hipMemcpyHostToDevice, st));
-    LCD_HIP(h, hipEventRecord(S.table_read[slot], st));
-    *d_jobs = S.d_table.as<FrameJob>();
     return LCD_OK;
 }
 
@@ -348,7 +330,7 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
                 }
             }
     }
-    PairScratch& S = h->pairs;
+    StatelessScratch& S = h->pairs;
     hipStream_t st = h->stream;
 
     SelectArgs g;
@@ -360,57 +342,34 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
     g.out_count = a->out_count; g.out_index = a->out_index; g.out_rows = a->out_rows; g.out_aux = a->out_aux;
 
     // ---- host entry: everything to the device, results back at the end (one synchronisation)
-    size_t o_count = 0, o_index = 0, o_rows = 0, o_aux = 0, out_bytes = 0;
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
+    int o_rows = 0, o_aux = 0;                                        // copied back by hand: only what each frame selected
     if (!on_device) {
-        const size_t i_resp = 0, i_pts = i_resp + up256((size_t)N * 4), i_rows = i_pts + up256(grid ? (size_t)N * 8 : 0),
-                     i_aux = i_rows + up256(with_rows ? (size_t)N * h->row_bytes : 0), in_bytes = i_aux + up256(with_aux ? (size_t)N * a->aux_bytes : 0);
-        o_count = 0; o_index = o_count + up256((size_t)nf * 4); o_rows = o_index + up256((size_t)N * 4);
-        o_aux = o_rows + up256(with_rows ? (size_t)N * h->row_bytes : 0); out_bytes = o_aux + up256(with_aux ? (size_t)N * a->aux_bytes : 0);
-        LCD_HIP(h, S.h_in.reserve(in_bytes + 256));
-        LCD_HIP(h, S.h_out.reserve(out_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_in, in_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_out, out_bytes + 256));
-        char* hp = S.h_in.as<char>();
-        if (N) std::memcpy(hp + i_resp, a->response, (size_t)N * 4);
-        if (N && grid) std::memcpy(hp + i_pts, a->points, (size_t)N * 8);
-        if (N && with_rows) {
-            const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-            if (src_row == (size_t)h->row_bytes) std::memcpy(hp + i_rows, a->rows, (size_t)N * src_row);
-            else {
-                std::memset(hp + i_rows, 0, (size_t)N * h->row_bytes);
-                for (int64_t i = 0; i < N; ++i) std::memcpy(hp + i_rows + (size_t)i * h->row_bytes, (const char*)a->rows + (size_t)i * src_row, src_row);
-            }
-        }
-        if (N && with_aux) std::memcpy(hp + i_aux, a->aux, (size_t)N * a->aux_bytes);
-        if (in_bytes) LCD_HIP(h, hipMemcpyAsync(S.d_in.p, hp, in_bytes, hipMemcpyHostToDevice, st));
-        const char* dp = S.d_in.as<char>();
-        char* dq = S.d_out.as<char>();
-        g.response = (const float*)(dp + i_resp); g.points = grid ? (const float2*)(dp + i_pts) : nullptr;
-        g.rows = with_rows ? dp + i_rows : nullptr; g.aux = with_aux ? dp + i_aux : nullptr;
-        g.out_count = (int32_t*)(dq + o_count); g.out_index = (int32_t*)(dq + o_index); g.out_rows = dq + o_rows; g.out_aux = dq + o_aux;
+        const size_t aux_bytes = with_aux ? (size_t)N * a->aux_bytes : 0;
+        const int i_resp = stage.add_in(a->response, (size_t)N * 4), i_pts = stage.add_in(a->points, grid ? (size_t)N * 8 : 0);
+        const int i_rows = stage.add_in_rows(a->rows, with_rows ? N : 0), i_aux = stage.add_in(a->aux, aux_bytes);
+        const int o_count = stage.add_out(a->out_count, (size_t)nf * 4), o_index = stage.add_out(a->out_index, (size_t)N * 4);
+        o_rows = stage.add_out(nullptr, with_rows ? (size_t)N * h->row_bytes : 0); o_aux = stage.add_out(nullptr, aux_bytes);
+        LCD_HIP(h, stage.commit(st, &h->bytes_device));
+        g.response = stage.in<float>(i_resp); g.points = grid ? stage.in<float2>(i_pts) : nullptr;
+        g.rows = with_rows ? stage.in<char>(i_rows) : nullptr; g.aux = with_aux ? stage.in<char>(i_aux) : nullptr;
+        g.out_count = stage.out<int32_t>(o_count); g.out_index = stage.out<int32_t>(o_index);
+        g.out_rows = stage.out<char>(o_rows); g.out_aux = stage.out<char>(o_aux);
     }
     g.row_vec = g.rows && g.row_bytes % 16 == 0 && aligned16(g.rows) && aligned16(g.out_rows) ? 16 : 4;
     g.aux_vec = g.aux && g.aux_bytes % 16 == 0 && aligned16(g.aux) && aligned16(g.out_aux) ? 16 : 4;
 
-    if (int rc = upload_jobs(h, jobs, &g.jobs)) return rc;
+    LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(FrameJob)));
     allow_large_lds();
     const int block = n_max > SMALL_FRAME ? BIG_BLOCK : SMALL_BLOCK;
     feature_select_kernel<<<dim3((unsigned)nf), dim3((unsigned)block), select_lds(g.p_max, a->grid_rows * a->grid_cols), st>>>(g);
     LCD_HIP(h, hipGetLastError());
     if (on_device) return LCD_OK;
-    LCD_HIP(h, hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    LCD_HIP(h, hipStreamSynchronize(st));
-    const char* ho = S.h_out.as<char>();
-    std::memcpy(a->out_count, ho + o_count, (size_t)nf * 4);
-    if (N) std::memcpy(a->out_index, ho + o_index, (size_t)N * 4);
+    LCD_HIP(h, stage.finish(st));
     for (int f = 0; f < nf && (with_rows || with_aux); ++f) {          // only what the frame wrote: the rest of its region stays as it was
-        const size_t cnt = (size_t)a->out_count[f], first = (size_t)off[f];
-        if (with_rows) {
-            const size_t dst_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-            if (dst_row == (size_t)h->row_bytes) std::memcpy((char*)a->out_rows + first * dst_row, ho + o_rows + first * dst_row, cnt * dst_row);
-            else for (size_t j = first; j < first + cnt; ++j) std::memcpy((char*)a->out_rows + j * dst_row, ho + o_rows + j * h->row_bytes, dst_row);
-        }
-        if (with_aux) std::memcpy((char*)a->out_aux + first * a->aux_bytes, ho + o_aux + first * a->aux_bytes, cnt * a->aux_bytes);
+        const size_t cnt = (size_t)a->out_count[f], first = (size_t)off[f], host_row = host_row_bytes(h), row = (size_t)h->row_bytes;
+        if (with_rows) unpack_rows((char*)a->out_rows + first * host_row, stage.host_out(o_rows) + first * row, (int64_t)cnt, host_row, row);
+        if (with_aux && cnt) std::memcpy((char*)a->out_aux + first * a->aux_bytes, stage.host_out(o_aux) + first * a->aux_bytes, cnt * a->aux_bytes);
     }
     return LCD_OK;
 }
@@ -435,41 +394,29 @@ int expand_word_ids(lcd_engine* h, const lcd_expand_args* a, bool on_device) {
                 if (a->index[j] < 0 || a->index[j] >= n) return bad(LCD_ERR_INVALID, "an index entry outside its frame");
         }
     if (N == 0) return LCD_OK;
-    PairScratch& S = h->pairs;
+    StatelessScratch& S = h->pairs;
     hipStream_t st = h->stream;
     std::vector<FrameJob> jobs((size_t)nf);
     for (int f = 0; f < nf; ++f) jobs[(size_t)f] = FrameJob{off[f], (int32_t)(off[f + 1] - off[f]), 1, 1, 0};
 
     ExpandArgs g;
     g.count = a->count; g.index = a->index; g.word_ids = a->word_ids; g.first_new_word_id = a->first_new_word_id; g.out_word_ids = a->out_word_ids;
-    size_t out_off = 0;
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
     if (!on_device) {
-        const size_t i_count = 0, i_index = i_count + up256((size_t)nf * 4), i_words = i_index + up256((size_t)N * 4),
-                     i_first = i_words + up256((size_t)N * 4), in_bytes = i_first + up256(a->first_new_word_id ? (size_t)nf * 4 : 0);
-        LCD_HIP(h, S.h_in.reserve(in_bytes + 256));
-        LCD_HIP(h, S.h_out.reserve((size_t)N * 4 + 256));
-        LCD_HIP(h, dreserve(h, S.d_in, in_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_out, (size_t)N * 4 + 256));
-        char* hp = S.h_in.as<char>();
-        std::memcpy(hp + i_count, a->count, (size_t)nf * 4);
-        std::memcpy(hp + i_index, a->index, (size_t)N * 4);
-        std::memcpy(hp + i_words, a->word_ids, (size_t)N * 4);
-        if (a->first_new_word_id) std::memcpy(hp + i_first, a->first_new_word_id, (size_t)nf * 4);
-        LCD_HIP(h, hipMemcpyAsync(S.d_in.p, hp, in_bytes, hipMemcpyHostToDevice, st));
-        const char* dp = S.d_in.as<char>();
-        g.count = (const int32_t*)(dp + i_count); g.index = (const int32_t*)(dp + i_index); g.word_ids = (const int32_t*)(dp + i_words);
-        g.first_new_word_id = a->first_new_word_id ? (const int32_t*)(dp + i_first) : nullptr;
-        g.out_word_ids = (int32_t*)(S.d_out.as<char>() + out_off);
+        const int i_count = stage.add_in(a->count, (size_t)nf * 4), i_index = stage.add_in(a->index, (size_t)N * 4);
+        const int i_words = stage.add_in(a->word_ids, (size_t)N * 4), i_first = stage.add_in(a->first_new_word_id, a->first_new_word_id ? (size_t)nf * 4 : 0);
+        const int o_words = stage.add_out(a->out_word_ids, (size_t)N * 4);
+        LCD_HIP(h, stage.commit(st, &h->bytes_device));
+        g.count = stage.in<int32_t>(i_count); g.index = stage.in<int32_t>(i_index); g.word_ids = stage.in<int32_t>(i_words);
+        g.first_new_word_id = a->first_new_word_id ? stage.in<int32_t>(i_first) : nullptr;
+        g.out_word_ids = stage.out<int32_t>(o_words);
     }
-    if (int rc = upload_jobs(h, jobs, &g.jobs)) return rc;
+    LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(FrameJob)));
     allow_large_lds();
     const int block = n_max > SMALL_FRAME ? BIG_BLOCK : SMALL_BLOCK;
     expand_word_ids_kernel<<<dim3((unsigned)nf), dim3((unsigned)block), expand_lds(n_max), st>>>(g, n_max);
     LCD_HIP(h, hipGetLastError());
-    if (on_device) return LCD_OK;
-    LCD_HIP(h, hipMemcpyAsync(S.h_out.p, S.d_out.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-    LCD_HIP(h, hipStreamSynchronize(st));
-    std::memcpy(a->out_word_ids, S.h_out.p, (size_t)N * 4);
+    if (!on_device) LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 
@@ -477,40 +424,9 @@ int expand_word_ids(lcd_engine* h, const lcd_expand_args* a, bool on_device) {
 
 extern "C" {
 
-int lcd_select_features(lcd_engine* h, const lcd_select_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_select_features");
-    LCD_DEV_NODRAIN(h);
-    return select_features(h, a, false);
-    LCD_CATCH(h)
-}
-
-int lcd_select_features_dev(lcd_engine* h, const lcd_select_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_select_features");
-    LCD_DEV_NODRAIN(h);
-    return select_features(h, a, true);
-    LCD_CATCH(h)
-}
-
-int lcd_expand_word_ids(lcd_engine* h, const lcd_expand_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_expand_word_ids");
-    LCD_DEV_NODRAIN(h);
-    return expand_word_ids(h, a, false);
-    LCD_CATCH(h)
-}
-
-int lcd_expand_word_ids_dev(lcd_engine* h, const lcd_expand_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_expand_word_ids");
-    LCD_DEV_NODRAIN(h);
-    return expand_word_ids(h, a, true);
-    LCD_CATCH(h)
-}
+int lcd_select_features(lcd_engine* h, const lcd_select_args* a) { return stateless_entry(h, "lcd_select_features", select_features, a, false); }
+int lcd_select_features_dev(lcd_engine* h, const lcd_select_args* a) { return stateless_entry(h, "lcd_select_features", select_features, a, true); }
+int lcd_expand_word_ids(lcd_engine* h, const lcd_expand_args* a) { return stateless_entry(h, "lcd_expand_word_ids", expand_word_ids, a, false); }
+int lcd_expand_word_ids_dev(lcd_engine* h, const lcd_expand_args* a) { return stateless_entry(h, "lcd_expand_word_ids", expand_word_ids, a, true); }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 //     smallest keys (distance bits << 32 | target index: the lowest index wins ties, top2_keys.cuh).  A wave reduction ends the query.
 //   the first-come rule (projected-to-frame): out_to_owner is filled with 0xFF bytes in front of the launch and every decision is an
 //     unsigned 32-bit atomicMin of the corner index on its to-row: a row nobody chose still reads -1.
-// Nothing of the engine is read or written: job tables and staged rows are PairScratch's (engine.h), as for lcd_match_pairs.
+// Nothing of the engine is read or written: job tables and staged rows are StatelessScratch's (stateless_scratch.h), as for lcd_match_pairs.
 #include "engine_impl.h"
 #include "dist_ref.cuh"
 #include "top2_keys.cuh"
@@ -211,16 +211,6 @@ using namespace lcd;
 
 namespace {
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// host rows (h->dim columns) laid out with h->row_bytes per row (u8 rows zero-padded), as upload_rows does
-void stage_rows(const lcd_engine* h, char* dst, const void* rows, int64_t n) {
-    const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-    if (src_row == (size_t)h->row_bytes) { std::memcpy(dst, rows, (size_t)n * src_row); return; }
-    std::memset(dst, 0, (size_t)n * h->row_bytes);
-    for (int64_t i = 0; i < n; ++i) std::memcpy(dst + (size_t)i * h->row_bytes, (const char*)rows + (size_t)i * src_row, src_row);
-}
-
 int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
     const char* who = on_device ? "lcd_match_guided_dev" : "lcd_match_guided";
     auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
@@ -256,7 +246,7 @@ int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
                 if (a->corner_from_row[c] < 0 || a->corner_from_row[c] >= nf) return bad(LCD_ERR_INVALID, "corner_from_row outside the pair's from-rows");
         }
     if (nquery == 0 && !(p2f && nto > 0)) return LCD_OK;
-    PairScratch& S = h->pairs;
+    StatelessScratch& S = h->pairs;
     hipStream_t st = h->stream;
 
     GuidedArgs g;
@@ -267,30 +257,21 @@ int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
     g.out_count = a->out_count; g.out_match = a->out_match; g.out_dist = a->out_dist; g.out_to_owner = (uint32_t*)a->out_to_owner;
 
     // ---- host entry: rows, points and corners to the device, results back at the end (one synchronisation)
-    size_t o_count = 0, o_match = 0, o_dist = 0, o_owner = 0, out_bytes = 0;
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
     if (!on_device) {
-        const size_t i_from = 0, i_to = i_from + up256((size_t)nfrom * h->row_bytes), i_cor = i_to + up256((size_t)nto * h->row_bytes),
-                     i_cfr = i_cor + up256((size_t)ncor * 8), i_pts = i_cfr + up256((size_t)ncor * 4), in_bytes = i_pts + up256((size_t)nto * 8);
-        o_count = 0; o_match = o_count + up256((size_t)nquery * 4); o_dist = o_match + up256((size_t)nquery * 4);
-        o_owner = o_dist + up256((size_t)nquery * 8); out_bytes = o_owner + up256((size_t)nto * 4);
-        LCD_HIP(h, S.h_in.reserve(in_bytes + 256));
-        LCD_HIP(h, S.h_out.reserve(out_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_in, in_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_out, out_bytes + 256));
-        char* hp = S.h_in.as<char>();
-        if (nfrom) stage_rows(h, hp + i_from, a->from, nfrom);
-        if (nto) { stage_rows(h, hp + i_to, a->to, nto); std::memcpy(hp + i_pts, a->to_points, (size_t)nto * 8); }
-        if (ncor) { std::memcpy(hp + i_cor, a->corners, (size_t)ncor * 8); std::memcpy(hp + i_cfr, a->corner_from_row, (size_t)ncor * 4); }
-        if (in_bytes) LCD_HIP(h, hipMemcpyAsync(S.d_in.p, hp, in_bytes, hipMemcpyHostToDevice, st));
-        const char* dp = S.d_in.as<char>();
-        char* dq = S.d_out.as<char>();
-        g.from = dp + i_from; g.to = dp + i_to;
-        g.corners = (const float2*)(dp + i_cor); g.corner_from_row = (const int32_t*)(dp + i_cfr); g.to_points = (const float2*)(dp + i_pts);
-        g.out_count = (int32_t*)(dq + o_count); g.out_match = (int32_t*)(dq + o_match);
-        g.out_dist = a->out_dist ? (float*)(dq + o_dist) : nullptr; g.out_to_owner = (uint32_t*)(dq + o_owner);
+        const int i_from = stage.add_in_rows(a->from, nfrom), i_to = stage.add_in_rows(a->to, nto);
+        const int i_cor = stage.add_in(a->corners, (size_t)ncor * 8), i_cfr = stage.add_in(a->corner_from_row, (size_t)ncor * 4);
+        const int i_pts = stage.add_in(a->to_points, (size_t)nto * 8);
+        const int o_count = stage.add_out(a->out_count, (size_t)nquery * 4), o_match = stage.add_out(a->out_match, (size_t)nquery * 4);
+        const int o_dist = stage.add_out(a->out_dist, (size_t)nquery * 8), o_owner = stage.add_out(p2f ? a->out_to_owner : nullptr, (size_t)nto * 4);
+        LCD_HIP(h, stage.commit(st, &h->bytes_device));
+        g.from = stage.in<char>(i_from); g.to = stage.in<char>(i_to);
+        g.corners = stage.in<float2>(i_cor); g.corner_from_row = stage.in<int32_t>(i_cfr); g.to_points = stage.in<float2>(i_pts);
+        g.out_count = stage.out<int32_t>(o_count); g.out_match = stage.out<int32_t>(o_match);
+        g.out_dist = a->out_dist ? stage.out<float>(o_dist) : nullptr; g.out_to_owner = stage.out<uint32_t>(o_owner);
     }
 
-    // ---- the job table: one entry per pair, through a pinned slot whose last copy has run
+    // ---- the job table: one entry per pair
     std::vector<GuidedJob> jobs((size_t)np);
     int64_t blocks = 0;
     for (int p = 0; p < np; ++p) {
@@ -300,29 +281,11 @@ int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
         J.block_first = (int32_t)blocks;
         blocks += ((p2f ? J.nc : J.nt) + QBLOCK - 1) / QBLOCK;       // at most 65535 x 512
     }
-    const size_t job_bytes = jobs.size() * sizeof(GuidedJob);
-    LCD_HIP(h, dreserve(h, S.d_table, job_bytes + 64));
-    const int slot = S.next_slot; S.next_slot ^= 1;
-    if (!S.table_read[slot]) LCD_HIP(h, hipEventCreateWithFlags(&S.table_read[slot], hipEventDisableTiming));
-    else LCD_HIP(h, hipEventSynchronize(S.table_read[slot]));
-    LCD_HIP(h, S.h_table[slot].reserve(job_bytes + 64));
-    std::memcpy(S.h_table[slot].p, jobs.data(), job_bytes);
-    LCD_HIP(h, hipMemcpyAsync(S.d_table.p, S.h_table[slot].p, job_bytes, hipMemcpyHostToDevice, st));
-    LCD_HIP(h, hipEventRecord(S.table_read[slot], st));
-    g.jobs = S.d_table.as<GuidedJob>();
+    LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(GuidedJob)));
 
     if (p2f && nto > 0) LCD_HIP(h, hipMemsetAsync(g.out_to_owner, 0xFF, (size_t)nto * 4, st));      // -1: nobody's
     LCD_HIP(h, launch_guided(h->dtype, h->kdim, g, blocks, st));
-    if (on_device) return LCD_OK;
-    LCD_HIP(h, hipMemcpyAsync(S.h_out.p, S.d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    LCD_HIP(h, hipStreamSynchronize(st));
-    const char* ho = S.h_out.as<char>();
-    if (nquery) {
-        std::memcpy(a->out_count, ho + o_count, (size_t)nquery * 4);
-        std::memcpy(a->out_match, ho + o_match, (size_t)nquery * 4);
-        if (a->out_dist) std::memcpy(a->out_dist, ho + o_dist, (size_t)nquery * 8);
-    }
-    if (p2f && nto) std::memcpy(a->out_to_owner, ho + o_owner, (size_t)nto * 4);
+    if (!on_device) LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 
@@ -330,22 +293,7 @@ int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
 
 extern "C" {
 
-int lcd_match_guided(lcd_engine* h, const lcd_guided_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_match_guided");
-    LCD_DEV_NODRAIN(h);
-    return match_guided(h, a, false);
-    LCD_CATCH(h)
-}
-
-int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_match_guided");
-    LCD_DEV_NODRAIN(h);
-    return match_guided(h, a, true);
-    LCD_CATCH(h)
-}
+int lcd_match_guided(lcd_engine* h, const lcd_guided_args* a) { return stateless_entry(h, "lcd_match_guided", match_guided, a, false); }
+int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a) { return stateless_entry(h, "lcd_match_guided", match_guided, a, true); }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 //                  and the to-frame's candidate bit rows from its thresholds, (3) the to-frame's decision loop (resolve_body again);
 //     cross-check: the row arg-min with (distance bits << 32 | from-row) keys, a 64-bit atomicMin per from-row over the to-rows that
 //                  chose it with (distance bits << 32 | to-row) keys, then the filter.
-// Nothing of the engine is read or written: the scratch is PairScratch's (engine.h), which is why the call does not drain a pipelined handle.
+// Nothing of the engine is read or written: the scratch is StatelessScratch's (stateless_scratch.h), which is why the call does not drain a pipelined handle.
 #include "engine_impl.h"
 #include "dist_ref.cuh"
 #include "resolve_body.cuh"
@@ -290,17 +290,6 @@ using namespace lcd;
 
 namespace {
 
-struct Staged { size_t from = 0, to = 0, ids = 0, out_a = 0, out_b = 0, in_bytes = 0, out_bytes = 0; };
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// host rows (h->dim columns) laid out with h->row_bytes per row (u8 rows zero-padded), as upload_rows does
-void stage_rows(const lcd_engine* h, char* dst, const void* rows, int64_t n) {
-    const size_t src_row = (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1);
-    if (src_row == (size_t)h->row_bytes) { std::memcpy(dst, rows, (size_t)n * src_row); return; }
-    std::memset(dst, 0, (size_t)n * h->row_bytes);
-    for (int64_t i = 0; i < n; ++i) std::memcpy(dst + (size_t)i * h->row_bytes, (const char*)rows + (size_t)i * src_row, src_row);
-}
-
 int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
     const char* who = on_device ? "lcd_match_pairs_dev" : "lcd_match_pairs";
     auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
@@ -336,37 +325,25 @@ int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
     }
     if (nfrom == 0 && nto == 0) return LCD_OK;
     const bool together = dict && (a->flags & ::LCD_Q_NEW_WORDS_COMPARED);
-    PairScratch& S = h->pairs;
+    StatelessScratch& S = h->pairs;
     hipStream_t st = h->stream;
 
     // ---- host entry: rows and ids to the device, results back at the end (one synchronisation)
     const void* d_from = a->from; const void* d_to = a->to; const int32_t* d_ids = with_ids ? a->from_word_ids : nullptr;
     int32_t* d_out_a = dict ? a->out_from_word_ids : a->out_to_match;      // per from-row (dictionary) / per to-row (cross-check)
     void* d_out_b = dict ? (void*)a->out_to_word_ids : (void*)a->out_to_dist;
-    Staged g;
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
     if (!on_device) {
-        g.from = 0; g.to = up256((size_t)nfrom * h->row_bytes); g.ids = g.to + up256((size_t)nto * h->row_bytes);
-        g.in_bytes = g.ids + (with_ids ? up256((size_t)nfrom * 4) : 0);
-        g.out_a = 0; g.out_b = up256((size_t)(dict ? nfrom : nto) * 4); g.out_bytes = g.out_b + up256((size_t)nto * 4);
-        LCD_HIP(h, S.h_in.reserve(g.in_bytes + 256));
-        LCD_HIP(h, S.h_out.reserve(g.out_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_in, g.in_bytes + 256));
-        LCD_HIP(h, dreserve(h, S.d_out, g.out_bytes + 256));
-        char* hp = S.h_in.as<char>();
-        if (nfrom) stage_rows(h, hp + g.from, a->from, nfrom);
-        if (nto) stage_rows(h, hp + g.to, a->to, nto);
-        if (with_ids) std::memcpy(hp + g.ids, a->from_word_ids, (size_t)nfrom * 4);
-        if (g.in_bytes) LCD_HIP(h, hipMemcpyAsync(S.d_in.p, hp, g.in_bytes, hipMemcpyHostToDevice, st));
-        char* dp = S.d_in.as<char>();
-        d_from = dp + g.from; d_to = dp + g.to; d_ids = with_ids ? (const int32_t*)(dp + g.ids) : nullptr;
-        d_out_a = (int32_t*)(S.d_out.as<char>() + g.out_a);
-        d_out_b = (!dict && !a->out_to_dist) ? nullptr : (void*)(S.d_out.as<char>() + g.out_b);
+        const int i_from = stage.add_in_rows(a->from, nfrom), i_to = stage.add_in_rows(a->to, nto);
+        const int i_ids = stage.add_in(a->from_word_ids, with_ids ? (size_t)nfrom * 4 : 0);
+        const int o_a = stage.add_out(d_out_a, (size_t)(dict ? nfrom : nto) * 4), o_b = stage.add_out(d_out_b, (size_t)nto * 4);
+        LCD_HIP(h, stage.commit(st, &h->bytes_device));
+        d_from = stage.in<char>(i_from); d_to = stage.in<char>(i_to); d_ids = with_ids ? stage.in<int32_t>(i_ids) : nullptr;
+        d_out_a = stage.out<int32_t>(o_a);
+        d_out_b = (!dict && !a->out_to_dist) ? nullptr : stage.out<void>(o_b);
     }
-    if (!S.ones_filled) {
-        LCD_HIP(h, dreserve(h, S.d_ones, MAX_SIDE / 8));
-        LCD_HIP(h, hipMemsetAsync(S.d_ones.p, 0xFF, MAX_SIDE / 8, st));
-        S.ones_filled = true;
-    }
+    MatchArgs m;
+    LCD_HIP(h, S.ones_row(&m.ones, MAX_SIDE / 8, st, &h->bytes_device));
 
     // ---- consecutive groups of pairs whose distance blocks fit the budget (a single pair always does)
     auto dist_floats = [&](int nf, int nt) {
@@ -403,21 +380,10 @@ int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
         const size_t pj_bytes = pj.size() * sizeof(PairJob), tj_bytes = tj.size() * sizeof(TileJob);
         LCD_HIP(h, dreserve(h, S.d_dist, (size_t)std::max<int64_t>(floats, 1) * 4));
         LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(words, 2) * 4));
-        LCD_HIP(h, dreserve(h, S.d_table, pj_bytes + tj_bytes + 64));
-        // the tables through a pinned slot whose last copy has run
-        const int slot = S.next_slot; S.next_slot ^= 1;
-        if (!S.table_read[slot]) LCD_HIP(h, hipEventCreateWithFlags(&S.table_read[slot], hipEventDisableTiming));
-        else LCD_HIP(h, hipEventSynchronize(S.table_read[slot]));
-        LCD_HIP(h, S.h_table[slot].reserve(pj_bytes + tj_bytes + 64));
-        std::memcpy(S.h_table[slot].p, pj.data(), pj_bytes);
-        if (tj_bytes) std::memcpy(S.h_table[slot].as<char>() + pj_bytes, tj.data(), tj_bytes);
-        LCD_HIP(h, hipMemcpyAsync(S.d_table.p, S.h_table[slot].p, pj_bytes + tj_bytes, hipMemcpyHostToDevice, st));
-        LCD_HIP(h, hipEventRecord(S.table_read[slot], st));
-        const PairJob* d_pairs = S.d_table.as<PairJob>();
-        const TileJob* d_tiles = (const TileJob*)(S.d_table.as<char>() + pj_bytes);
+        LCD_HIP(h, S.upload_table(&m.pairs, st, &h->bytes_device, pj.data(), pj_bytes, tj.data(), tj_bytes));
+        const TileJob* d_tiles = (const TileJob*)((const char*)m.pairs + pj_bytes);   // the tile jobs follow the pair jobs
         LCD_HIP(h, launch_pair_dist(h->dtype, h->kdim, d_from, d_to, d_tiles, (int)tj.size(), tiles, S.d_dist.as<float>(), st));
-        MatchArgs m;
-        m.pairs = d_pairs; m.dist = S.d_dist.as<float>(); m.small = S.d_small.as<uint32_t>(); m.ones = S.d_ones.as<uint32_t>();
+        m.dist = S.d_dist.as<float>(); m.small = S.d_small.as<uint32_t>();
         m.mode = a->mode; m.flags = a->flags; m.nndr = a->nndr_ratio; m.from_ids = d_ids;
         m.out_from = dict ? d_out_a : nullptr; m.out_to = dict ? (int32_t*)d_out_b : nullptr;
         m.out_match = dict ? nullptr : d_out_a; m.out_dist = dict ? nullptr : (float*)d_out_b;
@@ -425,17 +391,7 @@ int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
         LCD_HIP(h, hipGetLastError());
         p0 = p;
     }
-    if (on_device) return LCD_OK;
-    LCD_HIP(h, hipMemcpyAsync(S.h_out.p, S.d_out.p, g.out_bytes, hipMemcpyDeviceToHost, st));
-    LCD_HIP(h, hipStreamSynchronize(st));
-    const char* ho = S.h_out.as<char>();
-    if (dict) {
-        if (nfrom) std::memcpy(a->out_from_word_ids, ho + g.out_a, (size_t)nfrom * 4);
-        if (nto) std::memcpy(a->out_to_word_ids, ho + g.out_b, (size_t)nto * 4);
-    } else if (nto) {
-        std::memcpy(a->out_to_match, ho + g.out_a, (size_t)nto * 4);
-        if (a->out_to_dist) std::memcpy(a->out_to_dist, ho + g.out_b, (size_t)nto * 4);
-    }
+    if (!on_device) LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 
@@ -443,22 +399,7 @@ int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
 
 extern "C" {
 
-int lcd_match_pairs(lcd_engine* h, const lcd_match_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_match_pairs");
-    LCD_DEV_NODRAIN(h);
-    return match_pairs(h, a, false);
-    LCD_CATCH(h)
-}
-
-int lcd_match_pairs_dev(lcd_engine* h, const lcd_match_args* a) {
-    LCD_TRY
-    LCD_CHECK_HANDLE(h);
-    lcd_engine::Range range__(h, "lcd_match_pairs");
-    LCD_DEV_NODRAIN(h);
-    return match_pairs(h, a, true);
-    LCD_CATCH(h)
-}
+int lcd_match_pairs(lcd_engine* h, const lcd_match_args* a) { return stateless_entry(h, "lcd_match_pairs", match_pairs, a, false); }
+int lcd_match_pairs_dev(lcd_engine* h, const lcd_match_args* a) { return stateless_entry(h, "lcd_match_pairs", match_pairs, a, true); }
 
 }  // extern "C"
