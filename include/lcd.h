@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -454,7 +454,14 @@ int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a);
  * device entry with rows on a handle whose rows are padded (lcd_config.dim; the host entry serves it): LCD_ERR_UNSUPPORTED; offsets that do not
  * start at 0 or decrease, a NULL pointer where an input or output is needed, an unknown order, a wrong struct_size, a grid dimension < 1,
  * aux_bytes that is negative, above 64 or no multiple of 4: LCD_ERR_INVALID.  n_frames == 0 returns LCD_OK.
- * One kernel launch per call whatever the batch (one workgroup per frame), no private segment. */
+ * One kernel launch per call whatever the batch (one workgroup per frame), no private segment.
+ *
+ * Frame sizes only the device knows (n_in, n_features): behind lcd_keypoints_3d_dev's filter the host knows a frame's REGION, offsets[f] ..
+ * offsets[f+1], and the device knows how many features of it are left.  With n_in the selection's frame f is the first n = clamp(n_in[f], 0,
+ * region) features of its region: the cut decision n > max_features, the order and the counts go by n, the limits above (16384, the
+ * workgroup size) by the region; out_index reads -1 from out_count[f] to the END OF THE REGION.  With n_features the expansion numbers the
+ * first n features of the region and writes 0 behind them, to the end of the region; count[f] is clamped to n.  NULL: exactly the behaviour
+ * without the field.  In the host entries both arrays are host memory.  struct_size is the one sizeof of this header. */
 enum lcd_select_order { LCD_SELECT_KEEP_ORDER = 0, LCD_SELECT_BY_RESPONSE = 1 };
 typedef struct lcd_select_args {
     int32_t struct_size;            /* sizeof(lcd_select_args) */
@@ -474,6 +481,8 @@ typedef struct lcd_select_args {
     int32_t* out_index;             /* [N] */
     void* out_rows;                 /* [N x dim], needed with rows */
     void* out_aux;                  /* [N x aux_bytes], needed with aux */
+    const int32_t* n_in;            /* may be NULL; [n_frames], DEVICE memory for the _dev entry: frame f is the first
+                                       clamp(n_in[f], 0, offsets[f+1] - offsets[f]) features of its region (lcd_keypoints_3d_args.out_count) */
 } lcd_select_args;
 /* every pointer on the HOST; synchronises the engine stream */
 int lcd_select_features(lcd_engine* h, const lcd_select_args* a);
@@ -490,11 +499,113 @@ typedef struct lcd_expand_args {
     const int32_t* word_ids;        /* [N]: frame f's ids at offsets[f], count[f] of them valid, as lcd_quantize / lcd_frame_dev write them */
     const int32_t* first_new_word_id;   /* may be NULL; [n_frames] */
     int32_t* out_word_ids;          /* [N]: one id per feature */
+    const int32_t* n_features;      /* may be NULL; [n_frames], DEVICE memory for the _dev entry: frame f has clamp(n_features[f], 0, its region)
+                                       features (lcd_keypoints_3d_args.out_count) */
 } lcd_expand_args;
 /* every pointer on the HOST; synchronises the engine stream */
 int lcd_expand_word_ids(lcd_engine* h, const lcd_expand_args* a);
 /* count, index, word_ids, first_new_word_id and out_word_ids in DEVICE memory, the offsets on the HOST; enqueued on the engine stream, not synchronised */
 int lcd_expand_word_ids_dev(lcd_engine* h, const lcd_expand_args* a);
+
+/* ---- depth to 3-D keypoints and the depth filter, stateless: the depth stage in front of the selection (Memory.cpp:5683-5694, :5911-5915,
+ * RegistrationVis.cpp:926-969) for a caller whose keypoints and depth image are in device memory.  Feature2D::generateKeypoints3D ->
+ * util3d::generateKeypoints3DDepth (util3d_features.cpp:67-120) looks every keypoint up in the depth image (util2d::getDepth,
+ * util2d.cpp:947-1111) and projects it (util3d::projectDepthTo3D, util3d.cpp:215-244); Feature2D::filterKeypointsByDepth drops the
+ * keypoints without a point in range and compacts keypoints, descriptors and points (3-D overload Features2d.cpp:167-212, 2-D overload
+ * :105-165).  Stateless exactly as lcd_select_features: the calls borrow the handle's dtype, dim, device and stream, read and write nothing
+ * of its state, do not complete what a pipelined handle owes, and keep their job table in the scratch lcd_match_pairs uses.  A call serves
+ * any number of frames: frame f owns the features [offsets[f], offsets[f+1]) of every array and has its own depth image, images[f] (frames
+ * may share one).
+ *
+ * The rule.  All arithmetic is fp32, every operation rounded on its own: no product is fused into a sum anywhere (the reference's x86-64
+ * build has no fused multiply-add), division is IEEE division.  int(v) truncates toward zero.
+ *   Per frame (util3d_features.cpp:79-83): subCols = width / n_cameras (integer), subW = float(subCols);
+ *      factorX = 1.0f / (image_width > 0 ? float(image_width) / subW : 1.0f), factorY = 1.0f / (image_height > 0 ? float(image_height) /
+ *      float(height) : 1.0f), image_width and image_height those of cameras[0].
+ *   Per keypoint (:87-102): x = pt.x * factorX, y = pt.y * factorY, cam = int(x / subW).  The lookup runs in camera cam's SUB-IMAGE, the
+ *      columns [cam * subCols, (cam + 1) * subCols) of the depth image, at the coordinates (x - subW * float(cam), y), with the intrinsics
+ *      cx * factorX, cy * factorY, fx * factorX, fy * factorY of cameras[cam].  cols = subCols and rows = height below.
+ *   getDepth with smoothing = true, depthErrorRatio = 0.02f, estWithNeighborsIfNull = false (util2d.cpp:957-1110):
+ *      u = int(x + 0.5f), v = int(y + 0.5f) -- a coordinate in (-1.5, -0.5) therefore lands on pixel 0 (the reference's behaviour, restated);
+ *      u == cols && x < float(cols) gives u = cols - 1, the same for v and rows; outside [0, cols) x [0, rows) the depth is 0.
+ *      A u16 pixel p is a measurement when it is neither 0 nor 65535, its value float(p) * 0.001f, otherwise 0; an f32 pixel is taken as it is.
+ *      A centre depth of 0 or not finite gives 0.  Otherwise the window [max(u-1, 0), min(u+1, cols-1)] x [max(v-1, 0), min(v+1, rows-1)] --
+ *      clipped to the SUB-IMAGE, never reading across the seam to the next camera -- is visited with uu in the OUTER loop and vv in the inner
+ *      one, the centre left out (this order fixes the float sums).  A neighbour d counts when d != 0, d is finite and
+ *      fabs(d - depth) < 0.02f * depth, strictly; with uu == u or vv == v (an edge neighbour) sumWeights += 2.0f and sumDepths += d * 2.0f,
+ *      otherwise (a corner) sumWeights += 1.0f and sumDepths += d.  depth = (depth * 4.0f + sumDepths) / (sumWeights + 4.0f).
+ *   projectDepthTo3D (util3d.cpp:228-242): depth > 0 is required (a negative f32 depth is a bad point); a cx that is not > 0 is replaced by
+ *      float(cols / 2) - 0.5f, a cy by float(rows / 2) - 0.5f; X = ((x - cx) * depth) / fx, Y = ((y - cy) * depth) / fy, Z = depth.
+ *   Range test, before the local transform (util3d_features.cpp:104-115): the point stands iff X, Y and Z are finite and
+ *      (min_depth < 0 || Z > min_depth) && (max_depth <= 0 || Z <= max_depth); otherwise it is three quiet NaNs (0x7FC00000).  A point that
+ *      stands goes through transformPoint when has_local_transform (util3d_transforms.cpp:211-220, left to right):
+ *      X' = ((t[0] * X + t[1] * Y) + t[2] * Z) + t[3], Y' and Z' with t[4..7] and t[8..11].
+ *   LCD_KP3D_KEEP_ALL: every keypoint is kept: out_count[f] = n, out_index = 0 .. n - 1, out_xyz[i] is keypoint i's point; nothing else is written.
+ *   LCD_KP3D_FILTER_3D (Features2d.cpp:183-191): keep iff the three coordinates are finite and d2 = (X * X + Y * Y) + Z * Z satisfies
+ *      d2 >= min_depth * min_depth && (max_depth * max_depth == 0 || d2 <= max_depth * max_depth).
+ *   LCD_KP3D_FILTER_PIXEL (the 2-D overload the extractors call in front of limitKeypoints, :120-132): u = int(pt.x + 0.5f),
+ *      v = int(pt.y + 0.5f) in the WHOLE image, no factors and no clamp; outside [0, width) x [0, height) the keypoint goes; d = float(p) *
+ *      0.001f for a u16 pixel WITHOUT the 0 / 65535 test, the f32 pixel as it is; keep iff d is finite, d > min_depth and
+ *      (max_depth <= 0 || d < max_depth).  out_xyz may be NULL; where it is given, the kept keypoints' points are computed as above.
+ *   The engine's definitions, where the reference asserts or is undefined: a keypoint for which x + 0.5f, y + 0.5f or x / subW (with
+ *      LCD_KP3D_FILTER_PIXEL also pt.x + 0.5f, pt.y + 0.5f) is not finite or not inside (-2^31, 2^31), or whose cam is outside [0, n_cameras):
+ *      lcd_keypoints_3d returns LCD_ERR_INVALID; lcd_keypoints_3d_dev gives it the bad point, keeps it under no filter and reads no pixel for
+ *      it.  (Without out_xyz, LCD_KP3D_FILTER_PIXEL looks at pt alone.)  min_depth < 0 with a filter, 0 < max_depth <= min_depth, or a NaN
+ *      bound: LCD_ERR_INVALID (the reference's assertions).
+ * Outputs follow the selection's convention: frame f writes the first out_count[f] entries of ITS OWN region of out_index (kept features in
+ * ascending index; the rest of the region reads -1), out_xyz, out_points, out_response, out_rows and out_aux (the rest is unspecified), so
+ * out_count can be lcd_select_args.n_in and the out_* arrays the selection's inputs, nothing read back.  Outputs must not overlap inputs.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: n_frames > 65535, a handle of a sharded vocabulary,
+ * or a device entry with rows on a handle whose rows are padded: LCD_ERR_UNSUPPORTED; offsets that do not start at 0 or decrease, a NULL
+ * pointer where an input or output is needed (out_xyz except with LCD_KP3D_FILTER_PIXEL; with a filter out_points, and out_response, out_rows,
+ * out_aux with their inputs), an image without data, cameras or pixels, width % n_cameras != 0, an unknown type or filter, a pitch below
+ * the row or data / pitch not aligned to the pixel size, a wrong struct_size, aux_bytes that is negative, above 64 or no multiple of 4:
+ * LCD_ERR_INVALID.  n_frames == 0 returns LCD_OK.  There is no limit on the features of a frame: nothing is sorted.
+ * One kernel launch per call whatever the batch (one workgroup of 256 threads per frame), no private segment. */
+enum lcd_depth_type  { LCD_DEPTH_U16_MM = 0, LCD_DEPTH_F32_M = 1 };      /* CV_16UC1 millimetres, CV_32FC1 metres */
+enum lcd_kp3d_filter { LCD_KP3D_KEEP_ALL = 0, LCD_KP3D_FILTER_3D = 1, LCD_KP3D_FILTER_PIXEL = 2 };
+typedef struct lcd_camera {         /* HOST */
+    float fx, fy, cx, cy;           /* of the CameraModel, before the rgb-to-depth factors */
+    int32_t image_width, image_height;   /* CameraModel::imageWidth() / imageHeight(), may be 0; cameras[0]'s decide the factors */
+    int32_t has_local_transform;    /* the caller's !localTransform().isNull() && !localTransform().isIdentity() */
+    int32_t reserved;
+    float local_transform[12];      /* row-major 3 x 4 */
+} lcd_camera;
+typedef struct lcd_depth_image {    /* HOST array, one per frame */
+    const void* data;               /* DEVICE memory for the _dev entry, HOST memory for the host entry; aligned to the pixel size */
+    int64_t pitch_bytes;            /* bytes between rows, >= the row, a multiple of the pixel size */
+    int32_t width, height;          /* pixels, >= 1 */
+    int32_t type;                   /* lcd_depth_type */
+    int32_t n_cameras;              /* >= 1, width % n_cameras == 0: the sub-images side by side */
+    const lcd_camera* cameras;      /* HOST, [n_cameras] */
+} lcd_depth_image;
+typedef struct lcd_keypoints_3d_args {
+    int32_t struct_size;            /* sizeof(lcd_keypoints_3d_args) */
+    int32_t n_frames;               /* >= 0; 0 returns LCD_OK */
+    int32_t filter;                 /* lcd_kp3d_filter */
+    int32_t aux_bytes;              /* bytes of the caller's per-feature payload: a multiple of 4, 0..64 */
+    float min_depth, max_depth;     /* Kp/MinDepth, Kp/MaxDepth (Vis/MinDepth, Vis/MaxDepth for the registration) */
+    const int64_t* offsets;         /* HOST, [n_frames + 1], non-decreasing, [0] == 0 */
+    const lcd_depth_image* images;  /* HOST, [n_frames] */
+    const float* points;            /* [N x 2] cv::KeyPoint::pt (x, y) */
+    const float* response;          /* may be NULL: [N] */
+    const void* rows;               /* may be NULL: [N x dim] of the handle's dtype */
+    const void* aux;                /* may be NULL (aux_bytes == 0): [N x aux_bytes] */
+    int32_t* out_count;             /* [n_frames] */
+    int32_t* out_index;             /* [N]: the kept features in ascending index, the rest of the region -1 */
+    float* out_xyz;                 /* [N x 3]; may be NULL with LCD_KP3D_FILTER_PIXEL */
+    float* out_points;              /* [N x 2], needed with a filter */
+    float* out_response;            /* [N], needed with a filter and response */
+    void* out_rows;                 /* [N x dim], needed with a filter and rows */
+    void* out_aux;                  /* [N x aux_bytes], needed with a filter and aux */
+} lcd_keypoints_3d_args;
+/* every pointer on the HOST (the images' data too); synchronises the engine stream */
+int lcd_keypoints_3d(lcd_engine* h, const lcd_keypoints_3d_args* a);
+/* the images' data, points, response, rows, aux and out_* in DEVICE memory (points 8-byte aligned, the rest 4-byte; rows and aux are copied as
+ * 16-byte vectors where their addresses and sizes allow); offsets, images and cameras on the HOST (read during the call); enqueued on the
+ * engine stream, not synchronised */
+int lcd_keypoints_3d_dev(lcd_engine* h, const lcd_keypoints_3d_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

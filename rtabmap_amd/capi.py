@@ -19,6 +19,8 @@ LCD_MATCH_DICTIONARY, LCD_MATCH_CROSS_CHECK = 0, 1          # lcd_match_args.mod
 LCD_GUIDED_PROJECTED_TO_FRAME, LCD_GUIDED_FRAME_TO_PROJECTED = 0, 1   # lcd_guided_args.direction (include/lcd.h)
 LCD_GUIDED_RATIO, LCD_GUIDED_NEAREST = 0, 1                          # lcd_guided_args.nn_type
 LCD_SELECT_KEEP_ORDER, LCD_SELECT_BY_RESPONSE = 0, 1                 # lcd_select_args.order
+LCD_DEPTH_U16_MM, LCD_DEPTH_F32_M = 0, 1                             # lcd_depth_image.type
+LCD_KP3D_KEEP_ALL, LCD_KP3D_FILTER_3D, LCD_KP3D_FILTER_PIXEL = 0, 1, 2  # lcd_keypoints_3d_args.filter
 LCD_NEW_WORD_IDS_AUTO = -1      # lcd_frame_args.first_new_word_id: the device numbers the frame's new words (include/lcd.h)
 STATUS = {0: "LCD_OK", 1: "LCD_ERR_INVALID", 2: "LCD_ERR_HIP", 3: "LCD_ERR_NOMEM", 4: "LCD_ERR_STATE", 5: "LCD_ERR_UNSUPPORTED"}
 
@@ -28,7 +30,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -108,12 +110,32 @@ class LcdSelectArgs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("order", C.c_int32), ("max_features", C.c_int32), ("grid_rows", C.c_int32),
                 ("grid_cols", C.c_int32), ("aux_bytes", C.c_int32), ("reserved", C.c_int32), ("offsets", C.c_void_p), ("image_size", C.c_void_p),
                 ("response", C.c_void_p), ("points", C.c_void_p), ("rows", C.c_void_p), ("aux", C.c_void_p), ("out_count", C.c_void_p),
-                ("out_index", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p)]
+                ("out_index", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p), ("n_in", C.c_void_p)]
 
 
 class LcdExpandArgs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("offsets", C.c_void_p), ("count", C.c_void_p), ("index", C.c_void_p),
-                ("word_ids", C.c_void_p), ("first_new_word_id", C.c_void_p), ("out_word_ids", C.c_void_p)]
+                ("word_ids", C.c_void_p), ("first_new_word_id", C.c_void_p), ("out_word_ids", C.c_void_p), ("n_features", C.c_void_p)]
+
+
+class LcdCamera(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("image_width", C.c_int32), ("image_height", C.c_int32),
+                ("has_local_transform", C.c_int32), ("reserved", C.c_int32), ("local_transform", C.c_float * 12)]
+
+
+class LcdDepthImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("pitch_bytes", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("type", C.c_int32),
+                ("n_cameras", C.c_int32), ("cameras", C.POINTER(LcdCamera))]
+
+
+class LcdKeypoints3dArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("filter", C.c_int32), ("aux_bytes", C.c_int32), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("offsets", C.c_void_p), ("images", C.POINTER(LcdDepthImage)), ("points", C.c_void_p),
+                ("response", C.c_void_p), ("rows", C.c_void_p), ("aux", C.c_void_p), ("out_count", C.c_void_p), ("out_index", C.c_void_p),
+                ("out_xyz", C.c_void_p), ("out_points", C.c_void_p), ("out_response", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p)]
+
+
+KP3D_FILTERS = {"keep_all": LCD_KP3D_KEEP_ALL, "filter_3d": LCD_KP3D_FILTER_3D, "filter_pixel": LCD_KP3D_FILTER_PIXEL}
 
 
 SELECT_ORDERS = {"keep_order": LCD_SELECT_KEEP_ORDER, "by_response": LCD_SELECT_BY_RESPONSE}
@@ -190,6 +212,8 @@ def load():
     L.lcd_select_features_dev.argtypes = [vp, C.POINTER(LcdSelectArgs)]
     L.lcd_expand_word_ids.argtypes = [vp, C.POINTER(LcdExpandArgs)]
     L.lcd_expand_word_ids_dev.argtypes = [vp, C.POINTER(LcdExpandArgs)]
+    L.lcd_keypoints_3d.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
+    L.lcd_keypoints_3d_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -511,7 +535,7 @@ class Engine:
         a.offsets, a.image_size = off.ctypes.data, (None if size is None else size.ctypes.data)
         return a, off, size
 
-    def select_features(self, response, offsets, max_features, order="keep_order", grid=(1, 1), image_size=None, points=None, rows=None, aux=None):
+    def select_features(self, response, offsets, max_features, order="keep_order", grid=(1, 1), image_size=None, points=None, rows=None, aux=None, n_in=None):
         """lcd_select_features over host arrays: frame f owns the features [offsets[f], offsets[f+1]); aux is a [N x aux_bytes] uint8 payload.
         -> (count [n_frames], index [N], rows or None, aux or None); only the first count[f] entries of a frame's region are meaningful."""
         r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
@@ -527,20 +551,23 @@ class Engine:
         out_aux = None if x is None else np.zeros((max(n, 1), x.shape[1]), np.uint8)
         a.response, a.points, a.rows, a.aux = _p(r), _p(p), _p(d), _p(x)
         a.out_count, a.out_index, a.out_rows, a.out_aux = _p(count), _p(index), _p(out_rows), _p(out_aux)
+        k = None if n_in is None else np.ascontiguousarray(n_in, dtype=np.int32).reshape(a.n_frames)
+        a.n_in = _p(k)
         self._ck(self.L.lcd_select_features(self.h, C.byref(a)))
         return count[:a.n_frames], index[:n], (None if d is None else out_rows[:n]), (None if x is None else out_aux[:n])
 
     def select_features_dev(self, d_response, offsets, max_features, d_count, d_index, order="keep_order", grid=(1, 1), image_size=None,
-                            d_points=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_rows=None, d_out_aux=None):
+                            d_points=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_rows=None, d_out_aux=None, d_n_in=None):
         """lcd_select_features_dev on torch tensors of the engine's device (float32 responses and points, rows of the handle's dtype, int32
         outputs; offsets and image sizes stay on the host).  Enqueued on the engine stream, not synchronised."""
         a, _off, _size = self._select_args(offsets, max_features, order, grid, image_size, aux_bytes)
         ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
         a.response, a.points, a.rows, a.aux = ptr(d_response), ptr(d_points), ptr(d_rows), ptr(d_aux)
         a.out_count, a.out_index, a.out_rows, a.out_aux = ptr(d_count), ptr(d_index), ptr(d_out_rows), ptr(d_out_aux)
+        a.n_in = ptr(d_n_in)
         self._ck(self.L.lcd_select_features_dev(self.h, C.byref(a)))
 
-    def expand_word_ids(self, offsets, count, index, word_ids, first_new_word_id=None):
+    def expand_word_ids(self, offsets, count, index, word_ids, first_new_word_id=None, n_features=None):
         """lcd_expand_word_ids over host arrays -> one id per feature [N]"""
         off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         c = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
@@ -553,17 +580,85 @@ class Engine:
         out = np.zeros(max(n, 1), np.int32)
         a = LcdExpandArgs(C.sizeof(LcdExpandArgs), n_frames)
         a.offsets, a.count, a.index, a.word_ids, a.first_new_word_id, a.out_word_ids = off.ctypes.data, _p(c), _p(i), _p(w), _p(f), _p(out)
+        k = None if n_features is None else np.ascontiguousarray(n_features, dtype=np.int32).reshape(n_frames)
+        a.n_features = _p(k)
         self._ck(self.L.lcd_expand_word_ids(self.h, C.byref(a)))
         return out[:n]
 
-    def expand_word_ids_dev(self, offsets, d_count, d_index, d_word_ids, d_out_word_ids, d_first_new_word_id=None):
+    def expand_word_ids_dev(self, offsets, d_count, d_index, d_word_ids, d_out_word_ids, d_first_new_word_id=None, d_n_features=None):
         """lcd_expand_word_ids_dev on int32 torch tensors of the engine's device (the offsets stay on the host); enqueued, not synchronised"""
         off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
         a = LcdExpandArgs(C.sizeof(LcdExpandArgs), off.shape[0] - 1)
         a.offsets = off.ctypes.data
         a.count, a.index, a.word_ids, a.first_new_word_id, a.out_word_ids = ptr(d_count), ptr(d_index), ptr(d_word_ids), ptr(d_first_new_word_id), ptr(d_out_word_ids)
+        a.n_features = ptr(d_n_features)
         self._ck(self.L.lcd_expand_word_ids_dev(self.h, C.byref(a)))
+
+    # ---- depth to 3-D keypoints and the depth filter (stateless; include/lcd.h has the rule)
+    @staticmethod
+    def _kp3d_images(images, data_ptr):
+        """images: one dict per frame -- data (a 2-D uint16 or float32 array / tensor, possibly a view with a row stride), cameras (a list of
+        dicts fx, fy, cx, cy and optionally image_width, image_height, transform (12 floats or None)), optionally width (pixels, when the
+        array is wider than the image) -> (lcd_depth_image array, what must stay alive)"""
+        arr = (LcdDepthImage * max(len(images), 1))()
+        keep = []
+        for f, im in enumerate(images):
+            d = im["data"]
+            u16 = "16" in str(d.dtype)
+            cams = (LcdCamera * len(im["cameras"]))()
+            for c, m in enumerate(im["cameras"]):
+                t = m.get("transform")
+                cams[c] = LcdCamera(m["fx"], m["fy"], m["cx"], m["cy"], int(m.get("image_width", 0)), int(m.get("image_height", 0)),
+                                    0 if t is None else 1, 0, (C.c_float * 12)(*([0.0] * 12 if t is None else [float(v) for v in t])))
+            keep.append(cams)
+            pitch = im["pitch_bytes"] if "pitch_bytes" in im else int(d.strides[0] if hasattr(d, "strides") else d.stride(0) * d.element_size())
+            arr[f] = LcdDepthImage(data_ptr(d), pitch, int(im.get("width", d.shape[1])), int(im.get("height", d.shape[0])),
+                                   int(im.get("type", LCD_DEPTH_U16_MM if u16 else LCD_DEPTH_F32_M)), int(im.get("n_cameras", len(im["cameras"]))), cams)
+        return arr, keep
+
+    def keypoints_3d(self, points, offsets, images, filter="keep_all", min_depth=0.0, max_depth=0.0, response=None, rows=None, aux=None, xyz=True):
+        """lcd_keypoints_3d over host arrays -> dict(count [n_frames], index [N], xyz [N x 3] or None, points, response, rows, aux or None);
+        only the first count[f] entries of a frame's region are meaningful (outputs start as zeros)."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        n, n_frames = p.shape[0], off.shape[0] - 1
+        r = None if response is None else np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
+        d = None if rows is None else self._rows(rows)
+        x = None if aux is None else np.ascontiguousarray(aux, dtype=np.uint8).reshape(n, -1)
+        flt = KP3D_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        arr, keep = self._kp3d_images(images, lambda a: a.ctypes.data)
+        a = LcdKeypoints3dArgs(C.sizeof(LcdKeypoints3dArgs), n_frames, flt, 0 if x is None else x.shape[1], float(min_depth), float(max_depth))
+        a.offsets, a.images = off.ctypes.data, arr
+        out = dict(count=np.zeros(max(n_frames, 1), np.int32), index=np.zeros(max(n, 1), np.int32),
+                   xyz=np.zeros((max(n, 1), 3), np.float32) if xyz else None, points=np.zeros((max(n, 1), 2), np.float32),
+                   response=None if r is None else np.zeros(max(n, 1), np.float32),
+                   rows=None if d is None else np.zeros((max(n, 1), self.dim), self.np_dtype),
+                   aux=None if x is None else np.zeros((max(n, 1), x.shape[1]), np.uint8))
+        a.points, a.response, a.rows, a.aux = _p(p), _p(r), _p(d), _p(x)
+        a.out_count, a.out_index, a.out_xyz, a.out_points = _p(out["count"]), _p(out["index"]), _p(out["xyz"]), _p(out["points"])
+        a.out_response, a.out_rows, a.out_aux = _p(out["response"]), _p(out["rows"]), _p(out["aux"])
+        self._ck(self.L.lcd_keypoints_3d(self.h, C.byref(a)))
+        out["count"] = out["count"][:n_frames]
+        for k in ("index", "xyz", "points", "response", "rows", "aux"):
+            out[k] = None if out[k] is None else out[k][:n]
+        return out
+
+    def keypoints_3d_dev(self, d_points, offsets, images, d_count, d_index, d_xyz=None, filter="keep_all", min_depth=0.0, max_depth=0.0,
+                         d_response=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_points=None, d_out_response=None, d_out_rows=None,
+                         d_out_aux=None):
+        """lcd_keypoints_3d_dev on torch tensors of the engine's device (the images' data too; offsets, images and cameras stay on the host).
+        Enqueued on the engine stream, not synchronised."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        flt = KP3D_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        arr, keep = self._kp3d_images(images, lambda t: t.data_ptr())
+        a = LcdKeypoints3dArgs(C.sizeof(LcdKeypoints3dArgs), off.shape[0] - 1, flt, int(aux_bytes), float(min_depth), float(max_depth))
+        a.offsets, a.images = off.ctypes.data, arr
+        a.points, a.response, a.rows, a.aux = ptr(d_points), ptr(d_response), ptr(d_rows), ptr(d_aux)
+        a.out_count, a.out_index, a.out_xyz, a.out_points = ptr(d_count), ptr(d_index), ptr(d_xyz), ptr(d_out_points)
+        a.out_response, a.out_rows, a.out_aux = ptr(d_out_response), ptr(d_out_rows), ptr(d_out_aux)
+        self._ck(self.L.lcd_keypoints_3d_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

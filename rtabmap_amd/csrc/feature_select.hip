@@ -13,12 +13,13 @@
 //     "has no word" in feature order hands out -1, -2, ...
 // Nothing of the engine is read or written: the job table and the host entries' staging are StatelessScratch's (stateless_scratch.h), as for lcd_match_pairs and lcd_match_guided.
 #include "engine_impl.h"
+#include "compact_body.cuh"
 
 #include <cmath>
 #include <vector>
 
-static_assert(sizeof(lcd_select_args) == 112, "lcd_select_args: the layout include/lcd.h documents (LP64)");
-static_assert(sizeof(lcd_expand_args) == 56, "lcd_expand_args: the layout include/lcd.h documents (LP64)");
+static_assert(sizeof(lcd_select_args) == 120, "lcd_select_args: the layout include/lcd.h documents (LP64)");
+static_assert(sizeof(lcd_expand_args) == 64, "lcd_expand_args: the layout include/lcd.h documents (LP64)");
 
 namespace lcd {
 namespace {
@@ -34,7 +35,7 @@ constexpr int MAX_WAVES = BIG_BLOCK / 64;
 
 struct FrameJob {
     int64_t first;                           // the frame's first feature in every array
-    int32_t n;
+    int32_t n;                               // the frame's region; with n_in / n_features the device knows how much of it is the frame
     int32_t row_size, col_size;              // pixels per grid cell (1 where the frame is not cut)
     int32_t pad;
 };
@@ -45,34 +46,18 @@ struct SelectArgs {
     int p_max;                               // keys the LDS carve holds (a power of two >= every cut frame)
     int row_bytes, row_vec, aux_bytes, aux_vec;   // *_vec: 16 or 4, the widest copy the addresses and sizes allow
     const float* response; const float2* points; const void* rows; const void* aux;
+    const int32_t* n_in;                     // may be null: per frame, how many features of the region are the frame (clamped)
     int32_t* out_count; int32_t* out_index; void* out_rows; void* out_aux;
 };
 
 struct ExpandArgs {
     const FrameJob* jobs;
     const int32_t* count; const int32_t* index; const int32_t* word_ids; const int32_t* first_new_word_id;
+    const int32_t* n_features;               // may be null: as SelectArgs::n_in
     int32_t* out_word_ids;
 };
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fs_smem[];
-
-// exclusive rank of this thread's flag among the workgroup's flags in thread order, and their total (two barriers; wsum: one int per wave)
-__device__ __forceinline__ int block_rank(bool flag, int* wsum, int& total) {
-    const unsigned long long m = __ballot(flag);
-    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const int wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < n_waves; ++w) {
-        const int v = wsum[w];
-        if (w < wave) before += v;
-        all += v;
-    }
-    __syncthreads();
-    total = all;
-    return before + in_wave;
-}
 
 // Where key i lies in LDS: one spare slot behind every eight keys.  The network's threads walk the keys with strides of 8, 64, 512, .. keys
 // between neighbouring lanes; unpadded, those land on the same banks (64 banks of 4 bytes: 32 keys) up to sixteen lanes deep.
@@ -105,22 +90,9 @@ __device__ __forceinline__ void bitonic_pass(uint64_t* keys, int p2, int k, int 
     }
 }
 
-// dst row j = src row idx[j], j < count, `bytes` per row in pieces of V
-template <typename V>
-__device__ __forceinline__ void gather_rows(const void* src, void* dst, const int32_t* idx, int64_t first, int count, int bytes) {
-    const int per = bytes / (int)sizeof(V);
-    const V* s = reinterpret_cast<const V*>(src) + first * per;
-    V* d = reinterpret_cast<V*>(dst) + first * per;
-    const int total = count * per;                                    // at most 16384 x 128
-    for (int e = threadIdx.x; e < total; e += blockDim.x) {
-        const int j = e / per, c = e - j * per;
-        d[(size_t)j * per + c] = s[(size_t)idx[j] * per + c];
-    }
-}
-
 __global__ __launch_bounds__(BIG_BLOCK) void feature_select_kernel(SelectArgs a) {
     const FrameJob J = a.jobs[blockIdx.x];
-    const int n = J.n, tid = threadIdx.x, T = blockDim.x;
+    const int n = a.n_in ? min(max(a.n_in[blockIdx.x], 0), J.n) : J.n, tid = threadIdx.x, T = blockDim.x;
     const int n_cells = a.grid_rows * a.grid_cols;
     uint64_t* keys = reinterpret_cast<uint64_t*>(fs_smem);
     uint32_t* sel = reinterpret_cast<uint32_t*>(fs_smem + (size_t)padded(a.p_max) * 8);   // one bit per feature
@@ -190,8 +162,8 @@ __global__ __launch_bounds__(BIG_BLOCK) void feature_select_kernel(SelectArgs a)
                 count += total;
             }
         }
-        for (int i = count + tid; i < n; i += T) out_index[i] = -1;
     }
+    for (int i = count + tid; i < J.n; i += T) out_index[i] = -1;      // to the end of the region
     if (tid == 0) a.out_count[blockIdx.x] = count;
     if (!a.rows && !a.aux) return;
     __syncthreads();                                                   // the index list is read back by the threads that gather
@@ -207,7 +179,7 @@ __global__ __launch_bounds__(BIG_BLOCK) void feature_select_kernel(SelectArgs a)
 
 __global__ __launch_bounds__(BIG_BLOCK) void expand_word_ids_kernel(ExpandArgs a, int n_max) {
     const FrameJob J = a.jobs[blockIdx.x];
-    const int n = J.n, tid = threadIdx.x, T = blockDim.x;
+    const int n = a.n_features ? min(max(a.n_features[blockIdx.x], 0), J.n) : J.n, tid = threadIdx.x, T = blockDim.x;
     int32_t* all = reinterpret_cast<int32_t*>(fs_smem);                // the frame's resolved ids, 0 = no word
     int* wsum = all + n_max;
     const int count = min(max(a.count[blockIdx.x], 0), n);
@@ -232,6 +204,7 @@ __global__ __launch_bounds__(BIG_BLOCK) void expand_word_ids_kernel(ExpandArgs a
         if (i < n) a.out_word_ids[J.first + i] = id > 0 ? id : -(rank + 1);
         negatives += total;
     }
+    for (int i = n + tid; i < J.n; i += T) a.out_word_ids[J.first + i] = 0;   // behind the frame, to the end of the region
 }
 
 inline size_t select_lds(int p_max, int n_cells) { return ((size_t)padded(p_max) * 8 + (size_t)p_max / 8 + (size_t)(n_cells + 1) * 4 + MAX_WAVES * 4 + 15) & ~(size_t)15; }
@@ -306,6 +279,8 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
     if (N > 0 && (!a->response || !a->out_index)) return bad(LCD_ERR_INVALID, "null response or out_index");
     if (N > 0 && ((with_rows && !a->out_rows) || (with_aux && !a->out_aux))) return bad(LCD_ERR_INVALID, "rows or aux without an output");
     if (N > 0 && grid && (!a->points || !a->image_size)) return bad(LCD_ERR_INVALID, "a grid needs points and image sizes");
+    // the host entry knows n_in: what it checks per feature ends where the frame ends
+    auto frame_n = [&](int f) { const int64_t r = off[f + 1] - off[f]; return !on_device && a->n_in ? std::min<int64_t>(std::max<int64_t>(a->n_in[f], 0), r) : r; };
     std::vector<FrameJob> jobs((size_t)nf);
     int cut_max = 0;
     for (int f = 0; f < nf; ++f) {
@@ -319,12 +294,13 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
         J.row_size = height / a->grid_rows; J.col_size = width / a->grid_cols;
     }
     if (!on_device) {
-        for (int64_t i = 0; i < N; ++i) if (std::isnan(a->response[i])) return bad(LCD_ERR_INVALID, "a NaN response has no place in the order");
+        for (int f = 0; f < nf; ++f)
+            for (int64_t i = off[f]; i < off[f] + frame_n(f); ++i) if (std::isnan(a->response[i])) return bad(LCD_ERR_INVALID, "a NaN response has no place in the order");
         if (grid)
             for (int f = 0; f < nf; ++f) {
                 const FrameJob& J = jobs[(size_t)f];
-                if (!(a->max_features > 0 && J.n > a->max_features)) continue;
-                for (int64_t i = off[f]; i < off[f + 1]; ++i) {
+                if (!(a->max_features > 0 && frame_n(f) > a->max_features)) continue;
+                for (int64_t i = off[f]; i < off[f] + frame_n(f); ++i) {
                     const int cr = to_int_rz(a->points[2 * i + 1]) / J.row_size, cc = to_int_rz(a->points[2 * i]) / J.col_size;
                     if (cr < 0 || cr >= a->grid_rows || cc < 0 || cc >= a->grid_cols) return bad(LCD_ERR_INVALID, "a keypoint outside the grid");
                 }
@@ -339,6 +315,7 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
     while (g.p_max < cut_max) g.p_max <<= 1;
     g.row_bytes = h->row_bytes; g.aux_bytes = a->aux_bytes;
     g.response = a->response; g.points = (const float2*)a->points; g.rows = with_rows ? a->rows : nullptr; g.aux = with_aux ? a->aux : nullptr;
+    g.n_in = a->n_in;
     g.out_count = a->out_count; g.out_index = a->out_index; g.out_rows = a->out_rows; g.out_aux = a->out_aux;
 
     // ---- host entry: everything to the device, results back at the end (one synchronisation)
@@ -348,11 +325,13 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
         const size_t aux_bytes = with_aux ? (size_t)N * a->aux_bytes : 0;
         const int i_resp = stage.add_in(a->response, (size_t)N * 4), i_pts = stage.add_in(a->points, grid ? (size_t)N * 8 : 0);
         const int i_rows = stage.add_in_rows(a->rows, with_rows ? N : 0), i_aux = stage.add_in(a->aux, aux_bytes);
+        const int i_n = stage.add_in(a->n_in, a->n_in ? (size_t)nf * 4 : 0);
         const int o_count = stage.add_out(a->out_count, (size_t)nf * 4), o_index = stage.add_out(a->out_index, (size_t)N * 4);
         o_rows = stage.add_out(nullptr, with_rows ? (size_t)N * h->row_bytes : 0); o_aux = stage.add_out(nullptr, aux_bytes);
         LCD_HIP(h, stage.commit(st, &h->bytes_device));
         g.response = stage.in<float>(i_resp); g.points = grid ? stage.in<float2>(i_pts) : nullptr;
         g.rows = with_rows ? stage.in<char>(i_rows) : nullptr; g.aux = with_aux ? stage.in<char>(i_aux) : nullptr;
+        g.n_in = a->n_in ? stage.in<int32_t>(i_n) : nullptr;
         g.out_count = stage.out<int32_t>(o_count); g.out_index = stage.out<int32_t>(o_index);
         g.out_rows = stage.out<char>(o_rows); g.out_aux = stage.out<char>(o_aux);
     }
@@ -388,7 +367,8 @@ int expand_word_ids(lcd_engine* h, const lcd_expand_args* a, bool on_device) {
     if (N > 0 && (!a->index || !a->word_ids || !a->out_word_ids)) return bad(LCD_ERR_INVALID, "null index, word_ids or out_word_ids");
     if (!on_device)
         for (int f = 0; f < nf; ++f) {
-            const int64_t n = off[f + 1] - off[f];
+            const int64_t region = off[f + 1] - off[f];
+            const int64_t n = a->n_features ? std::min<int64_t>(std::max<int64_t>(a->n_features[f], 0), region) : region;
             if (a->count[f] < 0 || a->count[f] > n) return bad(LCD_ERR_INVALID, "count outside its frame");
             for (int64_t j = off[f]; j < off[f] + a->count[f]; ++j)
                 if (a->index[j] < 0 || a->index[j] >= n) return bad(LCD_ERR_INVALID, "an index entry outside its frame");
@@ -401,14 +381,17 @@ int expand_word_ids(lcd_engine* h, const lcd_expand_args* a, bool on_device) {
 
     ExpandArgs g;
     g.count = a->count; g.index = a->index; g.word_ids = a->word_ids; g.first_new_word_id = a->first_new_word_id; g.out_word_ids = a->out_word_ids;
+    g.n_features = a->n_features;
     HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
     if (!on_device) {
         const int i_count = stage.add_in(a->count, (size_t)nf * 4), i_index = stage.add_in(a->index, (size_t)N * 4);
         const int i_words = stage.add_in(a->word_ids, (size_t)N * 4), i_first = stage.add_in(a->first_new_word_id, a->first_new_word_id ? (size_t)nf * 4 : 0);
+        const int i_n = stage.add_in(a->n_features, a->n_features ? (size_t)nf * 4 : 0);
         const int o_words = stage.add_out(a->out_word_ids, (size_t)N * 4);
         LCD_HIP(h, stage.commit(st, &h->bytes_device));
         g.count = stage.in<int32_t>(i_count); g.index = stage.in<int32_t>(i_index); g.word_ids = stage.in<int32_t>(i_words);
         g.first_new_word_id = a->first_new_word_id ? stage.in<int32_t>(i_first) : nullptr;
+        g.n_features = a->n_features ? stage.in<int32_t>(i_n) : nullptr;
         g.out_word_ids = stage.out<int32_t>(o_words);
     }
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(FrameJob)));

@@ -1,0 +1,166 @@
+// keypoints_3d_rule.h -- the rule of lcd_keypoints_3d (include/lcd.h writes it down with the reference's line numbers) as functions the
+// kernel (keypoints_3d.hip), the host entry's checks and the host mirror (rtabmap_amd/host/Keypoints3D.cpp) compile alike.  All arithmetic is
+// fp32, one operation per statement or bracketed as the reference brackets it, and never contracted: no product is fused into a sum.  Internal.
+#pragma once
+#include <stdint.h>
+#include <cstring>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define KP3D_FN __host__ __device__ __forceinline__
+#else
+#define KP3D_FN inline
+#endif
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+namespace lcd {
+namespace kp3d {
+
+constexpr int DEPTH_U16_MM = 0, DEPTH_F32_M = 1;                   // lcd_depth_type
+constexpr int KEEP_ALL = 0, FILTER_3D = 1, FILTER_PIXEL = 2;       // lcd_kp3d_filter
+constexpr float DEPTH_ERROR_RATIO = 0.02f;
+
+// one depth image as a frame sees it
+struct Image {
+    const unsigned char* data;
+    int64_t pitch;                       // bytes between rows
+    int32_t width, height, type, n_cameras;
+    int32_t sub_cols;                    // width / n_cameras
+    float sub_w;                         // float(sub_cols)
+    float factor_x, factor_y;            // rgb-to-depth factors
+};
+
+// one camera, its intrinsics already multiplied by the factors
+struct Camera {
+    float cx, cy, fx, fy;
+    float t[12];                         // row-major 3 x 4
+    int32_t has_t;
+    int32_t pad[3];
+};
+
+KP3D_FN uint32_t bits_of(float v) { uint32_t b; memcpy(&b, &v, 4); return b; }
+KP3D_FN float float_of(uint32_t b) { float v; memcpy(&v, &b, 4); return v; }
+KP3D_FN bool finite(float v) { return (bits_of(v) & 0x7f800000u) != 0x7f800000u; }
+KP3D_FN float quiet_nan() { return float_of(0x7fc00000u); }
+// int(v) is defined: v is finite and within the range of int
+KP3D_FN bool convertible(float v) { return v > -2147483648.0f && v < 2147483648.0f; }
+
+// the factors and the sub-image of util3d_features.cpp:79-83 for an image whose data, pitch, width, height, type and n_cameras are set
+KP3D_FN void set_factors(Image& im, int image_width, int image_height) {
+    im.sub_cols = im.width / im.n_cameras;
+    im.sub_w = (float)im.sub_cols;
+    const float rx = image_width > 0 ? (float)image_width / im.sub_w : 1.0f;
+    const float ry = image_height > 0 ? (float)image_height / (float)im.height : 1.0f;
+    im.factor_x = 1.0f / rx;
+    im.factor_y = 1.0f / ry;
+}
+
+// the pixel (col, row) of the whole image in metres; checked: a u16 pixel of 0 or 65535 is no measurement (util2d.cpp:991-995)
+KP3D_FN float pixel(const Image& im, int col, int row, bool checked) {
+    const unsigned char* p = im.data + (int64_t)row * im.pitch;
+    if (im.type == DEPTH_U16_MM) {
+        const uint16_t v = reinterpret_cast<const uint16_t*>(p)[col];
+        if (checked && (v == 0 || v == 65535)) return 0.0f;
+        return (float)v * 0.001f;
+    }
+    return reinterpret_cast<const float*>(p)[col];
+}
+
+// util2d::getDepth (util2d.cpp:947-1111) with smoothing, depthErrorRatio 0.02 and without estWithNeighborsIfNull, in the sub-image whose
+// first column is col0; x + 0.5f and y + 0.5f are convertible
+KP3D_FN float get_depth(const Image& im, int col0, float x, float y) {
+    const int cols = im.sub_cols, rows = im.height;
+    int u = (int)(x + 0.5f);
+    int v = (int)(y + 0.5f);
+    if (u == cols && x < (float)cols) u = cols - 1;
+    if (v == rows && y < (float)rows) v = rows - 1;
+    if (!(u >= 0 && u < cols && v >= 0 && v < rows)) return 0.0f;
+    const int u_start = u - 1 > 0 ? u - 1 : 0, v_start = v - 1 > 0 ? v - 1 : 0;
+    const int u_end = u + 1 < cols - 1 ? u + 1 : cols - 1, v_end = v + 1 < rows - 1 ? v + 1 : rows - 1;
+    float depth = pixel(im, col0 + u, v, true);
+    if (depth == 0.0f || !finite(depth)) return 0.0f;
+    const float depth_error = DEPTH_ERROR_RATIO * depth;
+    float sum_weights = 0.0f, sum_depths = 0.0f;
+    for (int uu = u_start; uu <= u_end; ++uu) {
+        for (int vv = v_start; vv <= v_end; ++vv) {
+            if (uu == u && vv == v) continue;
+            float d = pixel(im, col0 + uu, vv, true);
+            if (d == 0.0f || !finite(d)) continue;
+            float diff = d - depth;
+            if (diff < 0.0f) diff = -diff;
+            if (!(diff < depth_error)) continue;
+            if (uu == u || vv == v) {
+                sum_weights = sum_weights + 2.0f;
+                d = d * 2.0f;
+            } else {
+                sum_weights = sum_weights + 1.0f;
+            }
+            sum_depths = sum_depths + d;
+        }
+    }
+    depth = depth * 4.0f;
+    sum_weights = sum_weights + 4.0f;
+    const float total = depth + sum_depths;
+    return total / sum_weights;
+}
+
+// generateKeypoints3DDepth's loop body (util3d_features.cpp:87-116) for the keypoint (px, py): the 3-D point, three quiet NaNs where there is
+// none.  Returns false, reads no pixel and gives the bad point where the reference asserts or is undefined: a coordinate that is not finite
+// or beyond the range of int, or a camera index outside [0, n_cameras).
+KP3D_FN bool point_of(const Image& im, const Camera* cams, float px, float py, float min_depth, float max_depth, float out[3]) {
+    out[0] = out[1] = out[2] = quiet_nan();
+    const float x = px * im.factor_x;
+    const float y = py * im.factor_y;
+    const float q = x / im.sub_w;
+    if (!convertible(x + 0.5f) || !convertible(y + 0.5f) || !convertible(q)) return false;
+    const int cam = (int)q;
+    if (cam < 0 || cam >= im.n_cameras) return false;
+    const Camera& C = cams[cam];
+    const float shift = im.sub_w * (float)cam;
+    const float xs = x - shift;
+    const float depth = get_depth(im, im.sub_cols * cam, xs, y);
+    if (!(depth > 0.0f)) return true;
+    // util3d::projectDepthTo3D (util3d.cpp:228-238)
+    const float cx = C.cx > 0.0f ? C.cx : (float)(im.sub_cols / 2) - 0.5f;
+    const float cy = C.cy > 0.0f ? C.cy : (float)(im.height / 2) - 0.5f;
+    const float dx = xs - cx, dy = y - cy;
+    const float nx = dx * depth, ny = dy * depth;
+    const float X = nx / C.fx, Y = ny / C.fy, Z = depth;
+    if (!(finite(X) && finite(Y) && finite(Z))) return true;
+    if (!((min_depth < 0.0f || Z > min_depth) && (max_depth <= 0.0f || Z <= max_depth))) return true;
+    if (!C.has_t) { out[0] = X; out[1] = Y; out[2] = Z; return true; }
+    // util3d::transformPoint (util3d_transforms.cpp:211-220), left to right
+    for (int r = 0; r < 3; ++r) {
+        const float a = C.t[4 * r] * X, b = C.t[4 * r + 1] * Y, c = C.t[4 * r + 2] * Z;
+        const float ab = a + b;
+        const float abc = ab + c;
+        out[r] = abc + C.t[4 * r + 3];
+    }
+    return true;
+}
+
+// Feature2D::filterKeypointsByDepth, the 3-D overload (Features2d.cpp:183-191)
+KP3D_FN bool keep_3d(const float p[3], float min_depth, float max_depth) {
+    if (!(finite(p[0]) && finite(p[1]) && finite(p[2]))) return false;
+    const float min_sqr = min_depth * min_depth, max_sqr = max_depth * max_depth;
+    const float xx = p[0] * p[0], yy = p[1] * p[1], zz = p[2] * p[2];
+    const float xy = xx + yy;
+    const float d2 = xy + zz;
+    return d2 >= min_sqr && (max_sqr == 0.0f || d2 <= max_sqr);
+}
+
+// ... the 2-D overload (:120-132): the nearest pixel of the whole image, no factors, no clamp.  *defined: the conversions are
+KP3D_FN bool keep_pixel(const Image& im, float px, float py, float min_depth, float max_depth, bool* defined) {
+    const float fu = px + 0.5f, fv = py + 0.5f;
+    *defined = convertible(fu) && convertible(fv);
+    if (!*defined) return false;
+    const int u = (int)fu, v = (int)fv;
+    if (!(u >= 0 && u < im.width && v >= 0 && v < im.height)) return false;
+    const float d = pixel(im, u, v, false);
+    return finite(d) && d > min_depth && (max_depth <= 0.0f || d < max_depth);
+}
+
+}  // namespace kp3d
+}  // namespace lcd

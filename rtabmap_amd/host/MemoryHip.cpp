@@ -26,7 +26,7 @@ struct Stage {
 }  // namespace
 
 MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
-    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _maxFeatures(500), _gridRows(1), _gridCols(1), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
+    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _maxFeatures(500), _gridRows(1), _gridCols(1), _minDepth(0.0f), _maxDepth(0.0f), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
     ParametersMap::const_iterator it = parameters.find("Mem/STMSize");
     if (it != parameters.end()) _maxStMemSize = atoi(it->second.c_str());
     it = parameters.find("Kp/TfIdfLikelihoodUsed");
@@ -34,6 +34,8 @@ MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
     if (_maxStMemSize < 0) _maxStMemSize = 0;
     if ((it = parameters.find("Kp/MaxFeatures")) != parameters.end()) _maxFeatures = atoi(it->second.c_str());
     if ((it = parameters.find("Kp/GridRows")) != parameters.end()) _gridRows = atoi(it->second.c_str());
+    if ((it = parameters.find("Kp/MinDepth")) != parameters.end()) _minDepth = (float)atof(it->second.c_str());
+    if ((it = parameters.find("Kp/MaxDepth")) != parameters.end()) _maxDepth = (float)atof(it->second.c_str());
     if ((it = parameters.find("Kp/GridCols")) != parameters.end()) _gridCols = atoi(it->second.c_str());
     _workingMem.insert(kIdVirtual);             // Memory.cpp:592
     static const char* names[] = {"TimingMem/Pre_update/ms", "TimingMem/Joining_dictionary_update/ms", "TimingMem/Add_new_words/ms",
@@ -127,7 +129,7 @@ bool MemoryHip::quantizeSelected(const Mat& forQuantization, const std::vector<i
         const int64_t offsets[2] = {0, rows};
         lcd_expand_args e;
         e.struct_size = (int32_t)sizeof(e); e.n_frames = 1; e.offsets = offsets; e.count = &count; e.index = idx.data(); e.word_ids = wid.data();
-        e.first_new_word_id = 0; e.out_word_ids = out.data();
+        e.first_new_word_id = 0; e.out_word_ids = out.data(); e.n_features = 0;
         if (lcd_expand_word_ids(eng, &e) != LCD_OK) { _selectError = lcd_last_error(eng); return false; }
         all.assign(out.begin(), out.end());
     } else if (!FeatureSelect::expandWordIds(rows, index.data(), ids.data(), count, 0, all)) {
@@ -136,6 +138,65 @@ bool MemoryHip::quantizeSelected(const Mat& forQuantization, const std::vector<i
     }
     wordIds.assign(all.begin(), all.end());
     return true;
+}
+
+int MemoryHip::update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
+                      const DepthImage& depth, const std::vector<DepthCamera>& cameras, std::vector<int>& outIds, std::vector<float>& keypoints3D,
+                      std::vector<int>& keptIndex) {
+    const int rows = descriptors.rows;
+    _selectError.clear();
+    if ((int)responses.size() != rows || (int)points.size() != 2 * rows || cameras.empty()) { _selectError = "one response and one point per descriptor, one camera at least"; return 0; }
+    // ---- the depth stage (:5683-5694, :5911-5915)
+    std::vector<float> xyz((size_t)rows * 3), keptResponses, keptPoints;
+    std::vector<unsigned char> keptRows;
+    std::vector<int> kept;
+    lcd_engine* eng = _vwd->engine();
+    if (eng && rows > 0) {
+        std::vector<lcd_camera> cams(cameras.size());
+        for (size_t c = 0; c < cameras.size(); ++c) {
+            lcd_camera& L = cams[c];
+            L.fx = cameras[c].fx; L.fy = cameras[c].fy; L.cx = cameras[c].cx; L.cy = cameras[c].cy;
+            L.image_width = cameras[c].imageWidth; L.image_height = cameras[c].imageHeight;
+            L.has_local_transform = cameras[c].hasLocalTransform ? 1 : 0; L.reserved = 0;
+            std::copy(cameras[c].localTransform, cameras[c].localTransform + 12, L.local_transform);
+        }
+        lcd_depth_image image;
+        image.data = depth.data; image.pitch_bytes = depth.pitchBytes; image.width = depth.width; image.height = depth.height;
+        image.type = depth.type; image.n_cameras = (int32_t)cams.size(); image.cameras = cams.data();
+        const int64_t offsets[2] = {0, rows};
+        int32_t count = 0;
+        std::vector<int32_t> index((size_t)rows);
+        keptResponses.resize((size_t)rows); keptPoints.resize((size_t)rows * 2); keptRows.resize(descriptors.data.size());
+        lcd_keypoints_3d_args k;
+        k.struct_size = (int32_t)sizeof(k); k.n_frames = 1; k.filter = LCD_KP3D_FILTER_3D; k.aux_bytes = 0; k.min_depth = _minDepth; k.max_depth = _maxDepth;
+        k.offsets = offsets; k.images = &image; k.points = points.data(); k.response = responses.data(); k.rows = descriptors.data.data(); k.aux = 0;
+        k.out_count = &count; k.out_index = index.data(); k.out_xyz = xyz.data(); k.out_points = keptPoints.data(); k.out_response = keptResponses.data();
+        k.out_rows = keptRows.data(); k.out_aux = 0;
+        if (lcd_keypoints_3d(eng, &k) != LCD_OK) { _selectError = lcd_last_error(eng); return 0; }
+        kept.assign(index.begin(), index.begin() + count);
+        xyz.resize((size_t)count * 3); keptResponses.resize((size_t)count); keptPoints.resize((size_t)count * 2);
+        keptRows.resize((size_t)count * descriptors.rowBytes());
+    } else {
+        if (!Keypoints3D::generateKeypoints3DDepth(points.data(), rows, depth, cameras.data(), (int)cameras.size(), _minDepth, _maxDepth, xyz.data())) {
+            _selectError = "generateKeypoints3DDepth: an image the cameras do not divide, or a keypoint that is not finite or in no camera's sub-image";
+            return 0;
+        }
+        if (!Keypoints3D::filterKeypointsByDepth(xyz.data(), rows, _minDepth, _maxDepth, kept)) { _selectError = "filterKeypointsByDepth: Kp/MinDepth < 0 or 0 < Kp/MaxDepth <= Kp/MinDepth"; return 0; }
+        std::vector<float> all;
+        all.swap(xyz);
+        for (size_t j = 0; j < kept.size(); ++j) {
+            const size_t i = (size_t)kept[j];
+            xyz.insert(xyz.end(), all.begin() + 3 * i, all.begin() + 3 * i + 3);
+            keptResponses.push_back(responses[i]);
+            keptPoints.push_back(points[2 * i]); keptPoints.push_back(points[2 * i + 1]);
+            keptRows.insert(keptRows.end(), descriptors.ptr((int)i), descriptors.ptr((int)i) + descriptors.rowBytes());
+        }
+    }
+    std::vector<int> ids;
+    const int id = this->update(Mat((int)kept.size(), descriptors.cols, descriptors.type(), keptRows.data()), keptResponses, keptPoints, imageWidth, imageHeight, ids);
+    if (!id) return 0;
+    outIds.swap(ids); keypoints3D.swap(xyz); keptIndex.swap(kept);
+    return id;
 }
 
 int MemoryHip::update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
@@ -159,7 +220,7 @@ int MemoryHip::update(const Mat& descriptors, const std::vector<float>& response
         s.struct_size = (int32_t)sizeof(s); s.n_frames = 1; s.order = LCD_SELECT_KEEP_ORDER; s.max_features = _maxFeatures;
         s.grid_rows = _gridRows < 1 ? 1 : _gridRows; s.grid_cols = _gridCols < 1 ? 1 : _gridCols; s.aux_bytes = 0; s.reserved = 0;
         s.offsets = offsets; s.image_size = size; s.response = responses.data(); s.points = grid ? points.data() : 0;
-        s.rows = descriptors.data.data(); s.aux = 0; s.out_count = &count; s.out_index = index.data(); s.out_rows = selected.data(); s.out_aux = 0;
+        s.rows = descriptors.data.data(); s.aux = 0; s.out_count = &count; s.out_index = index.data(); s.out_rows = selected.data(); s.out_aux = 0; s.n_in = 0;
         if (lcd_select_features(eng, &s) != LCD_OK) { _selectError = lcd_last_error(eng); return 0; }
         rawIndex.assign(index.begin(), index.begin() + count);
         forQuantization = Mat(count, descriptors.cols, descriptors.type(), selected.data());

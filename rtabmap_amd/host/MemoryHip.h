@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "Keypoints3D.h"
 #include "VWDictionaryHip.h"
 
 namespace rtabmap_amd {
@@ -38,6 +39,16 @@ public:
     // signature id, 0 when the selection is refused (lastSelectError(): a NaN response, a keypoint outside the grid, sizes that do not match).
     int update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
                std::vector<int>& wordIds);
+    // The same for an RGB-D frame, with the depth stage in front (Memory.cpp:5683-5694, :5911-5915): the keypoints' 3-D points by
+    // util3d::generateKeypoints3DDepth and Feature2D::filterKeypointsByDepth's 3-D overload with Kp/MinDepth and Kp/MaxDepth (0, 0) -- ONE
+    // lcd_keypoints_3d call that compacts descriptors, responses and points (without an engine: Keypoints3D's host code) --, then the
+    // selection, the frame and the expansion as above over the keypoints that are left.  keptIndex: the features that passed the depth
+    // filter, ascending; wordIds and keypoints3D (x, y, z each) have one entry per kept feature.  Returns 0 when a stage is refused.
+    int update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
+               const DepthImage& depth, const std::vector<DepthCamera>& cameras, std::vector<int>& wordIds, std::vector<float>& keypoints3D,
+               std::vector<int>& keptIndex);
+    float getMinDepth() const { return _minDepth; }
+    float getMaxDepth() const { return _maxDepth; }
     int getMaxFeatures() const { return _maxFeatures; }
     int getGridRows() const { return _gridRows; }
     int getGridCols() const { return _gridCols; }
@@ -131,6 +142,7 @@ private:
     std::set<int> _stMem, _workingMem;
     int _maxStMemSize;                              // Mem/STMSize (Parameters.h: 10)
     int _maxFeatures, _gridRows, _gridCols;         // Kp/MaxFeatures (500), Kp/GridRows (1), Kp/GridCols (1)
+    float _minDepth, _maxDepth;                     // Kp/MinDepth (0), Kp/MaxDepth (0)
     std::string _selectError;
     // quantises `forQuantization` as signature `id` the call-by-call way; rawIndex (may be NULL): its rows' places among the `rows` features
     bool quantizeSelected(const Mat& forQuantization, const std::vector<int>* rawIndex, int rows, int id, std::list<int>& wordIds);

@@ -2,11 +2,13 @@
 // host mirror exactly as they drive the oracle (same call sequence, same argument meaning).  Not part of lcd.h.
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 
 #include "BayesFilterHip.h"
 #include "DbLoaderHip.h"
 #include "FeatureSelect.h"
+#include "Keypoints3D.h"
 #include "MemoryHip.h"
 #include "RtabmapHip.h"
 
@@ -159,6 +161,75 @@ int hmem_update_select(void* h, const void* desc, int rows, int cols, int type, 
                                            points ? std::vector<float>(points, points + 2 * (size_t)rows) : std::vector<float>(), imageWidth, imageHeight, ids);
     for (size_t i = 0; i < ids.size(); ++i) outIds[i] = ids[i];
     return id;
+}
+// cameras as the Python glue passes them: nCameras x 20 floats -- fx, fy, cx, cy, imageWidth, imageHeight, hasLocalTransform, 0, then the 3 x 4 transform
+static std::vector<DepthCamera> make_cameras(const float* cameras, int nCameras) {
+    std::vector<DepthCamera> cams((size_t)(nCameras > 0 ? nCameras : 0));
+    for (size_t c = 0; c < cams.size(); ++c) {
+        const float* m = cameras + 20 * c;
+        DepthCamera& D = cams[c];
+        D.fx = m[0]; D.fy = m[1]; D.cx = m[2]; D.cy = m[3]; D.imageWidth = (int)m[4]; D.imageHeight = (int)m[5]; D.hasLocalTransform = m[6] != 0.0f;
+        std::copy(m + 8, m + 20, D.localTransform);
+    }
+    return cams;
+}
+static DepthImage make_depth(const void* data, long long pitchBytes, int width, int height, int type) {
+    DepthImage image;
+    image.data = data; image.pitchBytes = pitchBytes; image.width = width; image.height = height; image.type = type;
+    return image;
+}
+// the same for an RGB-D frame (MemoryHip::update with a depth image and cameras).  depthType: 0 u16 millimetres, 1 f32 metres.  outIds[rows],
+// outXyz[3 rows] and outKept[rows] receive one entry per feature the depth filter kept; *outKeptCount their number
+int hmem_update_depth(void* h, const void* desc, int rows, int cols, int type, const float* responses, const float* points, int imageWidth,
+                      int imageHeight, const void* depth, long long pitchBytes, int depthWidth, int depthHeight, int depthType,
+                      const float* cameras, int nCameras, int* outIds, float* outXyz, int* outKept, int* outKeptCount) {
+    const std::vector<DepthCamera> cams = make_cameras(cameras, nCameras);
+    const DepthImage image = make_depth(depth, pitchBytes, depthWidth, depthHeight, depthType);
+    std::vector<int> ids, kept;
+    std::vector<float> xyz;
+    const int id = ((MemoryHip*)h)->update(make_mat(desc, rows, cols, type), std::vector<float>(responses, responses + rows),
+                                           std::vector<float>(points, points + 2 * (size_t)rows), imageWidth, imageHeight, image, cams, ids, xyz, kept);
+    *outKeptCount = id ? (int)kept.size() : 0;
+    if (!id) return 0;
+    std::copy(ids.begin(), ids.end(), outIds);
+    std::copy(xyz.begin(), xyz.end(), outXyz);
+    std::copy(kept.begin(), kept.end(), outKept);
+    return id;
+}
+void* hmem_create_depth(int strategy, int incremental, float nndr, int together, int device, int stmSize, int maxFeatures, int gridRows, int gridCols,
+                        float minDepth, float maxDepth) {
+    ParametersMap p = make_params(strategy, incremental, nndr, together, "");
+    p["Mem/STMSize"] = std::to_string(stmSize);
+    p["Kp/MaxFeatures"] = std::to_string(maxFeatures);
+    p["Kp/GridRows"] = std::to_string(gridRows);
+    p["Kp/GridCols"] = std::to_string(gridCols);
+    char text[2][32];                                                  // nine digits: the float comes back as it was given
+    snprintf(text[0], sizeof text[0], "%.9g", (double)minDepth);
+    snprintf(text[1], sizeof text[1], "%.9g", (double)maxDepth);
+    p["Kp/MinDepth"] = text[0];
+    p["Kp/MaxDepth"] = text[1];
+    return new MemoryHip(p, device);
+}
+// Keypoints3D's three functions (no engine involved).  1 = done (the filters: the number kept), 0 / -1 = refused
+int hk3_generate(const float* points, int n, const void* depth, long long pitchBytes, int width, int height, int type, const float* cameras,
+                 int nCameras, float minDepth, float maxDepth, float* outXyz) {
+    const std::vector<DepthCamera> cams = make_cameras(cameras, nCameras);
+    const DepthImage image = make_depth(depth, pitchBytes, width, height, type);
+    return Keypoints3D::generateKeypoints3DDepth(points, n, image, cams.data(), nCameras, minDepth, maxDepth, outXyz) ? 1 : 0;
+}
+int hk3_filter_3d(const float* xyz, int n, float minDepth, float maxDepth, int* outKept) {
+    std::vector<int> kept;
+    if (!Keypoints3D::filterKeypointsByDepth(xyz, n, minDepth, maxDepth, kept)) return -1;
+    std::copy(kept.begin(), kept.end(), outKept);
+    return (int)kept.size();
+}
+int hk3_filter_pixel(const float* points, int n, const void* depth, long long pitchBytes, int width, int height, int type, float minDepth,
+                     float maxDepth, int* outKept) {
+    const DepthImage image = make_depth(depth, pitchBytes, width, height, type);
+    std::vector<int> kept;
+    if (!Keypoints3D::filterKeypointsByDepth(points, n, image, minDepth, maxDepth, kept)) return -1;
+    std::copy(kept.begin(), kept.end(), outKept);
+    return (int)kept.size();
 }
 const char* hmem_select_error(void* h) { return ((MemoryHip*)h)->lastSelectError().c_str(); }
 // FeatureSelect's three functions (no engine involved).  1 = done, 0 = refused

@@ -64,6 +64,12 @@ def lib():
         L.hmem_create_select.restype = vp
         L.hmem_create_select.argtypes = [ci, ci, cf, ci, ci, ci, ci, ci, ci]
         L.hmem_update_select.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp]
+        L.hmem_create_depth.restype = vp
+        L.hmem_create_depth.argtypes = [ci, ci, cf, ci, ci, ci, ci, ci, ci, cf, cf]
+        L.hmem_update_depth.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, C.c_longlong, ci, ci, ci, vp, ci, vp, vp, vp, vp]
+        L.hk3_generate.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, vp, ci, cf, cf, vp]
+        L.hk3_filter_3d.argtypes = [vp, ci, cf, cf, vp]
+        L.hk3_filter_pixel.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, cf, cf, vp]
         L.hmem_select_error.argtypes = [vp]
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -155,6 +161,51 @@ def expand_word_ids(n, index, word_ids, first_new_word_id=0):
     out = np.zeros(max(int(n), 1), np.int32)
     ok = lib().hfs_expand_word_ids(int(n), _p(i), _p(w), i.shape[0], int(first_new_word_id), _p(out))
     return out[:int(n)].copy() if ok else None
+
+
+# ---- Keypoints3D (rtabmap_amd/host/Keypoints3D.h): the depth stage's rule of include/lcd.h as plain host code, no engine
+def _cameras_flat(cameras):
+    """dicts fx, fy, cx, cy [, image_width, image_height, transform (12 floats or None)] -> [n x 20] float32 as c_shim.cpp reads them"""
+    out = np.zeros((len(cameras), 20), np.float32)
+    for c, m in enumerate(cameras):
+        t = m.get("transform")
+        out[c, :8] = [m["fx"], m["fy"], m["cx"], m["cy"], m.get("image_width", 0), m.get("image_height", 0), 0 if t is None else 1, 0]
+        if t is not None:
+            out[c, 8:] = np.asarray(t, np.float32).reshape(12)
+    return out
+
+
+def _depth_args(depth, width=None):
+    d = depth if depth.strides[1] == depth.itemsize else np.ascontiguousarray(depth)
+    assert d.dtype in (np.uint16, np.float32) and d.ndim == 2
+    return d, (d.ctypes.data_as(C.c_void_p), d.strides[0], int(d.shape[1] if width is None else width), d.shape[0], 0 if d.dtype == np.uint16 else 1)
+
+
+def generate_keypoints_3d_depth(points, depth, cameras, min_depth=0.0, max_depth=0.0, width=None):
+    """util3d::generateKeypoints3DDepth -> [n x 3] float32, or None where the host mirror refuses"""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    d, dargs = _depth_args(depth, width)
+    cams = _cameras_flat(cameras)
+    out = np.zeros((max(p.shape[0], 1), 3), np.float32)
+    ok = lib().hk3_generate(_p(p), p.shape[0], *dargs, _p(cams), cams.shape[0], float(min_depth), float(max_depth), _p(out))
+    return out[:p.shape[0]].copy() if ok else None
+
+
+def filter_keypoints_by_depth_3d(xyz, min_depth=0.0, max_depth=0.0):
+    """Feature2D::filterKeypointsByDepth, the 3-D overload -> the kept indices, or None where refused"""
+    x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(max(x.shape[0], 1), np.int32)
+    n = lib().hk3_filter_3d(_p(x), x.shape[0], float(min_depth), float(max_depth), _p(out))
+    return None if n < 0 else out[:n].copy()
+
+
+def filter_keypoints_by_depth_pixel(points, depth, min_depth=0.0, max_depth=0.0, width=None):
+    """... the 2-D overload -> the kept indices, or None where refused"""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    d, dargs = _depth_args(depth, width)
+    out = np.zeros(max(p.shape[0], 1), np.int32)
+    n = lib().hk3_filter_pixel(_p(p), p.shape[0], *dargs, float(min_depth), float(max_depth), _p(out))
+    return None if n < 0 else out[:n].copy()
 
 
 class VWDictionaryHip:
@@ -282,10 +333,14 @@ class VWDictionaryHip:
 
 class MemoryHip:
     def __init__(self, strategy=kNNBruteForceHIP, incremental=True, nndr=0.8, new_words_compared_together=True,
-                 dictionary_path="", device=0, stm_size=10, _handle=None, _owner=None, max_features=None, grid_rows=1, grid_cols=1):
+                 dictionary_path="", device=0, stm_size=10, _handle=None, _owner=None, max_features=None, grid_rows=1, grid_cols=1,
+                 min_depth=None, max_depth=0.0):
         self._owner = _owner                    # a RtabmapHip owns its memory
         if _handle is not None:
             self.h = _handle
+        elif min_depth is not None:             # ... and Kp/MinDepth, Kp/MaxDepth: update_depth() honours them
+            self.h = lib().hmem_create_depth(strategy, int(incremental), float(nndr), int(new_words_compared_together), device, int(stm_size),
+                                             int(500 if max_features is None else max_features), int(grid_rows), int(grid_cols), float(min_depth), float(max_depth))
         elif max_features is not None:          # Kp/MaxFeatures, Kp/GridRows, Kp/GridCols: update_select() honours them
             self.h = lib().hmem_create_select(strategy, int(incremental), float(nndr), int(new_words_compared_together), device, int(stm_size),
                                               int(max_features), int(grid_rows), int(grid_cols))
@@ -324,6 +379,23 @@ class MemoryHip:
         out = np.zeros(max(rows, 1), np.int32)
         sid = lib().hmem_update_select(self.h, _p(desc), rows, desc.shape[1], _type_of(desc), _p(r), _p(p), int(image_size[0]), int(image_size[1]), _p(out))
         return sid, out[:rows].tolist()
+
+    def update_depth(self, desc, responses, points, image_size, depth, cameras, width=None):
+        """MemoryHip::update for an RGB-D frame: the depth stage (Kp/MinDepth, Kp/MaxDepth), then the selection, the frame and the expansion
+        -> (signature id, one id per KEPT feature, their 3-D points [k x 3], their indices); id 0: refused (select_error())"""
+        desc = np.ascontiguousarray(desc)
+        rows = desc.shape[0]
+        r = np.ascontiguousarray(responses, dtype=np.float32).reshape(-1)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        if r.shape[0] != rows or p.shape[0] != rows:
+            raise ValueError("update_depth: one response and one point per descriptor")
+        d, dargs = _depth_args(depth, width)
+        cams = _cameras_flat(cameras)
+        ids, xyz, kept = np.zeros(max(rows, 1), np.int32), np.zeros((max(rows, 1), 3), np.float32), np.zeros(max(rows, 1), np.int32)
+        k = C.c_int(0)
+        sid = lib().hmem_update_depth(self.h, _p(desc), rows, desc.shape[1], _type_of(desc), _p(r), _p(p), int(image_size[0]), int(image_size[1]),
+                                      *dargs, _p(cams), cams.shape[0], _p(ids), _p(xyz), _p(kept), C.addressof(k))
+        return sid, ids[:k.value].tolist(), xyz[:k.value].copy(), kept[:k.value].copy()
 
     def select_error(self):
         return lib().hmem_select_error(self.h).decode()
