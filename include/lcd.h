@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_estimate_motion_3d with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -606,6 +606,106 @@ int lcd_keypoints_3d(lcd_engine* h, const lcd_keypoints_3d_args* a);
  * 16-byte vectors where their addresses and sizes allow); offsets, images and cameras on the HOST (read during the call); enqueued on the
  * engine stream, not synchronised */
 int lcd_keypoints_3d_dev(lcd_engine* h, const lcd_keypoints_3d_args* a);
+
+/* ---- 3-D to 3-D motion estimation, stateless: the verification behind a loop-closure hypothesis for a caller who holds both frames' word
+ * ids and 3-D points in device memory (RegistrationVis.cpp:1823-1871 with Vis/EstimationType = 0).  util3d::estimateMotion3DTo3D
+ * (util3d_motion_estimation.cpp:730-807), util3d::findCorrespondences (the map overload, util3d_correspondences.cpp:364-408) behind
+ * uMultimapToMapUnique (UStl.h:503-516) and the body of util3d::transformFromXYZCorrespondences (util3d_registration.cpp:63-238) are
+ * reproduced exactly, integers and control flow.  What that body calls in PCL (RandomSampleConsensus, SampleConsensusModelRegistration,
+ * TransformationEstimationSVD) is not in the reference tree: the sampling, the rigid fit and every summation order are the ENGINE'S, written
+ * out here, as the window of lcd_match_guided and the cross-check of lcd_match_pairs are.  No bit parity with a PCL build is claimed.
+ * Stateless exactly as lcd_keypoints_3d: the calls borrow the handle's device and stream, read and write nothing of its state, do not complete
+ * what a pipelined handle owes, and keep their job table and scratch where lcd_match_pairs keeps its own.  A call serves any number of pairs:
+ * pair i owns the rows [from_offsets[i], from_offsets[i+1]) of from_word_ids / from_xyz and [to_offsets[i], to_offsets[i+1]) of the to-arrays.
+ *
+ * The rule, per pair.  Point arithmetic is fp32, every operation rounded on its own (nothing fused), IEEE division and square root, only
+ * + - x / sqrt.  "fp64" marks the few places that are double.
+ *   1. Unique ids (UStl.h:503-516).  A row of a frame takes part iff its word id occurs exactly once in that frame.  No sign test.
+ *   2. Correspondences (util3d_correspondences.cpp:372-407, maxDepth = 0 at :751).  The participating from-ids that also participate in `to`,
+ *      ascending by id as signed integers; an id is kept iff all six coordinates are finite and neither point is (0, 0, 0).  m = the number
+ *      kept, `matches` = the kept ids, correspondence j = the j-th of them.  m < min_inliers (:762) or m < 3 (util3d_registration.cpp:82, a
+ *      separate guard that also holds for min_inliers < 3): LCD_M3D_FEW_CORRESPONDENCES.
+ *   3. Hypotheses.  h = 0 .. iterations - 1 draws three distinct correspondence indices: with uint32 arithmetic and
+ *      mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16,
+ *      draw k = mix(mix(seed + h) * 3 + k) % m for k = 0, 1, ..; a draw equal to an earlier kept one is skipped; a hypothesis without three
+ *      distinct indices after 16 draws is invalid and never wins.  Neither the pair's position nor the batch enters.  All hypotheses are
+ *      evaluated (no adaptive stop).
+ *   4. The rigid fit of an ordered set of n correspondences (from-points p onto to-points q, R p + t ~ q).
+ *      Sums: SUM(e_0 .. e_{n-1}) is defined for 256 lanes: lane l starts at +0.0f and adds e_l, e_{l+256}, .. in ascending order; then for
+ *      s = 128, 64, .., 1 lane l < s adds lane l + s; the sum is lane 0.  (For n = 3 this is ((0 + e_0) + (0 + e_2)) + (0 + e_1).)
+ *      cp_a = SUM(p_a) / float(n), cq_a = SUM(q_a) / float(n) for a = x, y, z; S_ab = SUM((p_a - cp_a) * (q_b - cq_b)) for the nine (a, b).
+ *      Horn's matrix, symmetric: N00 = (Sxx + Syy) + Szz, N01 = Syz - Szy, N02 = Szx - Sxz, N03 = Sxy - Syx, N11 = (Sxx - Syy) - Szz,
+ *      N12 = Sxy + Syx, N13 = Szx + Sxz, N22 = (Syy - Sxx) - Szz, N23 = Syz + Szy, N33 = (Szz - Sxx) - Syy.
+ *      Cyclic Jacobi, V = identity, LCD_M3D_SWEEPS sweeps, each over (p, q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  A pair with a_pq == 0 is
+ *      skipped.  Otherwise theta = (a_qq - a_pp) / (2 * a_pq); t = sgn(theta) / (|theta| + sqrt(theta * theta + 1)) with sgn(theta) = -1 for
+ *      theta < 0 and +1 otherwise; a theta (or theta * theta) that overflows to infinity therefore gives t = +-0 and a rotation by nothing.
+ *      c = 1 / sqrt(t * t + 1), s = t * c; a_pp -= t * a_pq, a_qq += t * a_pq, a_pq = 0; for the other two r: a_rp' = c * a_rp - s * a_rq,
+ *      a_rq' = s * a_rp + c * a_rq (both halves of the matrix kept); for every r: v_rp' = c * v_rp - s * v_rq, v_rq' = s * v_rp + c * v_rq.
+ *      The column of V under the largest diagonal entry, the lowest index on ties, is the quaternion (w, x, y, z) after division by
+ *      sqrt(((w*w + x*x) + y*y) + z*z).  R00 = 1 - 2 * (yy + zz), R01 = 2 * (xy - wz), R02 = 2 * (xz + wy), R10 = 2 * (xy + wz),
+ *      R11 = 1 - 2 * (xx + zz), R12 = 2 * (yz - wx), R20 = 2 * (xz - wy), R21 = 2 * (yz + wx), R22 = 1 - 2 * (xx + yy);
+ *      t_r = cq_r - ((R_r0 * cp_x + R_r1 * cp_y) + R_r2 * cp_z).  A hypothesis is the fit of its three correspondences in draw order.
+ *   5. Score.  d2 = (dx*dx + dy*dy) + dz*dz with dx = (((R00 * p_x + R01 * p_y) + R02 * p_z) + t_x) - q_x, dy and dz alike.  A correspondence
+ *      is an inlier of a model iff double(d2) < thr2, strictly, thr2 = threshold * threshold in fp64.  The best hypothesis has the most
+ *      inliers under inlier_distance, the lowest h on ties; no valid hypothesis or a best count of 0: LCD_M3D_NO_MODEL (:228).
+ *   6. Selection with the best model under inlier_distance: `inliers`, ascending correspondence index, and their d2 ("the last selection").
+ *   7. Refinement, refine_iterations > 0: the loop of util3d_registration.cpp:115-196 as written -- error_threshold starts at inlier_distance;
+ *      each pass fits prev_inliers (step 4, in their order; fewer than three leave the model as it is), records their number, selects under
+ *      error_threshold; an empty selection counts an iteration and `continue`s into the loop's condition; otherwise variance, then
+ *      error_threshold = min(inlier_distance, 3.0 * sqrt(variance)) in fp64, swap, the size test with the oscillation test on the last four
+ *      recorded sizes, the element-wise comparison; `while (inlier_changed && ++refine_iterations < refineIterations)`; the final swap makes
+ *      the set that was fitted LAST the inliers, and the model is the last fitted one.  computeVariance = 2.1981 * double(median), the median
+ *      the element of rank (size >> 1) in ascending order among the d2 of the last selection.
+ *   8. Result (:198-222, util3d_motion_estimation.cpp:787-806).  Fewer than 3 inliers: LCD_M3D_FEW_INLIERS.  Otherwise variance =
+ *      computeVariance of the last selection, out_inliers = matches[inlier] and out_n_inliers are returned, and the pose is the inverse of
+ *      the model: rows of R^T, and -(((R0r * t_x) + (R1r * t_y)) + (R2r * t_z)) behind row r; it is returned iff inliers >= min_inliers
+ *      (LCD_M3D_OK), otherwise twelve zeros (LCD_M3D_BELOW_MIN_INLIERS).
+ *   9. Twelve zero floats mean no transform (Transform::isNull); then out_status != LCD_M3D_OK.  With LCD_M3D_FEW_CORRESPONDENCES,
+ *      LCD_M3D_NO_MODEL and LCD_M3D_FEW_INLIERS out_n_inliers = 0 and out_variance = 1.0; out_matches / out_n_matches are always returned.
+ *   A NaN that coordinates near the limits of fp32 may produce inside a fit is no inlier of anything; its sign and payload are not pinned.
+ * Outputs: per pair out_transform [12], out_status, out_n_matches, out_n_inliers, out_variance; in the pair's FROM-region of out_matches the
+ * ids ascending, of out_inliers the ids in correspondence order, the rest of both regions 0.  Outputs must not overlap inputs.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on a side of a pair,
+ * n_pairs > 65535, iterations > 65535 or a handle of a sharded vocabulary: LCD_ERR_UNSUPPORTED; iterations < 1 (the reference's assertion),
+ * an inlier_distance that is not finite or <= 0, refine_iterations < 0, min_inliers < 1, n_pairs < 0, offsets that are missing, do not start
+ * at 0 or decrease, a NULL pointer where rows or outputs exist, or a wrong struct_size: LCD_ERR_INVALID.  n_pairs == 0 returns LCD_OK.
+ * One kernel launch per call whatever the batch: one workgroup of 256 threads per pair. */
+#define LCD_M3D_SWEEPS 5
+enum lcd_motion_3d_status {
+    LCD_M3D_OK = 0,
+    LCD_M3D_FEW_CORRESPONDENCES = 1,  /* m < min_inliers, or m < 3 */
+    LCD_M3D_NO_MODEL = 2,             /* no hypothesis with an inlier */
+    LCD_M3D_FEW_INLIERS = 3,          /* fewer than 3 inliers behind the refinement */
+    LCD_M3D_BELOW_MIN_INLIERS = 4     /* inliers and variance returned, no transform */
+};
+typedef struct lcd_motion_3d_args {
+    int32_t struct_size;            /* sizeof(lcd_motion_3d_args) */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t min_inliers;            /* Vis/MinInliers, >= 1 */
+    int32_t iterations;             /* Vis/Iterations, 1 .. 65535 */
+    int32_t refine_iterations;      /* Vis/RefineIterations, >= 0 */
+    uint32_t seed;
+    double inlier_distance;         /* Vis/InlierDistance, finite, > 0 */
+    const int32_t* from_word_ids;   /* [Nf] */
+    const float* from_xyz;          /* [Nf x 3] */
+    const int32_t* to_word_ids;     /* [Nt] */
+    const float* to_xyz;            /* [Nt x 3] */
+    const int64_t* from_offsets;    /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    const int64_t* to_offsets;      /* HOST, [n_pairs + 1] */
+    float* out_transform;           /* [n_pairs x 12], row-major 3 x 4 */
+    int32_t* out_status;            /* [n_pairs], lcd_motion_3d_status */
+    int32_t* out_n_matches;         /* [n_pairs] */
+    int32_t* out_n_inliers;         /* [n_pairs] */
+    double* out_variance;           /* [n_pairs] */
+    int32_t* out_matches;           /* [Nf] */
+    int32_t* out_inliers;           /* [Nf] */
+} lcd_motion_3d_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a);
+/* ids, points and out_* in DEVICE memory (4-byte aligned, out_variance 8-byte), the offsets on the HOST (read during the call); enqueued on the
+ * engine stream, not synchronised */
+int lcd_estimate_motion_3d_dev(lcd_engine* h, const lcd_motion_3d_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

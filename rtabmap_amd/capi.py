@@ -30,7 +30,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -135,6 +135,17 @@ class LcdKeypoints3dArgs(C.Structure):
                 ("out_xyz", C.c_void_p), ("out_points", C.c_void_p), ("out_response", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p)]
 
 
+class LcdMotion3dArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("min_inliers", C.c_int32), ("iterations", C.c_int32),
+                ("refine_iterations", C.c_int32), ("seed", C.c_uint32), ("inlier_distance", C.c_double), ("from_word_ids", C.c_void_p),
+                ("from_xyz", C.c_void_p), ("to_word_ids", C.c_void_p), ("to_xyz", C.c_void_p), ("from_offsets", C.c_void_p),
+                ("to_offsets", C.c_void_p), ("out_transform", C.c_void_p), ("out_status", C.c_void_p), ("out_n_matches", C.c_void_p),
+                ("out_n_inliers", C.c_void_p), ("out_variance", C.c_void_p), ("out_matches", C.c_void_p), ("out_inliers", C.c_void_p)]
+
+
+LCD_M3D_OK, LCD_M3D_FEW_CORRESPONDENCES, LCD_M3D_NO_MODEL, LCD_M3D_FEW_INLIERS, LCD_M3D_BELOW_MIN_INLIERS = 0, 1, 2, 3, 4  # lcd_motion_3d_status
+
+
 KP3D_FILTERS = {"keep_all": LCD_KP3D_KEEP_ALL, "filter_3d": LCD_KP3D_FILTER_3D, "filter_pixel": LCD_KP3D_FILTER_PIXEL}
 
 
@@ -214,6 +225,8 @@ def load():
     L.lcd_expand_word_ids_dev.argtypes = [vp, C.POINTER(LcdExpandArgs)]
     L.lcd_keypoints_3d.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
     L.lcd_keypoints_3d_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
+    L.lcd_estimate_motion_3d.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
+    L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -659,6 +672,46 @@ class Engine:
         a.out_count, a.out_index, a.out_xyz, a.out_points = ptr(d_count), ptr(d_index), ptr(d_xyz), ptr(d_out_points)
         a.out_response, a.out_rows, a.out_aux = ptr(d_out_response), ptr(d_out_rows), ptr(d_out_aux)
         self._ck(self.L.lcd_keypoints_3d_dev(self.h, C.byref(a)))
+
+    # ---- 3-D to 3-D motion estimation (stateless; include/lcd.h has the rule)
+    def estimate_motion_3d(self, from_ids, from_xyz, from_offsets, to_ids, to_xyz, to_offsets, min_inliers=20, inlier_distance=0.1, iterations=300,
+                           refine_iterations=5, seed=0, struct_size=None):
+        """lcd_estimate_motion_3d over host arrays, all pairs concatenated -> dict(transform [n_pairs x 12], status, n_matches, n_inliers,
+        variance [n_pairs], matches [Nf], inliers [Nf]); outputs start as -1 / NaN so that what the call left alone shows"""
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fi, ti = np.ascontiguousarray(from_ids, dtype=np.int32).reshape(-1), np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
+        fx, tx = np.ascontiguousarray(from_xyz, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+        n_pairs, n = fo.shape[0] - 1, fi.shape[0]
+        out = dict(transform=np.full((max(n_pairs, 1), 12), np.nan, np.float32), status=np.full(max(n_pairs, 1), -1, np.int32),
+                   n_matches=np.full(max(n_pairs, 1), -1, np.int32), n_inliers=np.full(max(n_pairs, 1), -1, np.int32),
+                   variance=np.full(max(n_pairs, 1), np.nan, np.float64), matches=np.full(max(n, 1), -1, np.int32), inliers=np.full(max(n, 1), -1, np.int32))
+        a = LcdMotion3dArgs(C.sizeof(LcdMotion3dArgs) if struct_size is None else struct_size, n_pairs, int(min_inliers), int(iterations),
+                            int(refine_iterations), int(seed) & 0xFFFFFFFF, float(inlier_distance))
+        a.from_word_ids, a.from_xyz, a.to_word_ids, a.to_xyz = _p(fi), _p(fx), _p(ti), _p(tx)
+        a.from_offsets, a.to_offsets = fo.ctypes.data, to.ctypes.data
+        a.out_transform, a.out_status, a.out_n_matches, a.out_n_inliers = _p(out["transform"]), _p(out["status"]), _p(out["n_matches"]), _p(out["n_inliers"])
+        a.out_variance, a.out_matches, a.out_inliers = _p(out["variance"]), _p(out["matches"]), _p(out["inliers"])
+        self._ck(self.L.lcd_estimate_motion_3d(self.h, C.byref(a)))
+        for k in ("transform", "status", "n_matches", "n_inliers", "variance"):
+            out[k] = out[k][:max(n_pairs, 0)]
+        out["matches"], out["inliers"] = out["matches"][:n], out["inliers"][:n]
+        return out
+
+    def estimate_motion_3d_dev(self, d_from_ids, d_from_xyz, from_offsets, d_to_ids, d_to_xyz, to_offsets, d_transform, d_status, d_n_matches,
+                               d_n_inliers, d_variance, d_matches, d_inliers, min_inliers=20, inlier_distance=0.1, iterations=300,
+                               refine_iterations=5, seed=0):
+        """lcd_estimate_motion_3d_dev on torch tensors of the engine's device (the offsets stay on the host).  Enqueued, not synchronised."""
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        a = LcdMotion3dArgs(C.sizeof(LcdMotion3dArgs), fo.shape[0] - 1, int(min_inliers), int(iterations), int(refine_iterations),
+                            int(seed) & 0xFFFFFFFF, float(inlier_distance))
+        a.from_word_ids, a.from_xyz, a.to_word_ids, a.to_xyz = ptr(d_from_ids), ptr(d_from_xyz), ptr(d_to_ids), ptr(d_to_xyz)
+        a.from_offsets, a.to_offsets = fo.ctypes.data, to.ctypes.data
+        a.out_transform, a.out_status, a.out_n_matches, a.out_n_inliers = ptr(d_transform), ptr(d_status), ptr(d_n_matches), ptr(d_n_inliers)
+        a.out_variance, a.out_matches, a.out_inliers = ptr(d_variance), ptr(d_matches), ptr(d_inliers)
+        self._ck(self.L.lcd_estimate_motion_3d_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

@@ -1,0 +1,432 @@
+// motion_3d.hip -- lcd_estimate_motion_3d and its _dev form: util3d::estimateMotion3DTo3D (reference util3d_motion_estimation.cpp:730-807,
+// RegistrationVis.cpp:1823-1871 with Vis/EstimationType = 0) for a caller who holds both frames' word ids and 3-D points in device memory.
+// The rule is include/lcd.h's; its arithmetic and its control flow (solve, refine) are motion_3d_rule.h's, compiled here for the device and
+// in host/Motion3D.cpp for the mirror.
+//   motion_3d_kernel: one launch per call, one workgroup of 256 threads per pair, in phases behind barriers:
+//     (a) join: both frames' 64-bit keys (id || row) are sorted in LDS (compact_body.cuh's network); a from-key whose neighbours carry other
+//         ids is looked up in the to-keys by binary search, the predicate is applied and the survivors are compacted in ascending id with the
+//         ballot scan.  Their ids go to out_matches, their six coordinates (one plane each) to the call's scratch -- and, when they fit
+//         beside the hypotheses, into the LDS the keys no longer need; larger pairs read them from the scratch through the same pointer.
+//     (b) hypotheses in chunks of 256: thread h draws and solves its three-point fit (the Jacobi sweeps fully unrolled) and leaves 12 floats
+//         in LDS; each wave takes hypotheses in turn, its lanes stride over the correspondences and count with a ballot, lane 0 raises a
+//         64-bit LDS maximum (count << 32 | ~h).
+//     (c) selection, refinement and median: the sums of a fit are the rule's (256 lane partials, halving tree in LDS), the median is a
+//         radix select over the bit patterns of the last selection's d2, the loop's scalars are the same in every thread.
+//     (d) outputs.
+// Nothing of the engine is read or written: the job table is StatelessScratch's, the per-row scratch its d_small.
+#include "engine_impl.h"
+#include "compact_body.cuh"
+#include "motion_3d_rule.h"
+
+#include <cmath>
+#include <vector>
+
+static_assert(sizeof(lcd_motion_3d_args) == 136, "lcd_motion_3d_args: the layout include/lcd.h documents (LP64)");
+static_assert(LCD_M3D_OK == lcd::m3d::ST_OK && LCD_M3D_FEW_CORRESPONDENCES == lcd::m3d::ST_FEW_CORRESPONDENCES && LCD_M3D_NO_MODEL == lcd::m3d::ST_NO_MODEL &&
+              LCD_M3D_FEW_INLIERS == lcd::m3d::ST_FEW_INLIERS && LCD_M3D_BELOW_MIN_INLIERS == lcd::m3d::ST_BELOW_MIN_INLIERS, "lcd_motion_3d_status");
+static_assert(LCD_M3D_SWEEPS == lcd::m3d::SWEEPS, "the sweep count include/lcd.h documents");
+
+namespace lcd {
+namespace {
+
+constexpr int BLOCK = m3d::LANES, WAVES = BLOCK / 64;
+constexpr int MAX_ROWS = m3d::MAX_ROWS;
+constexpr int MODEL_FLOATS = BLOCK * 12, RED_FLOATS = BLOCK * 9;
+constexpr size_t FIXED_BYTES = (size_t)(MODEL_FLOATS + RED_FLOATS) * 4;   // what phases (b) and (c) keep in the carve beside the coordinates
+constexpr int SCRATCH_WORDS = 9;                                         // per from-row: six coordinates, d2, two index sets
+
+inline size_t key_bytes(int p_max) { return (size_t)2 * padded(p_max) * 8; }
+constexpr size_t LDS_LIMIT = (size_t)2 * (MAX_ROWS + (MAX_ROWS >> 3)) * 8;   // key_bytes(MAX_ROWS): 144 KiB of the 160 KiB a workgroup may have
+
+struct M3dJob {
+    int64_t first_from, first_to;            // the pair's first row in the from- / to-arrays
+    int32_t n_from, n_to;
+};
+static_assert(sizeof(M3dJob) == 24, "the job table");
+
+struct M3dArgs {
+    const M3dJob* jobs;
+    int min_inliers, iterations, refine_iterations;
+    uint32_t seed;
+    double inlier_distance;
+    int p_max;                               // keys per side the LDS carve holds (a power of two >= every frame)
+    int stage_cap;                           // correspondences whose coordinates fit the carve behind the fixed part
+    const int32_t* from_ids; const float* from_xyz; const int32_t* to_ids; const float* to_xyz;
+    uint32_t* scratch;                       // [SCRATCH_WORDS x Nf] words; a pair's part starts at SCRATCH_WORDS x first_from
+    float* out_transform; int32_t* out_status; int32_t* out_n_matches; int32_t* out_n_inliers; double* out_variance;
+    int32_t* out_matches; int32_t* out_inliers;
+};
+
+extern __shared__ __attribute__((aligned(16))) unsigned char m3_smem[];
+
+// the backend of m3d::solve as a workgroup: every method is called by all 256 threads and returns the same value to each
+struct GroupBackend {
+    int m, tid;
+    const float* X;                          // coordinate c of correspondence i: X[c * stride + i]; LDS or the scratch
+    int stride;
+    uint32_t seed;
+    int iterations;
+    double thr2;
+    float* models; float* red;               // the carve: [BLOCK x 12], [9 x BLOCK]
+    int* valid; int* hist; int* wsum; unsigned long long* best; float* cur;
+    float* d2; int32_t* prev; int32_t* next;
+    int n_prev, n_next, n_last;
+
+    __device__ __forceinline__ bool hypothesis(uint32_t h, float model[12]) const {
+        int i0, i1, i2;
+        if (!m3d::draw3(seed, h, (uint32_t)m, i0, i1, i2)) return false;
+        float P[3][3], Q[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            P[0][a] = X[a * stride + i0]; Q[0][a] = X[(3 + a) * stride + i0];
+            P[1][a] = X[a * stride + i1]; Q[1][a] = X[(3 + a) * stride + i1];
+            P[2][a] = X[a * stride + i2]; Q[2][a] = X[(3 + a) * stride + i2];
+        }
+        m3d::fit3(P, Q, m3d::SWEEPS, model);
+        return true;
+    }
+    __device__ __forceinline__ float distance(const float model[12], int i) const {
+        return m3d::dist2(model, X[i], X[stride + i], X[2 * stride + i], X[3 * stride + i], X[4 * stride + i], X[5 * stride + i]);
+    }
+    __device__ __forceinline__ unsigned long long ransac() {
+        const int lane = tid & 63, wave = tid >> 6;
+        if (tid == 0) *best = 0ull;
+        __syncthreads();
+        for (int c0 = 0; c0 < iterations; c0 += BLOCK) {
+            const int h = c0 + tid;
+            float model[12];
+            const bool ok = h < iterations && hypothesis((uint32_t)h, model);
+            valid[tid] = ok ? 1 : 0;
+            if (ok) {
+#pragma unroll
+                for (int k = 0; k < 12; ++k) models[tid * 12 + k] = model[k];
+            }
+            __syncthreads();
+            const int nh = min(BLOCK, iterations - c0);
+            for (int j = wave; j < nh; j += WAVES) {
+                if (!valid[j]) continue;
+                float w[12];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) w[k] = models[j * 12 + k];
+                uint32_t count = 0;
+                for (int i0 = 0; i0 < m; i0 += 64) {
+                    const int i = i0 + lane;
+                    const bool in = i < m && (double)distance(w, i) < thr2;
+                    count += (uint32_t)__popcll(__ballot(in));
+                }
+                if (lane == 0 && count > 0) atomicMax(best, ((unsigned long long)count << 32) | (uint32_t)~(uint32_t)(c0 + j));
+            }
+            __syncthreads();
+        }
+        const unsigned long long key = *best;
+        if (key && tid == 0) {
+            float model[12];
+            (void)hypothesis(~(uint32_t)key, model);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) cur[k] = model[k];
+        }
+        __syncthreads();
+        return key;
+    }
+    // red[c * BLOCK + tid] = part[c], then the halving tree; the sums are red[c * BLOCK]; ends behind a barrier
+    template <int C>
+    __device__ __forceinline__ void tree(const float part[C]) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) red[c * BLOCK + tid] = part[c];
+        __syncthreads();
+        for (int s = BLOCK / 2; s >= 1; s >>= 1) {
+            if (tid < s) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) red[c * BLOCK + tid] = red[c * BLOCK + tid] + red[c * BLOCK + tid + s];
+            }
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ void fit_prev() {
+        const int n = n_prev;
+        if (n < 3) return;
+        float part[9];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) part[c] = 0.0f;
+        for (int i = tid; i < n; i += BLOCK) {
+            const int idx = prev[i];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) part[c] = part[c] + X[c * stride + idx];
+        }
+        tree<6>(part);
+        float cen[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) cen[c] = red[c * BLOCK] / (float)n;
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 9; ++c) part[c] = 0.0f;
+        for (int i = tid; i < n; i += BLOCK) {
+            const int idx = prev[i];
+            float dp[3], dq[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { dp[a] = X[a * stride + idx] - cen[a]; dq[a] = X[(3 + a) * stride + idx] - cen[3 + a]; }
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) {
+                    const float e = dp[a] * dq[b];
+                    part[3 * a + b] = part[3 * a + b] + e;
+                }
+        }
+        tree<9>(part);
+        if (tid == 0) {
+            float S[9], model[12];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) S[c] = red[c * BLOCK];
+            m3d::horn_fit(cen, cen + 3, S, m3d::SWEEPS, model);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) cur[k] = model[k];
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ int select(double t2) {
+        float w[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) w[k] = cur[k];
+        int count = 0;
+        for (int base = 0; base < m; base += BLOCK) {
+            const int i = base + tid;
+            float d = 0.0f;
+            bool in = false;
+            if (i < m) { d = distance(w, i); in = (double)d < t2; }
+            int total;
+            const int pos = count + block_rank(in, wsum, total);
+            if (in) { next[pos] = i; d2[pos] = d; }
+            count += total;
+        }
+        n_next = n_last = count;
+        __syncthreads();                                               // the set and its d2 are read by other threads
+        return count;
+    }
+    // radix select over the bit patterns (non-negative floats order as integers), eight bits a pass
+    __device__ __forceinline__ double variance() {
+        int rank = n_last >> 1;
+        uint32_t prefix = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < n_last; i += BLOCK) {
+                const uint32_t b = m3d::bits_of(d2[i]);
+                if ((((uint64_t)b ^ prefix) >> (shift + 8)) == 0) atomicAdd(&hist[(b >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            int before = 0, digit = 255;
+            for (int d = 0; d < 256; ++d) {
+                const int c = hist[d];
+                if (rank < before + c) { digit = d; break; }
+                before += c;
+            }
+            rank -= before;
+            prefix |= (uint32_t)digit << shift;
+            __syncthreads();
+        }
+        return m3d::VARIANCE_FACTOR * (double)m3d::float_of(prefix);
+    }
+    __device__ __forceinline__ void swap_sets() {
+        int32_t* p = prev; prev = next; next = p;
+        const int n = n_prev; n_prev = n_next; n_next = n;
+    }
+    __device__ __forceinline__ void clear_next() { n_next = 0; }
+    __device__ __forceinline__ int prev_n() const { return n_prev; }
+    __device__ __forceinline__ int next_n() const { return n_next; }
+    __device__ __forceinline__ bool same_members() const {            // (sizes are equal)
+        int differs = 0;
+        for (int i = tid; i < n_prev; i += BLOCK) differs |= prev[i] != next[i];
+        return !__syncthreads_or(differs);
+    }
+    __device__ __forceinline__ const float* model() const { return cur; }
+};
+
+__global__ __launch_bounds__(BLOCK) void motion_3d_kernel(M3dArgs a) {
+    __shared__ int wsum[WAVES];
+    __shared__ int valid[BLOCK];
+    __shared__ int hist[256];
+    __shared__ unsigned long long best;
+    __shared__ float cur[12];
+    const M3dJob J = a.jobs[blockIdx.x];
+    const int nf = J.n_from, nt = J.n_to, tid = threadIdx.x;
+    uint64_t* keys_t = reinterpret_cast<uint64_t*>(m3_smem);
+    uint64_t* keys_f = keys_t + padded(a.p_max);
+    uint32_t* scratch = a.scratch + (size_t)SCRATCH_WORDS * J.first_from;
+    float* gx = reinterpret_cast<float*>(scratch);                     // [6][nf]
+    int32_t* out_matches = a.out_matches + J.first_from;
+    int32_t* out_inliers = a.out_inliers + J.first_from;
+
+    // ---- (a) join
+    int p2t = 2, p2f = 2;
+    while (p2t < nt) p2t <<= 1;
+    while (p2f < nf) p2f <<= 1;                                        // both <= p_max
+    for (int i = tid; i < p2t; i += BLOCK) keys_t[padded(i)] = i < nt ? ((uint64_t)m3d::id_key(a.to_ids[J.first_to + i]) << 32) | (uint32_t)i : ~0ull;
+    for (int i = tid; i < p2f; i += BLOCK) keys_f[padded(i)] = i < nf ? ((uint64_t)m3d::id_key(a.from_ids[J.first_from + i]) << 32) | (uint32_t)i : ~0ull;
+    __syncthreads();
+    bitonic_sort(keys_t, p2t);
+    bitonic_sort(keys_f, p2f);
+    int m = 0;
+    for (int base = 0; base < nf; base += BLOCK) {
+        const int p = base + tid;
+        bool keep = false;
+        uint32_t idk = 0;
+        float c[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (p < nf) {
+            const uint64_t key = keys_f[padded(p)];
+            idk = (uint32_t)(key >> 32);
+            bool unique = (p == 0 || (uint32_t)(keys_f[padded(p - 1)] >> 32) != idk) && (p + 1 >= nf || (uint32_t)(keys_f[padded(p + 1)] >> 32) != idk);
+            int lo = 0, hi = nt;                                       // the first to-key whose id is not below
+            while (unique && lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((uint32_t)(keys_t[padded(mid)] >> 32) < idk) lo = mid + 1; else hi = mid;
+            }
+            if (unique && lo < nt) {
+                const uint64_t tk = keys_t[padded(lo)];
+                if ((uint32_t)(tk >> 32) == idk && (lo + 1 >= nt || (uint32_t)(keys_t[padded(lo + 1)] >> 32) != idk)) {
+                    const float* pf = a.from_xyz + (J.first_from + (int64_t)(uint32_t)key) * 3;
+                    const float* pt = a.to_xyz + (J.first_to + (int64_t)(uint32_t)tk) * 3;
+                    c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2]; c[3] = pt[0]; c[4] = pt[1]; c[5] = pt[2];
+                    keep = m3d::keep_pair(c[0], c[1], c[2], c[3], c[4], c[5]);
+                }
+            }
+        }
+        int total;
+        const int pos = m + block_rank(keep, wsum, total);
+        if (keep) {
+            out_matches[pos] = m3d::key_id(idk);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) gx[(size_t)k * nf + pos] = c[k];
+        }
+        m += total;
+    }
+    for (int i = m + tid; i < nf; i += BLOCK) out_matches[i] = 0;
+    __syncthreads();                                                   // the keys are dead, the coordinates written
+
+    GroupBackend b;
+    b.m = m; b.tid = tid; b.seed = a.seed; b.iterations = a.iterations; b.thr2 = a.inlier_distance * a.inlier_distance;
+    b.models = reinterpret_cast<float*>(m3_smem); b.red = b.models + MODEL_FLOATS;
+    b.valid = valid; b.hist = hist; b.wsum = wsum; b.best = &best; b.cur = cur;
+    b.d2 = gx + (size_t)6 * nf;
+    b.prev = reinterpret_cast<int32_t*>(scratch) + (size_t)7 * nf; b.next = b.prev + nf;
+    b.n_prev = b.n_next = b.n_last = 0;
+    if (m <= a.stage_cap) {
+        float* lx = b.red + RED_FLOATS;
+        for (int e = tid; e < 6 * m; e += BLOCK) { const int k = e / m, i = e - k * m; lx[e] = gx[(size_t)k * nf + i]; }
+        b.X = lx; b.stride = m;
+        __syncthreads();
+    } else {
+        b.X = gx; b.stride = nf;
+    }
+
+    // ---- (b), (c): the rule's own control flow
+    m3d::Result r;
+    m3d::solve(b, m, a.min_inliers, a.refine_iterations, a.inlier_distance, r);
+
+    // ---- (d) outputs
+    for (int j = tid; j < nf; j += BLOCK) out_inliers[j] = j < r.n_inliers ? out_matches[b.prev[j]] : 0;
+    if (tid == 0) {
+        float* t = a.out_transform + (size_t)blockIdx.x * 12;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) t[k] = r.transform[k];
+        a.out_status[blockIdx.x] = r.status;
+        a.out_n_matches[blockIdx.x] = m;
+        a.out_n_inliers[blockIdx.x] = r.n_inliers;
+        a.out_variance[blockIdx.x] = r.variance;
+    }
+}
+
+void allow_large_lds() {
+    static const bool once = [] {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&motion_3d_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) (void)hipGetLastError();
+        return true;
+    }();
+    (void)once;
+}
+
+}  // namespace
+}  // namespace lcd
+
+using namespace lcd;
+
+namespace {
+
+int estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a, bool on_device) {
+    const char* who = on_device ? "lcd_estimate_motion_3d_dev" : "lcd_estimate_motion_3d";
+    auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
+    // ---- everything that can be refused is refused before anything is enqueued or written
+    if (!a || a->struct_size != (int32_t)sizeof(lcd_motion_3d_args)) return bad(LCD_ERR_INVALID, "null arguments or wrong struct_size");
+    if (a->iterations < 1) return bad(LCD_ERR_INVALID, "iterations is >= 1");
+    if (a->iterations > 65535) return bad(LCD_ERR_UNSUPPORTED, "more than 65535 iterations");
+    if (!std::isfinite(a->inlier_distance) || !(a->inlier_distance > 0.0)) return bad(LCD_ERR_INVALID, "inlier_distance is finite and > 0");
+    if (a->refine_iterations < 0 || a->min_inliers < 1) return bad(LCD_ERR_INVALID, "refine_iterations is >= 0 and min_inliers >= 1");
+    if (a->n_pairs < 0) return bad(LCD_ERR_INVALID, "negative n_pairs");
+    if (a->n_pairs > 65535) return bad(LCD_ERR_UNSUPPORTED, "more than 65535 pairs per call");
+    if (h->shard_append || h->shard_first || h->shard_block) return bad(LCD_ERR_UNSUPPORTED, "not offered on the handles of a sharded vocabulary");
+    if (a->n_pairs == 0) return LCD_OK;
+    const int np = a->n_pairs;
+    const int64_t* fo = a->from_offsets;
+    const int64_t* to = a->to_offsets;
+    if (!fo || !to || fo[0] != 0 || to[0] != 0) return bad(LCD_ERR_INVALID, "offsets missing or not starting at 0");
+    for (int i = 0; i < np; ++i) if (fo[i + 1] < fo[i] || to[i + 1] < to[i]) return bad(LCD_ERR_INVALID, "decreasing offsets");
+    int n_max = 0, m_max = 0;
+    for (int i = 0; i < np; ++i) {
+        const int64_t nf = fo[i + 1] - fo[i], nt = to[i + 1] - to[i];
+        if (nf > MAX_ROWS || nt > MAX_ROWS) return bad(LCD_ERR_UNSUPPORTED, "more than 8192 rows on a side of a pair");
+        n_max = std::max(n_max, (int)std::max(nf, nt));
+        m_max = std::max(m_max, (int)std::min(nf, nt));
+    }
+    const int64_t Nf = fo[np], Nt = to[np];
+    if (!a->out_transform || !a->out_status || !a->out_n_matches || !a->out_n_inliers || !a->out_variance) return bad(LCD_ERR_INVALID, "a null per-pair output");
+    if (Nf > 0 && (!a->from_word_ids || !a->from_xyz || !a->out_matches || !a->out_inliers)) return bad(LCD_ERR_INVALID, "null from-arrays or id outputs");
+    if (Nt > 0 && (!a->to_word_ids || !a->to_xyz)) return bad(LCD_ERR_INVALID, "null to-arrays");
+
+    StatelessScratch& S = h->pairs;
+    hipStream_t st = h->stream;
+    std::vector<M3dJob> jobs((size_t)np);
+    for (int i = 0; i < np; ++i) jobs[(size_t)i] = M3dJob{fo[i], to[i], (int32_t)(fo[i + 1] - fo[i]), (int32_t)(to[i + 1] - to[i])};
+
+    M3dArgs g;
+    g.min_inliers = a->min_inliers; g.iterations = a->iterations; g.refine_iterations = a->refine_iterations; g.seed = a->seed;
+    g.inlier_distance = a->inlier_distance;
+    g.p_max = 64;
+    while (g.p_max < n_max) g.p_max <<= 1;
+    const size_t lds = std::max(key_bytes(g.p_max), std::min(FIXED_BYTES + (size_t)24 * m_max, LDS_LIMIT));
+    g.stage_cap = (int)((lds - FIXED_BYTES) / 24);
+    g.from_ids = a->from_word_ids; g.from_xyz = a->from_xyz; g.to_ids = a->to_word_ids; g.to_xyz = a->to_xyz;
+    g.out_transform = a->out_transform; g.out_status = a->out_status; g.out_n_matches = a->out_n_matches; g.out_n_inliers = a->out_n_inliers;
+    g.out_variance = a->out_variance; g.out_matches = a->out_matches; g.out_inliers = a->out_inliers;
+
+    // ---- host entry: everything to the device, results back at the end (one synchronisation)
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
+    if (!on_device) {
+        const int i_fi = stage.add_in(a->from_word_ids, (size_t)Nf * 4), i_fx = stage.add_in(a->from_xyz, (size_t)Nf * 12);
+        const int i_ti = stage.add_in(a->to_word_ids, (size_t)Nt * 4), i_tx = stage.add_in(a->to_xyz, (size_t)Nt * 12);
+        const int o_t = stage.add_out(a->out_transform, (size_t)np * 48), o_s = stage.add_out(a->out_status, (size_t)np * 4);
+        const int o_nm = stage.add_out(a->out_n_matches, (size_t)np * 4), o_ni = stage.add_out(a->out_n_inliers, (size_t)np * 4);
+        const int o_v = stage.add_out(a->out_variance, (size_t)np * 8);
+        const int o_m = stage.add_out(a->out_matches, (size_t)Nf * 4), o_i = stage.add_out(a->out_inliers, (size_t)Nf * 4);
+        LCD_HIP(h, stage.commit(st, &h->bytes_device));
+        g.from_ids = stage.in<int32_t>(i_fi); g.from_xyz = stage.in<float>(i_fx); g.to_ids = stage.in<int32_t>(i_ti); g.to_xyz = stage.in<float>(i_tx);
+        g.out_transform = stage.out<float>(o_t); g.out_status = stage.out<int32_t>(o_s); g.out_n_matches = stage.out<int32_t>(o_nm);
+        g.out_n_inliers = stage.out<int32_t>(o_ni); g.out_variance = stage.out<double>(o_v);
+        g.out_matches = stage.out<int32_t>(o_m); g.out_inliers = stage.out<int32_t>(o_i);
+    }
+    LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(Nf, 1) * SCRATCH_WORDS * 4));
+    g.scratch = S.d_small.as<uint32_t>();
+    LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(M3dJob)));
+    allow_large_lds();
+    motion_3d_kernel<<<dim3((unsigned)np), dim3(BLOCK), lds, st>>>(g);
+    LCD_HIP(h, hipGetLastError());
+    if (!on_device) LCD_HIP(h, stage.finish(st));
+    return LCD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lcd_estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a) { return stateless_entry(h, "lcd_estimate_motion_3d", estimate_motion_3d, a, false); }
+int lcd_estimate_motion_3d_dev(lcd_engine* h, const lcd_motion_3d_args* a) { return stateless_entry(h, "lcd_estimate_motion_3d", estimate_motion_3d, a, true); }
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 #include "FeatureSelect.h"
 #include "Keypoints3D.h"
 #include "MemoryHip.h"
+#include "Motion3D.h"
 #include "RtabmapHip.h"
 
 using namespace rtabmap_amd;
@@ -230,6 +231,35 @@ int hk3_filter_pixel(const float* points, int n, const void* depth, long long pi
     if (!Keypoints3D::filterKeypointsByDepth(points, n, image, minDepth, maxDepth, kept)) return -1;
     std::copy(kept.begin(), kept.end(), outKept);
     return (int)kept.size();
+}
+// motion3d_cpu (no engine involved).  outTransform[12], outScalars[3] = status, matches, inliers; outMatches / outInliers hold nFrom ids.  1 = done, 0 = refused
+int hm3_cpu(const int* fromIds, const float* fromXyz, int nFrom, const int* toIds, const float* toXyz, int nTo, int minInliers, double inlierDistance,
+            int iterations, int refineIterations, unsigned seed, int sweeps, float* outTransform, int* outScalars, double* outVariance, int* outMatches,
+            int* outInliers) {
+    Motion3DResult r;
+    if (!motion3d_cpu(fromIds, fromXyz, nFrom, toIds, toXyz, nTo, minInliers, inlierDistance, iterations, refineIterations, seed, r, sweeps)) return 0;
+    std::copy(r.transform, r.transform + 12, outTransform);
+    outScalars[0] = r.status; outScalars[1] = (int)r.matches.size(); outScalars[2] = (int)r.inliers.size();
+    *outVariance = r.variance;
+    std::copy(r.matches.begin(), r.matches.end(), outMatches);
+    std::copy(r.inliers.begin(), r.inliers.end(), outInliers);
+    return 1;
+}
+// Motion3D::estimateMotion3DTo3D through the dictionary's engine, the frames as parallel arrays.  outCovariance[36]; returns 1 with a transform, 0 without
+int hm3_estimate(void* h, const int* idsA, const float* xyzA, int nA, const int* idsB, const float* xyzB, int nB, int minInliers, double inliersDistance,
+                 int iterations, int refineIterations, unsigned seed, float* outTransform, double* outCovariance, int* outCounts, int* outMatches,
+                 int* outInliers) {
+    std::multimap<int, Point3f> a, b;
+    for (int i = 0; i < nA; ++i) a.insert(std::make_pair(idsA[i], Point3f{xyzA[3 * i], xyzA[3 * i + 1], xyzA[3 * i + 2]}));
+    for (int i = 0; i < nB; ++i) b.insert(std::make_pair(idsB[i], Point3f{xyzB[3 * i], xyzB[3 * i + 1], xyzB[3 * i + 2]}));
+    std::vector<int> matches, inliers;
+    const Transform3D t = Motion3D::estimateMotion3DTo3D(((VWDictionaryHip*)h)->engine(), a, b, minInliers, inliersDistance, iterations, refineIterations,
+                                                         outCovariance, &matches, &inliers, seed);
+    std::copy(t.data, t.data + 12, outTransform);
+    outCounts[0] = (int)matches.size(); outCounts[1] = (int)inliers.size();
+    std::copy(matches.begin(), matches.end(), outMatches);
+    std::copy(inliers.begin(), inliers.end(), outInliers);
+    return t.isNull() ? 0 : 1;
 }
 const char* hmem_select_error(void* h) { return ((MemoryHip*)h)->lastSelectError().c_str(); }
 // FeatureSelect's three functions (no engine involved).  1 = done, 0 = refused

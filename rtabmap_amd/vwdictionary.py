@@ -70,6 +70,8 @@ def lib():
         L.hk3_generate.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, vp, ci, cf, cf, vp]
         L.hk3_filter_3d.argtypes = [vp, ci, cf, cf, vp]
         L.hk3_filter_pixel.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, cf, cf, vp]
+        L.hm3_cpu.argtypes = [vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, ci, vp, vp, vp, vp, vp]
+        L.hm3_estimate.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, vp, vp, vp, vp, vp]
         L.hmem_select_error.argtypes = [vp]
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -208,6 +210,31 @@ def filter_keypoints_by_depth_pixel(points, depth, min_depth=0.0, max_depth=0.0,
     return None if n < 0 else out[:n].copy()
 
 
+def _frame_arrays(ids, xyz):
+    i = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    if x.shape[0] != i.shape[0]:
+        raise ValueError("one 3-D point per word id")
+    return i, x
+
+
+def motion3d_cpu(from_ids, from_xyz, to_ids, to_xyz, min_inliers=20, inlier_distance=0.1, iterations=300, refine_iterations=5, seed=0, sweeps=0):
+    """the rule of lcd_estimate_motion_3d on the CPU (host/Motion3D.cpp, no device) -> dict(transform [12], status, variance, matches, inliers),
+    or None where the call is refused.  sweeps != 0 is for measuring how the rule's Jacobi sweep count was chosen."""
+    fi, fx = _frame_arrays(from_ids, from_xyz)
+    ti, tx = _frame_arrays(to_ids, to_xyz)
+    n = max(fi.shape[0], 1)
+    t, sc, var = np.zeros(12, np.float32), np.zeros(3, np.int32), np.zeros(1, np.float64)
+    om, oi = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    if fi.shape[0] > 8192 or ti.shape[0] > 8192:
+        return None
+    ok = lib().hm3_cpu(_p(fi), _p(fx), fi.shape[0], _p(ti), _p(tx), ti.shape[0], int(min_inliers), float(inlier_distance), int(iterations),
+                       int(refine_iterations), int(seed) & 0xFFFFFFFF, int(sweeps), _p(t), _p(sc), _p(var), _p(om), _p(oi))
+    if not ok:
+        return None
+    return dict(transform=t, status=int(sc[0]), variance=var[0], matches=om[:sc[1]].copy(), inliers=oi[:sc[2]].copy())
+
+
 class VWDictionaryHip:
     def __init__(self, strategy=kNNBruteForceHIP, incremental=True, nndr=0.8, new_words_compared_together=True,
                  dictionary_path="", device=0, _handle=None, _owner=None):
@@ -273,6 +300,19 @@ class VWDictionaryHip:
         if not ok:
             raise RuntimeError("matchFramesGuided: " + self.last_error())
         return of[: f.shape[0]].tolist(), ot[: t.shape[0]].tolist(), op[: n.value].tolist()
+
+    def estimate_motion_3d(self, words3a, words3b, min_inliers=20, inliers_distance=0.1, iterations=300, refine_iterations=5, seed=0):
+        """Motion3D::estimateMotion3DTo3D (util3d_motion_estimation.cpp:730-807) over this dictionary's long-lived engine handle; a frame is
+        (word ids, [n x 3] points), an id may repeat as in RegistrationVis' multimaps.  -> (transform [12] or None, covariance [6 x 6],
+        matches, inliers)"""
+        ia, xa = _frame_arrays(*words3a)
+        ib, xb = _frame_arrays(*words3b)
+        n = max(ia.shape[0], 1)
+        t, cov, counts = np.zeros(12, np.float32), np.zeros(36, np.float64), np.zeros(2, np.int32)
+        om, oi = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ok = lib().hm3_estimate(self.h, _p(ia), _p(xa), ia.shape[0], _p(ib), _p(xb), ib.shape[0], int(min_inliers), float(inliers_distance),
+                                int(iterations), int(refine_iterations), int(seed) & 0xFFFFFFFF, _p(t), _p(cov), _p(counts), _p(om), _p(oi))
+        return (t if ok else None), cov.reshape(6, 6), om[:counts[0]].tolist(), oi[:counts[1]].tolist()
 
     def update(self):
         lib().hvwd_update(self.h)
