@@ -434,6 +434,41 @@ int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a);
  *      range.  A cut frame with height <= grid_rows or width <= grid_cols: LCD_ERR_INVALID from both entries (the reference's second assertion).
  *   LCD_SELECT_BY_RESPONSE (the compacting variant the extractors call, :356-400): a cut frame gives its max_features strongest in DESCENDING
  *      key order -- the order matters, addNewWords numbers new words in row order.  With a grid above 1 x 1: LCD_ERR_INVALID (no such variant).
+ *
+ * The selection rule with LCD_SELECT_SSC (Kp/SSC; Features2d.cpp:304-355 and :420-446 over util2d::SSC, util2d.cpp:2295-2366).  With the
+ * bit clear every call is what it was.  With it a frame that is not cut still selects everything in its own order; a CUT frame (n after
+ * n_in) of a width x height image is selected as follows.  The reference's integers, types and control flow are restated; the tie order,
+ * NaN, points outside the mask and the refusals are the ENGINE's.
+ *   Order.  b(i) = the bits of response[i], -0.0 taken as +0.0, mapped monotonically to unsigned (negative: ~bits; otherwise bits |
+ *      0x80000000).  Feature i PRECEDES j when b(i) > b(j), or b(i) == b(j) and i < j: cv::sortIdx(.., SORT_DESCENDING) on the SIGNED
+ *      response -- no fabs, unlike the key above -- with ties to the lower index, which is the engine's definition (the reference tree
+ *      does not hold cv::sortIdx).  A NaN response: lcd_select_features refuses it, lcd_select_features_dev orders it by the same mapped bits.
+ *   Scalars (:2299-2319, with their types).  tolerance is the float 0.1f and max_features * tolerance a float product; round() rounds
+ *      halves away from zero.  m = max_features - round(max_features * 0.1f).  int exp1 = height + width + 2 m; long long exp2 = 4 width +
+ *      4 m + 4 height m + height^2 + width^2 - 2 height width + 4 height width m; double exp3 = sqrt(exp2), exp4 = m - 1; sol1 =
+ *      -round((exp1 + exp3) / exp4), sol2 = -round((exp1 - exp3) / exp4); high = int(the larger of the two); low = max(1, floor(sqrt(
+ *      (double)n / m))); Kmin = round(m - m * 0.1f), Kmax = round(m + m * 0.1f), float arithmetic.
+ *   Search (:2325-2364).  prevWidth = -1 and the result is empty.  Repeat: width = low + (high - low) / 2 (C truncation); when width ==
+ *      prevWidth or low > high, leave with the result of the PREVIOUS iteration (empty before the first); otherwise c = width / 2.0, the
+ *      mask has the cells [0, floor(height / c)] x [0, floor(width / c)], feature i lies in cell (floor((double)y / c), floor((double)x /
+ *      c)), and the features are walked in the order above: a feature is selected iff no feature selected earlier in this iteration
+ *      lies within 2 rows AND 2 columns of its cell (width / c == 2 exactly: a selected feature covers the 5 x 5 cells around its own,
+ *      clamped to the mask -- the same set for cells inside the mask).  With Kmin <= size <= Kmax leave with this result; below Kmin high
+ *      = width - 1, above Kmax low = width + 1; prevWidth = width.
+ *      The number selected can therefore be 0 (a 16 x 16 image with n = 204 and max_features = 166 leaves before its first iteration), stay
+ *      below Kmin, or EXCEED max_features (n = 124, max_features = 59 on a 33 x 17 image can give 76): the reference's behaviour, restated
+ *      and not repaired.  out_count is the only place the count can be learnt.
+ *   Order of the output.  LCD_SELECT_KEEP_ORDER: ascending index (the inlier mask, what Memory.cpp:5966 calls); LCD_SELECT_BY_RESPONSE: the
+ *      order above (ResultVec, :336-354).
+ *   Undefined in the reference, refused before anything is written: a grid above 1 x 1 with the bit (:507 passes absolute coordinates with
+ *      a cell-sized image), max_features == 1 (exp4 == 0), and with a frame whose REGION is cut a NULL image_size or points or a width or
+ *      height < 1: LCD_ERR_INVALID from both entries.  A keypoint whose cell lies outside the mask makes the reference read outside it;
+ *      that needs a coordinate that is negative, above its image side or NaN (x == width and y == height are inside): lcd_select_features
+ *      returns LCD_ERR_INVALID for every such coordinate in a cut frame; lcd_select_features_dev, iteration by iteration, never selects a
+ *      feature whose cell lies outside that iteration's mask and lets it cover nothing -- the ENGINE's definition; the conversion
+ *      saturates and nothing is indexed out of range.  Limits: an image side above 16384 in a frame whose region is cut (a cell
+ *      coordinate fits 16 bits), or more than 8192 features in such a frame (sorted indices, cells and the table of selected cells share
+ *      one workgroup's LDS; without the bit the limit stays 16384): LCD_ERR_UNSUPPORTED.
  * Outputs.  Frame f writes the first out_count[f] entries of ITS OWN region of each output (the inputs' offsets): out_index (the rest of the
  * region reads -1), out_rows and out_aux (the rest is unspecified).  Its selected rows start at out_rows + offsets[f] * row bytes, ready to be
  * lcd_frame_args.d_descriptors where that address is 16-byte aligned.  With a 1 x 1 grid the host knows the count without a read-back
@@ -463,6 +498,7 @@ int lcd_match_guided_dev(lcd_engine* h, const lcd_guided_args* a);
  * first n features of the region and writes 0 behind them, to the end of the region; count[f] is clamped to n.  NULL: exactly the behaviour
  * without the field.  In the host entries both arrays are host memory.  struct_size is the one sizeof of this header. */
 enum lcd_select_order { LCD_SELECT_KEEP_ORDER = 0, LCD_SELECT_BY_RESPONSE = 1 };
+enum lcd_select_flags { LCD_SELECT_SSC = 1 };   /* Kp/SSC, Vis/SSC: cut frames are selected by the square covering */
 typedef struct lcd_select_args {
     int32_t struct_size;            /* sizeof(lcd_select_args) */
     int32_t n_frames;               /* >= 0; 0 returns LCD_OK */
@@ -470,11 +506,11 @@ typedef struct lcd_select_args {
     int32_t max_features;           /* Kp/MaxFeatures; <= 0: nothing is cut */
     int32_t grid_rows, grid_cols;   /* Kp/GridRows, Kp/GridCols, >= 1 */
     int32_t aux_bytes;              /* bytes of the caller's per-feature payload (the cv::KeyPoint, the 3-D point): a multiple of 4, 0..64 */
-    int32_t reserved;
+    int32_t flags;                  /* lcd_select_flags; the bits it does not name are ignored (the field was `reserved`) */
     const int64_t* offsets;         /* HOST, [n_frames + 1], non-decreasing, [0] == 0 */
-    const int32_t* image_size;      /* HOST, [n_frames x 2]: width, height; may be NULL with a 1 x 1 grid */
+    const int32_t* image_size;      /* HOST, [n_frames x 2]: width, height; may be NULL with a 1 x 1 grid and no frame cut under LCD_SELECT_SSC */
     const float* response;          /* [N] cv::KeyPoint::response */
-    const float* points;            /* [N x 2] cv::KeyPoint::pt (x, y); may be NULL with a 1 x 1 grid */
+    const float* points;            /* [N x 2] cv::KeyPoint::pt (x, y); may be NULL with a 1 x 1 grid and no frame cut under LCD_SELECT_SSC */
     const void* rows;               /* may be NULL: [N x dim] of the handle's dtype */
     const void* aux;                /* may be NULL (aux_bytes == 0): [N x aux_bytes] */
     int32_t* out_count;             /* [n_frames] */

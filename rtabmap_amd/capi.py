@@ -19,6 +19,7 @@ LCD_MATCH_DICTIONARY, LCD_MATCH_CROSS_CHECK = 0, 1          # lcd_match_args.mod
 LCD_GUIDED_PROJECTED_TO_FRAME, LCD_GUIDED_FRAME_TO_PROJECTED = 0, 1   # lcd_guided_args.direction (include/lcd.h)
 LCD_GUIDED_RATIO, LCD_GUIDED_NEAREST = 0, 1                          # lcd_guided_args.nn_type
 LCD_SELECT_KEEP_ORDER, LCD_SELECT_BY_RESPONSE = 0, 1                 # lcd_select_args.order
+LCD_SELECT_SSC = 1                                                   # lcd_select_args.flags: Kp/SSC, the square covering
 LCD_DEPTH_U16_MM, LCD_DEPTH_F32_M = 0, 1                             # lcd_depth_image.type
 LCD_KP3D_KEEP_ALL, LCD_KP3D_FILTER_3D, LCD_KP3D_FILTER_PIXEL = 0, 1, 2  # lcd_keypoints_3d_args.filter
 LCD_NEW_WORD_IDS_AUTO = -1      # lcd_frame_args.first_new_word_id: the device numbers the frame's new words (include/lcd.h)
@@ -108,7 +109,7 @@ GUIDED_NN_TYPES = {"ratio": LCD_GUIDED_RATIO, "nearest": LCD_GUIDED_NEAREST}
 
 class LcdSelectArgs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("order", C.c_int32), ("max_features", C.c_int32), ("grid_rows", C.c_int32),
-                ("grid_cols", C.c_int32), ("aux_bytes", C.c_int32), ("reserved", C.c_int32), ("offsets", C.c_void_p), ("image_size", C.c_void_p),
+                ("grid_cols", C.c_int32), ("aux_bytes", C.c_int32), ("flags", C.c_int32), ("offsets", C.c_void_p), ("image_size", C.c_void_p),
                 ("response", C.c_void_p), ("points", C.c_void_p), ("rows", C.c_void_p), ("aux", C.c_void_p), ("out_count", C.c_void_p),
                 ("out_index", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p), ("n_in", C.c_void_p)]
 
@@ -535,7 +536,7 @@ class Engine:
         self._ck(self.L.lcd_match_guided_dev(self.h, C.byref(a)))
 
     # ---- keypoint limiting and the -1, -2, ... word ids (stateless; include/lcd.h has the rule)
-    def _select_args(self, offsets, max_features, order, grid, image_size, aux_bytes):
+    def _select_args(self, offsets, max_features, order, grid, image_size, aux_bytes, ssc=False):
         off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         n_frames = off.shape[0] - 1
         if n_frames < 0:
@@ -544,18 +545,20 @@ class Engine:
         size = None if image_size is None else np.ascontiguousarray(image_size, dtype=np.int32).reshape(-1, 2)
         if size is not None and size.shape[0] != n_frames:
             raise ValueError("select_features: one (width, height) per frame")
-        a = LcdSelectArgs(C.sizeof(LcdSelectArgs), n_frames, order, int(max_features), int(grid[0]), int(grid[1]), int(aux_bytes), 0)
+        a = LcdSelectArgs(C.sizeof(LcdSelectArgs), n_frames, order, int(max_features), int(grid[0]), int(grid[1]), int(aux_bytes),
+                          LCD_SELECT_SSC if ssc else 0)
         a.offsets, a.image_size = off.ctypes.data, (None if size is None else size.ctypes.data)
         return a, off, size
 
-    def select_features(self, response, offsets, max_features, order="keep_order", grid=(1, 1), image_size=None, points=None, rows=None, aux=None, n_in=None):
+    def select_features(self, response, offsets, max_features, order="keep_order", grid=(1, 1), image_size=None, points=None, rows=None, aux=None, n_in=None, ssc=False):
         """lcd_select_features over host arrays: frame f owns the features [offsets[f], offsets[f+1]); aux is a [N x aux_bytes] uint8 payload.
-        -> (count [n_frames], index [N], rows or None, aux or None); only the first count[f] entries of a frame's region are meaningful."""
+        -> (count [n_frames], index [N], rows or None, aux or None); only the first count[f] entries of a frame's region are meaningful.
+        ssc: LCD_SELECT_SSC, Kp/SSC's square covering (points and image sizes are needed; count is data-dependent)."""
         r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
         p = None if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
         d = None if rows is None else self._rows(rows)
         x = None if aux is None else np.ascontiguousarray(aux, dtype=np.uint8).reshape(r.shape[0], -1)
-        a, off, _size = self._select_args(offsets, max_features, order, grid, image_size, 0 if x is None else x.shape[1])
+        a, off, _size = self._select_args(offsets, max_features, order, grid, image_size, 0 if x is None else x.shape[1], ssc)
         n = r.shape[0]
         if int(off[-1]) != n or (p is not None and p.shape[0] != n) or (d is not None and d.shape[0] != n):
             raise ValueError("select_features: the last offset is the number of features; one point and one row per feature")
@@ -570,10 +573,10 @@ class Engine:
         return count[:a.n_frames], index[:n], (None if d is None else out_rows[:n]), (None if x is None else out_aux[:n])
 
     def select_features_dev(self, d_response, offsets, max_features, d_count, d_index, order="keep_order", grid=(1, 1), image_size=None,
-                            d_points=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_rows=None, d_out_aux=None, d_n_in=None):
+                            d_points=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_rows=None, d_out_aux=None, d_n_in=None, ssc=False):
         """lcd_select_features_dev on torch tensors of the engine's device (float32 responses and points, rows of the handle's dtype, int32
         outputs; offsets and image sizes stay on the host).  Enqueued on the engine stream, not synchronised."""
-        a, _off, _size = self._select_args(offsets, max_features, order, grid, image_size, aux_bytes)
+        a, _off, _size = self._select_args(offsets, max_features, order, grid, image_size, aux_bytes, ssc)
         ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
         a.response, a.points, a.rows, a.aux = ptr(d_response), ptr(d_points), ptr(d_rows), ptr(d_aux)
         a.out_count, a.out_index, a.out_rows, a.out_aux = ptr(d_count), ptr(d_index), ptr(d_out_rows), ptr(d_out_aux)

@@ -1,4 +1,4 @@
-// FeatureSelect.h -- Feature2D::limitKeypoints (reference Features2d.cpp:293-516, without Kp/SSC) and the -1, -2, ... word ids of
+// FeatureSelect.h -- Feature2D::limitKeypoints (reference Features2d.cpp:293-516, Kp/SSC's util2d::SSC included) and the -1, -2, ... word ids of
 // Memory::createSignature (Memory.cpp:6029-6059) as plain host code: the rule include/lcd.h writes down for lcd_select_features and
 // lcd_expand_word_ids, for small frames and for a process without a device.  No engine is involved.
 #pragma once
@@ -17,6 +17,15 @@ public:
     // The compacting form (:293-410): kept = the indices in output order -- the maxKeypoints strongest first when the frame is cut, the
     // frame's own order otherwise.  false on a NaN response.
     static bool limitKeypoints(const float* response, int n, int maxKeypoints, std::vector<int>& kept);
+    // Kp/SSC, the inlier mask (:420-446 over util2d.cpp:2295-2366): the LCD_SELECT_SSC rule of include/lcd.h.  points[2 n] (x, y).  The
+    // number of inliers can be 0, below and above maxKeypoints.  false -- inliers untouched -- where the rule refuses: a NaN response,
+    // maxKeypoints == 1, and for a cut frame NULL points, an image side < 1 or above 16384, a coordinate that is NaN or outside [0, side].
+    static bool limitKeypointsSSC(const float* response, const float* points, int n, int maxKeypoints, int imageWidth, int imageHeight,
+                                  std::vector<bool>& inliers);
+    // Kp/SSC, the compacting form (:304-355): kept = the selected indices in descending response, among equal responses the lower index
+    // first (the engine's reading of cv::sortIdx); the frame's own order when it is not cut.  false as above.
+    static bool limitKeypointsSSC(const float* response, const float* points, int n, int maxKeypoints, int imageWidth, int imageHeight,
+                                  std::vector<int>& kept);
     // :6029-6059.  index[count], wordIds[count]: feature index[j] has id wordIds[j]; an id > 0 stands, a code -(k+1) becomes firstNewWordId + k
     // when firstNewWordId > 0, anything else is "no word"; the features without a word are numbered -1, -2, ... in feature order.
     // false -- all untouched -- on a count or an index outside [0, n].

@@ -26,7 +26,7 @@ struct Stage {
 }  // namespace
 
 MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
-    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _maxFeatures(500), _gridRows(1), _gridCols(1), _minDepth(0.0f), _maxDepth(0.0f), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
+    : _vwd(new VWDictionaryHip(parameters, device)), _idCount(0), _maxStMemSize(10), _maxFeatures(500), _gridRows(1), _gridCols(1), _ssc(false), _minDepth(0.0f), _maxDepth(0.0f), _deviceFrames(true), _tfIdfLikelihoodUsed(true), _likeSig(0), _likeSortedValid(false) {
     ParametersMap::const_iterator it = parameters.find("Mem/STMSize");
     if (it != parameters.end()) _maxStMemSize = atoi(it->second.c_str());
     it = parameters.find("Kp/TfIdfLikelihoodUsed");
@@ -37,6 +37,7 @@ MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
     if ((it = parameters.find("Kp/MinDepth")) != parameters.end()) _minDepth = (float)atof(it->second.c_str());
     if ((it = parameters.find("Kp/MaxDepth")) != parameters.end()) _maxDepth = (float)atof(it->second.c_str());
     if ((it = parameters.find("Kp/GridCols")) != parameters.end()) _gridCols = atoi(it->second.c_str());
+    if ((it = parameters.find("Kp/SSC")) != parameters.end()) _ssc = it->second == "true" || it->second == "1" || it->second == "True" || it->second == "TRUE";
     _workingMem.insert(kIdVirtual);             // Memory.cpp:592
     static const char* names[] = {"TimingMem/Pre_update/ms", "TimingMem/Joining_dictionary_update/ms", "TimingMem/Add_new_words/ms",
                                   "Timing/Likelihood_computation/ms", "Timing/Forgetting/ms", "Keypoint/Dictionary_size/words",
@@ -205,7 +206,8 @@ int MemoryHip::update(const Mat& descriptors, const std::vector<float>& response
     const bool grid = _gridRows > 1 || _gridCols > 1;
     _selectError.clear();
     if (!(_maxFeatures > 0 && rows > _maxFeatures)) return this->update(descriptors, -1, outIds);     // :5954: nothing to select
-    if ((int)responses.size() != rows || (grid && (int)points.size() != 2 * rows)) { _selectError = "one response (and one point) per descriptor"; return 0; }
+    if ((int)responses.size() != rows || ((grid || _ssc) && (int)points.size() != 2 * rows)) { _selectError = "one response (and one point) per descriptor"; return 0; }
+    if (_ssc && grid) { _selectError = "Kp/SSC with a grid above 1 x 1: the reference indexes its covering mask outside its bounds"; return 0; }
     // ---- the selection (:5951-6023)
     std::vector<int> rawIndex;
     Mat forQuantization;
@@ -218,16 +220,21 @@ int MemoryHip::update(const Mat& descriptors, const std::vector<float>& response
         std::vector<unsigned char> selected(descriptors.data.size());
         lcd_select_args s;
         s.struct_size = (int32_t)sizeof(s); s.n_frames = 1; s.order = LCD_SELECT_KEEP_ORDER; s.max_features = _maxFeatures;
-        s.grid_rows = _gridRows < 1 ? 1 : _gridRows; s.grid_cols = _gridCols < 1 ? 1 : _gridCols; s.aux_bytes = 0; s.reserved = 0;
-        s.offsets = offsets; s.image_size = size; s.response = responses.data(); s.points = grid ? points.data() : 0;
+        s.grid_rows = _gridRows < 1 ? 1 : _gridRows; s.grid_cols = _gridCols < 1 ? 1 : _gridCols; s.aux_bytes = 0; s.flags = _ssc ? LCD_SELECT_SSC : 0;
+        s.offsets = offsets; s.image_size = size; s.response = responses.data(); s.points = grid || _ssc ? points.data() : 0;
         s.rows = descriptors.data.data(); s.aux = 0; s.out_count = &count; s.out_index = index.data(); s.out_rows = selected.data(); s.out_aux = 0; s.n_in = 0;
         if (lcd_select_features(eng, &s) != LCD_OK) { _selectError = lcd_last_error(eng); return 0; }
         rawIndex.assign(index.begin(), index.begin() + count);
         forQuantization = Mat(count, descriptors.cols, descriptors.type(), selected.data());
     } else {
         std::vector<bool> inliers;
-        if (!FeatureSelect::limitKeypoints(responses.data(), grid ? points.data() : 0, rows, _maxFeatures, imageWidth, imageHeight,
-                                           _gridRows < 1 ? 1 : _gridRows, _gridCols < 1 ? 1 : _gridCols, inliers)) {
+        if (_ssc) {
+            if (!FeatureSelect::limitKeypointsSSC(responses.data(), points.data(), rows, _maxFeatures, imageWidth, imageHeight, inliers)) {
+                _selectError = "limitKeypoints (Kp/SSC): a NaN response, Kp/MaxFeatures == 1, a keypoint outside the image or an image side outside 1 .. 16384";
+                return 0;
+            }
+        } else if (!FeatureSelect::limitKeypoints(responses.data(), grid ? points.data() : 0, rows, _maxFeatures, imageWidth, imageHeight,
+                                                  _gridRows < 1 ? 1 : _gridRows, _gridCols < 1 ? 1 : _gridCols, inliers)) {
             _selectError = "limitKeypoints: a NaN response, a keypoint outside the grid or an image not larger than the grid";
             return 0;
         }

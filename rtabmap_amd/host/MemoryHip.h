@@ -37,6 +37,8 @@ public:
     // it (without an engine: FeatureSelect's host code).  responses: one per descriptor (cv::KeyPoint::response); points: x, y per descriptor
     // (needed with a grid above 1 x 1, like the image size, which is the caller's pick among the camera models, :5958-5992).  Returns the
     // signature id, 0 when the selection is refused (lastSelectError(): a NaN response, a keypoint outside the grid, sizes that do not match).
+    // Kp/SSC (false) selects by util2d::SSC's square covering instead (LCD_SELECT_SSC; points and the image size are needed, a grid above
+    // 1 x 1 is refused as the entry refuses it).
     int update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
                std::vector<int>& wordIds);
     // The same for an RGB-D frame, with the depth stage in front (Memory.cpp:5683-5694, :5911-5915): the keypoints' 3-D points by
@@ -52,6 +54,7 @@ public:
     int getMaxFeatures() const { return _maxFeatures; }
     int getGridRows() const { return _gridRows; }
     int getGridCols() const { return _gridCols; }
+    bool isSSC() const { return _ssc; }
     const std::string& lastSelectError() const { return _selectError; }
     // a signature given directly by its word ids (database replay, Memory.cpp:447-480)
     int addSignature(const std::vector<int>& wordIds, int id = 0);
@@ -142,6 +145,7 @@ private:
     std::set<int> _stMem, _workingMem;
     int _maxStMemSize;                              // Mem/STMSize (Parameters.h: 10)
     int _maxFeatures, _gridRows, _gridCols;         // Kp/MaxFeatures (500), Kp/GridRows (1), Kp/GridCols (1)
+    bool _ssc;                                      // Kp/SSC (false)
     float _minDepth, _maxDepth;                     // Kp/MinDepth (0), Kp/MaxDepth (0)
     std::string _selectError;
     // quantises `forQuantization` as signature `id` the call-by-call way; rawIndex (may be NULL): its rows' places among the `rows` features

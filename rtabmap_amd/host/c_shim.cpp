@@ -154,6 +154,16 @@ void* hmem_create_select(int strategy, int incremental, float nndr, int together
     p["Kp/GridCols"] = std::to_string(gridCols);
     return new MemoryHip(p, device);
 }
+// ... and Kp/SSC
+void* hmem_create_select_ssc(int strategy, int incremental, float nndr, int together, int device, int stmSize, int maxFeatures, int gridRows, int gridCols, int ssc) {
+    ParametersMap p = make_params(strategy, incremental, nndr, together, "");
+    p["Mem/STMSize"] = std::to_string(stmSize);
+    p["Kp/MaxFeatures"] = std::to_string(maxFeatures);
+    p["Kp/GridRows"] = std::to_string(gridRows);
+    p["Kp/GridCols"] = std::to_string(gridCols);
+    p["Kp/SSC"] = ssc ? "true" : "false";
+    return new MemoryHip(p, device);
+}
 // responses[rows], points[2 rows] (may be NULL with a 1 x 1 grid); returns the signature id, 0 = refused (hmem_select_error)
 int hmem_update_select(void* h, const void* desc, int rows, int cols, int type, const float* responses, const float* points, int imageWidth,
                        int imageHeight, int* outIds) {
@@ -274,6 +284,19 @@ int hfs_limit_keypoints(const float* response, const float* points, int n, int m
 int hfs_limit_keypoints_compact(const float* response, int n, int maxKeypoints, int* outKept) {
     std::vector<int> kept;
     if (!FeatureSelect::limitKeypoints(response, n, maxKeypoints, kept)) return -1;
+    std::copy(kept.begin(), kept.end(), outKept);
+    return (int)kept.size();
+}
+// the Kp/SSC forms: points[2 n] and the image size are needed when the frame is cut
+int hfs_limit_keypoints_ssc(const float* response, const float* points, int n, int maxKeypoints, int imageWidth, int imageHeight, unsigned char* outInliers) {
+    std::vector<bool> inliers;
+    if (!FeatureSelect::limitKeypointsSSC(response, points, n, maxKeypoints, imageWidth, imageHeight, inliers)) return 0;
+    for (size_t i = 0; i < inliers.size(); ++i) outInliers[i] = inliers[i] ? 1 : 0;
+    return 1;
+}
+int hfs_limit_keypoints_ssc_compact(const float* response, const float* points, int n, int maxKeypoints, int imageWidth, int imageHeight, int* outKept) {
+    std::vector<int> kept;
+    if (!FeatureSelect::limitKeypointsSSC(response, points, n, maxKeypoints, imageWidth, imageHeight, kept)) return -1;
     std::copy(kept.begin(), kept.end(), outKept);
     return (int)kept.size();
 }

@@ -76,6 +76,10 @@ def lib():
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
         L.hfs_limit_keypoints_compact.argtypes = [vp, ci, ci, vp]
+        L.hfs_limit_keypoints_ssc.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+        L.hfs_limit_keypoints_ssc_compact.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+        L.hmem_create_select_ssc.restype = vp
+        L.hmem_create_select_ssc.argtypes = [ci, ci, cf, ci, ci, ci, ci, ci, ci, ci]
         L.hfs_expand_word_ids.argtypes = [ci, vp, vp, ci, ci, vp]
         L.hmem_time_loop.argtypes = [vp, vp, ci, ci, ci, ci, ci]
         L.hmem_time_loop.restype = C.c_double
@@ -134,22 +138,35 @@ def lib():
 
 
 # ---- FeatureSelect (rtabmap_amd/host/FeatureSelect.h): the selection and expansion rule of include/lcd.h as plain host code, no engine
-def limit_keypoints(response, points=None, max_keypoints=0, image_size=(0, 0), grid_rows=1, grid_cols=1):
+def limit_keypoints(response, points=None, max_keypoints=0, image_size=(0, 0), grid_rows=1, grid_cols=1, ssc=False):
     """Feature2D::limitKeypoints' inlier mask -> bool array, or None where the host mirror refuses (NaN response, keypoint outside the grid,
-    image not larger than the grid)."""
+    image not larger than the grid).  ssc: Kp/SSC's square covering (a grid above 1 x 1, max_keypoints == 1, a keypoint outside the image and
+    image sides outside 1 .. 16384 are refused as well)."""
     r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
     p = None if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
     if p is not None and p.shape[0] != r.shape[0]:
         raise ValueError("limit_keypoints: one point per response")
     out = np.zeros(max(r.shape[0], 1), np.uint8)
+    if ssc:
+        if grid_rows * grid_cols != 1:
+            return None
+        ok = lib().hfs_limit_keypoints_ssc(_p(r), _p(p), r.shape[0], int(max_keypoints), int(image_size[0]), int(image_size[1]), _p(out))
+        return out[:r.shape[0]].astype(bool) if ok else None
     ok = lib().hfs_limit_keypoints(_p(r), _p(p), r.shape[0], int(max_keypoints), int(image_size[0]), int(image_size[1]), int(grid_rows), int(grid_cols), _p(out))
     return out[:r.shape[0]].astype(bool) if ok else None
 
 
-def limit_keypoints_compact(response, max_keypoints=0):
-    """the compacting form -> the kept indices in output order, or None on a NaN response"""
+def limit_keypoints_compact(response, max_keypoints=0, points=None, image_size=(0, 0), ssc=False):
+    """the compacting form -> the kept indices in output order, or None on a NaN response.  ssc: Kp/SSC's square covering over points and
+    image_size, refusing what limit_keypoints(ssc=True) refuses."""
     r = np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
     out = np.zeros(max(r.shape[0], 1), np.int32)
+    if ssc:
+        p = None if points is None else np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        if p is not None and p.shape[0] != r.shape[0]:
+            raise ValueError("limit_keypoints_compact: one point per response")
+        n = lib().hfs_limit_keypoints_ssc_compact(_p(r), _p(p), r.shape[0], int(max_keypoints), int(image_size[0]), int(image_size[1]), _p(out))
+        return None if n < 0 else out[:n].copy()
     n = lib().hfs_limit_keypoints_compact(_p(r), r.shape[0], int(max_keypoints), _p(out))
     return None if n < 0 else out[:n].copy()
 
@@ -374,7 +391,7 @@ class VWDictionaryHip:
 class MemoryHip:
     def __init__(self, strategy=kNNBruteForceHIP, incremental=True, nndr=0.8, new_words_compared_together=True,
                  dictionary_path="", device=0, stm_size=10, _handle=None, _owner=None, max_features=None, grid_rows=1, grid_cols=1,
-                 min_depth=None, max_depth=0.0):
+                 min_depth=None, max_depth=0.0, ssc=False):
         self._owner = _owner                    # a RtabmapHip owns its memory
         if _handle is not None:
             self.h = _handle
@@ -382,8 +399,8 @@ class MemoryHip:
             self.h = lib().hmem_create_depth(strategy, int(incremental), float(nndr), int(new_words_compared_together), device, int(stm_size),
                                              int(500 if max_features is None else max_features), int(grid_rows), int(grid_cols), float(min_depth), float(max_depth))
         elif max_features is not None:          # Kp/MaxFeatures, Kp/GridRows, Kp/GridCols: update_select() honours them
-            self.h = lib().hmem_create_select(strategy, int(incremental), float(nndr), int(new_words_compared_together), device, int(stm_size),
-                                              int(max_features), int(grid_rows), int(grid_cols))
+            self.h = lib().hmem_create_select_ssc(strategy, int(incremental), float(nndr), int(new_words_compared_together), device, int(stm_size),
+                                                  int(max_features), int(grid_rows), int(grid_cols), int(bool(ssc)))
         else:
             self.h = lib().hmem_create_stm(
                 strategy, int(incremental), float(nndr), int(new_words_compared_together), dictionary_path.encode(), device, int(stm_size))
@@ -408,8 +425,8 @@ class MemoryHip:
         return sid, out[:rows].tolist()
 
     def update_select(self, desc, responses, points=None, image_size=(0, 0)):
-        """MemoryHip::update with the reference's own selection (Kp/MaxFeatures, Kp/GridRows, Kp/GridCols) -> (signature id, one id per
-        descriptor); id 0: refused (select_error())"""
+        """MemoryHip::update with the reference's own selection (Kp/MaxFeatures, Kp/GridRows, Kp/GridCols, Kp/SSC) -> (signature id, one id
+        per descriptor); id 0: refused (select_error())"""
         desc = np.ascontiguousarray(desc)
         rows = desc.shape[0]
         r = np.ascontiguousarray(responses, dtype=np.float32).reshape(-1)
