@@ -279,8 +279,9 @@ class _Backend:
         self.prev, self.next = self.next, self.prev
 
 
-def refine(b, inlier_distance, refine_iterations, trace):
-    """util3d_registration.cpp:115-196; trace receives one word per pass"""
+def refine(b, inlier_distance, refine_iterations, trace, first_differing=None):
+    """util3d_registration.cpp:115-196; trace receives one word per pass, first_differing (a list, if given) the first index at which the two
+    compared sets differ, once per pass that says members_changed"""
     error_threshold = D(inlier_distance)
     it = 0
     inlier_changed = False
@@ -308,6 +309,8 @@ def refine(b, inlier_distance, refine_iterations, trace):
                 inlier_changed = True
             elif b.prev != b.next:
                 trace.append("members_changed")
+                if first_differing is not None:
+                    first_differing.append(next(i for i, (p, n) in enumerate(zip(b.prev, b.next)) if p != n))
                 inlier_changed = True
             else:
                 trace.append("converged")
@@ -326,13 +329,14 @@ def check_args(n_from, n_to, min_inliers, inlier_distance, iterations, refine_it
 
 
 def estimate(from_ids, from_xyz, to_ids, to_xyz, min_inliers=20, inlier_distance=0.1, iterations=300, refine_iterations=5, seed=0, sweeps=SWEEPS):
-    """one pair -> dict(transform [12] f32, status, matches, inliers (ids), variance f64, inlier_index, model, trace, best, counts)"""
+    """one pair -> dict(transform [12] f32, status, matches, inliers (ids), variance f64, inlier_index, model, trace, best, counts, last_d2 (the
+    d2 of the last selection, what the variance is the median of), first_differing (see refine))"""
     matches, P, Q = correspondences(from_ids, from_xyz, to_ids, to_xyz)
     check_args(np.asarray(from_ids).size, np.asarray(to_ids).size, min_inliers, inlier_distance, iterations, refine_iterations)
     m = len(matches)
     thr = D(inlier_distance)
     r = dict(transform=np.zeros(12, np.float32), status=OK, matches=matches, inliers=np.zeros(0, np.int32), variance=D(1.0),
-             inlier_index=[], model=None, trace=[], best=None, counts=None, P=P, Q=Q)
+             inlier_index=[], model=None, trace=[], best=None, counts=None, P=P, Q=Q, last_d2=np.zeros(0, np.float32), first_differing=[])
     if m < min_inliers or m < 3:
         r["status"] = FEW_CORRESPONDENCES
         return r
@@ -346,9 +350,10 @@ def estimate(from_ids, from_xyz, to_ids, to_xyz, min_inliers=20, inlier_distance
     b.swap_sets()
     b.next = []
     if refine_iterations > 0:
-        refine(b, thr, refine_iterations, r["trace"])
+        refine(b, thr, refine_iterations, r["trace"], r["first_differing"])
         b.swap_sets()
     r["model"] = b.cur
+    r["last_d2"] = b.last_d2
     n = len(b.prev)
     if n < 3:
         r["status"] = FEW_INLIERS

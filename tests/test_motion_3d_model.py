@@ -174,6 +174,25 @@ def test_host_mirror_equals_the_model_on_the_generators():
     both(I.exact_pair(300), **KW)
 
 
+def test_host_mirror_equals_the_model_where_the_kernel_changes_shape():
+    """the inputs of tests/test_gpu_motion_3d_shapes.py (but the largest): the mirror joins with a std::map, picks with a comparison of keys
+    and selects the median with nth_element, the model does each its own way"""
+    kw = dict(min_inliers=3, inlier_distance=0.1, iterations=50, refine_iterations=2, seed=1)
+    for pair in I.asymmetric_pairs() + I.duplicate_run_pairs() + I.extreme_id_pairs() + [I.predicate_pair()]:
+        both(pair, **kw)
+    m, invalid, seed = I.TIE_INVALID_FIRST
+    for iterations in I.TIE_ITERATIONS:
+        assert both(I.exact_pair(m), min_inliers=3, inlier_distance=0.1, iterations=iterations, refine_iterations=0, seed=seed)["best"] == invalid
+    for h, iterations in I.LATE_CASES + tuple((h, h) for h in I.CUT_OFF):
+        both(I.late_winner_pair(), **I.late_kw(h, iterations))
+    for seed in sorted(I.LATE_MEMBERS):
+        both(I.late_members_pair(seed), seed=seed, **I.LATE_MEMBERS_KW)
+    for pair, kw in I.select_cases().values():
+        both(pair, **kw)
+    for kw in I.scratch_table_kws():
+        both(I.scratch_table_pair(), **kw)
+
+
 def test_host_mirror_refuses_what_the_entry_refuses():
     pair = I.exact_pair(5)
     for bad in (dict(iterations=0), dict(iterations=65536), dict(min_inliers=0), dict(refine_iterations=-1), dict(inlier_distance=0.0),
