@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -147,6 +147,19 @@ class LcdMotion3dArgs(C.Structure):
 LCD_M3D_OK, LCD_M3D_FEW_CORRESPONDENCES, LCD_M3D_NO_MODEL, LCD_M3D_FEW_INLIERS, LCD_M3D_BELOW_MIN_INLIERS = 0, 1, 2, 3, 4  # lcd_motion_3d_status
 
 
+class LcdMotionPnpArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("min_inliers", C.c_int32), ("iterations", C.c_int32),
+                ("refine_iterations", C.c_int32), ("variance_median_ratio", C.c_int32), ("seed", C.c_uint32), ("max_variance", C.c_float),
+                ("reproj_error", C.c_double), ("from_word_ids", C.c_void_p), ("from_xyz", C.c_void_p), ("to_word_ids", C.c_void_p),
+                ("to_points", C.c_void_p), ("to_xyz", C.c_void_p), ("from_offsets", C.c_void_p), ("to_offsets", C.c_void_p),
+                ("cameras", C.c_void_p), ("guesses", C.c_void_p), ("out_transform", C.c_void_p), ("out_status", C.c_void_p),
+                ("out_n_matches", C.c_void_p), ("out_n_inliers", C.c_void_p), ("out_variance_lin", C.c_void_p), ("out_angle_cos", C.c_void_p),
+                ("out_variance_kind", C.c_void_p), ("out_matches", C.c_void_p), ("out_inliers", C.c_void_p)]
+
+
+LCD_PNP_OK, LCD_PNP_FEW_CORRESPONDENCES, LCD_PNP_NO_MODEL, LCD_PNP_BELOW_MIN_INLIERS, LCD_PNP_VARIANCE_REJECTED = 0, 1, 2, 3, 4  # lcd_motion_pnp_status
+
+
 KP3D_FILTERS = {"keep_all": LCD_KP3D_KEEP_ALL, "filter_3d": LCD_KP3D_FILTER_3D, "filter_pixel": LCD_KP3D_FILTER_PIXEL}
 
 
@@ -228,6 +241,8 @@ def load():
     L.lcd_keypoints_3d_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
     L.lcd_estimate_motion_3d.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
+    L.lcd_estimate_motion_pnp.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
+    L.lcd_estimate_motion_pnp_dev.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -715,6 +730,77 @@ class Engine:
         a.out_transform, a.out_status, a.out_n_matches, a.out_n_inliers = ptr(d_transform), ptr(d_status), ptr(d_n_matches), ptr(d_n_inliers)
         a.out_variance, a.out_matches, a.out_inliers = ptr(d_variance), ptr(d_matches), ptr(d_inliers)
         self._ck(self.L.lcd_estimate_motion_3d_dev(self.h, C.byref(a)))
+
+    # ---- 3-D to 2-D motion estimation, PnP (stateless; include/lcd.h has the rule)
+    @staticmethod
+    def _pnp_cameras(cameras, n_pairs):
+        """cameras: one dict(fx, fy, cx, cy[, image_width, image_height, local_transform]) for every pair, or a list of them"""
+        if cameras is None:
+            return None
+        cams = [cameras] * max(n_pairs, 0) if isinstance(cameras, dict) else list(cameras)
+        arr = (LcdCamera * max(len(cams), 1))()
+        for i, m in enumerate(cams):
+            t = m.get("local_transform")
+            arr[i] = LcdCamera(m["fx"], m["fy"], m["cx"], m["cy"], int(m.get("image_width", 0)), int(m.get("image_height", 0)),
+                               0 if t is None else 1, 0, (C.c_float * 12)(*([0.0] * 12 if t is None else [float(v) for v in np.asarray(t).reshape(-1)])))
+        return arr
+
+    def _pnp_args(self, n_pairs, fo, to, cams, guesses, min_inliers, iterations, refine_iterations, variance_median_ratio, seed, max_variance,
+                  reproj_error, struct_size=None):
+        a = LcdMotionPnpArgs(C.sizeof(LcdMotionPnpArgs) if struct_size is None else struct_size, n_pairs, int(min_inliers), int(iterations),
+                             int(refine_iterations), int(variance_median_ratio), int(seed) & 0xFFFFFFFF, float(max_variance), float(reproj_error))
+        a.from_offsets, a.to_offsets = None if fo is None else fo.ctypes.data, None if to is None else to.ctypes.data
+        a.cameras = None if cams is None else C.cast(cams, C.c_void_p)
+        a.guesses = None if guesses is None else guesses.ctypes.data
+        return a
+
+    def estimate_motion_pnp(self, from_ids, from_xyz, from_offsets, to_ids, to_points, to_offsets, cameras, to_xyz=None, guesses=None, min_inliers=20,
+                            iterations=100, reproj_error=2.0, refine_iterations=1, variance_median_ratio=4, max_variance=0.0, seed=0, struct_size=None):
+        """lcd_estimate_motion_pnp over host arrays, all pairs concatenated -> dict(transform [n_pairs x 12], status, n_matches, n_inliers,
+        variance_lin, angle_cos, variance_kind [n_pairs], matches [Nt], inliers [Nt]); outputs start as -1 / NaN so that what the call left
+        alone shows"""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fi, ti = np.ascontiguousarray(from_ids, dtype=np.int32).reshape(-1), np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
+        fx, tp = np.ascontiguousarray(from_xyz, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
+        tx = None if to_xyz is None else np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        n_pairs, n = (to if to is not None else fo).shape[0] - 1, ti.shape[0]
+        np1 = max(n_pairs, 1)
+        out = dict(transform=np.full((np1, 12), np.nan, np.float32), status=np.full(np1, -1, np.int32), n_matches=np.full(np1, -1, np.int32),
+                   n_inliers=np.full(np1, -1, np.int32), variance_lin=np.full(np1, np.nan, np.float64), angle_cos=np.full(np1, np.nan, np.float64),
+                   variance_kind=np.full(np1, -1, np.int32), matches=np.full(max(n, 1), -1, np.int32), inliers=np.full(max(n, 1), -1, np.int32))
+        cams = self._pnp_cameras(cameras, n_pairs)
+        a = self._pnp_args(n_pairs, fo, to, cams, gs, min_inliers, iterations, refine_iterations, variance_median_ratio, seed, max_variance,
+                           reproj_error, struct_size)
+        a.from_word_ids, a.from_xyz, a.to_word_ids, a.to_points, a.to_xyz = _p(fi), _p(fx), _p(ti), _p(tp), None if tx is None else _p(tx)
+        a.out_transform, a.out_status, a.out_n_matches, a.out_n_inliers = _p(out["transform"]), _p(out["status"]), _p(out["n_matches"]), _p(out["n_inliers"])
+        a.out_variance_lin, a.out_angle_cos, a.out_variance_kind = _p(out["variance_lin"]), _p(out["angle_cos"]), _p(out["variance_kind"])
+        a.out_matches, a.out_inliers = _p(out["matches"]), _p(out["inliers"])
+        self._ck(self.L.lcd_estimate_motion_pnp(self.h, C.byref(a)))
+        for k in ("transform", "status", "n_matches", "n_inliers", "variance_lin", "angle_cos", "variance_kind"):
+            out[k] = out[k][:max(n_pairs, 0)]
+        out["matches"], out["inliers"] = out["matches"][:n], out["inliers"][:n]
+        return out
+
+    def estimate_motion_pnp_dev(self, d_from_ids, d_from_xyz, from_offsets, d_to_ids, d_to_points, to_offsets, cameras, d_transform, d_status,
+                                d_n_matches, d_n_inliers, d_variance_lin, d_angle_cos, d_variance_kind, d_matches, d_inliers, d_to_xyz=None,
+                                guesses=None, min_inliers=20, iterations=100, reproj_error=2.0, refine_iterations=1, variance_median_ratio=4,
+                                max_variance=0.0, seed=0):
+        """lcd_estimate_motion_pnp_dev on torch tensors of the engine's device (offsets, cameras and guesses stay on the host).  Enqueued, not
+        synchronised."""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        n_pairs = (to if to is not None else fo).shape[0] - 1
+        cams = self._pnp_cameras(cameras, n_pairs)
+        a = self._pnp_args(n_pairs, fo, to, cams, gs, min_inliers, iterations, refine_iterations, variance_median_ratio, seed, max_variance, reproj_error)
+        a.from_word_ids, a.from_xyz, a.to_word_ids, a.to_points, a.to_xyz = ptr(d_from_ids), ptr(d_from_xyz), ptr(d_to_ids), ptr(d_to_points), ptr(d_to_xyz)
+        a.out_transform, a.out_status, a.out_n_matches, a.out_n_inliers = ptr(d_transform), ptr(d_status), ptr(d_n_matches), ptr(d_n_inliers)
+        a.out_variance_lin, a.out_angle_cos, a.out_variance_kind = ptr(d_variance_lin), ptr(d_angle_cos), ptr(d_variance_kind)
+        a.out_matches, a.out_inliers = ptr(d_matches), ptr(d_inliers)
+        self._ck(self.L.lcd_estimate_motion_pnp_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

@@ -1,4 +1,4 @@
-// compact_body.cuh -- what the per-frame kernels of feature_select.hip, keypoints_3d.hip and motion_3d.hip share: the ballot scan that
+// compact_body.cuh -- what the per-frame kernels of feature_select.hip, keypoints_3d.hip, motion_3d.hip and motion_pnp.hip share: the ballot scan that
 // compacts a workgroup's flags in thread order, the gather of rows behind an index list, and the bitonic sort of 64-bit keys in LDS.  Device code only.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>

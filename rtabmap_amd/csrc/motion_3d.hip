@@ -15,8 +15,8 @@
 //     (d) outputs.
 // Nothing of the engine is read or written: the job table is StatelessScratch's, the per-row scratch its d_small.
 #include "engine_impl.h"
-#include "compact_body.cuh"
 #include "motion_3d_rule.h"
+#include "motion_join.cuh"
 
 #include <cmath>
 #include <vector>
@@ -258,14 +258,8 @@ __global__ __launch_bounds__(BLOCK) void motion_3d_kernel(M3dArgs a) {
     int32_t* out_inliers = a.out_inliers + J.first_from;
 
     // ---- (a) join
-    int p2t = 2, p2f = 2;
-    while (p2t < nt) p2t <<= 1;
-    while (p2f < nf) p2f <<= 1;                                        // both <= p_max
-    for (int i = tid; i < p2t; i += BLOCK) keys_t[padded(i)] = i < nt ? ((uint64_t)m3d::id_key(a.to_ids[J.first_to + i]) << 32) | (uint32_t)i : ~0ull;
-    for (int i = tid; i < p2f; i += BLOCK) keys_f[padded(i)] = i < nf ? ((uint64_t)m3d::id_key(a.from_ids[J.first_from + i]) << 32) | (uint32_t)i : ~0ull;
-    __syncthreads();
-    bitonic_sort(keys_t, p2t);
-    bitonic_sort(keys_f, p2f);
+    join_sort_keys(keys_t, a.to_ids + J.first_to, nt);
+    join_sort_keys(keys_f, a.from_ids + J.first_from, nf);
     int m = 0;
     for (int base = 0; base < nf; base += BLOCK) {
         const int p = base + tid;
@@ -273,22 +267,12 @@ __global__ __launch_bounds__(BLOCK) void motion_3d_kernel(M3dArgs a) {
         uint32_t idk = 0;
         float c[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         if (p < nf) {
-            const uint64_t key = keys_f[padded(p)];
-            idk = (uint32_t)(key >> 32);
-            bool unique = (p == 0 || (uint32_t)(keys_f[padded(p - 1)] >> 32) != idk) && (p + 1 >= nf || (uint32_t)(keys_f[padded(p + 1)] >> 32) != idk);
-            int lo = 0, hi = nt;                                       // the first to-key whose id is not below
-            while (unique && lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if ((uint32_t)(keys_t[padded(mid)] >> 32) < idk) lo = mid + 1; else hi = mid;
-            }
-            if (unique && lo < nt) {
-                const uint64_t tk = keys_t[padded(lo)];
-                if ((uint32_t)(tk >> 32) == idk && (lo + 1 >= nt || (uint32_t)(keys_t[padded(lo + 1)] >> 32) != idk)) {
-                    const float* pf = a.from_xyz + (J.first_from + (int64_t)(uint32_t)key) * 3;
-                    const float* pt = a.to_xyz + (J.first_to + (int64_t)(uint32_t)tk) * 3;
-                    c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2]; c[3] = pt[0]; c[4] = pt[1]; c[5] = pt[2];
-                    keep = m3d::keep_pair(c[0], c[1], c[2], c[3], c[4], c[5]);
-                }
+            uint32_t row_f, row_t;
+            if (join_lookup(keys_f, nf, keys_t, nt, p, idk, row_f, row_t)) {
+                const float* pf = a.from_xyz + (J.first_from + (int64_t)row_f) * 3;
+                const float* pt = a.to_xyz + (J.first_to + (int64_t)row_t) * 3;
+                c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2]; c[3] = pt[0]; c[4] = pt[1]; c[5] = pt[2];
+                keep = m3d::keep_pair(c[0], c[1], c[2], c[3], c[4], c[5]);
             }
         }
         int total;

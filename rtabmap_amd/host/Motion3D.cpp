@@ -6,6 +6,7 @@
 
 #include "../../include/lcd.h"
 #include "../csrc/motion_3d_rule.h"
+#include "LaneSum.h"
 
 namespace rtabmap_amd {
 
@@ -13,16 +14,8 @@ namespace {
 
 namespace rule = lcd::m3d;
 
-// the sum of e(0) .. e(n - 1) in the rule's order: lane l adds the elements l, l + LANES, ... in ascending order, then a halving tree
 template <class F>
-float laneTreeSum(int n, F e) {
-    float part[rule::LANES];
-    for (int l = 0; l < rule::LANES; ++l) part[l] = 0.0f;
-    for (int i = 0; i < n; ++i) part[i % rule::LANES] = part[i % rule::LANES] + e(i);
-    for (int s = rule::LANES / 2; s >= 1; s >>= 1)
-        for (int l = 0; l < s; ++l) part[l] = part[l] + part[l + s];
-    return part[0];
-}
+float laneTreeSum(int n, F e) { return rtabmap_amd::laneTreeSum<rule::LANES>(n, e); }
 
 // the backend of rule::solve as a loop; X: the correspondences' coordinates, [6][m] (from x, y, z, to x, y, z)
 struct CpuBackend {

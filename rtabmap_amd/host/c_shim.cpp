@@ -10,6 +10,7 @@
 #include "FeatureSelect.h"
 #include "Keypoints3D.h"
 #include "MemoryHip.h"
+#include "Motion2D.h"
 #include "Motion3D.h"
 #include "RtabmapHip.h"
 
@@ -265,6 +266,55 @@ int hm3_estimate(void* h, const int* idsA, const float* xyzA, int nA, const int*
     std::vector<int> matches, inliers;
     const Transform3D t = Motion3D::estimateMotion3DTo3D(((VWDictionaryHip*)h)->engine(), a, b, minInliers, inliersDistance, iterations, refineIterations,
                                                          outCovariance, &matches, &inliers, seed);
+    std::copy(t.data, t.data + 12, outTransform);
+    outCounts[0] = (int)matches.size(); outCounts[1] = (int)inliers.size();
+    std::copy(matches.begin(), matches.end(), outMatches);
+    std::copy(inliers.begin(), inliers.end(), outInliers);
+    return t.isNull() ? 0 : 1;
+}
+// motion_pnp_cpu (no engine involved).  camera[4] = fx, fy, cx, cy; image[2]; local: 12 floats or null; guess: 12 floats or null; toXyz may be null.
+// outTransform[12], outScalars[4] = status, matches, inliers, variance kind; outVariance[2] = linear, cosine; outMatches / outInliers hold nTo ids.
+// 1 = done, 0 = refused
+int hmp_cpu(const int* fromIds, const float* fromXyz, int nFrom, const int* toIds, const float* toPoints, const float* toXyz, int nTo, const float* camera,
+            const int* image, const float* local, const float* guess, int minInliers, int iterations, double reprojError, int refineIterations,
+            int varianceMedianRatio, float maxVariance, unsigned seed, int steps, float* outTransform, int* outScalars, double* outVariance, int* outMatches,
+            int* outInliers) {
+    lcd_camera cam = {};
+    cam.fx = camera[0]; cam.fy = camera[1]; cam.cx = camera[2]; cam.cy = camera[3]; cam.image_width = image[0]; cam.image_height = image[1];
+    cam.has_local_transform = local ? 1 : 0;
+    if (local) std::copy(local, local + 12, cam.local_transform);
+    MotionPnpParams p;
+    p.minInliers = minInliers; p.iterations = iterations; p.reprojError = reprojError; p.refineIterations = refineIterations;
+    p.varianceMedianRatio = varianceMedianRatio; p.maxVariance = maxVariance; p.seed = seed; p.steps = steps;
+    MotionPnpResult r;
+    if (!motion_pnp_cpu(fromIds, fromXyz, nFrom, toIds, toPoints, toXyz, nTo, cam, guess, p, r)) return 0;
+    std::copy(r.transform, r.transform + 12, outTransform);
+    outScalars[0] = r.status; outScalars[1] = (int)r.matches.size(); outScalars[2] = (int)r.inliers.size(); outScalars[3] = r.varianceKind;
+    outVariance[0] = r.varianceLin; outVariance[1] = r.angleCos;
+    std::copy(r.matches.begin(), r.matches.end(), outMatches);
+    std::copy(r.inliers.begin(), r.inliers.end(), outInliers);
+    return 1;
+}
+// Motion2D::estimateMotion3DTo2D through the dictionary's engine, the frames as parallel arrays.  outCovariance[36]; returns 1 with a transform, 0 without
+int hmp_estimate(void* h, const int* idsA, const float* xyzA, int nA, const int* idsB, const float* pointsB, const float* xyzB, int nB, const float* camera,
+                 const int* image, const float* local, const float* guess, int minInliers, int iterations, double reprojError, int refineIterations,
+                 int varianceMedianRatio, float maxVariance, unsigned seed, float* outTransform, double* outCovariance, int* outCounts, int* outMatches,
+                 int* outInliers) {
+    lcd_camera cam = {};
+    cam.fx = camera[0]; cam.fy = camera[1]; cam.cx = camera[2]; cam.cy = camera[3]; cam.image_width = image[0]; cam.image_height = image[1];
+    cam.has_local_transform = local ? 1 : 0;
+    if (local) std::copy(local, local + 12, cam.local_transform);
+    std::multimap<int, Point3f> a, b3;
+    std::multimap<int, Point2f> b;
+    for (int i = 0; i < nA; ++i) a.insert(std::make_pair(idsA[i], Point3f{xyzA[3 * i], xyzA[3 * i + 1], xyzA[3 * i + 2]}));
+    for (int i = 0; i < nB; ++i) b.insert(std::make_pair(idsB[i], Point2f{pointsB[2 * i], pointsB[2 * i + 1]}));
+    if (xyzB)
+        for (int i = 0; i < nB; ++i) b3.insert(std::make_pair(idsB[i], Point3f{xyzB[3 * i], xyzB[3 * i + 1], xyzB[3 * i + 2]}));
+    Transform3D g;
+    if (guess) std::copy(guess, guess + 12, g.data);
+    std::vector<int> matches, inliers;
+    const Transform3D t = Motion2D::estimateMotion3DTo2D(((VWDictionaryHip*)h)->engine(), a, b, cam, minInliers, iterations, reprojError, refineIterations,
+                                                         varianceMedianRatio, maxVariance, g, b3, outCovariance, &matches, &inliers, seed);
     std::copy(t.data, t.data + 12, outTransform);
     outCounts[0] = (int)matches.size(); outCounts[1] = (int)inliers.size();
     std::copy(matches.begin(), matches.end(), outMatches);

@@ -72,6 +72,8 @@ def lib():
         L.hk3_filter_pixel.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, cf, cf, vp]
         L.hm3_cpu.argtypes = [vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, ci, vp, vp, vp, vp, vp]
         L.hm3_estimate.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, vp, vp, vp, vp, vp]
+        L.hmp_cpu.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, C.c_double, ci, ci, cf, C.c_uint, ci, vp, vp, vp, vp, vp]
+        L.hmp_estimate.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, C.c_double, ci, ci, cf, C.c_uint, vp, vp, vp, vp, vp]
         L.hmem_select_error.argtypes = [vp]
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -252,6 +254,45 @@ def motion3d_cpu(from_ids, from_xyz, to_ids, to_xyz, min_inliers=20, inlier_dist
     return dict(transform=t, status=int(sc[0]), variance=var[0], matches=om[:sc[1]].copy(), inliers=oi[:sc[2]].copy())
 
 
+def _pnp_arrays(to_ids, to_points, to_xyz, camera, image_size, local_transform, guess):
+    ti = np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
+    tp = np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
+    tx = None if to_xyz is None else np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+    if tp.shape[0] != ti.shape[0] or (tx is not None and tx.shape[0] != ti.shape[0]):
+        raise ValueError("one keypoint (and one 3-D point) per word id")
+    cam = np.ascontiguousarray(camera, dtype=np.float32).reshape(4)
+    img = np.ascontiguousarray(image_size, dtype=np.int32).reshape(2)
+    loc = None if local_transform is None else np.ascontiguousarray(local_transform, dtype=np.float32).reshape(12)
+    gs = None if guess is None else np.ascontiguousarray(guess, dtype=np.float32).reshape(12)
+    return ti, tp, tx, cam, img, loc, gs
+
+
+def _pn(a):
+    return None if a is None else _p(a)
+
+
+def motion_pnp_cpu(from_ids, from_xyz, to_ids, to_points, to_xyz=None, camera=(525.0, 525.0, 319.5, 239.5), image_size=(0, 0), local_transform=None,
+                   guess=None, min_inliers=20, iterations=100, reproj_error=2.0, refine_iterations=1, variance_median_ratio=4, max_variance=0.0,
+                   seed=0, steps=0):
+    """the rule of lcd_estimate_motion_pnp on the CPU (host/Motion2D.cpp, no device) -> dict(transform [12], status, variance_lin, angle_cos,
+    variance_kind, matches, inliers), or None where the call is refused.  steps != 0 is for measuring how the rule's Gauss-Newton step count
+    was chosen."""
+    fi, fx = _frame_arrays(from_ids, from_xyz)
+    ti, tp, tx, cam, img, loc, gs = _pnp_arrays(to_ids, to_points, to_xyz, camera, image_size, local_transform, guess)
+    if fi.shape[0] > 8192 or ti.shape[0] > 8192:
+        return None
+    n = max(ti.shape[0], 1)
+    t, sc, var = np.zeros(12, np.float32), np.zeros(4, np.int32), np.zeros(2, np.float64)
+    om, oi = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ok = lib().hmp_cpu(_p(fi), _p(fx), fi.shape[0], _p(ti), _p(tp), _pn(tx), ti.shape[0], _p(cam), _p(img), _pn(loc), _pn(gs), int(min_inliers),
+                       int(iterations), float(reproj_error), int(refine_iterations), int(variance_median_ratio), float(max_variance),
+                       int(seed) & 0xFFFFFFFF, int(steps), _p(t), _p(sc), _p(var), _p(om), _p(oi))
+    if not ok:
+        return None
+    return dict(transform=t, status=int(sc[0]), variance_lin=var[0], angle_cos=var[1], variance_kind=int(sc[3]), matches=om[:sc[1]].copy(),
+                inliers=oi[:sc[2]].copy())
+
+
 class VWDictionaryHip:
     def __init__(self, strategy=kNNBruteForceHIP, incremental=True, nndr=0.8, new_words_compared_together=True,
                  dictionary_path="", device=0, _handle=None, _owner=None):
@@ -329,6 +370,22 @@ class VWDictionaryHip:
         om, oi = np.zeros(n, np.int32), np.zeros(n, np.int32)
         ok = lib().hm3_estimate(self.h, _p(ia), _p(xa), ia.shape[0], _p(ib), _p(xb), ib.shape[0], int(min_inliers), float(inliers_distance),
                                 int(iterations), int(refine_iterations), int(seed) & 0xFFFFFFFF, _p(t), _p(cov), _p(counts), _p(om), _p(oi))
+        return (t if ok else None), cov.reshape(6, 6), om[:counts[0]].tolist(), oi[:counts[1]].tolist()
+
+    def estimate_motion_pnp(self, words3a, words2b, words3b=None, camera=(525.0, 525.0, 319.5, 239.5), image_size=(0, 0), local_transform=None,
+                            guess=None, min_inliers=20, iterations=100, reproj_error=2.0, refine_iterations=1, variance_median_ratio=4,
+                            max_variance=0.0, seed=0):
+        """Motion2D::estimateMotion3DTo2D (util3d_motion_estimation.cpp:59-289) over this dictionary's long-lived engine handle; words3a is
+        (word ids, [n x 3] points), words2b (word ids, [n x 2] keypoints), words3b None or the [n x 3] points of words2b's rows; an id may
+        repeat as in RegistrationVis' multimaps.  -> (transform [12] or None, covariance [6 x 6], matches, inliers)"""
+        ia, xa = _frame_arrays(*words3a)
+        ib, pb, xb, cam, img, loc, gs = _pnp_arrays(words2b[0], words2b[1], words3b, camera, image_size, local_transform, guess)
+        n = max(ib.shape[0], 1)
+        t, cov, counts = np.zeros(12, np.float32), np.zeros(36, np.float64), np.zeros(2, np.int32)
+        om, oi = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ok = lib().hmp_estimate(self.h, _p(ia), _p(xa), ia.shape[0], _p(ib), _p(pb), _pn(xb), ib.shape[0], _p(cam), _p(img), _pn(loc), _pn(gs),
+                                int(min_inliers), int(iterations), float(reproj_error), int(refine_iterations), int(variance_median_ratio),
+                                float(max_variance), int(seed) & 0xFFFFFFFF, _p(t), _p(cov), _p(counts), _p(om), _p(oi))
         return (t if ok else None), cov.reshape(6, 6), om[:counts[0]].tolist(), oi[:counts[1]].tolist()
 
     def update(self):
