@@ -120,13 +120,57 @@ template <int M>
 __device__ __forceinline__ void lds_read_ops(const uint32_t (&addr)[8], uint4 (&out)[8], uint32_t addr32, float& out32) {
     if (M == 1) lds_read4_b128(addr, out, addr32, out32); else lds_read8_b128(addr, out, addr32, out32);
 }
-// third smallest of two sorted triples
-__device__ __forceinline__ uint64_t third_of_two_triples(uint64_t a0, uint64_t a1, uint64_t a2, uint64_t b0, uint64_t b1, uint64_t b2) {
-    const uint64_t x = a1 > b0 ? a1 : b0, y = a0 > b1 ? a0 : b1;
-    uint64_t m = a2 < b2 ? a2 : b2;
+// third smallest of two sorted triples (K: the 64-bit merge keys, or the 32-bit record keys below)
+template <class K>
+__device__ __forceinline__ K third_of_two_triples(K a0, K a1, K a2, K b0, K b1, K b2) {
+    const K x = a1 > b0 ? a1 : b0, y = a0 > b1 ? a0 : b1;
+    K m = a2 < b2 ? a2 : b2;
     m = m < x ? m : x;
     return m < y ? m : y;
 }
+// The two halves of a query's rows meet (lanes l and l ^ 32 hold the sorted triples of the same query): the best two of the six keys and the
+// third, the bound on everything dropped.
+__device__ __forceinline__ uint32_t shfl_xor_key(uint32_t v, int m) { return (uint32_t)__shfl_xor((int)v, m, 64); }
+__device__ __forceinline__ uint64_t shfl_xor_key(uint64_t v, int m) { return shfl_xor_u64(v, m); }
+template <class K>
+__device__ __forceinline__ void merge_halves(K a0, K a1, K a2, K& m0, K& m1, K& third) {
+    const K b0 = shfl_xor_key(a0, 32), b1 = shfl_xor_key(a1, 32), b2 = shfl_xor_key(a2, 32);
+    m0 = a0 < b0 ? a0 : b0;
+    const K hx = a0 < b0 ? b0 : a0, lx = a1 < b1 ? a1 : b1;
+    m1 = hx < lx ? hx : lx;
+    third = third_of_two_triples(a0, a1, a2, b0, b1, b2);
+}
+
+// ---- what a filter hands to the re-rank: one record per (row block, query), block-major ([n_blocks][qpad]: the filter's lanes own consecutive
+// queries of ONE block, so its records leave as full lines -- a wave's 32 queries make one 512-byte write; query-major they were 16-byte
+// pieces of 112 000 different lines per frame, and the write-back of those partial lines at the end of the launch was a third of launch
+// A's wall time).  The record type is the filter's:
+//   StripRecord  (the 64-float filters, whose block is ONE strip): 16 bytes, stored with one instruction and fetched with one request.  The two
+//                kept keys stay 32-bit strip keys; the block's first tile follows from the block index, and the half of the tile's rows the
+//                key's lane held travels in bit 0 of the index -- the filters select 4-row groups (push_group4, bf_pair: index 4 st), so the
+//                index's two low bits are free and the score keeps every bit it has in a strip key.  record_key() writes a key,
+//                record_widen() -- the one place that calls widen_key for these filters -- rebuilds the merge key on the reader's side.
+//   ShareRecords (the 128- / 256-float filter, wide_filter_body.cuh): a share is up to FOUR strips; strip, tile and group fill the index's
+//                seven bits, so no bit is left for the half: that filter keeps two 64-bit merge keys and the bound in arrays of their own.
+struct __attribute__((aligned(16))) StripRecord { uint32_t key[BF_KEEP]; uint32_t bound; uint32_t spare; };
+static_assert(sizeof(StripRecord) == 16 && BF_KEEP == 2, "one 16-byte store, one 16-byte request");
+constexpr uint32_t REC_KEY_NONE = (uint32_t)MF_KEY_NONE;
+constexpr uint32_t REC_HALF_BIT = 1u;
+static_assert((MF_IDX_MASK & 3u) == 3u && REC_HALF_BIT < 4u, "the group index leaves the two low index bits free");
+// strip key of a 4-row group (lane half `half`) -> record key.  A slightly negative score (rounding of a distance ~ 0) becomes +0 HERE, so that
+// record keys compare (unsigned) exactly as the merge keys they widen to: score bits, then tile, group and half = score bits, then row.
+__device__ __forceinline__ uint32_t record_key(int32_t k, int half) {
+    if (k == MF_KEY_NONE) return REC_KEY_NONE;
+    return (k < 0 ? ((uint32_t)k & MF_IDX_MASK) : (uint32_t)k) | (half ? REC_HALF_BIT : 0u);
+}
+// record key -> merge key (score bits << 32 | the group's first vocabulary row); tile0: the first tile of the record's block
+__device__ __forceinline__ uint64_t record_widen(uint32_t k, int tile0) {
+    if (k == REC_KEY_NONE) return KEY_NONE;
+    return widen_key((int32_t)(k & ~REC_HALF_BIT), tile0, (int)(k & REC_HALF_BIT));
+}
+// the score bits of a record key (KEY_NONE -> +inf), without the row
+__device__ __forceinline__ uint32_t record_score(uint32_t k) { return k == REC_KEY_NONE ? 0x7f800000u : min(k & ~MF_IDX_MASK, 0x7f800000u); }
+struct ShareRecords { uint64_t* keys; uint32_t* bound; };        // keys [n_blocks][qpad][BF_KEEP], bound [n_blocks][qpad] f32 bits
 
 // ---- same-frame distance matrix, computed by extra workgroups of the filter launch (independent of the 2-NN; a launch of its own
 // costs more than the work).  One workgroup = one 64 x 64 tile of the upper triangle of D[r][c] = |q_r - q_c|^2 in the reference's
@@ -283,33 +327,19 @@ __device__ __forceinline__ void flush_pending(const f32x16& p0, const f32x16& p1
 }
 
 // The two halves of a query's rows meet in registers: best two of the six keys, and the third as the bound on everything this workgroup
-// dropped for the query (qi; the strip starts at tile0 and is row block bx).
-// partial_keys [n_blocks][qpad][BF_KEEP] u64, partial_bound [n_blocks][qpad] f32 bits (block-major: the filter's lanes own consecutive
-// queries of ONE block, so its records leave as full lines -- a wave's 32 queries make one 512-byte write; query-major they were 16-byte
-// pieces of 112 000 different lines per frame, and the write-back of those partial lines at the end of the launch was a third of launch
-// A's wall time).
-__device__ __forceinline__ void merge_store_keys(int32_t k0, int32_t k1, int32_t k2, int tile0, int half, int qi, int qpad, int bx,
-                                                 uint64_t* __restrict__ partial_keys, uint32_t* __restrict__ partial_bound) {
-    const uint64_t a0 = widen_key(k0, tile0, half), a1 = widen_key(k1, tile0, half), a2 = widen_key(k2, tile0, half);
-    const uint64_t b0 = shfl_xor_u64(a0, 32), b1 = shfl_xor_u64(a1, 32), b2 = shfl_xor_u64(a2, 32);
-    const uint64_t m0 = a0 < b0 ? a0 : b0;
-    const uint64_t hx = a0 < b0 ? b0 : a0, lx = a1 < b1 ? a1 : b1;
-    const uint64_t m1 = hx < lx ? hx : lx;
-    const uint64_t third = third_of_two_triples(a0, a1, a2, b0, b1, b2);
-    if (half == 0 && qi < qpad) {
-        uint64_t* dst = partial_keys + ((size_t)bx * qpad + qi) * BF_KEEP;
-        dst[0] = m0;
-        dst[1] = m1;
-        partial_bound[(size_t)bx * qpad + qi] = (uint32_t)min(third >> 32, (uint64_t)0x7f800000u);
-    }
+// dropped for the query (qi; row block bx) -- one StripRecord, records[bx][qi], one 16-byte store.
+__device__ __forceinline__ void merge_store_keys(int32_t k0, int32_t k1, int32_t k2, int half, int qi, int qpad, int bx, StripRecord* __restrict__ records) {
+    uint32_t m0, m1, third;
+    merge_halves(record_key(k0, half), record_key(k1, half), record_key(k2, half), m0, m1, third);
+    if (half == 0 && qi < qpad)
+        *reinterpret_cast<uint4*>(records + (size_t)bx * qpad + qi) = make_uint4(m0, m1, record_score(third), 0u);
 }
 
 // The one-strip filter.  Grid (1-D): n_blocks x ceil(nq / 512) filter workgroups first, then sd.n_tiles distance-matrix workgroups.
 template <int M>
 __device__ __forceinline__ void knn_bf16_filter_body(float* s_dyn, int bid, const float* __restrict__ vocab_bf, const float* __restrict__ row_norm,
                                                      int n_rows, const float* __restrict__ queries, int nq, int qpad,
-                                                     int tiles_per_block, int n_blocks, uint64_t* __restrict__ partial_keys,
-                                                     uint32_t* __restrict__ partial_bound, const SelfdistJob& sd,
+                                                     int tiles_per_block, int n_blocks, StripRecord* __restrict__ records, const SelfdistJob& sd,
                                                      const int32_t* __restrict__ n_lo = nullptr) {
     // n_lo: the number of rows this search may see, on the device (a pipelined handle appends the previous frames' new words while
     // this launch runs: rows at or beyond n_lo[0] -- up to n_rows, the host's upper bound -- are masked with an infinite |row|^2)
@@ -412,7 +442,7 @@ __device__ __forceinline__ void knn_bf16_filter_body(float* s_dyn, int bid, cons
     if (tile0 < tile1) flush_pending(p0, p1, (uint32_t)(tile1 - 1 - tile0), k0, k1, k2);
     MF_STAMP(2);
 #pragma unroll
-    for (int g = 0; g < NG; ++g) merge_store_keys(k0[g], k1[g], k2[g], tile0, half, q0 + g * 32 + col, qpad, bx, partial_keys, partial_bound);
+    for (int g = 0; g < NG; ++g) merge_store_keys(k0[g], k1[g], k2[g], half, q0 + g * 32 + col, qpad, bx, records);
     MF_STAMP(3);
 }
 
@@ -500,8 +530,8 @@ __device__ __forceinline__ void load_group_presplit(const uint4* qsplit, const f
 template <int M>
 __device__ __forceinline__ void knn_bf16_filter_body_q(float* s_dyn, int bid, const float* __restrict__ vocab_bf, const float* __restrict__ row_norm,
                                                        int n_rows, const uint4* qsplit, const float* qnorm, int nq, int qpad,
-                                                       int tiles_per_block, int n_blocks, uint64_t* __restrict__ partial_keys,
-                                                       uint32_t* __restrict__ partial_bound, const SelfdistJob& sd, const int32_t* __restrict__ n_lo) {
+                                                       int tiles_per_block, int n_blocks, StripRecord* __restrict__ records, const SelfdistJob& sd,
+                                                       const int32_t* __restrict__ n_lo) {
     constexpr int NG = BF_NG;
     constexpr int NW = MF_WAVES;
     constexpr int QW = BF_QW;
@@ -597,7 +627,7 @@ __device__ __forceinline__ void knn_bf16_filter_body_q(float* s_dyn, int bid, co
     if (tile0 < tile1) flush_pending(p0, p1, (uint32_t)(tile1 - 1 - tile0), k0, k1, k2);
     MF_STAMP(2);
 #pragma unroll
-    for (int g = 0; g < NG; ++g) merge_store_keys(k0[g], k1[g], k2[g], tile0, half, q0 + g * 32 + col, qpad, bx, partial_keys, partial_bound);
+    for (int g = 0; g < NG; ++g) merge_store_keys(k0[g], k1[g], k2[g], half, q0 + g * 32 + col, qpad, bx, records);
     MF_STAMP(3);
 }
 
@@ -722,8 +752,7 @@ __device__ __forceinline__ void bf_lds_barrier() { asm volatile("s_waitcnt lgkmc
 template <int M>
 __device__ __forceinline__ void knn_bf16_filter_body_p(float* s_dyn, int bid, const float* __restrict__ vocab_bf, const float* __restrict__ row_norm,
                                                        int n_rows, const float* __restrict__ queries, int nq, int qpad,
-                                                       int tiles_per_block, int n_blocks, int px, uint64_t* __restrict__ partial_keys,
-                                                       uint32_t* __restrict__ partial_bound, const SelfdistJob& sd,
+                                                       int tiles_per_block, int n_blocks, int px, StripRecord* __restrict__ records, const SelfdistJob& sd,
                                                        const int32_t* __restrict__ n_lo = nullptr) {
     if (n_lo) n_rows = min(n_rows, max(n_lo[0], 1));                 // rows the search may see (see knn_bf16_filter_body); the sentinel entry follows them
     constexpr int NG = BF_NG;
@@ -822,7 +851,7 @@ __device__ __forceinline__ void knn_bf16_filter_body_p(float* s_dyn, int bid, co
         }
         if (tile0 < tile1) flush_pending(p0, p1, (uint32_t)(tile1 - 1 - tile0), k0, k1, k2);
 #pragma unroll
-        for (int g = 0; g < NG; ++g) merge_store_keys(k0[g], k1[g], k2[g], tile0, half, q0 + g * 32 + col, qpad, bx, partial_keys, partial_bound);
+        for (int g = 0; g < NG; ++g) merge_store_keys(k0[g], k1[g], k2[g], half, q0 + g * 32 + col, qpad, bx, records);
         if (s + 2 < n_my) {                                          // strip s is read by every wave: its slots take strip s + 2
             bf_lds_barrier();
             bf_request_strip<M>(vocab_bf, row_norm, n_rows, bx0 + (s + 2) * px, tiles_per_block, n_tiles, lane, wave, col, half,

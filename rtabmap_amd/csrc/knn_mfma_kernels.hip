@@ -444,21 +444,18 @@ __global__ __launch_bounds__(MF_BLOCK, 1) void knn_mfma_filter_kernel(const floa
 template <int M>
 __global__ __launch_bounds__(256) void knn_bf16_filter_kernel_p(const float* __restrict__ vocab_bf, const float* __restrict__ row_norm, int n_rows,
                                                                 const float* __restrict__ queries, int nq, int qpad, int tiles_per_block, int n_blocks,
-                                                                int px, uint64_t* __restrict__ partial_keys, uint32_t* __restrict__ partial_bound,
-                                                                SelfdistJob sd) {
+                                                                int px, StripRecord* __restrict__ records, SelfdistJob sd) {
     extern __shared__ __attribute__((aligned(16))) float s_dyn_p[];
-    knn_bf16_filter_body_p<M>(s_dyn_p, (int)blockIdx.x, vocab_bf, row_norm, n_rows, queries, nq, qpad, tiles_per_block, n_blocks, px, partial_keys,
-                           partial_bound, sd);
+    knn_bf16_filter_body_p<M>(s_dyn_p, (int)blockIdx.x, vocab_bf, row_norm, n_rows, queries, nq, qpad, tiles_per_block, n_blocks, px, records, sd);
 }
 
 template <int M>
 __global__ __launch_bounds__(MF_WAVES * 64) void knn_bf16_filter_kernel(const float* __restrict__ vocab_bf, const float* __restrict__ row_norm,
                                                                       int n_rows, const float* __restrict__ queries, int nq, int qpad,
-                                                                      int tiles_per_block, int n_blocks, uint64_t* __restrict__ partial_keys,
-                                                                      uint32_t* __restrict__ partial_bound, SelfdistJob sd) {
+                                                                      int tiles_per_block, int n_blocks, StripRecord* __restrict__ records,
+                                                                      SelfdistJob sd) {
     extern __shared__ __attribute__((aligned(16))) float s_dyn_f[];
-    knn_bf16_filter_body<M>(s_dyn_f, (int)blockIdx.x, vocab_bf, row_norm, n_rows, queries, nq, qpad, tiles_per_block, n_blocks, partial_keys,
-                             partial_bound, sd);
+    knn_bf16_filter_body<M>(s_dyn_f, (int)blockIdx.x, vocab_bf, row_norm, n_rows, queries, nq, qpad, tiles_per_block, n_blocks, records, sd);
 }
 
 // ------------------------------------------------------------------------------------------------ re-rank + certificate
@@ -466,15 +463,14 @@ __global__ __launch_bounds__(MF_WAVES * 64) void knn_bf16_filter_kernel(const fl
 #include "rerank_body.cuh"
 
 template <int DIM, int KEEP, bool LAST_KEY_BOUNDS, bool BF16>
-__global__ __launch_bounds__(MF_BLOCK) void knn_mfma_rerank_kernel(const uint64_t* __restrict__ partial_keys,
-                                                                   const uint32_t* __restrict__ partial_lmin, int n_blocks, int nq,
+__global__ __launch_bounds__(MF_BLOCK) void knn_mfma_rerank_kernel(KeptKeys<BF16> kk, int n_blocks, int nq,
                                                                    const float* __restrict__ vocab, const float* __restrict__ queries,
                                                                    const int32_t* __restrict__ row_id,
                                                                    const uint32_t* __restrict__ norm_max_bits,
                                                                    int32_t* __restrict__ out_row, int32_t* __restrict__ out_word,
                                                                    float* __restrict__ out_dist, int32_t* __restrict__ fail_list,
                                                                    int32_t* __restrict__ fail_count, CandBits cb, int f16, int n_rows) {
-    knn_mfma_rerank_body<DIM, KEEP, LAST_KEY_BOUNDS, BF16>((int)blockIdx.x, partial_keys, partial_lmin, n_blocks, nq, vocab, queries, row_id,
+    knn_mfma_rerank_body<DIM, KEEP, LAST_KEY_BOUNDS, BF16>((int)blockIdx.x, kk, n_blocks, nq, vocab, queries, row_id,
                                                           norm_max_bits, out_row, out_word, out_dist, fail_list, fail_count, cb, nullptr, nullptr,
                                                           n_rows, nullptr, 0, f16);
 }
@@ -495,13 +491,13 @@ __global__ __launch_bounds__(MF_BLOCK) void knn_mfma_rerank_kernel(const uint64_
 // previous launch (A -> B -> A ...).  The per-frame scratch exists twice (see engine.h).
 struct FilterArgs {
     const float* vocab_bf; const float* row_norm; int n_rows; const float* queries; int nq, qpad, tiles_per_block, n_blocks;
-    uint64_t* pk; uint32_t* pl; SelfdistJob sd; const int32_t* n_lo;
+    StripRecord* records; SelfdistJob sd; const int32_t* n_lo;
     const uint4* qsplit; const float* qnorm;                           // pre-split queries (non-persistent pipelined launch)
     int delay;                                                         // PipeOpts::filter_delay (timing experiments)
     const float* sh_bf; const float* sh_norm; int sh_rows; float* sh_x; int sh_ld;   // shadow scores (shadow_scores_body): the operand rows of the frame before, the score matrix
 };
 struct RerankArgs {
-    const uint64_t* pk; const uint32_t* pl; int n_blocks, nq; const float* vocab; const float* queries; const int32_t* row_id;
+    KeptKeys<true> kk; int n_blocks, nq; const float* vocab; const float* queries; const int32_t* row_id;
     const uint32_t* norm_max_bits; int32_t* out_row; int32_t* out_word; float* out_dist; int32_t* fail_list; int32_t* fail_count; CandBits cb;
     const int32_t* n_lo; const int32_t* n_hi; int plan_rows;
     int stage_rows;                                                    // rows the launch's dynamic LDS stages (0: none)
@@ -542,11 +538,11 @@ __device__ __forceinline__ void frame_a_body(float* s_dyn, const FilterArgs& f, 
     if (bid >= after_filter + tr.n_q_wgs) { frame_resolve_part<PIPE_BLOCK>((uint32_t*)s_dyn, r, bid - after_filter - tr.n_q_wgs + 1, 1 + tr.n_redo); A_STAMP(1); return; }
     for (int i = 0; i < f.delay; ++i) __builtin_amdgcn_s_sleep(1);      // (0 unless "filter_delay" is set)
     if constexpr (PERSISTENT)
-        knn_bf16_filter_body_p<M>(s_dyn, bid - n_front, f.vocab_bf, f.row_norm, f.n_rows, f.queries, f.nq, f.qpad, f.tiles_per_block, f.n_blocks, px, f.pk,
-                               f.pl, f.sd, f.n_lo);
+        knn_bf16_filter_body_p<M>(s_dyn, bid - n_front, f.vocab_bf, f.row_norm, f.n_rows, f.queries, f.nq, f.qpad, f.tiles_per_block, f.n_blocks, px,
+                               f.records, f.sd, f.n_lo);
     else
-        knn_bf16_filter_body_q<M>(s_dyn, bid - n_front, f.vocab_bf, f.row_norm, f.n_rows, f.qsplit, f.qnorm, f.nq, f.qpad, f.tiles_per_block, f.n_blocks, f.pk,
-                               f.pl, f.sd, f.n_lo);
+        knn_bf16_filter_body_q<M>(s_dyn, bid - n_front, f.vocab_bf, f.row_norm, f.n_rows, f.qsplit, f.qnorm, f.nq, f.qpad, f.tiles_per_block, f.n_blocks,
+                               f.records, f.sd, f.n_lo);
     A_STAMP(1);
 }
 // two workgroups per compute unit: 66 KB of LDS each, and a register budget of two waves per SIMD
@@ -605,7 +601,7 @@ __global__ __launch_bounds__(PIPE_B_BLOCK, 6) void frame_b_kernel(RerankArgs k, 
         if (2 * pair >= k.nq) return;
         extern __shared__ __attribute__((aligned(16))) float s_dyn_b[];
         const bool wr_any = !WITH_APPEND && app.ap.enabled && app.ap.defer_rows;
-        knn_mfma_rerank_body<64, BF_KEEP, false, true, 2>(2 * pair, k.pk, k.pl, k.n_blocks, k.nq, k.vocab, k.queries, k.row_id, k.norm_max_bits, k.out_row,
+        knn_mfma_rerank_body<64, BF_KEEP, false, true, 2>(2 * pair, k.kk, k.n_blocks, k.nq, k.vocab, k.queries, k.row_id, k.norm_max_bits, k.out_row,
                                                           k.out_word, k.out_dist, k.fail_list, k.fail_count, k.cb, k.n_lo, k.n_hi, k.plan_rows,
                                                           s_dyn_b, k.stage_rows, k.f16, k.pend_desc, k.pend_list, k.pend_first_id, k.cross, k.cross_ld
                                                           , app, wr_any && (n_wr == 0 || rows_only), rows_only ? wr_index : pair, n_wr > 0 ? n_wr : (k.nq + 1) / 2
@@ -776,7 +772,8 @@ hipError_t launch_knn_mfma(int dim, const void* vocab, const float* row_norm, co
         if (ev_end) { e = hipEventRecord(ev_end, s); if (e != hipSuccess) return e; }
     }
     if (dim != 64) return hipErrorInvalidValue;
-    knn_mfma_rerank_kernel<64, MF_KEEP, true, false><<<p.q, MF_BLOCK, 0, s>>>(pk, pl, p.n_blocks, p.q, (const float*)vocab,
+    const KeptKeys<false> kk{pk, pl};
+    knn_mfma_rerank_kernel<64, MF_KEEP, true, false><<<p.q, MF_BLOCK, 0, s>>>(kk, p.n_blocks, p.q, (const float*)vocab,
                                                                                    (const float*)queries, row_id, norm_max_bits, out_row,
                                                                                    out_word, out_dist, fail_list, fail_count,
                                                                                    cb ? *cb : CandBits{}, 0, p.n_rows);
@@ -815,9 +812,12 @@ MfmaPlan knn_bf16_plan(int q, int n_rows, int other_wgs) {
     p.n_blocks = n_tiles > 0 ? (n_tiles + tpb - 1) / tpb : 0;
     return p;
 }
+// StripRecord [n_blocks][qpad].  The floor of ONE block is load-bearing: the re-rank's record requests carry no condition, a thread without a
+// block asks for block max(n_blocks - 1, 0) (knn_mfma_rerank_body, the up-front requests) -- with no block at all that is block 0 of this buffer.
 size_t knn_bf16_partial_bytes(const MfmaPlan& p) {
     const size_t nb = (size_t)(p.n_blocks > 0 ? p.n_blocks : 1);
-    return nb * BF_KEEP * p.qpad * sizeof(uint64_t) + nb * p.qpad * sizeof(uint32_t);
+    static_assert(sizeof(StripRecord) == 16, "one 16-byte request per (block, query)");
+    return nb * p.qpad * sizeof(StripRecord);
 }
 hipError_t launch_vocab_bf16(const void* vocab, int first, int n, int dim, void* bf, hipStream_t s, int f16) {
     if (n <= 0) return hipSuccess;
@@ -874,8 +874,7 @@ hipError_t launch_knn_bf16(int dim, const void* vocab, const void* vocab_bf, con
     if (p.q == 0) return hipSuccess;
     if (dim != 64) return hipErrorInvalidValue;
     if (!s_rerank || !ev_bridge) s_rerank = s;
-    uint64_t* pk = (uint64_t*)partial;
-    uint32_t* pl = (uint32_t*)(pk + (size_t)(p.n_blocks > 0 ? p.n_blocks : 1) * BF_KEEP * p.qpad);
+    StripRecord* records = (StripRecord*)partial;
     hipError_t e = hipSuccess;
     if (reset_count) {
         // ... and [3], the "redo done" flag: a stand-alone redo (knn_rowpar_kernel) leaves it raised, and the decision workgroup of a fused frame
@@ -907,11 +906,11 @@ hipError_t launch_knn_bf16(int dim, const void* vocab, const void* vocab_bf, con
             const int gp = sd.n_tiles + px * ((p.q + BF_QB - 1) / BF_QB);
             auto kern = p.f16 ? knn_bf16_filter_kernel_p<1> : knn_bf16_filter_kernel_p<0>;
             kern<<<gp, 256, BF_LDS_BYTES_P, s>>>((const float*)vocab_bf, row_norm, p.n_rows, (const float*)queries, p.q, p.qpad, p.tiles_per_block,
-                                                 p.n_blocks, px, pk, pl, sd);
+                                                 p.n_blocks, px, records, sd);
         } else {
             auto kern = p.f16 ? knn_bf16_filter_kernel<1> : knn_bf16_filter_kernel<0>;
             kern<<<grid, 256, BF_LDS_BYTES, s>>>((const float*)vocab_bf, row_norm, p.n_rows, (const float*)queries, p.q, p.qpad, p.tiles_per_block,
-                                                 p.n_blocks, pk, pl, sd);
+                                                 p.n_blocks, records, sd);
         }
         e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -923,8 +922,9 @@ hipError_t launch_knn_bf16(int dim, const void* vocab, const void* vocab_bf, con
         e = hipStreamWaitEvent(s_rerank, ev_bridge, 0);
         if (e != hipSuccess) return e;
     }
+    const KeptKeys<true> kk{records, p.tiles_per_block};
     knn_mfma_rerank_kernel<64, BF_KEEP, false, true><<<p.q, MF_BLOCK, 0, s_rerank>>>(
-        pk, pl, p.n_blocks, p.q, (const float*)vocab, (const float*)queries, row_id, norm_max_bits, out_row, out_word, out_dist, fail_list,
+        kk, p.n_blocks, p.q, (const float*)vocab, (const float*)queries, row_id, norm_max_bits, out_row, out_word, out_dist, fail_list,
         fail_count, cb ? *cb : CandBits{}, p.f16, p.n_rows);
     return hipGetLastError();
 }
@@ -988,14 +988,14 @@ size_t knn_wide_partial_bytes(const WidePlan& p) {
 }
 
 template <int DIM, int M>
-static hipError_t launch_wide_filter(const WidePlan& p, const float* vocab, const int32_t* row_id, const float* queries, uint64_t* pk, uint32_t* pl,
+static hipError_t launch_wide_filter(const WidePlan& p, const float* vocab, const int32_t* row_id, const float* queries, const ShareRecords& rec,
                                      uint32_t* norm_max_bits, hipStream_t s) {
     // (per launch, checked: <256, 0> needs more than the 64 KB a kernel gets unasked, and the attribute belongs to the current device)
     const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_wide_filter_kernel<DIM, M>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideShape<DIM, M>::LDS_BYTES);
     if (attr != hipSuccess) return attr;
     knn_wide_filter_kernel<DIM, M><<<dim3(p.n_wgs, p.n_qblocks), WD_BLOCK, WideShape<DIM, M>::LDS_BYTES, s>>>(vocab, row_id, p.n_rows, queries, p.q, p.qpad,
-                                                                                                             p.tiles_per_block, p.n_blocks, pk, pl, norm_max_bits);
+                                                                                                             p.tiles_per_block, p.n_blocks, rec, norm_max_bits);
     return hipGetLastError();
 }
 
@@ -1004,22 +1004,23 @@ hipError_t launch_knn_wide(const WidePlan& p, int f16, const void* vocab, const 
                            hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, bool reset_count) {
     if (p.q == 0) return hipSuccess;
     if (!knn_wide_mfma_supported(0, p.dim) || p.n_blocks <= 0 || p.n_rows <= 0) return hipErrorInvalidValue;
-    uint64_t* pk = (uint64_t*)partial;
-    uint32_t* pl = (uint32_t*)(pk + (size_t)p.n_blocks * BF_KEEP * p.qpad);
+    ShareRecords rec;
+    rec.keys = (uint64_t*)partial;
+    rec.bound = (uint32_t*)(rec.keys + (size_t)p.n_blocks * BF_KEEP * p.qpad);
     const float* v = (const float*)vocab; const float* qq = (const float*)queries;
     knn_wide_reset_kernel<<<1, 64, 0, s>>>(fail_count, reset_count ? 1 : 0, norm_max_bits);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (ev_begin) { e = hipEventRecord(ev_begin, s); if (e != hipSuccess) return e; }
-    if (p.dim == 128) e = f16 ? launch_wide_filter<128, 1>(p, v, row_id, qq, pk, pl, norm_max_bits, s) : launch_wide_filter<128, 0>(p, v, row_id, qq, pk, pl, norm_max_bits, s);
-    else e = f16 ? launch_wide_filter<256, 1>(p, v, row_id, qq, pk, pl, norm_max_bits, s) : launch_wide_filter<256, 0>(p, v, row_id, qq, pk, pl, norm_max_bits, s);
+    if (p.dim == 128) e = f16 ? launch_wide_filter<128, 1>(p, v, row_id, qq, rec, norm_max_bits, s) : launch_wide_filter<128, 0>(p, v, row_id, qq, rec, norm_max_bits, s);
+    else e = f16 ? launch_wide_filter<256, 1>(p, v, row_id, qq, rec, norm_max_bits, s) : launch_wide_filter<256, 0>(p, v, row_id, qq, rec, norm_max_bits, s);
     if (e != hipSuccess) return e;
     if (ev_end) { e = hipEventRecord(ev_end, s); if (e != hipSuccess) return e; }
     if (p.dim == 128)
-        knn_wide_rerank_kernel<128><<<p.q, MF_BLOCK, 0, s>>>(pk, pl, p.n_blocks, p.q, p.qpad, v, qq, row_id, p.n_rows, norm_max_bits, out_row, out_word, out_dist,
+        knn_wide_rerank_kernel<128><<<p.q, MF_BLOCK, 0, s>>>(rec, p.n_blocks, p.q, p.qpad, v, qq, row_id, p.n_rows, norm_max_bits, out_row, out_word, out_dist,
                                                              fail_list, fail_count, f16);
     else
-        knn_wide_rerank_kernel<256><<<p.q, MF_BLOCK, 0, s>>>(pk, pl, p.n_blocks, p.q, p.qpad, v, qq, row_id, p.n_rows, norm_max_bits, out_row, out_word, out_dist,
+        knn_wide_rerank_kernel<256><<<p.q, MF_BLOCK, 0, s>>>(rec, p.n_blocks, p.q, p.qpad, v, qq, row_id, p.n_rows, norm_max_bits, out_row, out_word, out_dist,
                                                              fail_list, fail_count, f16);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1059,11 +1060,9 @@ hipError_t launch_frame_a(const PipeKnn* kp, const QSplitArgs* qsp, const TailLa
     if (kp) {
         const PipeKnn& k = *kp;
         p = k.plan;
-        uint64_t* pk = (uint64_t*)k.partial;
-        uint32_t* pl = (uint32_t*)(pk + (size_t)(p.n_blocks > 0 ? p.n_blocks : 1) * BF_KEEP * p.qpad);
         if (p.n_shadow > 0 && k.sh_bf && k.sh_norm && k.sh_rows > 0 && k.sh_x) { f.sh_bf = (const float*)k.sh_bf; f.sh_norm = k.sh_norm; f.sh_rows = k.sh_rows; f.sh_x = k.sh_x; f.sh_ld = k.sh_ld; }
         f.vocab_bf = (const float*)k.vocab_bf; f.row_norm = k.row_norm; f.n_rows = p.n_rows; f.queries = (const float*)k.queries; f.nq = p.q; f.qpad = p.qpad;
-        f.tiles_per_block = p.tiles_per_block; f.n_blocks = p.n_blocks; f.pk = pk; f.pl = pl; f.n_lo = k.n_lo;
+        f.tiles_per_block = p.tiles_per_block; f.n_blocks = p.n_blocks; f.records = (StripRecord*)k.partial; f.n_lo = k.n_lo;
         f.qsplit = (const uint4*)k.qsplit; f.qnorm = k.qnorm;
         if (k.cb.selfdist) {                                          // the same-frame distance matrix rides along
             f.sd.queries = (const float*)k.queries; f.sd.nq = p.q; f.sd.out = const_cast<float*>(k.cb.selfdist); f.sd.ld = k.cb.ld; f.sd.n_tiles = f.sd.n_self = selfdist_tiles(p.q);
@@ -1121,8 +1120,7 @@ hipError_t launch_frame_b(const PipeKnn* k, const ScoreArgs* score, int score_wg
     int n_rerank = 0;
     if (k) {
         const MfmaPlan& p = k->plan;
-        uint64_t* pk = (uint64_t*)k->partial;
-        rk.pk = pk; rk.pl = (uint32_t*)(pk + (size_t)(p.n_blocks > 0 ? p.n_blocks : 1) * BF_KEEP * p.qpad);
+        rk.kk.records = (const StripRecord*)k->partial; rk.kk.tiles_per_block = p.tiles_per_block;
         rk.n_blocks = p.n_blocks; rk.nq = p.q; rk.vocab = (const float*)k->vocab; rk.queries = (const float*)k->queries; rk.row_id = k->row_id;
         rk.norm_max_bits = k->norm_max_bits; rk.out_row = k->out_row; rk.out_word = k->out_word; rk.out_dist = k->out_dist;
         rk.fail_list = k->fail_list; rk.fail_count = k->fail_count; rk.cb = k->cb; rk.n_lo = k->n_lo; rk.n_hi = k->n_hi; rk.plan_rows = p.n_rows; rk.f16 = p.f16;

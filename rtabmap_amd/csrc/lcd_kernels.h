@@ -196,7 +196,7 @@ hipError_t launch_shard_merge(const void* all_cand, int world, int rank, int q, 
 // split of the vocabulary (256 bytes per row) kept by launch_vocab_bf16 next to the rows.
 MfmaPlan knn_bf16_plan(int q, int n_rows, int other_wgs = 0 /* long-running workgroups sharing the launch */);
 int knn_selfdist_wgs(int q);   // distance-matrix workgroups of a q-descriptor frame
-size_t knn_bf16_partial_bytes(const MfmaPlan& p);
+size_t knn_bf16_partial_bytes(const MfmaPlan& p);   // one 16-byte record (two 32-bit keys, the bound) per (strip, padded query)
 hipError_t launch_vocab_bf16(const void* vocab, int first, int n, int dim, void* bf, hipStream_t s, int f16 = 0);
 hipError_t launch_knn_bf16(int dim, const void* vocab, const void* vocab_bf, const float* row_norm, const uint32_t* norm_max_bits,
                            const int32_t* row_id, const void* queries, const MfmaPlan& p, void* partial, int32_t* out_row, int32_t* out_word,

@@ -99,9 +99,15 @@ __device__ __forceinline__ const float4* staged_chunk(const float* stage, int r,
 // barriers (every barrier of the body is reached by all threads: the conditions around them are launch-uniform).
 // The phases: rows-only exit | up-front requests | pass 1 (tau, bound) | staging of the pending rows | pass 2 (candidates) | exact distances |
 // pending scan | top-2 and winner slots | results and certificate | candidate bits | row writes and mirror.
+// What the filter kept for the re-rank, by the filter's kind -- the body's BF16 flag picks the type, so a caller cannot fill the other form:
+//   KeptKeys<true>   `records`, one StripRecord per (row block, query) of a bf16 / fp16 filter (bf16_filter_body.cuh), whose blocks are
+//                    tiles_per_block tiles each;
+//   KeptKeys<false>  the f32 filter's query-major arrays, keys [q][n_blocks][KEEP] and lmin [q][n_blocks].
+template <bool BF16> struct KeptKeys;
+template <> struct KeptKeys<true> { const StripRecord* records; int tiles_per_block; };
+template <> struct KeptKeys<false> { const uint64_t* keys; const uint32_t* lmin; };
 template <int DIM, int KEEP, bool LAST_KEY_BOUNDS, bool BF16, int HALVES = 1>
-__device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_t* __restrict__ partial_keys,
-                                                     const uint32_t* __restrict__ partial_lmin, int n_blocks, int nq,
+__device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const KeptKeys<BF16>& kk, int n_blocks, int nq,
                                                      const float* __restrict__ vocab, const float* __restrict__ queries,
                                                      const int32_t* __restrict__ row_id,
                                                      const uint32_t* __restrict__ norm_max_bits,
@@ -287,14 +293,18 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     const int n_keys = n_blocks * KEEP;
     constexpr int GS = BF16 ? 4 : 1;                                   // rows a key stands for (see the exact phase)
     constexpr int RR_KEYS = RR_MAX_CAND / GS;                          // keys under the threshold a query may have before it goes to the exact redo
-    // key c of the query: block c / KEEP, entry c % KEEP.  The bf16 filter's records are block-major ([block][query][KEEP], see
-    // knn_bf16_filter_body), the f32 filter's query-major
+    // The bf16 / fp16 filters leave ONE 16-byte record per (block, query), block-major (StripRecord: both kept keys and the bound, one request);
+    // the f32 filter query-major arrays: key c of the query is block c / KEEP, entry c % KEEP
+    static_assert(!BF16 || KEEP == BF_KEEP, "a StripRecord holds BF_KEEP keys");
     const int qpad_t = (nq + 63) / 64 * 64;
-    auto key_at = [&](int c) -> uint64_t {
-        return BF16 ? partial_keys[((size_t)(c / KEEP) * qpad_t + qi) * KEEP + (c % KEEP)] : partial_keys[(size_t)qi * n_keys + c];
-    };
-    auto bound_at = [&](int b) -> uint32_t { return BF16 ? partial_lmin[(size_t)b * qpad_t + qi] : partial_lmin[(size_t)qi * n_blocks + b]; };
     constexpr uint32_t INF = 0x7f800000u;
+    // (each accessor exists for its own form only: the other form's members are not there to be read)
+    auto rec_at = [&](int b) -> uint4 {
+        if constexpr (BF16) return *reinterpret_cast<const uint4*>(kk.records + (size_t)b * qpad_t + qi); else return make_uint4(0u, 0u, 0u, 0u);
+    };
+    auto rec_tile0 = [&](int b) -> int { if constexpr (BF16) return b * kk.tiles_per_block; else return 0; };   // the first tile of block b
+    auto key_at = [&](int c) -> uint64_t { if constexpr (!BF16) return kk.keys[(size_t)qi * n_keys + c]; else return KEY_NONE; };
+    auto bound_at = [&](int b) -> uint32_t { if constexpr (!BF16) return kk.lmin[(size_t)qi * n_blocks + b]; else return INF; };
     __shared__ uint32_t s_a0_all[HALVES][MF_WAVES], s_a1_all[HALVES][MF_WAVES], s_bound_all[HALVES][MF_WAVES];
     __shared__ int s_ncand_all[HALVES];
     __shared__ uint64_t s_cand_all[HALVES][RR_MAX_CAND], s_exact_all[HALVES][RR_MAX_CAND];
@@ -312,17 +322,31 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
     const float4* const s_q = s_q_all[hf];
 
     // ---- up-front requests.  Everything that does not depend on other loads is requested here (the kernel is a chain of round trips): the
-    // first three keys and the first bound of every thread, the query slice, the vocabulary norm bound, -- for the candidate bits -- the
+    // thread's first two records (f32 filter: its first three keys and first bound), the query slice, the vocabulary norm bound, -- for the candidate bits -- the
     // thread's two entries of the query's row of the same-frame distance matrix, the shadow scores and, LAST, the thread's list and mask entries:
     // requested in front of the keys (where they used to be) they are waited for before the first key's address is formed -- a round trip of
     // their own at the head of every re-rank workgroup.
     // Register budget (frame_b_kernel<false>: 80, no scratch -- tests/test_pipeline_scratch.py): the query slice goes to LDS as soon as its norm
     // is taken, the waves' bounds stay in LDS until the certificate, and the half / query index is scalar.
     RR_STAMP(0);
-    const uint64_t kreg0 = tid < n_keys ? key_at(tid) : KEY_NONE;
-    const uint64_t kreg1 = tid + MF_BLOCK < n_keys ? key_at(tid + MF_BLOCK) : KEY_NONE;
-    const uint64_t kreg2 = tid + 2 * MF_BLOCK < n_keys ? key_at(tid + 2 * MF_BLOCK) : KEY_NONE;   // (219 strips x 3 keys: a third of the threads have a third key)
-    const uint32_t breg0 = tid < n_blocks ? bound_at(tid) : INF;
+    // BF16: the thread's first two records (219 strips at the headline: one request per thread, none for the last 37), nothing else of the filter's
+    const uint4 rec_none = make_uint4(REC_KEY_NONE, REC_KEY_NONE, INF, 0u);
+    uint4 rreg0 = rec_none, rreg1 = rec_none;
+    uint64_t kreg0 = KEY_NONE, kreg1 = KEY_NONE, kreg2 = KEY_NONE;
+    uint32_t breg0 = INF;
+    if constexpr (BF16) {
+        // (no condition on the requests: a load under a condition gets a wait of its own inside its branch -- the ISA of the first version of
+        // this block had one behind each record, two round trips in front of the query's.  A thread without a block asks for the last block's
+        // record, which its neighbours fetch anyway, and drops it in front of pass 1; the buffer holds a block's records even when there is none)
+        const int b_last = max(n_blocks - 1, 0);
+        rreg0 = rec_at(min(tid, b_last));
+        rreg1 = rec_at(min(tid + MF_BLOCK, b_last));
+    } else {
+        if (tid < n_keys) kreg0 = key_at(tid);
+        if (tid + MF_BLOCK < n_keys) kreg1 = key_at(tid + MF_BLOCK);
+        if (tid + 2 * MF_BLOCK < n_keys) kreg2 = key_at(tid + 2 * MF_BLOCK);
+        if (tid < n_blocks) breg0 = bound_at(tid);
+    }
     const float4 q4 = reinterpret_cast<const float4*>(queries + (size_t)qi * DIM)[lane & 15];
     const float vn_max = __uint_as_float(norm_max_bits[0]);
     float dreg0 = __int_as_float(0x7f800000), dreg1 = __int_as_float(0x7f800000);
@@ -340,18 +364,30 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
 
     // ---- pass 1: tau and the bound on dropped rows
     uint32_t a0 = INF, a1 = INF, bound = breg0;
-    auto see = [&](uint64_t key, int c) {
-        const uint32_t sc = min((uint32_t)(key >> 32), INF);                // KEY_NONE -> +inf
-        if (LAST_KEY_BOUNDS && (c % KEEP) == KEEP - 1) bound = min(bound, sc);   // rows the block merge dropped are no better than its last key
+    auto see_score = [&](uint32_t sc) {
         const uint32_t h = max(a0, sc);
         a0 = min(a0, sc);
         a1 = min(a1, h);
     };
-    see(kreg0, tid);
-    see(kreg1, tid + MF_BLOCK);
-    see(kreg2, tid + 2 * MF_BLOCK);
-    for (int c = tid + 3 * MF_BLOCK; c < n_keys; c += MF_BLOCK) see(key_at(c), c);
-    for (int c = tid + MF_BLOCK; c < n_blocks; c += MF_BLOCK) bound = min(bound, bound_at(c));
+    auto see = [&](uint64_t key, int c) {
+        const uint32_t sc = min((uint32_t)(key >> 32), INF);                // KEY_NONE -> +inf
+        if (LAST_KEY_BOUNDS && (c % KEEP) == KEEP - 1) bound = min(bound, sc);   // rows the block merge dropped are no better than its last key
+        see_score(sc);
+    };
+    auto see_record = [&](const uint4& r) { see_score(record_score(r.x)); see_score(record_score(r.y)); bound = min(bound, r.z); };
+    if constexpr (BF16) {
+        if (tid >= n_blocks) rreg0 = rec_none;                             // (a thread without a block: see the requests)
+        if (tid + MF_BLOCK >= n_blocks) rreg1 = rec_none;
+        see_record(rreg0);
+        see_record(rreg1);
+        for (int b = tid + 2 * MF_BLOCK; b < n_blocks; b += MF_BLOCK) see_record(rec_at(b));
+    } else {
+        see(kreg0, tid);
+        see(kreg1, tid + MF_BLOCK);
+        see(kreg2, tid + 2 * MF_BLOCK);
+        for (int c = tid + 3 * MF_BLOCK; c < n_keys; c += MF_BLOCK) see(key_at(c), c);
+        for (int c = tid + MF_BLOCK; c < n_blocks; c += MF_BLOCK) bound = min(bound, bound_at(c));
+    }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const uint32_t o0 = (uint32_t)__shfl_xor((int)a0, m, 64), o1 = (uint32_t)__shfl_xor((int)a1, m, 64);
@@ -406,10 +442,28 @@ __device__ __forceinline__ void knn_mfma_rerank_body(int qi_first, const uint64_
             if (slot < RR_KEYS) s_cand[slot] = key;
         }
     };
-    take(kreg0);
-    take(kreg1);
-    take(kreg2);
-    for (int c = tid + 3 * MF_BLOCK; c < n_keys; c += MF_BLOCK) take(key_at(c));
+    // (a record's keys are widened HERE, and only those under the threshold: record_widen, the block's first tile from its index)
+    auto take_record = [&](const uint4& r, int b) {
+        const uint32_t rk[BF_KEEP] = {r.x, r.y};
+#pragma unroll
+        for (int e = 0; e < BF_KEEP; ++e) {
+            const uint32_t sc = record_score(rk[e]);                           // (KEY_NONE -> +inf)
+            if (sc < INF && __uint_as_float(sc) <= thr) {
+                const int slot = atomicAdd(&s_ncand, 1);
+                if (slot < RR_KEYS) s_cand[slot] = record_widen(rk[e], rec_tile0(b));
+            }
+        }
+    };
+    if constexpr (BF16) {
+        take_record(rreg0, tid);
+        take_record(rreg1, tid + MF_BLOCK);
+        for (int b = tid + 2 * MF_BLOCK; b < n_blocks; b += MF_BLOCK) take_record(rec_at(b), b);
+    } else {
+        take(kreg0);
+        take(kreg1);
+        take(kreg2);
+        for (int c = tid + 3 * MF_BLOCK; c < n_keys; c += MF_BLOCK) take(key_at(c));
+    }
     if (sh_q > 0) {                                                  // ... and the descriptors of the frame before that became words
         auto take_sh = [&](uint32_t j, float xs) {
             if (j < (uint32_t)sh_q && xs <= thr && sh_isword(j)) {

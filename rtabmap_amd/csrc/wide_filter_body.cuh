@@ -24,7 +24,9 @@
 //     and merged into a running triple.  A vocabulary of more shares than compute units gives every workgroup several (share blockIdx.x,
 //     + gridDim.x, ...): the queries stay in registers.  1024 rows per record keep the records small (20 bytes per query and 1024 rows) and the
 //     bound tight enough (tests/test_certificate_model.py's model at that size rejects a few queries in a hundred).
-// Records: partial_keys [n_blocks][qpad][BF_KEEP] u64, partial_bound [n_blocks][qpad] f32 bits, as the 64-float bf16 filter writes them.
+// Records: ShareRecords (bf16_filter_body.cuh) -- keys [n_blocks][qpad][BF_KEEP] u64 merge keys, bound [n_blocks][qpad] f32 bits.  NOT the 16-byte
+// StripRecord of the 64-float filters: a share is up to four strips, and strip (2 bits), tile (3) and group (2) fill the seven index bits of a
+// 32-bit key -- the half of the tile's rows a lane held, which the reader needs for the row, would cost the score a bit.
 #pragma once
 
 constexpr int WD_WAVES = 8;
@@ -58,8 +60,7 @@ __device__ __forceinline__ void top3_merge64(uint64_t& r0, uint64_t& r1, uint64_
 template <int DIM, int M>
 __global__ __launch_bounds__(WD_BLOCK) void knn_wide_filter_kernel(const float* __restrict__ vocab, const int32_t* __restrict__ row_id, int n_rows,
                                                                    const float* __restrict__ queries, int nq, int qpad, int tiles_per_block,
-                                                                   int n_blocks, uint64_t* __restrict__ partial_keys,
-                                                                   uint32_t* __restrict__ partial_bound, uint32_t* __restrict__ norm_max_bits) {
+                                                                   int n_blocks, ShareRecords rec, uint32_t* __restrict__ norm_max_bits) {
     typedef WideShape<DIM, M> S;
     constexpr int NG = S::NG, STEPS = S::STEPS, KINDS = S::KINDS, U = S::U;
     extern __shared__ __attribute__((aligned(16))) float s_dyn_w[];
@@ -194,17 +195,13 @@ __global__ __launch_bounds__(WD_BLOCK) void knn_wide_filter_kernel(const float* 
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const int qi = q0 + g * 32 + col;
-            const uint64_t a0 = r0[g], a1 = r1[g], a2 = r2[g];
-            const uint64_t b0 = shfl_xor_u64(a0, 32), b1 = shfl_xor_u64(a1, 32), b2 = shfl_xor_u64(a2, 32);
-            const uint64_t m0 = a0 < b0 ? a0 : b0;
-            const uint64_t hx = a0 < b0 ? b0 : a0, lx = a1 < b1 ? a1 : b1;
-            const uint64_t m1 = hx < lx ? hx : lx;
-            const uint64_t third = third_of_two_triples(a0, a1, a2, b0, b1, b2);
+            uint64_t m0, m1, third;
+            merge_halves(r0[g], r1[g], r2[g], m0, m1, third);
             if (half == 0 && qi < qpad) {
-                uint64_t* dst = partial_keys + ((size_t)bx * qpad + qi) * BF_KEEP;
+                uint64_t* dst = rec.keys + ((size_t)bx * qpad + qi) * BF_KEEP;
                 dst[0] = m0;
                 dst[1] = m1;
-                partial_bound[(size_t)bx * qpad + qi] = (uint32_t)min(third >> 32, (uint64_t)0x7f800000u);
+                rec.bound[(size_t)bx * qpad + qi] = (uint32_t)min(third >> 32, (uint64_t)0x7f800000u);
             }
         }
     }
@@ -231,8 +228,7 @@ __global__ void knn_wide_reset_kernel(int32_t* __restrict__ fail_count, int rese
 // bound - eps > exact second distance.  eps is eps_bf16 / eps_f16 at DIM with the filter's own norm maximum.  Anything else -- more than
 // RR_MAX_CAND candidate rows, a measured error of half of eps, fp16 operands out of range -- sends the query to the exact redo.
 template <int DIM>
-__global__ __launch_bounds__(MF_BLOCK) void knn_wide_rerank_kernel(const uint64_t* __restrict__ partial_keys, const uint32_t* __restrict__ partial_bound,
-                                                                   int n_blocks, int nq, int qpad, const float* __restrict__ vocab,
+__global__ __launch_bounds__(MF_BLOCK) void knn_wide_rerank_kernel(ShareRecords rec, int n_blocks, int nq, int qpad, const float* __restrict__ vocab,
                                                                    const float* __restrict__ queries, const int32_t* __restrict__ row_id, int n_rows,
                                                                    const uint32_t* __restrict__ norm_max_bits, int32_t* __restrict__ out_row,
                                                                    int32_t* __restrict__ out_word, float* __restrict__ out_dist,
@@ -248,7 +244,7 @@ __global__ __launch_bounds__(MF_BLOCK) void knn_wide_rerank_kernel(const uint64_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qi = blockIdx.x;
     const int n_keys = n_blocks * BF_KEEP;
-    auto key_at = [&](int c) -> uint64_t { return partial_keys[((size_t)(c / BF_KEEP) * qpad + qi) * BF_KEEP + (c % BF_KEEP)]; };
+    auto key_at = [&](int c) -> uint64_t { return rec.keys[((size_t)(c / BF_KEEP) * qpad + qi) * BF_KEEP + (c % BF_KEEP)]; };
 
     // the query and |q|^2 (DIM / 4 <= 64 lanes of wave 0)
     {
@@ -275,7 +271,7 @@ __global__ __launch_bounds__(MF_BLOCK) void knn_wide_rerank_kernel(const uint64_
         a0 = min(a0, sc);
         a1 = min(a1, h);
     }
-    for (int b = tid; b < n_blocks; b += MF_BLOCK) bound = min(bound, partial_bound[(size_t)b * qpad + qi]);
+    for (int b = tid; b < n_blocks; b += MF_BLOCK) bound = min(bound, rec.bound[(size_t)b * qpad + qi]);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const uint32_t o0 = (uint32_t)__shfl_xor((int)a0, m, 64), o1 = (uint32_t)__shfl_xor((int)a1, m, 64);
