@@ -184,18 +184,26 @@ def sort_length(n):
     return p
 
 
+def pad_side(rng, pair, side, base, rows, columns):
+    """one frame of `pair` grown to exactly `rows` rows in place: the new rows carry the ids base, base + 1, .. (of this side only) and, per
+    (key, low, high) of `columns`, values uniform in [low, high); then the frame's rows are shuffled"""
+    extra = rows - pair[side + "_ids"].shape[0]
+    assert extra >= 0
+    ids = np.concatenate([pair[side + "_ids"], base + np.arange(extra, dtype=np.int32)])
+    grown = [np.concatenate([pair[key], rng.uniform(low, high, (extra, pair[key].shape[1])).astype(np.float32)]) for key, low, high in columns]
+    perm = rng.permutation(rows)
+    pair[side + "_ids"] = ids[perm].astype(np.int32)
+    for (key, _, _), a in zip(columns, grown):
+        pair[key] = np.ascontiguousarray(a[perm])
+
+
 def sized_pair(seed, m, n_from, n_to, **kw):
     """random_pair's m correspondences (no decoys) inside frames of exactly n_from and n_to rows: the rest are ids of one side only"""
     rng = np.random.default_rng(seed)
     pair = random_pair(rng, m, decoys=False, **kw)
     out = dict(pair)
-    for side, base, rows in (("from", 1 << 20, n_from), ("to", 1 << 21, n_to)):
-        extra = rows - m
-        assert extra >= 0
-        ids = np.concatenate([pair[side + "_ids"], base + np.arange(extra, dtype=np.int32)])
-        xyz = np.concatenate([pair[side + "_xyz"], rng.uniform(-3, 3, (extra, 3)).astype(np.float32)])
-        perm = rng.permutation(rows)
-        out[side + "_ids"], out[side + "_xyz"] = ids[perm].astype(np.int32), np.ascontiguousarray(xyz[perm])
+    pad_side(rng, out, "from", 1 << 20, n_from, (("from_xyz", -3, 3),))
+    pad_side(rng, out, "to", 1 << 21, n_to, (("to_xyz", -3, 3),))
     return out
 
 
@@ -232,6 +240,25 @@ def _run_frame(distinct, runs, other_runs):
     return np.repeat(distinct, counts), carried
 
 
+def run_id_frames(rng, rot):
+    """the ids of two frames of RUN_ROWS rows over the same distinct ids, in sorted order.  Frame A holds a run from sorted position 0 and a
+    run over each of RUN_BOUNDARIES that ends just behind it, frame B a run over each boundary that starts just in front of it (another
+    length there) and a run up to its last position; `rot` rotates the lengths through RUN_LENGTHS.  An id that runs in one frame stands
+    once in the other.  -> (distinct, ids_a, ids_b, the indices into distinct that run in A, those that run in B)"""
+    L = [RUN_LENGTHS[(rot + k) % 3] for k in range(3)]
+    edge = L[0]                                                        # the length of the run at either end
+    n_distinct = RUN_ROWS - (edge - 1) - sum(l - 1 for l in RUN_LENGTHS)
+    distinct = np.sort(rng.permutation(20000)[:n_distinct].astype(np.int64) - 10000)
+    runs_a = {0: edge}
+    runs_b = {RUN_ROWS - edge: edge}
+    for k, b in enumerate(RUN_BOUNDARIES):
+        runs_a[b + 2 - L[k]] = L[k]
+        runs_b[b] = L[(k + 1) % 3]
+    ids_a, carried_a = _run_frame(distinct, runs_a, ())
+    ids_b, carried_b = _run_frame(distinct, runs_b, set(carried_a))
+    return distinct, ids_a, ids_b, carried_a, carried_b
+
+
 def duplicate_run_pairs(seed=32):
     """Six pairs of RUN_ROWS x RUN_ROWS rows over the same ids on both sides.  In each, one frame holds a run from sorted position 0 and a
     run over each of RUN_BOUNDARIES, the other a run that ends at its last sorted position and a run over each boundary; the run lengths
@@ -240,19 +267,8 @@ def duplicate_run_pairs(seed=32):
     rng = np.random.default_rng(seed)
     pairs = []
     for rot in range(3):
-        L = [RUN_LENGTHS[(rot + k) % 3] for k in range(3)]
-        edge = L[0]                                                    # the length of the run at either end
-        n_distinct = RUN_ROWS - (edge - 1) - sum(l - 1 for l in RUN_LENGTHS)
-        distinct = np.sort(rng.permutation(20000)[:n_distinct].astype(np.int64) - 10000)
-        # frame A: from position 0, and over each boundary ending just behind it; frame B: over each boundary starting just in front of it
-        # (another length there), and up to the last position
-        runs_a = {0: edge}
-        runs_b = {RUN_ROWS - edge: edge}
-        for k, b in enumerate(RUN_BOUNDARIES):
-            runs_a[b + 2 - L[k]] = L[k]
-            runs_b[b] = L[(k + 1) % 3]
-        ids_a, carried_a = _run_frame(distinct, runs_a, ())
-        ids_b, carried_b = _run_frame(distinct, runs_b, set(carried_a))
+        distinct, ids_a, ids_b, carried_a, carried_b = run_id_frames(rng, rot)
+        n_distinct = len(distinct)
         R, t = rotation(rng.normal(size=3), rng.uniform(0.2, 1.2)), rng.uniform(-1, 1, 3)
         P = rng.uniform(-3, 3, (n_distinct, 3))
         Q = P @ R.T + t + rng.normal(size=(n_distinct, 3)) * 0.01
@@ -283,6 +299,21 @@ EXTREME_IDS = (INT32_MIN, INT32_MIN + 1, -1, 0, 1, INT32_MAX)
 EXTREME_ROWS = (13, 70)                                               # no power of two: INT32_MAX's key stands next to the all-ones padding keys
 
 
+def extreme_id_lists(rng, case, nf, nt):
+    """the ids of a from-frame of nf rows and a to-frame of nt: EXTREME_IDS and five ordinary ids on both sides and ids of one side only.
+    case 0: INT32_MIN + 1 is in `from` only.  1: INT32_MAX twice in `to`.  2: INT32_MAX twice in `from`."""
+    common = [int(v) for v in rng.permutation(4000)[:5] - 2000 + 5000 * (rng.random(5) < 0.5)]
+    f_ids = list(EXTREME_IDS) + common
+    t_ids = [i for i in EXTREME_IDS if not (case == 0 and i == INT32_MIN + 1)] + common
+    if case == 1:
+        t_ids.append(INT32_MAX)
+    if case == 2:
+        f_ids.append(INT32_MAX)
+    f_ids += [int(v) for v in 100000 + np.arange(nf - len(f_ids))]
+    t_ids += [int(v) for v in 200000 + np.arange(nt - len(t_ids))]
+    return f_ids, t_ids
+
+
 def extreme_id_pairs(seed=33):
     """three pairs of EXTREME_ROWS rows.  0: INT32_MIN, -1, 0, 1 and INT32_MAX are correspondences, INT32_MIN + 1 is in `from` only.
     1: as 0 with INT32_MIN + 1 a correspondence too and INT32_MAX twice in `to`.  2: as 1 with INT32_MAX twice in `from` and once in `to`."""
@@ -290,15 +321,7 @@ def extreme_id_pairs(seed=33):
     nf, nt = EXTREME_ROWS
     pairs = []
     for case in range(3):
-        common = [int(v) for v in rng.permutation(4000)[:5] - 2000 + 5000 * (rng.random(5) < 0.5)]
-        f_ids = list(EXTREME_IDS) + common
-        t_ids = [i for i in EXTREME_IDS if not (case == 0 and i == INT32_MIN + 1)] + common
-        if case == 1:
-            t_ids.append(INT32_MAX)
-        if case == 2:
-            f_ids.append(INT32_MAX)
-        f_ids += [int(v) for v in 100000 + np.arange(nf - len(f_ids))]
-        t_ids += [int(v) for v in 200000 + np.arange(nt - len(t_ids))]
+        f_ids, t_ids = extreme_id_lists(rng, case, nf, nt)
         P = {i: rng.uniform(-3, 3, 3) for i in set(f_ids) | set(t_ids)}
         R, t = rotation(rng.normal(size=3), 0.7), rng.uniform(-1, 1, 3)
         f_xyz = np.array([P[i] for i in f_ids], np.float32)

@@ -240,7 +240,8 @@ def p3p(P, B, P4, UV4, cam, sweeps=5):
 
 # ---- the fit of an ordered set
 
-def quat_of_model(m):
+def quat_of_model(m, record=None):
+    """record (a dict, if given): "picks" receives the case taken"""
     m = np.asarray(m, np.float32)
     r00, r01, r02, r10, r11, r12, r20, r21, r22 = m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]
     with np.errstate(all="ignore"):
@@ -251,6 +252,8 @@ def quat_of_model(m):
         for k in (1, 2, 3):
             if c[k] > top:
                 pick, top = k, c[k]
+        if record is not None:
+            record["picks"].append(pick)
         r = np.sqrt(top)
         big, f = F(0.5) * r, F(0.5) / r
         fm21, fm02, fm10 = (r21 - r12) * f, (r02 - r20) * f, (r10 - r01) * f
@@ -353,11 +356,12 @@ def pose_update(q, t, delta):
     return q2, t2
 
 
-def fit_set(model, cam, P, UV, steps=STEPS):
-    """the fit of an ordered set (P, UV [n x ...]) from `model`"""
+def fit_set(model, cam, P, UV, steps=STEPS, record=None):
+    """the fit of an ordered set (P, UV [n x ...]) from `model`; record (a dict, if given): "picks" receives the fit's Shepperd case and
+    "refused" the number of its steps that gn_solve refused"""
     if P.shape[0] < 4:
         return model
-    q = quat_of_model(model)
+    q = quat_of_model(model, record)
     t = np.array([model[3], model[7], model[11]], np.float32)
     for _ in range(steps):
         cur, q = model_of_pose(q, t)
@@ -365,6 +369,8 @@ def fit_set(model, cam, P, UV, steps=STEPS):
         delta = gn_solve(S)
         if delta is not None:
             q, t = pose_update(q, t, delta)
+        elif record is not None:
+            record["refused"].append(1)
     return model_of_pose(q, t)[0]
 
 
@@ -430,6 +436,7 @@ class _Backend:
         self.cur = np.zeros(12, np.float32)
         self.prev, self.next, self.last_e = [], [], np.zeros(0, np.float32)
         self.counts = None
+        self.record = dict(picks=[], refused=[], first_differing=[])
 
     def ransac(self, thr):
         """-> the best candidate or None; counts [iterations + 1]"""
@@ -456,7 +463,7 @@ class _Backend:
         return best
 
     def fit_prev(self):
-        self.cur = fit_set(self.cur, self.cam, self.P[self.prev], self.UV[self.prev], self.steps)
+        self.cur = fit_set(self.cur, self.cam, self.P[self.prev], self.UV[self.prev], self.steps, self.record)
 
     def select(self, thr):
         e, front = reproj_error(self.cur, self.cam, self.P, self.UV)
@@ -496,6 +503,7 @@ def refine(b, thr0, refine_iterations, min_count, trace):
                 trace.append("size_changed")
                 inlier_changed = True
             elif b.prev != b.next:
+                b.record["first_differing"].append(next(i for i, (p, n) in enumerate(zip(b.prev, b.next)) if p != n))
                 trace.append("members_changed")
                 inlier_changed = True
             else:
@@ -521,14 +529,15 @@ def check_args(n_from, n_to, min_inliers, reproj_error, iterations, refine_itera
 def estimate(from_ids, from_xyz, to_ids, to_points, to_xyz=None, camera=None, guess=None, min_inliers=20, iterations=100, reproj_error=2.0,
              refine_iterations=1, variance_median_ratio=4, max_variance=0.0, seed=0, steps=STEPS):
     """one pair -> dict(transform [12] f32, status, matches, inliers (ids), variance_lin f64, angle_cos f64, variance_kind, inlier_index, model,
-    trace, best, counts)"""
+    trace, best, counts, picks (the Shepperd case of every fit), refused (the Gauss-Newton steps that gn_solve refused, over all fits),
+    first_differing (per members_changed pass, the first position at which the two index sets differ))"""
     cam = camera if camera is not None else Camera()
     check_args(np.asarray(from_ids).size, np.asarray(to_ids).size, min_inliers, reproj_error, iterations, refine_iterations, variance_median_ratio,
                max_variance)
     matches, P, UV, T = correspondences(from_ids, from_xyz, to_ids, to_points, to_xyz)
     m = len(matches)
     r = dict(transform=np.zeros(12, np.float32), status=OK, matches=matches, inliers=np.zeros(0, np.int32), variance_lin=D(1.0), angle_cos=D(1.0),
-             variance_kind=0, inlier_index=[], model=None, trace=[], best=None, counts=None, P=P, UV=UV, T=T)
+             variance_kind=0, inlier_index=[], model=None, trace=[], best=None, counts=None, P=P, UV=UV, T=T, picks=[], refused=[], first_differing=[])
     if m < min_inliers or m < 4:
         r["status"] = FEW_CORRESPONDENCES
         return r
@@ -536,6 +545,7 @@ def estimate(from_ids, from_xyz, to_ids, to_points, to_xyz=None, camera=None, gu
     thr_ransac = F(D(thr0) * D(thr0))
     model0 = model_of_guess(IDENTITY if guess is None else guess, cam.local)
     b = _Backend(P, UV, T, cam, model0, seed & M32, iterations, steps)
+    b.record = {k: r[k] for k in b.record}
     r["best"] = b.ransac(thr_ransac)
     r["counts"] = b.counts
     if r["best"] is None:

@@ -201,3 +201,14 @@ def test_the_fit_and_the_minimal_solver_against_float64():
     print("fit against float64 least squares over %d fits: rotation %.3e, translation %.3e; P3P held-out reprojection %.3e px" % (n, rotation, translation, pixels))
     assert n == 2 * len(sets) == 54
     assert rotation <= ROTATION_BOUND and translation <= TRANSLATION_BOUND and pixels <= P3P_BOUND
+
+
+@pytest.mark.parametrize("section", I.SHAPE_SECTIONS)
+def test_mirror_equals_model_on_the_shape_inputs(section):
+    """every call of tests/test_gpu_motion_pnp_shapes.py, pair by pair: a disagreement between the two CPU implementations shows here"""
+    calls = I.section_calls(section)
+    assert calls
+    for name, call in calls.items():
+        cams = [call["cam"]] * len(call["pairs"]) if isinstance(call["cam"], dict) else call["cam"]
+        for k, pair in enumerate(call["pairs"]):
+            both(pair, cam=cams[k], guess=None if call["guesses"] is None else call["guesses"][k], to_xyz=call["to_xyz"], **call["kw"])
