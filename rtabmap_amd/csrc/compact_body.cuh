@@ -1,5 +1,7 @@
-// compact_body.cuh -- what the per-frame kernels of feature_select.hip, keypoints_3d.hip, motion_3d.hip and motion_pnp.hip share: the ballot scan that
-// compacts a workgroup's flags in thread order, the gather of rows behind an index list, and the bitonic sort of 64-bit keys in LDS.  Device code only.  Internal.
+// compact_body.cuh -- what the per-frame kernels of feature_select.hip and keypoints_3d.hip and the motion kernels (motion_3d.hip and
+// motion_pnp.hip, through motion_join.cuh's sort and motion_group.cuh's compaction and selection) share: the ballot scan that compacts a
+// workgroup's flags in thread order, the gather of rows behind an index list, and the bitonic sort of 64-bit keys in LDS.  Device code only.
+// Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -2,21 +2,18 @@
 // RegistrationVis.cpp:1823-1871 with Vis/EstimationType = 0) for a caller who holds both frames' word ids and 3-D points in device memory.
 // The rule is include/lcd.h's; its arithmetic and its control flow (solve, refine) are motion_3d_rule.h's, compiled here for the device and
 // in host/Motion3D.cpp for the mirror.
-//   motion_3d_kernel: one launch per call, one workgroup of 256 threads per pair, in phases behind barriers:
-//     (a) join: both frames' 64-bit keys (id || row) are sorted in LDS (compact_body.cuh's network); a from-key whose neighbours carry other
-//         ids is looked up in the to-keys by binary search, the predicate is applied and the survivors are compacted in ascending id with the
-//         ballot scan.  Their ids go to out_matches, their six coordinates (one plane each) to the call's scratch -- and, when they fit
-//         beside the hypotheses, into the LDS the keys no longer need; larger pairs read them from the scratch through the same pointer.
-//     (b) hypotheses in chunks of 256: thread h draws and solves its three-point fit (the Jacobi sweeps fully unrolled) and leaves 12 floats
-//         in LDS; each wave takes hypotheses in turn, its lanes stride over the correspondences and count with a ballot, lane 0 raises a
-//         64-bit LDS maximum (count << 32 | ~h).
-//     (c) selection, refinement and median: the sums of a fit are the rule's (256 lane partials, halving tree in LDS), the median is a
-//         radix select over the bit patterns of the last selection's d2, the loop's scalars are the same in every thread.
+//   motion_3d_kernel: one launch per call, one workgroup of 256 threads per pair, in phases behind barriers.  The phases' machinery is
+//   motion_group.cuh's, shared with motion_pnp.hip; what is written here is what the 3-D rule puts into it:
+//     (a) join (join_compact): the from-frame's ids are walked, the predicate is m3d::keep_pair, the six coordinates (one plane each) go to
+//         the call's scratch and, when they fit beside the hypotheses, into LDS (Group::init).
+//     (b) hypotheses in chunks of 256 (Group::ransac): thread h draws and solves its three-point fit (the Jacobi sweeps fully unrolled); an
+//         inlier is a correspondence whose squared distance is below the threshold's square.
+//     (c) selection, refinement and median: the sums of a fit are the rule's (Group::tree), the median is the radix select (Group::ranked)
+//         over the bit patterns of the last selection's d2, the loop's scalars are the same in every thread.
 //     (d) outputs.
 // Nothing of the engine is read or written: the job table is StatelessScratch's, the per-row scratch its d_small.
-#include "engine_impl.h"
 #include "motion_3d_rule.h"
-#include "motion_join.cuh"
+#include "motion_group.cuh"
 
 #include <cmath>
 #include <vector>
@@ -29,14 +26,9 @@ static_assert(LCD_M3D_SWEEPS == lcd::m3d::SWEEPS, "the sweep count include/lcd.h
 namespace lcd {
 namespace {
 
-constexpr int BLOCK = m3d::LANES, WAVES = BLOCK / 64;
-constexpr int MAX_ROWS = m3d::MAX_ROWS;
-constexpr int MODEL_FLOATS = BLOCK * 12, RED_FLOATS = BLOCK * 9;
-constexpr size_t FIXED_BYTES = (size_t)(MODEL_FLOATS + RED_FLOATS) * 4;   // what phases (b) and (c) keep in the carve beside the coordinates
+constexpr int SUMS = 9;                                                  // rows of lane partials: a fit's nine products
+constexpr size_t FIXED_BYTES = group_fixed_bytes(SUMS);
 constexpr int SCRATCH_WORDS = 9;                                         // per from-row: six coordinates, d2, two index sets
-
-inline size_t key_bytes(int p_max) { return (size_t)2 * padded(p_max) * 8; }
-constexpr size_t LDS_LIMIT = (size_t)2 * (MAX_ROWS + (MAX_ROWS >> 3)) * 8;   // key_bytes(MAX_ROWS): 144 KiB of the 160 KiB a workgroup may have
 
 struct M3dJob {
     int64_t first_from, first_to;            // the pair's first row in the from- / to-arrays
@@ -60,17 +52,11 @@ struct M3dArgs {
 extern __shared__ __attribute__((aligned(16))) unsigned char m3_smem[];
 
 // the backend of m3d::solve as a workgroup: every method is called by all 256 threads and returns the same value to each
-struct GroupBackend {
-    int m, tid;
-    const float* X;                          // coordinate c of correspondence i: X[c * stride + i]; LDS or the scratch
-    int stride;
+struct GroupBackend : Group {
     uint32_t seed;
     int iterations;
     double thr2;
-    float* models; float* red;               // the carve: [BLOCK x 12], [9 x BLOCK]
-    int* valid; int* hist; int* wsum; unsigned long long* best; float* cur;
-    float* d2; int32_t* prev; int32_t* next;
-    int n_prev, n_next, n_last;
+    float* d2;
 
     __device__ __forceinline__ bool hypothesis(uint32_t h, float model[12]) const {
         int i0, i1, i2;
@@ -89,58 +75,8 @@ struct GroupBackend {
         return m3d::dist2(model, X[i], X[stride + i], X[2 * stride + i], X[3 * stride + i], X[4 * stride + i], X[5 * stride + i]);
     }
     __device__ __forceinline__ unsigned long long ransac() {
-        const int lane = tid & 63, wave = tid >> 6;
-        if (tid == 0) *best = 0ull;
-        __syncthreads();
-        for (int c0 = 0; c0 < iterations; c0 += BLOCK) {
-            const int h = c0 + tid;
-            float model[12];
-            const bool ok = h < iterations && hypothesis((uint32_t)h, model);
-            valid[tid] = ok ? 1 : 0;
-            if (ok) {
-#pragma unroll
-                for (int k = 0; k < 12; ++k) models[tid * 12 + k] = model[k];
-            }
-            __syncthreads();
-            const int nh = min(BLOCK, iterations - c0);
-            for (int j = wave; j < nh; j += WAVES) {
-                if (!valid[j]) continue;
-                float w[12];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) w[k] = models[j * 12 + k];
-                uint32_t count = 0;
-                for (int i0 = 0; i0 < m; i0 += 64) {
-                    const int i = i0 + lane;
-                    const bool in = i < m && (double)distance(w, i) < thr2;
-                    count += (uint32_t)__popcll(__ballot(in));
-                }
-                if (lane == 0 && count > 0) atomicMax(best, ((unsigned long long)count << 32) | (uint32_t)~(uint32_t)(c0 + j));
-            }
-            __syncthreads();
-        }
-        const unsigned long long key = *best;
-        if (key && tid == 0) {
-            float model[12];
-            (void)hypothesis(~(uint32_t)key, model);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) cur[k] = model[k];
-        }
-        __syncthreads();
-        return key;
-    }
-    // red[c * BLOCK + tid] = part[c], then the halving tree; the sums are red[c * BLOCK]; ends behind a barrier
-    template <int C>
-    __device__ __forceinline__ void tree(const float part[C]) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) red[c * BLOCK + tid] = part[c];
-        __syncthreads();
-        for (int s = BLOCK / 2; s >= 1; s >>= 1) {
-            if (tid < s) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) red[c * BLOCK + tid] = red[c * BLOCK + tid] + red[c * BLOCK + tid + s];
-            }
-            __syncthreads();
-        }
+        return Group::ransac(iterations, [&](uint32_t h, float* model) __attribute__((always_inline)) { return hypothesis(h, model); },
+                             [&](const float* w, int i) __attribute__((always_inline)) { return (double)distance(w, i) < thr2; });
     }
     __device__ __forceinline__ void fit_prev() {
         const int n = n_prev;
@@ -188,58 +124,12 @@ struct GroupBackend {
         float w[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) w[k] = cur[k];
-        int count = 0;
-        for (int base = 0; base < m; base += BLOCK) {
-            const int i = base + tid;
-            float d = 0.0f;
-            bool in = false;
-            if (i < m) { d = distance(w, i); in = (double)d < t2; }
-            int total;
-            const int pos = count + block_rank(in, wsum, total);
-            if (in) { next[pos] = i; d2[pos] = d; }
-            count += total;
-        }
-        n_next = n_last = count;
-        __syncthreads();                                               // the set and its d2 are read by other threads
-        return count;
+        return Group::select(d2, [&](int i, float& d) __attribute__((always_inline)) { d = distance(w, i); return (double)d < t2; });
     }
-    // radix select over the bit patterns (non-negative floats order as integers), eight bits a pass
+    // the median of the last selection's d2: non-negative floats order as their bit patterns
     __device__ __forceinline__ double variance() {
-        int rank = n_last >> 1;
-        uint32_t prefix = 0;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n_last; i += BLOCK) {
-                const uint32_t b = m3d::bits_of(d2[i]);
-                if ((((uint64_t)b ^ prefix) >> (shift + 8)) == 0) atomicAdd(&hist[(b >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            int before = 0, digit = 255;
-            for (int d = 0; d < 256; ++d) {
-                const int c = hist[d];
-                if (rank < before + c) { digit = d; break; }
-                before += c;
-            }
-            rank -= before;
-            prefix |= (uint32_t)digit << shift;
-            __syncthreads();
-        }
-        return m3d::VARIANCE_FACTOR * (double)m3d::float_of(prefix);
+        return m3d::VARIANCE_FACTOR * (double)m3d::float_of(ranked(reinterpret_cast<const uint32_t*>(d2), n_last, n_last >> 1));
     }
-    __device__ __forceinline__ void swap_sets() {
-        int32_t* p = prev; prev = next; next = p;
-        const int n = n_prev; n_prev = n_next; n_next = n;
-    }
-    __device__ __forceinline__ void clear_next() { n_next = 0; }
-    __device__ __forceinline__ int prev_n() const { return n_prev; }
-    __device__ __forceinline__ int next_n() const { return n_next; }
-    __device__ __forceinline__ bool same_members() const {            // (sizes are equal)
-        int differs = 0;
-        for (int i = tid; i < n_prev; i += BLOCK) differs |= prev[i] != next[i];
-        return !__syncthreads_or(differs);
-    }
-    __device__ __forceinline__ const float* model() const { return cur; }
 };
 
 __global__ __launch_bounds__(BLOCK) void motion_3d_kernel(M3dArgs a) {
@@ -249,67 +139,32 @@ __global__ __launch_bounds__(BLOCK) void motion_3d_kernel(M3dArgs a) {
     __shared__ unsigned long long best;
     __shared__ float cur[12];
     const M3dJob J = a.jobs[blockIdx.x];
-    const int nf = J.n_from, nt = J.n_to, tid = threadIdx.x;
-    uint64_t* keys_t = reinterpret_cast<uint64_t*>(m3_smem);
-    uint64_t* keys_f = keys_t + padded(a.p_max);
+    const int nf = J.n_from, nt = J.n_to;
     uint32_t* scratch = a.scratch + (size_t)SCRATCH_WORDS * J.first_from;
     float* gx = reinterpret_cast<float*>(scratch);                     // [6][nf]
     int32_t* out_matches = a.out_matches + J.first_from;
-    int32_t* out_inliers = a.out_inliers + J.first_from;
 
-    // ---- (a) join
-    join_sort_keys(keys_t, a.to_ids + J.first_to, nt);
-    join_sort_keys(keys_f, a.from_ids + J.first_from, nf);
-    int m = 0;
-    for (int base = 0; base < nf; base += BLOCK) {
-        const int p = base + tid;
-        bool keep = false;
-        uint32_t idk = 0;
-        float c[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (p < nf) {
-            uint32_t row_f, row_t;
-            if (join_lookup(keys_f, nf, keys_t, nt, p, idk, row_f, row_t)) {
-                const float* pf = a.from_xyz + (J.first_from + (int64_t)row_f) * 3;
-                const float* pt = a.to_xyz + (J.first_to + (int64_t)row_t) * 3;
-                c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2]; c[3] = pt[0]; c[4] = pt[1]; c[5] = pt[2];
-                keep = m3d::keep_pair(c[0], c[1], c[2], c[3], c[4], c[5]);
-            }
-        }
-        int total;
-        const int pos = m + block_rank(keep, wsum, total);
-        if (keep) {
-            out_matches[pos] = m3d::key_id(idk);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) gx[(size_t)k * nf + pos] = c[k];
-        }
-        m += total;
-    }
-    for (int i = m + tid; i < nf; i += BLOCK) out_matches[i] = 0;
-    __syncthreads();                                                   // the keys are dead, the coordinates written
+    // ---- (a) join: walk the from-frame's ids
+    const int m = join_compact<6>(m3_smem, a.p_max, a.to_ids + J.first_to, nt, a.from_ids + J.first_from, nf, 6, out_matches, gx, wsum,
+                                  [&](uint32_t row_f, uint32_t row_t, float* c) __attribute__((always_inline)) {
+        const float* pf = a.from_xyz + (J.first_from + (int64_t)row_f) * 3;
+        const float* pt = a.to_xyz + (J.first_to + (int64_t)row_t) * 3;
+        c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2]; c[3] = pt[0]; c[4] = pt[1]; c[5] = pt[2];
+        return m3d::keep_pair(c[0], c[1], c[2], c[3], c[4], c[5]);
+    });
 
     GroupBackend b;
-    b.m = m; b.tid = tid; b.seed = a.seed; b.iterations = a.iterations; b.thr2 = a.inlier_distance * a.inlier_distance;
-    b.models = reinterpret_cast<float*>(m3_smem); b.red = b.models + MODEL_FLOATS;
-    b.valid = valid; b.hist = hist; b.wsum = wsum; b.best = &best; b.cur = cur;
+    b.seed = a.seed; b.iterations = a.iterations; b.thr2 = a.inlier_distance * a.inlier_distance;
     b.d2 = gx + (size_t)6 * nf;
-    b.prev = reinterpret_cast<int32_t*>(scratch) + (size_t)7 * nf; b.next = b.prev + nf;
-    b.n_prev = b.n_next = b.n_last = 0;
-    if (m <= a.stage_cap) {
-        float* lx = b.red + RED_FLOATS;
-        for (int e = tid; e < 6 * m; e += BLOCK) { const int k = e / m, i = e - k * m; lx[e] = gx[(size_t)k * nf + i]; }
-        b.X = lx; b.stride = m;
-        __syncthreads();
-    } else {
-        b.X = gx; b.stride = nf;
-    }
+    b.init(m, m3_smem, SUMS, wsum, valid, hist, &best, cur, reinterpret_cast<int32_t*>(scratch) + (size_t)7 * nf, gx, 6, nf, a.stage_cap);
 
     // ---- (b), (c): the rule's own control flow
     m3d::Result r;
     m3d::solve(b, m, a.min_inliers, a.refine_iterations, a.inlier_distance, r);
 
     // ---- (d) outputs
-    for (int j = tid; j < nf; j += BLOCK) out_inliers[j] = j < r.n_inliers ? out_matches[b.prev[j]] : 0;
-    if (tid == 0) {
+    b.write_inliers(a.out_inliers + J.first_from, out_matches, nf, r.n_inliers);
+    if (threadIdx.x == 0) {
         float* t = a.out_transform + (size_t)blockIdx.x * 12;
 #pragma unroll
         for (int k = 0; k < 12; ++k) t[k] = r.transform[k];
@@ -318,14 +173,6 @@ __global__ __launch_bounds__(BLOCK) void motion_3d_kernel(M3dArgs a) {
         a.out_n_inliers[blockIdx.x] = r.n_inliers;
         a.out_variance[blockIdx.x] = r.variance;
     }
-}
-
-void allow_large_lds() {
-    static const bool once = [] {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&motion_3d_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) (void)hipGetLastError();
-        return true;
-    }();
-    (void)once;
 }
 
 }  // namespace
@@ -344,22 +191,13 @@ int estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a, bool on_devic
     if (a->iterations > 65535) return bad(LCD_ERR_UNSUPPORTED, "more than 65535 iterations");
     if (!std::isfinite(a->inlier_distance) || !(a->inlier_distance > 0.0)) return bad(LCD_ERR_INVALID, "inlier_distance is finite and > 0");
     if (a->refine_iterations < 0 || a->min_inliers < 1) return bad(LCD_ERR_INVALID, "refine_iterations is >= 0 and min_inliers >= 1");
-    if (a->n_pairs < 0) return bad(LCD_ERR_INVALID, "negative n_pairs");
-    if (a->n_pairs > 65535) return bad(LCD_ERR_UNSUPPORTED, "more than 65535 pairs per call");
-    if (h->shard_append || h->shard_first || h->shard_block) return bad(LCD_ERR_UNSUPPORTED, "not offered on the handles of a sharded vocabulary");
+    if (const int rc = refuse_pairs(h, a->n_pairs, bad)) return rc;
     if (a->n_pairs == 0) return LCD_OK;
     const int np = a->n_pairs;
     const int64_t* fo = a->from_offsets;
     const int64_t* to = a->to_offsets;
-    if (!fo || !to || fo[0] != 0 || to[0] != 0) return bad(LCD_ERR_INVALID, "offsets missing or not starting at 0");
-    for (int i = 0; i < np; ++i) if (fo[i + 1] < fo[i] || to[i + 1] < to[i]) return bad(LCD_ERR_INVALID, "decreasing offsets");
-    int n_max = 0, m_max = 0;
-    for (int i = 0; i < np; ++i) {
-        const int64_t nf = fo[i + 1] - fo[i], nt = to[i + 1] - to[i];
-        if (nf > MAX_ROWS || nt > MAX_ROWS) return bad(LCD_ERR_UNSUPPORTED, "more than 8192 rows on a side of a pair");
-        n_max = std::max(n_max, (int)std::max(nf, nt));
-        m_max = std::max(m_max, (int)std::min(nf, nt));
-    }
+    int n_max, m_max;
+    if (const int rc = refuse_offsets(np, fo, to, bad, n_max, m_max)) return rc;
     const int64_t Nf = fo[np], Nt = to[np];
     if (!a->out_transform || !a->out_status || !a->out_n_matches || !a->out_n_inliers || !a->out_variance) return bad(LCD_ERR_INVALID, "a null per-pair output");
     if (Nf > 0 && (!a->from_word_ids || !a->from_xyz || !a->out_matches || !a->out_inliers)) return bad(LCD_ERR_INVALID, "null from-arrays or id outputs");
@@ -373,10 +211,8 @@ int estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a, bool on_devic
     M3dArgs g;
     g.min_inliers = a->min_inliers; g.iterations = a->iterations; g.refine_iterations = a->refine_iterations; g.seed = a->seed;
     g.inlier_distance = a->inlier_distance;
-    g.p_max = 64;
-    while (g.p_max < n_max) g.p_max <<= 1;
-    const size_t lds = std::max(key_bytes(g.p_max), std::min(FIXED_BYTES + (size_t)24 * m_max, LDS_LIMIT));
-    g.stage_cap = (int)((lds - FIXED_BYTES) / 24);
+    const GroupPlan plan = group_plan(n_max, m_max, FIXED_BYTES, 24);
+    g.p_max = plan.p_max; g.stage_cap = plan.stage_cap;
     g.from_ids = a->from_word_ids; g.from_xyz = a->from_xyz; g.to_ids = a->to_word_ids; g.to_xyz = a->to_xyz;
     g.out_transform = a->out_transform; g.out_status = a->out_status; g.out_n_matches = a->out_n_matches; g.out_n_inliers = a->out_n_inliers;
     g.out_variance = a->out_variance; g.out_matches = a->out_matches; g.out_inliers = a->out_inliers;
@@ -399,8 +235,8 @@ int estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a, bool on_devic
     LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(Nf, 1) * SCRATCH_WORDS * 4));
     g.scratch = S.d_small.as<uint32_t>();
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(M3dJob)));
-    allow_large_lds();
-    motion_3d_kernel<<<dim3((unsigned)np), dim3(BLOCK), lds, st>>>(g);
+    allow_large_lds<&motion_3d_kernel>();
+    motion_3d_kernel<<<dim3((unsigned)np), dim3(BLOCK), plan.lds, st>>>(g);
     LCD_HIP(h, hipGetLastError());
     if (!on_device) LCD_HIP(h, stage.finish(st));
     return LCD_OK;

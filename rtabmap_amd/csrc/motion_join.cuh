@@ -1,5 +1,6 @@
-// motion_join.cuh -- the unique-id join of two frames that motion_3d.hip and motion_pnp.hip share: both frames' 64-bit keys (id || row) sorted
-// in LDS (compact_body.cuh's network), and the lookup of one side's sorted position in the other.  Device code only.  Internal.
+// motion_join.cuh -- the unique-id join of two frames for motion_3d.hip and motion_pnp.hip: both frames' 64-bit keys (id || row) sorted in LDS
+// (compact_body.cuh's network), and the lookup of one side's sorted position in the other.  Its one caller is motion_group.cuh's join_compact,
+// which walks a side and compacts the survivors.  Device code only.  Internal.
 #pragma once
 #include "compact_body.cuh"
 #include "motion_rule_common.h"

@@ -2,21 +2,20 @@
 // :843-986, RegistrationVis.cpp:1676-1819 with Vis/EstimationType = 1) for a caller who holds the from-frame's word ids and 3-D points and
 // the to-frame's word ids and keypoints in device memory.  The rule is include/lcd.h's; its arithmetic and its control flow (solve, refine)
 // are motion_pnp_rule.h's, compiled here for the device and in host/Motion2D.cpp for the mirror.
-//   motion_pnp_kernel: one launch per call, one workgroup of 256 threads per pair, in phases behind barriers:
-//     (a) join (motion_join.cuh, shared with motion_3d.hip): a to-key whose neighbours carry other ids is looked up in the from-keys, the
-//         from-point's finiteness is tested and the survivors are compacted in ascending id.  Their ids go to out_matches, their coordinates
-//         (one plane each: from x, y, z, to u, v and, with to_xyz, to x, y, z) to the call's scratch -- and, when they fit beside the
-//         candidates, into the LDS the keys no longer need; larger pairs read them from the scratch through the same pointer.
-//     (b) candidates in chunks of 256: thread c takes candidate c (0: the guess's model, h + 1: hypothesis h, P3P and the fourth point) and
-//         leaves 12 floats in LDS; each wave takes candidates in turn, its lanes stride over the correspondences and count with a ballot,
-//         lane 0 raises a 64-bit LDS maximum (count << 32 | ~c).
-//     (c) selection and refinement: a fit's 27 sums per Gauss-Newton step are 256 lane partials and a halving tree in LDS, the 6 x 6 system
-//         is thread 0's; mean and variance of a selection's errors are thread 0's walk in the reference's order.
-//     (d) covariance inputs: per inlier the squared distance and the cosine as ordered keys, two radix selects; or thread 0's RMS sum.
+//   motion_pnp_kernel: one launch per call, one workgroup of 256 threads per pair, in phases behind barriers.  The phases' machinery is
+//   motion_group.cuh's, shared with motion_3d.hip; what is written here is what the PnP rule puts into it:
+//     (a) join (join_compact): the to-frame's ids are walked, the from-point's finiteness is tested, the coordinates (one plane each: from
+//         x, y, z, to u, v and, with to_xyz, to x, y, z) go to the call's scratch and, when they fit beside the candidates, into LDS
+//         (Group::init).
+//     (b) candidates in chunks of 256 (Group::ransac): candidate 0 is the guess's model, h + 1 hypothesis h, P3P and the fourth point; an
+//         inlier is pnp::is_inlier of the reprojection error.
+//     (c) selection and refinement: a fit's 27 sums per Gauss-Newton step are 256 lane partials and the halving tree (Group::tree), the
+//         6 x 6 system is thread 0's; mean and variance of a selection's errors are thread 0's walk in the reference's order.
+//     (d) covariance inputs: per inlier the squared distance and the cosine as ordered keys, two radix selects (Group::ranked); or thread
+//         0's RMS sum.
 //     (e) outputs.
 // Nothing of the engine is read or written: the job table is StatelessScratch's, the per-row scratch its d_small.
-#include "engine_impl.h"
-#include "motion_join.cuh"
+#include "motion_group.cuh"
 #include "motion_pnp_rule.h"
 
 #include <cmath>
@@ -30,15 +29,9 @@ static_assert(LCD_PNP_STEPS == lcd::pnp::STEPS && LCD_PNP_BISECT == lcd::pnp::BI
 namespace lcd {
 namespace {
 
-constexpr int BLOCK = m3d::LANES, WAVES = BLOCK / 64;
-constexpr int MAX_ROWS = m3d::MAX_ROWS;
-constexpr int MODEL_FLOATS = BLOCK * 12, RED_FLOATS = BLOCK * pnp::SUMS;
-constexpr size_t FIXED_BYTES = (size_t)(MODEL_FLOATS + RED_FLOATS) * 4;   // what phases (b) and (c) keep in the carve beside the coordinates
+constexpr size_t FIXED_BYTES = group_fixed_bytes(pnp::SUMS);
 constexpr int MAX_PLANES = 8;
 constexpr int SCRATCH_WORDS = MAX_PLANES + 3;                            // per to-row: the coordinate planes, the errors / distance keys, two index sets
-
-inline size_t key_bytes(int p_max) { return (size_t)2 * padded(p_max) * 8; }
-constexpr size_t LDS_LIMIT = (size_t)2 * (MAX_ROWS + (MAX_ROWS >> 3)) * 8;   // key_bytes(MAX_ROWS): 144 KiB of the 160 KiB a workgroup may have
 
 struct PnpJob {
     int64_t first_from, first_to;            // the pair's first row in the from- / to-arrays
@@ -68,19 +61,14 @@ struct PnpArgs {
 extern __shared__ __attribute__((aligned(16))) unsigned char pnp_smem[];
 
 // the backend of pnp::solve as a workgroup: every method is called by all 256 threads and returns the same value to each
-struct GroupBackend {
-    int m, tid;
-    const float* X;                          // coordinate c of correspondence i: X[c * stride + i]; LDS or the scratch
-    int stride;
+struct GroupBackend : Group {
     bool has_to;
     pnp::Camera cam;
     const float* model0;
     uint32_t seed;
     int iterations;
-    float* models; float* red;               // the carve: [BLOCK x 12], [SUMS x BLOCK]
-    int* valid; int* hist; int* wsum; unsigned long long* best; float* cur; double* bcast;
-    float* err; int32_t* prev; int32_t* next;
-    int n_prev, n_next, n_last;
+    double* bcast;
+    float* err;
 
     __device__ __forceinline__ bool candidate(uint32_t c, float model[12]) const {
         if (c == 0) {
@@ -101,65 +89,14 @@ struct GroupBackend {
     __device__ __forceinline__ float error(const float model[12], int i, bool& front) const {
         return pnp::reproj_error(model, cam, X[i], X[stride + i], X[2 * stride + i], X[3 * stride + i], X[4 * stride + i], front);
     }
-    __device__ __forceinline__ unsigned long long ransac(float thr) {
-        const int lane = tid & 63, wave = tid >> 6;
-        const int n_cand = iterations + 1;
-        if (tid == 0) *best = 0ull;
-        __syncthreads();
-        for (int c0 = 0; c0 < n_cand; c0 += BLOCK) {
-            const int c = c0 + tid;
-            float model[12];
-            const bool ok = c < n_cand && candidate((uint32_t)c, model);
-            valid[tid] = ok ? 1 : 0;
-            if (ok) {
-#pragma unroll
-                for (int k = 0; k < 12; ++k) models[tid * 12 + k] = model[k];
-            }
-            __syncthreads();
-            const int nc = min(BLOCK, n_cand - c0);
-            for (int j = wave; j < nc; j += WAVES) {
-                if (!valid[j]) continue;
-                float w[12];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) w[k] = models[j * 12 + k];
-                uint32_t count = 0;
-                for (int i0 = 0; i0 < m; i0 += 64) {
-                    const int i = i0 + lane;
-                    bool in = false;
-                    if (i < m) {
-                        bool front;
-                        const float e = error(w, i, front);
-                        in = pnp::is_inlier(e, front, thr);
-                    }
-                    count += (uint32_t)__popcll(__ballot(in));
-                }
-                if (lane == 0 && count > 0) atomicMax(best, ((unsigned long long)count << 32) | (uint32_t)~(uint32_t)(c0 + j));
-            }
-            __syncthreads();
-        }
-        const unsigned long long key = *best;
-        if (key && tid == 0) {
-            float model[12];
-            (void)candidate(~(uint32_t)key, model);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) cur[k] = model[k];
-        }
-        __syncthreads();
-        return key;
+    __device__ __forceinline__ bool inlier(const float model[12], int i, float thr, float& e) const {
+        bool front;
+        e = error(model, i, front);
+        return pnp::is_inlier(e, front, thr);
     }
-    // red[c * BLOCK + tid] = part[c], then the halving tree; the sums are red[c * BLOCK]; ends behind a barrier
-    template <int C>
-    __device__ __forceinline__ void tree(const float part[C]) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) red[c * BLOCK + tid] = part[c];
-        __syncthreads();
-        for (int s = BLOCK / 2; s >= 1; s >>= 1) {
-            if (tid < s) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) red[c * BLOCK + tid] = red[c * BLOCK + tid] + red[c * BLOCK + tid + s];
-            }
-            __syncthreads();
-        }
+    __device__ __forceinline__ unsigned long long ransac(float thr) {
+        return Group::ransac(iterations + 1, [&](uint32_t c, float* model) __attribute__((always_inline)) { return candidate(c, model); },
+                             [&](const float* w, int i) __attribute__((always_inline)) { float e; return inlier(w, i, thr, e); });
     }
     __device__ __forceinline__ void fit_prev() {
         const int n = n_prev;
@@ -207,24 +144,7 @@ struct GroupBackend {
         float w[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) w[k] = cur[k];
-        int count = 0;
-        for (int base = 0; base < m; base += BLOCK) {
-            const int i = base + tid;
-            float e = 0.0f;
-            bool in = false;
-            if (i < m) {
-                bool front;
-                e = error(w, i, front);
-                in = pnp::is_inlier(e, front, thr);
-            }
-            int total;
-            const int pos = count + block_rank(in, wsum, total);
-            if (in) { next[pos] = i; err[pos] = e; }
-            count += total;
-        }
-        n_next = n_last = count;
-        __syncthreads();                                               // the set and its errors are read by other threads
-        return count;
+        return Group::select(err, [&](int i, float& e) __attribute__((always_inline)) { return inlier(w, i, thr, e); });
     }
     __device__ __forceinline__ float threshold(float thr0) {
         if (tid == 0) *bcast = (double)pnp::refined_threshold(err, n_last, thr0);
@@ -232,29 +152,6 @@ struct GroupBackend {
         const float v = (float)*bcast;
         __syncthreads();
         return v;
-    }
-    // the key of rank `rank` among keys[0 .. n): radix select, eight bits a pass
-    __device__ __forceinline__ uint32_t ranked(const uint32_t* keys, int n, int rank) {
-        uint32_t prefix = 0;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += BLOCK) {
-                const uint32_t b = keys[i];
-                if ((((uint64_t)b ^ prefix) >> (shift + 8)) == 0) atomicAdd(&hist[(b >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            int before = 0, digit = 255;
-            for (int d = 0; d < 256; ++d) {
-                const int c = hist[d];
-                if (rank < before + c) { digit = d; break; }
-                before += c;
-            }
-            rank -= before;
-            prefix |= (uint32_t)digit << shift;
-            __syncthreads();
-        }
-        return prefix;
     }
     __device__ __forceinline__ void covariance(int kind, const float pose[12], int ratio, double& lin, double& cosine) {
         const int n = n_prev;
@@ -296,19 +193,6 @@ struct GroupBackend {
             __syncthreads();
         }
     }
-    __device__ __forceinline__ void swap_sets() {
-        int32_t* p = prev; prev = next; next = p;
-        const int n = n_prev; n_prev = n_next; n_next = n;
-    }
-    __device__ __forceinline__ void clear_next() { n_next = 0; }
-    __device__ __forceinline__ int prev_n() const { return n_prev; }
-    __device__ __forceinline__ int next_n() const { return n_next; }
-    __device__ __forceinline__ bool same_members() const {            // (sizes are equal)
-        int differs = 0;
-        for (int i = tid; i < n_prev; i += BLOCK) differs |= prev[i] != next[i];
-        return !__syncthreads_or(differs);
-    }
-    __device__ __forceinline__ const float* model() const { return cur; }
 };
 
 __global__ __launch_bounds__(BLOCK) void motion_pnp_kernel(PnpArgs a) {
@@ -324,76 +208,42 @@ __global__ __launch_bounds__(BLOCK) void motion_pnp_kernel(PnpArgs a) {
     const int nf = J.n_from, nt = J.n_to, tid = threadIdx.x;
     const int64_t first_from = J.first_from, first_to = J.first_to;
     if (tid < 12) { model0[tid] = J.model0[tid]; local[tid] = J.local[tid]; cur[tid] = 0.0f; }
-    uint64_t* keys_f = reinterpret_cast<uint64_t*>(pnp_smem);
-    uint64_t* keys_t = keys_f + padded(a.p_max);
     uint32_t* scratch = a.scratch + (size_t)SCRATCH_WORDS * first_to;
     float* gx = reinterpret_cast<float*>(scratch);                     // [planes][nt]
     int32_t* out_matches = a.out_matches + first_to;
-    int32_t* out_inliers = a.out_inliers + first_to;
     const bool has_to = a.planes == MAX_PLANES;
 
     // ---- (a) join: walk the to-frame's ids (util3d_motion_estimation.cpp:89-106)
-    join_sort_keys(keys_f, a.from_ids + first_from, nf);
-    join_sort_keys(keys_t, a.to_ids + first_to, nt);
-    int m = 0;
-    for (int base = 0; base < nt; base += BLOCK) {
-        const int p = base + tid;
-        bool keep = false;
-        uint32_t idk = 0;
-        float c[MAX_PLANES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (p < nt) {
-            uint32_t row_t, row_f;
-            if (join_lookup(keys_t, nt, keys_f, nf, p, idk, row_t, row_f)) {
-                const float* pf = a.from_xyz + (first_from + (int64_t)row_f) * 3;
-                c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2];
-                keep = m3d::finite(c[0]) && m3d::finite(c[1]) && m3d::finite(c[2]);
-                if (keep) {
-                    const float* pp = a.to_points + (first_to + (int64_t)row_t) * 2;
-                    c[3] = pp[0]; c[4] = pp[1];
-                    if (has_to) {
-                        const float* pt = a.to_xyz + (first_to + (int64_t)row_t) * 3;
-                        c[5] = pt[0]; c[6] = pt[1]; c[7] = pt[2];
-                    }
-                }
+    const int m = join_compact<MAX_PLANES>(pnp_smem, a.p_max, a.from_ids + first_from, nf, a.to_ids + first_to, nt, a.planes, out_matches, gx, wsum,
+                                           [&](uint32_t row_t, uint32_t row_f, float* c) __attribute__((always_inline)) {
+        const float* pf = a.from_xyz + (first_from + (int64_t)row_f) * 3;
+        c[0] = pf[0]; c[1] = pf[1]; c[2] = pf[2];
+        const bool keep = m3d::finite(c[0]) && m3d::finite(c[1]) && m3d::finite(c[2]);
+        if (keep) {
+            const float* pp = a.to_points + (first_to + (int64_t)row_t) * 2;
+            c[3] = pp[0]; c[4] = pp[1];
+            if (has_to) {
+                const float* pt = a.to_xyz + (first_to + (int64_t)row_t) * 3;
+                c[5] = pt[0]; c[6] = pt[1]; c[7] = pt[2];
             }
         }
-        int total;
-        const int pos = m + block_rank(keep, wsum, total);
-        if (keep) {
-            out_matches[pos] = m3d::key_id(idk);
-#pragma unroll
-            for (int k = 0; k < MAX_PLANES; ++k)
-                if (k < a.planes) gx[(size_t)k * nt + pos] = c[k];
-        }
-        m += total;
-    }
-    for (int i = m + tid; i < nt; i += BLOCK) out_matches[i] = 0;
-    __syncthreads();                                                   // the keys are dead, the coordinates written
+        return keep;
+    });
 
     GroupBackend b;
-    b.m = m; b.tid = tid; b.seed = a.seed; b.iterations = a.iterations; b.has_to = has_to;
+    b.seed = a.seed; b.iterations = a.iterations; b.has_to = has_to;
     b.cam = pnp::Camera{J.fx, J.fy, J.cx, J.cy, J.width, J.height};
-    b.model0 = model0;
-    b.models = reinterpret_cast<float*>(pnp_smem); b.red = b.models + MODEL_FLOATS;
-    b.valid = valid; b.hist = hist; b.wsum = wsum; b.best = &best; b.cur = cur; b.bcast = &bcast;
+    b.model0 = model0; b.bcast = &bcast;
     b.err = gx + (size_t)MAX_PLANES * nt;
-    b.prev = reinterpret_cast<int32_t*>(scratch) + (size_t)(MAX_PLANES + 1) * nt; b.next = b.prev + nt;
-    b.n_prev = b.n_next = b.n_last = 0;
-    if (m <= a.stage_cap) {
-        float* lx = b.red + RED_FLOATS;
-        for (int e = tid; e < a.planes * m; e += BLOCK) { const int k = e / m, i = e - k * m; lx[e] = gx[(size_t)k * nt + i]; }
-        b.X = lx; b.stride = m;
-        __syncthreads();
-    } else {
-        b.X = gx; b.stride = nt;
-    }
+    b.init(m, pnp_smem, pnp::SUMS, wsum, valid, hist, &best, cur, reinterpret_cast<int32_t*>(scratch) + (size_t)(MAX_PLANES + 1) * nt, gx, a.planes, nt,
+           a.stage_cap);
 
     // ---- (b), (c), (d): the rule's own control flow
     pnp::Result r;
     pnp::solve(b, m, a.min_inliers, a.refine_iterations, a.reproj_error, a.ratio, a.max_variance, J.kind, J.has_local != 0, local, r);
 
     // ---- (e) outputs
-    for (int j = tid; j < nt; j += BLOCK) out_inliers[j] = j < r.n_inliers ? out_matches[b.prev[j]] : 0;
+    b.write_inliers(a.out_inliers + first_to, out_matches, nt, r.n_inliers);
     if (tid == 0) {
         float* t = a.out_transform + (size_t)blockIdx.x * 12;
 #pragma unroll
@@ -405,14 +255,6 @@ __global__ __launch_bounds__(BLOCK) void motion_pnp_kernel(PnpArgs a) {
         a.out_angle_cos[blockIdx.x] = r.angle_cos;
         a.out_variance_kind[blockIdx.x] = r.kind;
     }
-}
-
-void allow_large_lds() {
-    static const bool once = [] {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&motion_pnp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess) (void)hipGetLastError();
-        return true;
-    }();
-    (void)once;
 }
 
 const float IDENTITY[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -437,22 +279,13 @@ int estimate_motion_pnp(lcd_engine* h, const lcd_motion_pnp_args* a, bool on_dev
     if (a->refine_iterations < 0 || a->min_inliers < 1) return bad(LCD_ERR_INVALID, "refine_iterations is >= 0 and min_inliers >= 1");
     if (a->variance_median_ratio <= 1) return bad(LCD_ERR_INVALID, "variance_median_ratio is > 1");
     if (!(a->max_variance >= 0.0f) || !std::isfinite(a->max_variance)) return bad(LCD_ERR_INVALID, "max_variance is finite and >= 0");
-    if (a->n_pairs < 0) return bad(LCD_ERR_INVALID, "negative n_pairs");
-    if (a->n_pairs > 65535) return bad(LCD_ERR_UNSUPPORTED, "more than 65535 pairs per call");
-    if (h->shard_append || h->shard_first || h->shard_block) return bad(LCD_ERR_UNSUPPORTED, "not offered on the handles of a sharded vocabulary");
+    if (const int rc = refuse_pairs(h, a->n_pairs, bad)) return rc;
     if (a->n_pairs == 0) return LCD_OK;
     const int np = a->n_pairs;
     const int64_t* fo = a->from_offsets;
     const int64_t* to = a->to_offsets;
-    if (!fo || !to || fo[0] != 0 || to[0] != 0) return bad(LCD_ERR_INVALID, "offsets missing or not starting at 0");
-    for (int i = 0; i < np; ++i) if (fo[i + 1] < fo[i] || to[i + 1] < to[i]) return bad(LCD_ERR_INVALID, "decreasing offsets");
-    int n_max = 0, m_max = 0;
-    for (int i = 0; i < np; ++i) {
-        const int64_t nf = fo[i + 1] - fo[i], nt = to[i + 1] - to[i];
-        if (nf > MAX_ROWS || nt > MAX_ROWS) return bad(LCD_ERR_UNSUPPORTED, "more than 8192 rows on a side of a pair");
-        n_max = std::max(n_max, (int)std::max(nf, nt));
-        m_max = std::max(m_max, (int)std::min(nf, nt));
-    }
+    int n_max, m_max;
+    if (const int rc = refuse_offsets(np, fo, to, bad, n_max, m_max)) return rc;
     if (!a->cameras) return bad(LCD_ERR_INVALID, "null cameras");
     for (int i = 0; i < np; ++i) {
         const lcd_camera& c = a->cameras[i];
@@ -483,11 +316,8 @@ int estimate_motion_pnp(lcd_engine* h, const lcd_motion_pnp_args* a, bool on_dev
     g.min_inliers = a->min_inliers; g.iterations = a->iterations; g.refine_iterations = a->refine_iterations; g.ratio = a->variance_median_ratio;
     g.seed = a->seed; g.max_variance = a->max_variance; g.reproj_error = a->reproj_error;
     g.planes = has_to ? MAX_PLANES : 5;
-    g.p_max = 64;
-    while (g.p_max < n_max) g.p_max <<= 1;
-    const size_t per = (size_t)g.planes * 4;
-    const size_t lds = std::max(key_bytes(g.p_max), std::min(FIXED_BYTES + per * m_max, LDS_LIMIT));
-    g.stage_cap = (int)((lds - FIXED_BYTES) / per);
+    const GroupPlan plan = group_plan(n_max, m_max, FIXED_BYTES, (size_t)g.planes * 4);
+    g.p_max = plan.p_max; g.stage_cap = plan.stage_cap;
     g.from_ids = a->from_word_ids; g.from_xyz = a->from_xyz; g.to_ids = a->to_word_ids; g.to_points = a->to_points; g.to_xyz = a->to_xyz;
     g.out_transform = a->out_transform; g.out_status = a->out_status; g.out_n_matches = a->out_n_matches; g.out_n_inliers = a->out_n_inliers;
     g.out_variance_lin = a->out_variance_lin; g.out_angle_cos = a->out_angle_cos; g.out_variance_kind = a->out_variance_kind;
@@ -515,8 +345,8 @@ int estimate_motion_pnp(lcd_engine* h, const lcd_motion_pnp_args* a, bool on_dev
     LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(Nt, 1) * SCRATCH_WORDS * 4));
     g.scratch = S.d_small.as<uint32_t>();
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(PnpJob)));
-    allow_large_lds();
-    motion_pnp_kernel<<<dim3((unsigned)np), dim3(BLOCK), lds, st>>>(g);
+    allow_large_lds<&motion_pnp_kernel>();
+    motion_pnp_kernel<<<dim3((unsigned)np), dim3(BLOCK), plan.lds, st>>>(g);
     LCD_HIP(h, hipGetLastError());
     if (!on_device) LCD_HIP(h, stage.finish(st));
     return LCD_OK;

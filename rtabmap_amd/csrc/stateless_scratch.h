@@ -8,14 +8,20 @@
 #include "devbuf.h"
 #include "stage_rows.h"
 
-// Scratch of lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip), lcd_select_features and lcd_expand_word_ids
-// (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip), lcd_estimate_motion_3d (motion_3d.hip) and lcd_estimate_motion_pnp (motion_pnp.hip) with their _dev forms: the calls that do not complete what a pipelined handle owes.  Everything they write on the
-// device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The buffers only grow, and a growth
-// frees the old allocation after the engine stream has drained (DevBuf::reserve): work of an earlier call that is still enqueued keeps
-// what it reads.  The protocol is the methods' and HostStage's; the callers own only d_dist and d_small.
+// Scratch of the calls that do not complete what a pipelined handle owes, with their _dev forms:
+//   lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip),
+//   lcd_select_features and lcd_expand_word_ids (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip),
+//   lcd_estimate_motion_3d (motion_3d.hip) and lcd_estimate_motion_pnp (motion_pnp.hip).
+// Everything they write on the device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The
+// buffers only grow, and a growth frees the old allocation after the engine stream has drained (DevBuf::reserve): work of an earlier call
+// that is still enqueued keeps what it reads.  The protocol is the methods' and HostStage's; the callers own only d_dist and d_small.
 struct StatelessScratch {
     lcd::DevBuf d_dist;                                 // the distance blocks of one group of pairs (to x from; from x from and to x to when new words are compared)
-    lcd::DevBuf d_small;                                // per pair: the to-rows' 2-NN among the from-words, word ranks, candidate bit rows / the cross-check keys / lcd_estimate_motion_3d: 36 bytes per from-row (six coordinate planes, d2, two index sets) / lcd_estimate_motion_pnp: 44 bytes per to-row (eight coordinate planes, errors, two index sets)
+    // d_small, by caller:
+    //   the matching calls: per pair the to-rows' 2-NN among the from-words, word ranks, candidate bit rows / the cross-check keys
+    //   lcd_estimate_motion_3d: 36 bytes per from-row (six coordinate planes, d2, two index sets)
+    //   lcd_estimate_motion_pnp: 44 bytes per to-row (eight coordinate planes, errors, two index sets)
+    lcd::DevBuf d_small;
     int64_t budget_bytes = 0;                           // lcd_set_option("pair_match_budget"): distance-block bytes per group (0: built-in, 256 MiB)
 
     // A call's job table (one or two host arrays, back to back) reaches d_table through one of two pinned slots, taken in turn by every

@@ -6,6 +6,7 @@
 
 #include "../csrc/motion_pnp_rule.h"
 #include "LaneSum.h"
+#include "MotionMirror.h"
 
 namespace rtabmap_amd {
 
@@ -15,20 +16,21 @@ namespace rule = lcd::pnp;
 namespace common = lcd::m3d;
 
 // the backend of rule::solve as a loop; X: the correspondences' coordinates, [planes][m] (from x, y, z, to u, v and, with points, to x, y, z)
-struct CpuBackend {
+struct CpuBackend : MirrorState {
     int m;
     const float* X;
     bool has_to;
     rule::Camera cam;
     uint32_t seed;
     int iterations, steps;
-    float model0[12], cur[12];
-    std::vector<int> prev, next;
+    float model0[12];
     std::vector<float> last_e;
 
     float at(int c, int i) const { return X[(size_t)c * m + i]; }
-    float error(const float model[12], int i, bool& front) const {
-        return rule::reproj_error(model, cam, at(0, i), at(1, i), at(2, i), at(3, i), at(4, i), front);
+    bool inlier(const float model[12], int i, float thr, float& e) const {
+        bool front;
+        e = rule::reproj_error(model, cam, at(0, i), at(1, i), at(2, i), at(3, i), at(4, i), front);
+        return rule::is_inlier(e, front, thr);
     }
     bool hypothesis(int h, float model[12]) const {
         int i[4];
@@ -46,21 +48,8 @@ struct CpuBackend {
         return true;
     }
     uint64_t ransac(float thr) {
-        uint64_t best = 0;
-        for (int c = 0; c <= iterations; ++c) {
-            float model[12];
-            if (!candidate(c, model)) continue;
-            uint32_t count = 0;
-            for (int i = 0; i < m; ++i) {
-                bool front;
-                const float e = error(model, i, front);
-                if (rule::is_inlier(e, front, thr)) ++count;
-            }
-            const uint64_t key = ((uint64_t)count << 32) | (uint32_t)~(uint32_t)c;
-            if (count > 0 && key > best) best = key;
-        }
-        if (best) (void)candidate((int)~(uint32_t)best, cur);
-        return best;
+        return bestCandidate(iterations + 1, m, cur, [&](int c, float* model) { return candidate(c, model); },
+                             [&](const float* model, int i) { float e; return inlier(model, i, thr, e); });
     }
     void fit_prev() {
         const int n = (int)prev.size();
@@ -81,14 +70,7 @@ struct CpuBackend {
         rule::model_of_pose(q, t, cur);
     }
     int select(float thr) {
-        next.clear();
-        last_e.clear();
-        for (int i = 0; i < m; ++i) {
-            bool front;
-            const float e = error(cur, i, front);
-            if (rule::is_inlier(e, front, thr)) { next.push_back(i); last_e.push_back(e); }
-        }
-        return (int)next.size();
+        return MirrorState::select(m, last_e, [&](int i, float& e) { return inlier(cur, i, thr, e); });
     }
     float threshold(float thr0) const { return rule::refined_threshold(last_e.data(), (int)last_e.size(), thr0); }
     void covariance(int kind, const float pose[12], int ratio, double& lin, double& cosine) const {
@@ -123,12 +105,6 @@ struct CpuBackend {
             lin = (double)sqrtf(mean);
         }
     }
-    void swap_sets() { prev.swap(next); }
-    void clear_next() { next.clear(); }
-    int prev_n() const { return (int)prev.size(); }
-    int next_n() const { return (int)next.size(); }
-    bool same_members() const { return prev == next; }
-    const float* model() const { return cur; }
 };
 
 const float IDENTITY[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -143,14 +119,6 @@ bool motion_pnp_cpu(const int32_t* fromIds, const float* fromXyz, int nFrom, con
         !(p.maxVariance >= 0.0f) || !std::isfinite(p.maxVariance))
         return false;
     if ((nFrom > 0 && (!fromIds || !fromXyz)) || (nTo > 0 && (!toIds || !toPoints))) return false;
-    // uMultimapToMapUnique (UStl.h:503-516): the rows whose id occurs once in their frame, by id
-    auto uniqueRows = [](const int32_t* ids, int n) {
-        std::map<int32_t, std::pair<int, int> > seen;                  // id -> (occurrences, row)
-        for (int r = 0; r < n; ++r) { std::pair<int, int>& s = seen[ids[r]]; ++s.first; s.second = r; }
-        std::map<int32_t, int> rows;
-        for (const auto& s : seen) if (s.second.first == 1) rows[s.first] = s.second.second;
-        return rows;
-    };
     const std::map<int32_t, int> from = uniqueRows(fromIds, nFrom), to = uniqueRows(toIds, nTo);
     const bool has_to = toXyz != nullptr;
     const int planes = has_to ? 8 : 5;

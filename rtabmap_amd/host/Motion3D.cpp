@@ -7,6 +7,7 @@
 #include "../../include/lcd.h"
 #include "../csrc/motion_3d_rule.h"
 #include "LaneSum.h"
+#include "MotionMirror.h"
 
 namespace rtabmap_amd {
 
@@ -18,17 +19,16 @@ template <class F>
 float laneTreeSum(int n, F e) { return rtabmap_amd::laneTreeSum<rule::LANES>(n, e); }
 
 // the backend of rule::solve as a loop; X: the correspondences' coordinates, [6][m] (from x, y, z, to x, y, z)
-struct CpuBackend {
+struct CpuBackend : MirrorState {
     int m;
     const float* X;
     uint32_t seed;
     int iterations, sweeps;
     double thr2;
-    float cur[12];
-    std::vector<int> prev, next;
     std::vector<float> last_d2;
 
     float at(int c, int i) const { return X[(size_t)c * m + i]; }
+    float distance(const float model[12], int i) const { return rule::dist2(model, at(0, i), at(1, i), at(2, i), at(3, i), at(4, i), at(5, i)); }
     bool hypothesis(int h, float model[12]) const {
         int i[3];
         if (!rule::draw3(seed, (uint32_t)h, (uint32_t)m, i[0], i[1], i[2])) return false;
@@ -39,18 +39,8 @@ struct CpuBackend {
         return true;
     }
     uint64_t ransac() {
-        uint64_t best = 0;
-        for (int h = 0; h < iterations; ++h) {
-            float model[12];
-            if (!hypothesis(h, model)) continue;
-            uint32_t count = 0;
-            for (int i = 0; i < m; ++i)
-                if ((double)rule::dist2(model, at(0, i), at(1, i), at(2, i), at(3, i), at(4, i), at(5, i)) < thr2) ++count;
-            const uint64_t key = ((uint64_t)count << 32) | (uint32_t)~(uint32_t)h;
-            if (count > 0 && key > best) best = key;
-        }
-        if (best) (void)hypothesis((int)~(uint32_t)best, cur);
-        return best;
+        return bestCandidate(iterations, m, cur, [&](int h, float* model) { return hypothesis(h, model); },
+                             [&](const float* model, int i) { return (double)distance(model, i) < thr2; });
     }
     void fit_prev() {
         const int n = (int)prev.size();
@@ -71,13 +61,7 @@ struct CpuBackend {
         rule::horn_fit(cp, cq, S, sweeps, cur);
     }
     int select(double t2) {
-        next.clear();
-        last_d2.clear();
-        for (int i = 0; i < m; ++i) {
-            const float d2 = rule::dist2(cur, at(0, i), at(1, i), at(2, i), at(3, i), at(4, i), at(5, i));
-            if ((double)d2 < t2) { next.push_back(i); last_d2.push_back(d2); }
-        }
-        return (int)next.size();
+        return MirrorState::select(m, last_d2, [&](int i, float& d2) { d2 = distance(cur, i); return (double)d2 < t2; });
     }
     double variance() const {
         std::vector<uint32_t> b(last_d2.size());
@@ -85,12 +69,6 @@ struct CpuBackend {
         std::nth_element(b.begin(), b.begin() + (b.size() >> 1), b.end());
         return rule::VARIANCE_FACTOR * (double)rule::float_of(b[b.size() >> 1]);
     }
-    void swap_sets() { prev.swap(next); }
-    void clear_next() { next.clear(); }
-    int prev_n() const { return (int)prev.size(); }
-    int next_n() const { return (int)next.size(); }
-    bool same_members() const { return prev == next; }
-    const float* model() const { return cur; }
 };
 
 }  // namespace
@@ -100,14 +78,6 @@ bool motion3d_cpu(const int32_t* fromIds, const float* fromXyz, int nFrom, const
     if (nFrom < 0 || nTo < 0 || nFrom > rule::MAX_ROWS || nTo > rule::MAX_ROWS || minInliers < 1 || iterations < 1 || iterations > 65535 ||
         refineIterations < 0 || !std::isfinite(inlierDistance) || !(inlierDistance > 0.0) || sweeps < 0) return false;
     if ((nFrom > 0 && (!fromIds || !fromXyz)) || (nTo > 0 && (!toIds || !toXyz))) return false;
-    // uMultimapToMapUnique (UStl.h:503-516): the rows whose id occurs once in their frame, by id
-    auto uniqueRows = [](const int32_t* ids, int n) {
-        std::map<int32_t, std::pair<int, int> > seen;                  // id -> (occurrences, row)
-        for (int r = 0; r < n; ++r) { std::pair<int, int>& s = seen[ids[r]]; ++s.first; s.second = r; }
-        std::map<int32_t, int> rows;
-        for (const auto& s : seen) if (s.second.first == 1) rows[s.first] = s.second.second;
-        return rows;
-    };
     const std::map<int32_t, int> from = uniqueRows(fromIds, nFrom), to = uniqueRows(toIds, nTo);
     Motion3DResult r;
     std::vector<float> coords[6];
