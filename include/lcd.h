@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_estimate_motion_3d / lcd_estimate_motion_pnp with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_register_icp with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -864,6 +864,134 @@ int lcd_estimate_motion_pnp(lcd_engine* h, const lcd_motion_pnp_args* a);
 /* ids, points and out_* in DEVICE memory (4-byte aligned, the doubles 8-byte), offsets, cameras and guesses on the HOST (read during the
  * call); enqueued on the engine stream, not synchronised */
 int lcd_estimate_motion_pnp_dev(lcd_engine* h, const lcd_motion_pnp_args* a);
+
+/* ---- Scan registration (point-to-point ICP), stateless: the other half of the registration step, Reg/Strategy = 1 (ICP) and 2 (visual, then
+ * ICP), for a caller who holds both laser scans in device memory.  RegistrationIcp::computeTransformationImpl, the point-to-point branch
+ * with Icp/Strategy = 0 (RegistrationIcp.cpp:662-971): util3d::icp (util3d_registration.cpp:384-434), util3d::computeVarianceAndCorrespondences
+ * (:327-360) and the gates and the result of RegistrationIcp.cpp:856-961.  What is in the reference tree is reproduced exactly, integers and
+ * control flow: the roles (source = the from-scan, target = guess x the to-scan), Reg/Force3DoF choosing the 2-D estimator, the
+ * transformation epsilon epsilon x epsilon, in computeVarianceAndCorrespondences the larger cloud as the target (cloud B, the to-scan, on equal
+ * sizes), correspondences that are ALWAYS reciprocal (the `reciprocal` argument is ignored at :343, as written), the >= 3 guard, the rank
+ * size >> 1, variance = 2.1981 x median in fp64, the ratio against max_laser_scans when it is set and against the larger scan otherwise, the
+ * gate ratio <= Icp/CorrespondenceRatio, transform = icpT.inverse() x guess.  pcl::IterativeClosestPoint, its kd-tree, its convergence
+ * criteria and its two estimators are not in the reference tree: the loop, the search's tie rule, the fits and every summation order are the
+ * ENGINE'S, modelled on PCL's defaults and written out here.  No bit parity with a PCL build is claimed.  Stateless exactly as
+ * lcd_estimate_motion_3d; pair i owns the rows [from_offsets[i], from_offsets[i+1]) of from_xyz and out_match, [to_offsets[i],
+ * to_offsets[i+1]) of to_xyz, and guesses[12 i .. 12 i + 11].  For Reg/Strategy = 2 the guess is the out_transform of
+ * lcd_estimate_motion_3d / lcd_estimate_motion_pnp, copied to the host by the caller.
+ *
+ * The rule, per pair.  fp32, every operation rounded on its own (nothing fused), IEEE division and square root, only + - x / sqrt; "fp64"
+ * marks the few places that are double.  SUM's lanes and tree, the rigid fit and inverse(T) are those of lcd_estimate_motion_3d (steps 4 and
+ * 8 there); T(p) and A x B those of lcd_estimate_motion_pnp (its preamble and step 3).
+ *   1. Clouds.  A row takes part iff its three coordinates are finite (the host entry refuses any other row).  The source P_0 is the
+ *      participating from-rows; the target Q is T_guess(to-row) of the participating to-rows (whatever T_guess gives, finite or not).  Row
+ *      indices stay those of the pair's regions; n_f and n_t are the numbers of participating rows.  n_f == 0 or n_t == 0: LCD_ICP_EMPTY.
+ *   2. The nearest neighbour of p in a cloud C.  d2(c) = (dx*dx + dy*dy) + dz*dz with dx = p_x - c_x, dy and dz alike; all three coordinates
+ *      enter, also with force_3dof.  The participating row of C with the smallest d2 wins, the lowest row index on ties (the order of the
+ *      keys bits(d2) << 32 | row); a d2 that is NaN or +inf never wins, so p may have no neighbour.  The neighbour is a CORRESPONDENCE iff
+ *      double(d2) <= thr2, thr2 = max_correspondence_distance * max_correspondence_distance in fp64 (PCL drops distance > max_dist_sqr).
+ *      How an implementation finds the row (brute force, a grid) is not part of the rule; it returns this row, bit for bit.
+ *   3. Iteration k = 0, 1, ..  The correspondences of the current cloud P_k against Q, NOT reciprocal (util3d::icp never sets PCL's flag);
+ *      c = their number.  c < 3: LCD_ICP_NOT_CONVERGED with stop LCD_ICP_STOP_FEW_CORRESPONDENCES, and out_iterations = k.
+ *      mse_k = SUM(d2) / float(c).  SUM over source rows is the 256-lane sum taken over the ROW INDEX: lane l starts at +0.0f and walks
+ *      the rows l, l + 256, .. of the pair's from-region in ascending order; a row without a correspondence (or that takes no part) adds
+ *      nothing -- it is skipped, not added as zero; then the halving tree.  No compaction is part of the rule.
+ *   4. The fit T_k of the correspondences (p_i, q_j(i)), q from Q.  cp_a = SUM(p_a) / float(c), cq_a = SUM(q_a) / float(c),
+ *      S_ab = SUM((p_a - cp_a) * (q_b - cq_b)) with this SUM.
+ *      3-D: Horn's quaternion by LCD_M3D_SWEEPS Jacobi sweeps and t_r, exactly step 4 of lcd_estimate_motion_3d from cp, cq and S on.
+ *      2-D (force_3dof): A = Sxx + Syy, B = Sxy - Syx, n = sqrt(A*A + B*B); if n is 0 or not finite c = 1, s = 0, else c = A / n, s = B / n.
+ *      T_k = [[c, -s, 0, cq_x - (c*cp_x - s*cp_y)], [s, c, 0, cq_y - (s*cp_x + c*cp_y)], [0, 0, 1, 0]] (PCL's 2-D estimator without the
+ *      arc tangent; -s is the negation of s, no rounding).
+ *   5. Update.  P_{k+1} = T_k(P_k), every participating row, incrementally as PCL does.  F <- T_k x F (A x B with A = T_k: each entry
+ *      ((A_r0 B_0c + A_r1 B_1c) + A_r2 B_2c), + A_r3 in the last column), F starting as the identity.  iterations = k + 1.
+ *   6. Stop, tested in this order, each of them meaning converged: iterations >= max_iterations: LCD_ICP_STOP_ITERATIONS;
+ *      0.5f * (((R00 + R11) + R22) - 1.0f) >= 1.0f - eps2 and (t_x*t_x + t_y*t_y) + t_z*t_z <= eps2, R and t of T_k, eps2 = epsilon * epsilon
+ *      in fp32: LCD_ICP_STOP_TRANSFORM; |mse_k - mse_{k-1}| < 1e-12f with mse_{-1} = FLT_MAX: LCD_ICP_STOP_MSE.  Otherwise k + 1 follows.
+ *   7. The registered cloud A = F(P_0) -- not P_k: PCL transforms the input by the final transformation.
+ *   8. Variance and correspondences (:327-360) over A and B = Q.  The target is the one with more participating rows, B on equal numbers;
+ *      the other is the source.  For each source row i, its nearest target row j (step 2) that is a correspondence is kept iff the nearest
+ *      row of target row j in the source (step 2, no threshold) is i.  out_n_correspondences = the number kept.  out_match is written on the
+ *      FROM-rows whichever cloud played the source: the to-row kept with that from-row, or -1.  With >= 3 kept out_variance =
+ *      2.1981 * double(the d2 of rank (number >> 1) ascending among the kept, d2 the source row's), fp64 and undivided; otherwise 1.0.
+ *   9. Ratio and result.  out_ratio = float(number) / float(max_laser_scans) when max_laser_scans > 0, otherwise / float(max(n_f, n_t)).
+ *      X = inverse(F) x guess; out_correction = inverse(guess) x X; out_icp_transform = F.  out_ratio <= correspondence_ratio:
+ *      LCD_ICP_BELOW_RATIO and out_transform = twelve zeros; otherwise out_transform = X and LCD_ICP_OK.
+ *  10. Twelve zero floats mean no transform; then out_status != LCD_ICP_OK.  With LCD_ICP_EMPTY and LCD_ICP_NOT_CONVERGED out_icp_transform
+ *      and out_correction are twelve zeros too, out_n_correspondences = 0, out_ratio = 0, out_variance = 1.0, out_match = -1 everywhere;
+ *      out_stop is LCD_ICP_STOP_NONE with LCD_ICP_EMPTY.  out_icp_transform, out_correction, the counts and the variance are returned whenever
+ *      the loop converged.
+ * The remaining steps of :856-928 take out_correction and out_variance and are the HOST mirror's (host/RegistrationIcp.cpp), as the arc cosine
+ * of lcd_estimate_motion_pnp is: the Icp/MaxTranslation / Icp/MaxRotation gate (Euler angles: an arc tangent), variance /= 10, and the
+ * covariance (eye x variance, the rotation block / 10).
+ * Out of scope: point-to-plane (Icp/PointToPlane, normals, the low-complexity fallback), libpointmatcher and CCCoreLib (Icp/Strategy 1, 2),
+ * Icp/Force4DoF, the scan filters in front (Icp/VoxelSize, DownsamplingStep, RangeMin / RangeMax), intensity, scans above 8192 points, sharded
+ * handles, and on the device the Euler-angle gate and the covariance.
+ *
+ * search: how step 2 is carried out, never what the call returns.  LCD_ICP_SEARCH_BRUTE walks the whole target for every row.
+ * LCD_ICP_SEARCH_GRID sorts the target once by cell (and the registered source for step 8) and looks at the 27 cells around a row; the cell is
+ * float(max_correspondence_distance) * 1.0625, a coordinate's cell floor(x / cell).  Every output is the same bit for bit: only
+ * correspondences (d2 <= thr2) and the reciprocal test reach an output, and no pair within the threshold sits more than one cell apart
+ * (rtabmap_amd/csrc/icp_rule.h has the argument).  A target with a coordinate beyond +-65 535 cells is searched in the brute form inside the
+ * same call, and so is a single row beyond that range.  LCD_ICP_SEARCH_AUTO takes the grid form for a target of 1 024 participating rows
+ * or more, the measured size at which it overtakes the brute form on a single pair.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on a side of a pair,
+ * n_pairs > 65535 or a handle of a sharded vocabulary: LCD_ERR_UNSUPPORTED; max_iterations < 1, max_laser_scans < 0, a
+ * search that is no lcd_icp_search, a max_correspondence_distance that is not finite or <= 0 or whose square is not finite, an epsilon that
+ * is negative or not finite, a correspondence_ratio outside [0, 1], n_pairs < 0, offsets that are missing, do not start at 0 or decrease,
+ * NULL guesses or a guess entry that is not finite, a NULL pointer where rows or outputs exist, a wrong struct_size, and on the HOST entry a
+ * row with a coordinate that is not finite (the reference demands finite clouds): LCD_ERR_INVALID.  On the device entry such a row takes part
+ * in nothing and counts towards no size.  n_pairs == 0 returns LCD_OK.  One kernel launch per call whatever the batch: one workgroup of 256
+ * threads per pair. */
+enum lcd_icp_status {
+    LCD_ICP_OK = 0,
+    LCD_ICP_EMPTY = 1,                /* a side has no participating row */
+    LCD_ICP_NOT_CONVERGED = 2,        /* fewer than 3 correspondences in an iteration */
+    LCD_ICP_BELOW_RATIO = 3           /* everything returned but the transform */
+};
+enum lcd_icp_stop {
+    LCD_ICP_STOP_NONE = 0,
+    LCD_ICP_STOP_ITERATIONS = 1,
+    LCD_ICP_STOP_TRANSFORM = 2,
+    LCD_ICP_STOP_MSE = 3,
+    LCD_ICP_STOP_FEW_CORRESPONDENCES = 4
+};
+enum lcd_icp_search {
+    LCD_ICP_SEARCH_AUTO = 0,
+    LCD_ICP_SEARCH_BRUTE = 1,
+    LCD_ICP_SEARCH_GRID = 2
+};
+typedef struct lcd_icp_args {
+    int32_t struct_size;            /* sizeof(lcd_icp_args) */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t max_iterations;         /* Icp/Iterations, >= 1 */
+    int32_t force_3dof;             /* Reg/Force3DoF: != 0 selects the 2-D estimator */
+    int32_t max_laser_scans;        /* the scan's maximum number of points; 0 = the ratio is relative to the larger scan */
+    int32_t search;                 /* lcd_icp_search */
+    double max_correspondence_distance; /* Icp/MaxCorrespondenceDistance, finite, > 0 */
+    float epsilon;                  /* Icp/Epsilon, >= 0 */
+    float correspondence_ratio;     /* Icp/CorrespondenceRatio, 0 .. 1 */
+    const float* from_xyz;          /* [Nf x 3], in the from-scan's base frame; a 2-D scan has z = 0 */
+    const float* to_xyz;            /* [Nt x 3], in the to-scan's base frame */
+    const int64_t* from_offsets;    /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    const int64_t* to_offsets;      /* HOST, [n_pairs + 1] */
+    const float* guesses;           /* HOST, [n_pairs x 12], row-major 3 x 4, finite */
+    float* out_transform;           /* [n_pairs x 12] */
+    float* out_icp_transform;       /* [n_pairs x 12]: F, source onto target */
+    float* out_correction;          /* [n_pairs x 12]: guess^-1 x F^-1 x guess */
+    int32_t* out_status;            /* [n_pairs], lcd_icp_status */
+    int32_t* out_stop;              /* [n_pairs], lcd_icp_stop */
+    int32_t* out_iterations;        /* [n_pairs] */
+    int32_t* out_n_correspondences; /* [n_pairs] */
+    float* out_ratio;               /* [n_pairs] */
+    double* out_variance;           /* [n_pairs], undivided */
+    int32_t* out_match;             /* [Nf] */
+} lcd_icp_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_register_icp(lcd_engine* h, const lcd_icp_args* a);
+/* points and out_* in DEVICE memory (4-byte aligned, out_variance 8-byte), offsets and guesses on the HOST (read during the call); enqueued on
+ * the engine stream, not synchronised */
+int lcd_register_icp_dev(lcd_engine* h, const lcd_icp_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -144,6 +144,20 @@ class LcdMotion3dArgs(C.Structure):
                 ("out_n_inliers", C.c_void_p), ("out_variance", C.c_void_p), ("out_matches", C.c_void_p), ("out_inliers", C.c_void_p)]
 
 
+class LcdIcpArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("max_iterations", C.c_int32), ("force_3dof", C.c_int32),
+                ("max_laser_scans", C.c_int32), ("search", C.c_int32), ("max_correspondence_distance", C.c_double), ("epsilon", C.c_float),
+                ("correspondence_ratio", C.c_float), ("from_xyz", C.c_void_p), ("to_xyz", C.c_void_p), ("from_offsets", C.c_void_p),
+                ("to_offsets", C.c_void_p), ("guesses", C.c_void_p), ("out_transform", C.c_void_p), ("out_icp_transform", C.c_void_p),
+                ("out_correction", C.c_void_p), ("out_status", C.c_void_p), ("out_stop", C.c_void_p), ("out_iterations", C.c_void_p),
+                ("out_n_correspondences", C.c_void_p), ("out_ratio", C.c_void_p), ("out_variance", C.c_void_p), ("out_match", C.c_void_p)]
+
+
+LCD_ICP_OK, LCD_ICP_EMPTY, LCD_ICP_NOT_CONVERGED, LCD_ICP_BELOW_RATIO = 0, 1, 2, 3  # lcd_icp_status
+LCD_ICP_STOP_NONE, LCD_ICP_STOP_ITERATIONS, LCD_ICP_STOP_TRANSFORM, LCD_ICP_STOP_MSE, LCD_ICP_STOP_FEW_CORRESPONDENCES = 0, 1, 2, 3, 4  # lcd_icp_stop
+LCD_ICP_SEARCH_AUTO, LCD_ICP_SEARCH_BRUTE, LCD_ICP_SEARCH_GRID = 0, 1, 2  # lcd_icp_search
+
+
 LCD_M3D_OK, LCD_M3D_FEW_CORRESPONDENCES, LCD_M3D_NO_MODEL, LCD_M3D_FEW_INLIERS, LCD_M3D_BELOW_MIN_INLIERS = 0, 1, 2, 3, 4  # lcd_motion_3d_status
 
 
@@ -243,6 +257,8 @@ def load():
     L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_pnp.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
     L.lcd_estimate_motion_pnp_dev.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
+    L.lcd_register_icp.argtypes = [vp, C.POINTER(LcdIcpArgs)]
+    L.lcd_register_icp_dev.argtypes = [vp, C.POINTER(LcdIcpArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -801,6 +817,51 @@ class Engine:
         a.out_variance_lin, a.out_angle_cos, a.out_variance_kind = ptr(d_variance_lin), ptr(d_angle_cos), ptr(d_variance_kind)
         a.out_matches, a.out_inliers = ptr(d_matches), ptr(d_inliers)
         self._ck(self.L.lcd_estimate_motion_pnp_dev(self.h, C.byref(a)))
+
+    # ---- scan registration, point-to-point ICP (stateless; include/lcd.h has the rule)
+    @staticmethod
+    def _icp_args(n_pairs, max_iterations, force_3dof, max_laser_scans, search, max_correspondence_distance, epsilon, correspondence_ratio, struct_size):
+        return LcdIcpArgs(C.sizeof(LcdIcpArgs) if struct_size is None else struct_size, n_pairs, int(max_iterations), int(bool(force_3dof)),
+                          int(max_laser_scans), int(search), float(max_correspondence_distance), float(epsilon), float(correspondence_ratio))
+
+    def register_icp(self, from_xyz, from_offsets, to_xyz, to_offsets, guesses, max_iterations=30, force_3dof=False, max_laser_scans=0,
+                     search=LCD_ICP_SEARCH_AUTO, max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1, struct_size=None):
+        """lcd_register_icp over host arrays, all pairs concatenated -> dict(transform, icp_transform, correction [n_pairs x 12], status, stop,
+        iterations, n_correspondences, ratio, variance [n_pairs], match [Nf]); outputs start as -7 / NaN so that what the call left alone shows"""
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fx, tx = np.ascontiguousarray(from_xyz, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        n_pairs, n = fo.shape[0] - 1, fx.shape[0]
+        m = max(n_pairs, 1)
+        out = dict(transform=np.full((m, 12), np.nan, np.float32), icp_transform=np.full((m, 12), np.nan, np.float32),
+                   correction=np.full((m, 12), np.nan, np.float32), status=np.full(m, -7, np.int32), stop=np.full(m, -7, np.int32),
+                   iterations=np.full(m, -7, np.int32), n_correspondences=np.full(m, -7, np.int32), ratio=np.full(m, np.nan, np.float32),
+                   variance=np.full(m, np.nan, np.float64), match=np.full(max(n, 1), -7, np.int32))
+        a = self._icp_args(n_pairs, max_iterations, force_3dof, max_laser_scans, search, max_correspondence_distance, epsilon, correspondence_ratio, struct_size)
+        a.from_xyz, a.to_xyz, a.from_offsets, a.to_offsets, a.guesses = _p(fx), _p(tx), fo.ctypes.data, to.ctypes.data, None if gs is None else _p(gs)
+        a.out_transform, a.out_icp_transform, a.out_correction = _p(out["transform"]), _p(out["icp_transform"]), _p(out["correction"])
+        a.out_status, a.out_stop, a.out_iterations, a.out_n_correspondences = _p(out["status"]), _p(out["stop"]), _p(out["iterations"]), _p(out["n_correspondences"])
+        a.out_ratio, a.out_variance, a.out_match = _p(out["ratio"]), _p(out["variance"]), _p(out["match"])
+        self._ck(self.L.lcd_register_icp(self.h, C.byref(a)))
+        for k in out:
+            out[k] = out[k][:n] if k == "match" else out[k][:max(n_pairs, 0)]
+        return out
+
+    def register_icp_dev(self, d_from_xyz, from_offsets, d_to_xyz, to_offsets, guesses, d_transform, d_icp_transform, d_correction, d_status, d_stop,
+                         d_iterations, d_n_correspondences, d_ratio, d_variance, d_match, max_iterations=30, force_3dof=False, max_laser_scans=0,
+                         search=LCD_ICP_SEARCH_AUTO, max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1):
+        """lcd_register_icp_dev on torch tensors of the engine's device (offsets and guesses stay on the host).  Enqueued, not synchronised."""
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        a = self._icp_args(fo.shape[0] - 1, max_iterations, force_3dof, max_laser_scans, search, max_correspondence_distance, epsilon, correspondence_ratio, None)
+        a.from_xyz, a.to_xyz, a.from_offsets, a.to_offsets, a.guesses = ptr(d_from_xyz), ptr(d_to_xyz), fo.ctypes.data, to.ctypes.data, None if gs is None else _p(gs)
+        a.out_transform, a.out_icp_transform, a.out_correction = ptr(d_transform), ptr(d_icp_transform), ptr(d_correction)
+        a.out_status, a.out_stop, a.out_iterations, a.out_n_correspondences = ptr(d_status), ptr(d_stop), ptr(d_iterations), ptr(d_n_correspondences)
+        a.out_ratio, a.out_variance, a.out_match = ptr(d_ratio), ptr(d_variance), ptr(d_match)
+        self._ck(self.L.lcd_register_icp_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

@@ -11,6 +11,7 @@ namespace pnp {
 
 using m3d::apply;
 using m3d::bits_of;
+using m3d::compose;
 using m3d::finite;
 using m3d::float_of;
 using m3d::invert;
@@ -27,20 +28,6 @@ struct Camera {
     float fx, fy, cx, cy;
     int32_t width, height;
 };
-
-// a x b for two rigid 3 x 4
-M3D_FN void compose(const float a[12], const float b[12], float out[12]) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float p0 = a[4 * r] * b[c], p1 = a[4 * r + 1] * b[4 + c], p2 = a[4 * r + 2] * b[8 + c];
-            const float p01 = p0 + p1;
-            const float p012 = p01 + p2;
-            out[4 * r + c] = c == 3 ? p012 + a[4 * r + 3] : p012;
-        }
-    }
-}
 
 // the model a guess enters as (util3d_motion_estimation.cpp:121): (guess x local).inverse()
 M3D_FN void model_of_guess(const float guess[12], bool has_local, const float local[12], float model[12]) {

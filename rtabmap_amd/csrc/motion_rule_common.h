@@ -1,7 +1,7 @@
-// motion_rule_common.h -- what the rules of lcd_estimate_motion_3d (motion_3d_rule.h) and lcd_estimate_motion_pnp (motion_pnp_rule.h) share:
-// the bit helpers, the id keys, the counter-based mix, the three-element sum in the order of the 256-lane sum, and the rigid fit (Horn's
-// quaternion by cyclic Jacobi).  fp32, one rounded operation per statement, never contracted; division and square root are IEEE.  Compiled for
-// the kernels and for the host mirrors alike.  Internal.
+// motion_rule_common.h -- what the rules of lcd_estimate_motion_3d (motion_3d_rule.h), lcd_estimate_motion_pnp (motion_pnp_rule.h) and
+// lcd_register_icp (icp_rule.h) share: the bit helpers, the id keys, the counter-based mix, the three-element sum in the order of the 256-lane
+// sum, the rigid fit (Horn's quaternion by cyclic Jacobi), and a rigid model applied, inverted and composed.  fp32, one rounded operation
+// per statement, never contracted; division and square root are IEEE.  Compiled for the kernels and for the host mirrors alike.  Internal.
 #pragma once
 #include <stdint.h>
 #include <cmath>
@@ -201,6 +201,20 @@ M3D_FN void invert(const float m[12], float out[12]) {
         const float abc = ab + c;
         out[4 * r] = m[r]; out[4 * r + 1] = m[4 + r]; out[4 * r + 2] = m[8 + r];
         out[4 * r + 3] = -abc;
+    }
+}
+
+// a x b for two rigid 3 x 4
+M3D_FN void compose(const float a[12], const float b[12], float out[12]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float p0 = a[4 * r] * b[c], p1 = a[4 * r + 1] * b[4 + c], p2 = a[4 * r + 2] * b[8 + c];
+            const float p01 = p0 + p1;
+            const float p012 = p01 + p2;
+            out[4 * r + c] = c == 3 ? p012 + a[4 * r + 3] : p012;
+        }
     }
 }
 

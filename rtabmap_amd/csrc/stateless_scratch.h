@@ -11,7 +11,7 @@
 // Scratch of the calls that do not complete what a pipelined handle owes, with their _dev forms:
 //   lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip),
 //   lcd_select_features and lcd_expand_word_ids (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip),
-//   lcd_estimate_motion_3d (motion_3d.hip) and lcd_estimate_motion_pnp (motion_pnp.hip).
+//   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip) and lcd_register_icp (register_icp.hip).
 // Everything they write on the device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The
 // buffers only grow, and a growth frees the old allocation after the engine stream has drained (DevBuf::reserve): work of an earlier call
 // that is still enqueued keeps what it reads.  The protocol is the methods' and HostStage's; the callers own only d_dist and d_small.
@@ -21,6 +21,7 @@ struct StatelessScratch {
     //   the matching calls: per pair the to-rows' 2-NN among the from-words, word ranks, candidate bit rows / the cross-check keys
     //   lcd_estimate_motion_3d: 36 bytes per from-row (six coordinate planes, d2, two index sets)
     //   lcd_estimate_motion_pnp: 44 bytes per to-row (eight coordinate planes, errors, two index sets)
+    //   lcd_register_icp: 20 bytes per row of either side (three coordinate planes, the nearest row, its d2)
     lcd::DevBuf d_small;
     int64_t budget_bytes = 0;                           // lcd_set_option("pair_match_budget"): distance-block bytes per group (0: built-in, 256 MiB)
 

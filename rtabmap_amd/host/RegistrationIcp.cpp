@@ -1,0 +1,250 @@
+// RegistrationIcp.cpp -- see RegistrationIcp.h.
+#include "RegistrationIcp.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+
+#include "../../include/lcd.h"
+#include "../csrc/icp_rule.h"
+
+namespace rtabmap_amd {
+
+namespace {
+
+namespace rule = lcd::icp;
+
+// SUM over the rows 0 .. n - 1 that has(i) holds for: lane (i mod LANES) adds e(i) in ascending order from +0, a row without is skipped; then
+// the halving tree
+template <class H, class F>
+float laneTreeSumIf(int n, H has, F e) {
+    constexpr int LANES = lcd::m3d::LANES;
+    float part[LANES];
+    for (int l = 0; l < LANES; ++l) part[l] = 0.0f;
+    for (int i = 0; i < n; ++i)
+        if (has(i)) part[i % LANES] = part[i % LANES] + e(i);
+    for (int s = LANES / 2; s >= 1; s >>= 1)
+        for (int l = 0; l < s; ++l) part[l] = part[l] + part[l + s];
+    return part[0];
+}
+
+struct Cloud {
+    std::vector<float> xyz;                  // [n x 3]
+    std::vector<char> part;                  // the rows that take part
+    std::vector<int> nn;                     // the last search's nearest row in the other cloud, -1: none
+    std::vector<float> d2;
+    int n() const { return (int)part.size(); }
+    const float* row(int i) const { return &xyz[(size_t)3 * i]; }
+};
+
+// step 2 for every row of q in c: brute force in the words of the rule, or -- where rule::wants_grid says so and every participating row of c
+// fits the key's cell range -- over c's sorted cell keys, a row of q outside the range walking the whole cloud
+void search(Cloud& q, const Cloud& c, int mode, float h) {
+    const int rows = (int)std::count(c.part.begin(), c.part.end(), (char)1);
+    bool grid = rule::wants_grid(mode, rows);
+    std::vector<uint64_t> keys;
+    for (int j = 0; grid && j < c.n(); ++j) {
+        if (!c.part[(size_t)j]) continue;
+        uint64_t k = 0;
+        grid = rule::key_of(c.row(j)[0], c.row(j)[1], c.row(j)[2], h, (uint64_t)j, k);
+        keys.push_back(k);
+    }
+    std::sort(keys.begin(), keys.end());
+    for (int i = 0; i < q.n(); ++i) {
+        float best = std::numeric_limits<float>::infinity();
+        int row = -1;
+        if (q.part[(size_t)i]) {
+            const float* p = q.row(i);
+            const bool found = grid && rule::grid_nearest([&](int a) { return keys[(size_t)a]; }, (int)keys.size(),
+                                                          [&](int r, float& x, float& y, float& z) { x = c.row(r)[0]; y = c.row(r)[1]; z = c.row(r)[2]; },
+                                                          p[0], p[1], p[2], h, best, row);
+            for (int j = 0; !found && j < c.n(); ++j) {
+                if (!c.part[(size_t)j]) continue;
+                const float* t = c.row(j);
+                const float d = rule::dist2(p[0], p[1], p[2], t[0], t[1], t[2]);
+                if (rule::nearer(d, j, best, row)) { best = d; row = j; }
+            }
+        }
+        q.nn[(size_t)i] = row; q.d2[(size_t)i] = best;
+    }
+}
+
+// the backend of rule::solve as a loop
+struct CpuBackend {
+    Cloud from, to;                          // the source's current cloud, Q
+    const float* raw_from;
+    double thr2;
+    int mode;                                // lcd_icp_search
+    float h;                                 // the grid's cell
+    std::vector<int> match;
+    std::vector<uint32_t> keys;
+
+    int count(const Cloud& c) const { return (int)std::count(c.part.begin(), c.part.end(), (char)1); }
+    int n_from() const { return count(from); }
+    int n_to() const { return count(to); }
+    bool has(int i) const { return from.part[(size_t)i] && rule::corresponds(from.nn[(size_t)i], from.d2[(size_t)i], thr2); }
+    int correspond(float& sum_d2) {
+        search(from, to, mode, h);
+        int c = 0;
+        for (int i = 0; i < from.n(); ++i) c += has(i) ? 1 : 0;
+        sum_d2 = laneTreeSumIf(from.n(), [&](int i) { return has(i); }, [&](int i) { return from.d2[(size_t)i]; });
+        return c;
+    }
+    void fit(int c, bool flat, float T[12]) {
+        const int n = from.n();
+        auto h = [&](int i) { return has(i); };
+        float cp[3], cq[3], S[9];
+        for (int a = 0; a < 3; ++a) {
+            const float sp = laneTreeSumIf(n, h, [&](int i) { return from.row(i)[a]; });
+            const float sq = laneTreeSumIf(n, h, [&](int i) { return to.row(from.nn[(size_t)i])[a]; });
+            cp[a] = sp / (float)c;
+            cq[a] = sq / (float)c;
+        }
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b)
+                S[3 * a + b] = laneTreeSumIf(n, h, [&](int i) {
+                    const float dp = from.row(i)[a] - cp[a], dq = to.row(from.nn[(size_t)i])[b] - cq[b];
+                    return dp * dq;
+                });
+        rule::fit(cp, cq, S, flat, T);
+    }
+    void move(const float T[12], const float* src) {
+        for (int i = 0; i < from.n(); ++i) {
+            if (!from.part[(size_t)i]) continue;
+            float x, y, z;
+            rule::apply(T, src[(size_t)3 * i], src[(size_t)3 * i + 1], src[(size_t)3 * i + 2], x, y, z);
+            from.xyz[(size_t)3 * i] = x; from.xyz[(size_t)3 * i + 1] = y; from.xyz[(size_t)3 * i + 2] = z;
+        }
+    }
+    void advance(const float T[12]) { move(T, from.xyz.data()); }
+    void set_registered(const float F[12]) { move(F, raw_from); }
+    int reciprocal(bool from_is_target) {
+        search(from, to, mode, h);
+        search(to, from, mode, h);
+        Cloud& src = from_is_target ? to : from;
+        const Cloud& tgt = from_is_target ? from : to;
+        keys.clear();
+        for (int i = 0; i < src.n(); ++i) {
+            const int row = src.nn[(size_t)i];
+            if (!rule::corresponds(row, src.d2[(size_t)i], thr2) || tgt.nn[(size_t)row] != i) continue;
+            keys.push_back(lcd::m3d::bits_of(src.d2[(size_t)i]));                  // non-negative: they order as integers
+            if (from_is_target) match[(size_t)row] = i;
+            else match[(size_t)i] = row;
+        }
+        return (int)keys.size();
+    }
+    float median(int n) {
+        std::nth_element(keys.begin(), keys.begin() + (n >> 1), keys.end());
+        return lcd::m3d::float_of(keys[(size_t)(n >> 1)]);
+    }
+};
+
+void fill(Cloud& c, const float* xyz, int n) {
+    c.xyz.assign(xyz, xyz + (size_t)3 * n);
+    c.part.resize((size_t)n); c.nn.assign((size_t)n, -1); c.d2.assign((size_t)n, 0.0f);
+    for (int i = 0; i < n; ++i) c.part[(size_t)i] = rule::takes_part(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]) ? 1 : 0;
+}
+
+}  // namespace
+
+float icp_cells(const float* x, int n, double maxCorrespondenceDistance, int* outCells) {
+    const float h = rule::cell_size(maxCorrespondenceDistance);
+    for (int i = 0; i < n; ++i)
+        if (!rule::cell_of(x[i], h, outCells[i])) outCells[i] = std::numeric_limits<int>::min();
+    return h;
+}
+
+bool register_icp_cpu(const float* fromXyz, int nFrom, const float* toXyz, int nTo, const float guess[12], int maxIterations, bool force3DoF,
+                      int maxLaserScans, double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, int search, bool deviceEntry,
+                      IcpResult& out) {
+    const double thr2 = maxCorrespondenceDistance * maxCorrespondenceDistance;
+    if (nFrom < 0 || nTo < 0 || nFrom > lcd::m3d::MAX_ROWS || nTo > lcd::m3d::MAX_ROWS || maxIterations < 1 || maxLaserScans < 0 ||
+        (search != rule::SEARCH_AUTO && search != rule::SEARCH_BRUTE && search != rule::SEARCH_GRID) || !std::isfinite(maxCorrespondenceDistance) || !(maxCorrespondenceDistance > 0.0) ||
+        !std::isfinite(thr2) || !std::isfinite(epsilon) || !(epsilon >= 0.0f) || !(correspondenceRatio >= 0.0f) || !(correspondenceRatio <= 1.0f) || !guess)
+        return false;
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(guess[k])) return false;
+    if ((nFrom > 0 && !fromXyz) || (nTo > 0 && !toXyz)) return false;
+    CpuBackend b;
+    fill(b.from, fromXyz, nFrom);
+    fill(b.to, toXyz, nTo);
+    if (!deviceEntry && (b.n_from() != nFrom || b.n_to() != nTo)) return false;
+    for (int j = 0; j < nTo; ++j)
+        rule::apply(guess, toXyz[3 * j], toXyz[3 * j + 1], toXyz[3 * j + 2], b.to.xyz[(size_t)3 * j], b.to.xyz[(size_t)3 * j + 1], b.to.xyz[(size_t)3 * j + 2]);
+    b.raw_from = fromXyz; b.thr2 = thr2; b.mode = search; b.h = rule::cell_size(maxCorrespondenceDistance);
+    b.match.assign((size_t)nFrom, -1);
+    rule::Result res;
+    rule::solve(b, maxIterations, force3DoF, maxLaserScans, epsilon, correspondenceRatio, guess, res);
+    IcpResult r;
+    for (int k = 0; k < 12; ++k) { r.transform[k] = res.transform[k]; r.icpTransform[k] = res.icp[k]; r.correction[k] = res.correction[k]; }
+    r.status = res.status; r.stop = res.stop; r.iterations = res.iterations; r.correspondences = res.n_correspondences;
+    r.ratio = res.ratio; r.variance = res.variance;
+    r.match = b.match;
+    out = r;
+    return true;
+}
+
+Transform3D RegistrationIcpHip::finish(const IcpResult& r, RegistrationInfoIcp& info) const {
+    Transform3D transform;
+    char msg[256];
+    if (r.status != LCD_ICP_OK && r.status != LCD_ICP_BELOW_RATIO) {   // :962: icpT is null or the loop did not converge
+        snprintf(msg, sizeof msg, "Cannot compute transform (converged=false var=%f)", r.variance);
+        info.rejectedMsg = msg;
+        return transform;
+    }
+    // :858-862: pcl::getTranslationAndEulerAngles over the correction in the target's referential
+    const float* c = r.correction;
+    const float roll = std::atan2(c[9], c[10]), pitch = std::asin(-c[8]), yaw = std::atan2(c[4], c[0]);
+    info.icpTranslation = std::max(std::fabs(c[3]), std::max(std::fabs(c[7]), std::fabs(c[11])));
+    info.icpRotation = std::max(std::fabs(roll), std::max(std::fabs(pitch), std::fabs(yaw)));
+    if ((maxTranslation > 0.0f && info.icpTranslation > maxTranslation) || (maxRotation > 0.0f && info.icpRotation > maxRotation)) {
+        snprintf(msg, sizeof msg, "Cannot compute transform (ICP correction too large -> %f m %f rad, limits=%f m, %f rad)", info.icpTranslation,
+                 info.icpRotation, maxTranslation, maxRotation);
+        info.rejectedMsg = msg;
+        return transform;
+    }
+    const double variance = r.variance / 10.0;                         // :898
+    if (r.correspondences != 0) {                                      // :917-918
+        for (int k = 0; k < 36; ++k) info.covariance[k] = 0.0;
+        for (int k = 0; k < 3; ++k) { info.covariance[7 * k] = variance; info.covariance[7 * (k + 3)] = variance / 10.0; }
+    }
+    info.icpInliersRatio = r.ratio;
+    info.icpCorrespondences = r.correspondences;
+    if (r.status == LCD_ICP_BELOW_RATIO) {                             // :930
+        snprintf(msg, sizeof msg, "Cannot compute transform (cor=%d corrRatio=%f/%f)", r.correspondences, r.ratio, correspondenceRatio);
+        info.rejectedMsg = msg;
+        return transform;
+    }
+    for (int k = 0; k < 12; ++k) transform.data[k] = r.transform[k];
+    return transform;
+}
+
+Transform3D RegistrationIcpHip::computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, const std::vector<Point3f>& toScan,
+                                                      const Transform3D& guess, int maxLaserScans, RegistrationInfoIcp& info) const {
+    info = RegistrationInfoIcp();
+    if (fromScan.empty() || toScan.empty()) {                          // :972
+        info.rejectedMsg = "Laser scans empty ?!?";
+        return Transform3D();
+    }
+    static_assert(sizeof(Point3f) == 12, "a scan is handed over as [n x 3] floats");
+    const int64_t fromOffsets[2] = {0, (int64_t)fromScan.size()}, toOffsets[2] = {0, (int64_t)toScan.size()};
+    IcpResult r;
+    r.match.assign(fromScan.size(), -1);
+    int32_t status = 0, stop = 0, iterations = 0, correspondences = 0;
+    lcd_icp_args a;
+    a.struct_size = (int32_t)sizeof a; a.n_pairs = 1; a.max_iterations = maxIterations; a.force_3dof = force3DoF ? 1 : 0;
+    a.max_laser_scans = maxLaserScans; a.search = LCD_ICP_SEARCH_AUTO;
+    a.max_correspondence_distance = maxCorrespondenceDistance; a.epsilon = epsilon; a.correspondence_ratio = correspondenceRatio;
+    a.from_xyz = &fromScan[0].x; a.to_xyz = &toScan[0].x; a.from_offsets = fromOffsets; a.to_offsets = toOffsets; a.guesses = guess.data;
+    a.out_transform = r.transform; a.out_icp_transform = r.icpTransform; a.out_correction = r.correction;
+    a.out_status = &status; a.out_stop = &stop; a.out_iterations = &iterations; a.out_n_correspondences = &correspondences;
+    a.out_ratio = &r.ratio; a.out_variance = &r.variance; a.out_match = r.match.data();
+    if (!engine || lcd_register_icp(engine, &a) != LCD_OK) {
+        info.rejectedMsg = "the engine refused the call";
+        return Transform3D();
+    }
+    r.status = status; r.stop = stop; r.iterations = iterations; r.correspondences = correspondences;
+    return finish(r, info);
+}
+
+}  // namespace rtabmap_amd

@@ -1,0 +1,65 @@
+// RegistrationIcp.h -- RegistrationIcp::computeTransformationImpl, the point-to-point branch with Icp/Strategy = 0 (RegistrationIcp.cpp:662-971),
+// over the project's minimal types: the entry that hands the work to the engine (lcd_register_icp) and applies what the rule leaves to the
+// host (the Icp/MaxTranslation / Icp/MaxRotation gate over Euler angles, variance /= 10, the covariance), and register_icp_cpu, the whole rule
+// of include/lcd.h as plain host code for a process without a device.  The arithmetic is the engine's own (csrc/icp_rule.h, compiled here for
+// the host), so a pair gets the same bits with and without a device.  tools/sanitize_register_icp.cpp drives register_icp_cpu under the host
+// sanitizers.
+#pragma once
+#include <stdint.h>
+#include <string>
+#include <vector>
+
+#include "Motion3D.h"
+
+struct lcd_engine;
+
+namespace rtabmap_amd {
+
+struct IcpResult {
+    float transform[12];                 // twelve zeros: no transform
+    float icpTransform[12];              // F: source onto target
+    float correction[12];                // guess^-1 x F^-1 x guess
+    int status, stop, iterations;        // lcd_icp_status, lcd_icp_stop
+    int correspondences;
+    float ratio;
+    double variance;                     // undivided
+    std::vector<int> match;              // per from-row: the to-row it is kept with, or -1
+};
+
+// The rule on the CPU: one pair of scans as [n x 3] rows.  false (out untouched): what the entry refuses -- deviceEntry chooses whose
+// refusals: lcd_register_icp's (a row that is not finite is refused) or lcd_register_icp_dev's (such a row takes no part).
+bool register_icp_cpu(const float* fromXyz, int nFrom, const float* toXyz, int nTo, const float guess[12], int maxIterations, bool force3DoF,
+                      int maxLaserScans, double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, int search, bool deviceEntry,
+                      IcpResult& out);
+
+// The grid form's cell of each of n coordinates under a correspondence distance, INT_MIN where a coordinate does not fit the key's cell range;
+// returns the cell size.  What the tests prove the one-cell margin of the grid with.
+float icp_cells(const float* x, int n, double maxCorrespondenceDistance, int* outCells);
+
+struct RegistrationInfoIcp {             // the fields of RegistrationInfo that the ICP step fills
+    float icpTranslation = 0.0f, icpRotation = 0.0f, icpInliersRatio = 0.0f;
+    int icpCorrespondences = 0;
+    double covariance[36];               // row-major 6 x 6; the identity until a variance is known
+    std::string rejectedMsg;
+    RegistrationInfoIcp() { for (int k = 0; k < 36; ++k) covariance[k] = k % 7 == 0 ? 1.0 : 0.0; }
+};
+
+class RegistrationIcpHip {
+public:
+    int maxIterations = 30;                      // Icp/Iterations
+    float maxTranslation = 0.2f;                 // Icp/MaxTranslation, 0 = off
+    float maxRotation = 0.78f;                   // Icp/MaxRotation, 0 = off
+    double maxCorrespondenceDistance = 0.1;      // Icp/MaxCorrespondenceDistance
+    float epsilon = 0.0f;                        // Icp/Epsilon
+    float correspondenceRatio = 0.1f;            // Icp/CorrespondenceRatio
+    bool force3DoF = false;                      // Reg/Force3DoF
+
+    // The reference's shape: both scans as point rows in their base frames, the guess, the scan's maximum number of points (0: the ratio is
+    // relative).  A null transform when the registration is rejected (info.rejectedMsg says why) or the engine refuses the call.
+    Transform3D computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, const std::vector<Point3f>& toScan, const Transform3D& guess,
+                                      int maxLaserScans, RegistrationInfoIcp& info) const;
+    // RegistrationIcp.cpp:856-961 behind the rule: what computeTransformation does with the engine's (or register_icp_cpu's) result
+    Transform3D finish(const IcpResult& r, RegistrationInfoIcp& info) const;
+};
+
+}  // namespace rtabmap_amd

@@ -12,6 +12,7 @@
 #include "MemoryHip.h"
 #include "Motion2D.h"
 #include "Motion3D.h"
+#include "RegistrationIcp.h"
 #include "RtabmapHip.h"
 
 using namespace rtabmap_amd;
@@ -271,6 +272,63 @@ int hm3_estimate(void* h, const int* idsA, const float* xyzA, int nA, const int*
     std::copy(matches.begin(), matches.end(), outMatches);
     std::copy(inliers.begin(), inliers.end(), outInliers);
     return t.isNull() ? 0 : 1;
+}
+// register_icp_cpu (no engine involved).  guess[12]; outTransforms[36] = transform, icp transform, correction; outScalars[4] = status, stop, iterations,
+// correspondences; outMatch holds nFrom rows.  1 = done, 0 = refused
+int hicp_cpu(const float* fromXyz, int nFrom, const float* toXyz, int nTo, const float* guess, int maxIterations, int force3DoF, int maxLaserScans,
+             double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, int search, int deviceEntry, float* outTransforms, int* outScalars,
+             float* outRatio, double* outVariance, int* outMatch) {
+    IcpResult r;
+    if (!register_icp_cpu(fromXyz, nFrom, toXyz, nTo, guess, maxIterations, force3DoF != 0, maxLaserScans, maxCorrespondenceDistance, epsilon,
+                          correspondenceRatio, search, deviceEntry != 0, r)) return 0;
+    std::copy(r.transform, r.transform + 12, outTransforms);
+    std::copy(r.icpTransform, r.icpTransform + 12, outTransforms + 12);
+    std::copy(r.correction, r.correction + 12, outTransforms + 24);
+    outScalars[0] = r.status; outScalars[1] = r.stop; outScalars[2] = r.iterations; outScalars[3] = r.correspondences;
+    *outRatio = r.ratio; *outVariance = r.variance;
+    std::copy(r.match.begin(), r.match.end(), outMatch);
+    return 1;
+}
+// the grid form's cell of every coordinate (csrc/icp_rule.h: cell_size, cell_of); INT_MIN where it does not fit the key's range.  Returns the cell size
+float hicp_cells(const float* x, int n, double maxCorrespondenceDistance, int* outCells) {
+    return icp_cells(x, n, maxCorrespondenceDistance, outCells);
+}
+static int icp_info_out(const Transform3D& t, const RegistrationInfoIcp& info, float* outTransform, float* outInfo, int* outCorrespondences, double* outCovariance) {
+    std::copy(t.data, t.data + 12, outTransform);
+    outInfo[0] = info.icpTranslation; outInfo[1] = info.icpRotation; outInfo[2] = info.icpInliersRatio;
+    *outCorrespondences = info.icpCorrespondences;
+    std::copy(info.covariance, info.covariance + 36, outCovariance);
+    return t.isNull() ? 0 : 1;
+}
+// RegistrationIcpHip::finish over a rule's result (no engine involved): transforms[36] and scalars[4] as hicp_cpu writes them.  outInfo[3] =
+// icpTranslation, icpRotation, icpInliersRatio; outCovariance[36]; returns 1 with a transform, 0 without
+int hicp_finish(const float* transforms, const int* scalars, float ratio, double variance, float maxTranslation, float maxRotation, float correspondenceRatio,
+                float* outTransform, float* outInfo, int* outCorrespondences, double* outCovariance) {
+    IcpResult r;
+    std::copy(transforms, transforms + 12, r.transform);
+    std::copy(transforms + 12, transforms + 24, r.icpTransform);
+    std::copy(transforms + 24, transforms + 36, r.correction);
+    r.status = scalars[0]; r.stop = scalars[1]; r.iterations = scalars[2]; r.correspondences = scalars[3]; r.ratio = ratio; r.variance = variance;
+    RegistrationIcpHip reg;
+    reg.maxTranslation = maxTranslation; reg.maxRotation = maxRotation; reg.correspondenceRatio = correspondenceRatio;
+    RegistrationInfoIcp info;
+    return icp_info_out(reg.finish(r, info), info, outTransform, outInfo, outCorrespondences, outCovariance);
+}
+// RegistrationIcpHip::computeTransformation through the dictionary's engine, the scans as [n x 3] rows; outputs as hicp_finish
+int hicp_compute(void* h, const float* fromXyz, int nFrom, const float* toXyz, int nTo, const float* guess, int maxIterations, int force3DoF,
+                 int maxLaserScans, double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, float maxTranslation, float maxRotation,
+                 float* outTransform, float* outInfo, int* outCorrespondences, double* outCovariance) {
+    std::vector<Point3f> from((size_t)nFrom), to((size_t)nTo);
+    for (int i = 0; i < nFrom; ++i) from[(size_t)i] = Point3f{fromXyz[3 * i], fromXyz[3 * i + 1], fromXyz[3 * i + 2]};
+    for (int i = 0; i < nTo; ++i) to[(size_t)i] = Point3f{toXyz[3 * i], toXyz[3 * i + 1], toXyz[3 * i + 2]};
+    Transform3D g;
+    std::copy(guess, guess + 12, g.data);
+    RegistrationIcpHip reg;
+    reg.maxIterations = maxIterations; reg.force3DoF = force3DoF != 0; reg.maxCorrespondenceDistance = maxCorrespondenceDistance; reg.epsilon = epsilon;
+    reg.correspondenceRatio = correspondenceRatio; reg.maxTranslation = maxTranslation; reg.maxRotation = maxRotation;
+    RegistrationInfoIcp info;
+    return icp_info_out(reg.computeTransformation(((VWDictionaryHip*)h)->engine(), from, to, g, maxLaserScans, info), info, outTransform, outInfo,
+                        outCorrespondences, outCovariance);
 }
 // motion_pnp_cpu (no engine involved).  camera[4] = fx, fy, cx, cy; image[2]; local: 12 floats or null; guess: 12 floats or null; toXyz may be null.
 // outTransform[12], outScalars[4] = status, matches, inliers, variance kind; outVariance[2] = linear, cosine; outMatches / outInliers hold nTo ids.

@@ -74,6 +74,11 @@ def lib():
         L.hm3_estimate.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, vp, vp, vp, vp, vp]
         L.hmp_cpu.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, C.c_double, ci, ci, cf, C.c_uint, ci, vp, vp, vp, vp, vp]
         L.hmp_estimate.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, C.c_double, ci, ci, cf, C.c_uint, vp, vp, vp, vp, vp]
+        L.hicp_cpu.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, ci, ci, vp, vp, vp, vp, vp]
+        L.hicp_cells.argtypes = [vp, ci, C.c_double, vp]
+        L.hicp_cells.restype = C.c_float
+        L.hicp_finish.argtypes = [vp, vp, cf, C.c_double, cf, cf, cf, vp, vp, vp, vp]
+        L.hicp_compute.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, cf, vp, vp, vp, vp]
         L.hmem_select_error.argtypes = [vp]
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -254,6 +259,59 @@ def motion3d_cpu(from_ids, from_xyz, to_ids, to_xyz, min_inliers=20, inlier_dist
     return dict(transform=t, status=int(sc[0]), variance=var[0], matches=om[:sc[1]].copy(), inliers=oi[:sc[2]].copy())
 
 
+IDENTITY_GUESS = (1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)
+
+
+def _scan_arrays(from_xyz, to_xyz, guess):
+    fx = np.ascontiguousarray(from_xyz, dtype=np.float32).reshape(-1, 3)
+    tx = np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+    gs = np.ascontiguousarray(IDENTITY_GUESS if guess is None else guess, dtype=np.float32).reshape(12)
+    return fx, tx, gs
+
+
+def register_icp_cpu(from_xyz, to_xyz, guess=None, max_iterations=30, force_3dof=False, max_laser_scans=0, search=0, max_correspondence_distance=0.1,
+                     epsilon=0.0, correspondence_ratio=0.1, device_entry=False):
+    """the rule of lcd_register_icp on the CPU (host/RegistrationIcp.cpp, no device) -> dict(transform, icp_transform, correction [12], status, stop,
+    iterations, n_correspondences, ratio, variance, match [n_from]), or None where the call is refused; device_entry: the refusals of
+    lcd_register_icp_dev (a row that is not finite takes no part) instead of lcd_register_icp's (it is refused)"""
+    fx, tx, gs = _scan_arrays(from_xyz, to_xyz, guess)
+    if fx.shape[0] > 8192 or tx.shape[0] > 8192:
+        return None
+    t, sc, ratio, var = np.zeros(36, np.float32), np.zeros(4, np.int32), np.zeros(1, np.float32), np.zeros(1, np.float64)
+    match = np.zeros(max(fx.shape[0], 1), np.int32)
+    ok = lib().hicp_cpu(_p(fx), fx.shape[0], _p(tx), tx.shape[0], _p(gs), int(max_iterations), int(bool(force_3dof)), int(max_laser_scans),
+                        float(max_correspondence_distance), float(epsilon), float(correspondence_ratio), int(search), int(bool(device_entry)), _p(t), _p(sc),
+                        _p(ratio), _p(var), _p(match))
+    if not ok:
+        return None
+    return dict(transform=t[:12].copy(), icp_transform=t[12:24].copy(), correction=t[24:].copy(), status=int(sc[0]), stop=int(sc[1]), iterations=int(sc[2]),
+                n_correspondences=int(sc[3]), ratio=ratio[0], variance=var[0], match=match[:fx.shape[0]].copy())
+
+
+def register_icp_cells(x, max_correspondence_distance):
+    """the grid form's cell of every coordinate (csrc/icp_rule.h) -> (cells int64 with None-like INT_MIN where out of range, the cell size)"""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    out = np.zeros(max(x.shape[0], 1), np.int32)
+    h = lib().hicp_cells(_p(x), x.shape[0], float(max_correspondence_distance), _p(out))
+    return out[:x.shape[0]].astype(np.int64), np.float32(h)
+
+
+def _icp_info(ok, t, info, corr, cov):
+    return (t if ok else None), dict(icp_translation=info[0], icp_rotation=info[1], icp_inliers_ratio=info[2], icp_correspondences=int(corr[0]),
+                                     covariance=cov.reshape(6, 6))
+
+
+def register_icp_finish(result, max_translation=0.2, max_rotation=0.78, correspondence_ratio=0.1):
+    """RegistrationIcpHip::finish (RegistrationIcp.cpp:856-961: the Euler-angle gate, variance / 10, the covariance) over a result of
+    register_icp_cpu or of one pair of the engine's -> (transform [12] or None, info dict)"""
+    tr = np.concatenate([np.asarray(result[k], np.float32).reshape(12) for k in ("transform", "icp_transform", "correction")])
+    sc = np.array([result["status"], result["stop"], result["iterations"], result["n_correspondences"]], np.int32)
+    t, info, corr, cov = np.zeros(12, np.float32), np.zeros(3, np.float32), np.zeros(1, np.int32), np.zeros(36, np.float64)
+    ok = lib().hicp_finish(_p(tr), _p(sc), float(result["ratio"]), float(result["variance"]), float(max_translation), float(max_rotation),
+                           float(correspondence_ratio), _p(t), _p(info), _p(corr), _p(cov))
+    return _icp_info(ok, t, info, corr, cov)
+
+
 def _pnp_arrays(to_ids, to_points, to_xyz, camera, image_size, local_transform, guess):
     ti = np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
     tp = np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
@@ -387,6 +445,17 @@ class VWDictionaryHip:
                                 int(min_inliers), int(iterations), float(reproj_error), int(refine_iterations), int(variance_median_ratio),
                                 float(max_variance), int(seed) & 0xFFFFFFFF, _p(t), _p(cov), _p(counts), _p(om), _p(oi))
         return (t if ok else None), cov.reshape(6, 6), om[:counts[0]].tolist(), oi[:counts[1]].tolist()
+
+    def register_icp(self, from_scan, to_scan, guess=None, max_laser_scans=0, max_iterations=30, force_3dof=False, max_correspondence_distance=0.1,
+                     epsilon=0.0, correspondence_ratio=0.1, max_translation=0.2, max_rotation=0.78):
+        """RegistrationIcpHip::computeTransformation (RegistrationIcp.cpp:662-971, point to point, Icp/Strategy = 0) over this dictionary's
+        long-lived engine handle; a scan is [n x 3] points in its base frame.  -> (transform [12] or None, info dict as register_icp_finish)"""
+        fx, tx, gs = _scan_arrays(from_scan, to_scan, guess)
+        t, info, corr, cov = np.zeros(12, np.float32), np.zeros(3, np.float32), np.zeros(1, np.int32), np.zeros(36, np.float64)
+        ok = lib().hicp_compute(self.h, _p(fx), fx.shape[0], _p(tx), tx.shape[0], _p(gs), int(max_iterations), int(bool(force_3dof)), int(max_laser_scans),
+                                float(max_correspondence_distance), float(epsilon), float(correspondence_ratio), float(max_translation), float(max_rotation),
+                                _p(t), _p(info), _p(corr), _p(cov))
+        return _icp_info(ok, t, info, corr, cov)
 
     def update(self):
         lib().hvwd_update(self.h)
