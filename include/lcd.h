@@ -923,7 +923,8 @@ int lcd_estimate_motion_pnp_dev(lcd_engine* h, const lcd_motion_pnp_args* a);
  * The remaining steps of :856-928 take out_correction and out_variance and are the HOST mirror's (host/RegistrationIcp.cpp), as the arc cosine
  * of lcd_estimate_motion_pnp is: the Icp/MaxTranslation / Icp/MaxRotation gate (Euler angles: an arc tangent), variance /= 10, and the
  * covariance (eye x variance, the rotation block / 10).
- * Out of scope: point-to-plane (Icp/PointToPlane, normals, the low-complexity fallback), libpointmatcher and CCCoreLib (Icp/Strategy 1, 2),
+ * Out of scope here: point-to-plane (Icp/PointToPlane, normals, the low-complexity fallback), which is lcd_register_icp_plane below;
+ * libpointmatcher and CCCoreLib (Icp/Strategy 1, 2),
  * Icp/Force4DoF, the scan filters in front (Icp/VoxelSize, DownsamplingStep, RangeMin / RangeMax), intensity, scans above 8192 points, sharded
  * handles, and on the device the Euler-angle gate and the covariance.
  *
@@ -947,14 +948,16 @@ enum lcd_icp_status {
     LCD_ICP_OK = 0,
     LCD_ICP_EMPTY = 1,                /* a side has no participating row */
     LCD_ICP_NOT_CONVERGED = 2,        /* fewer than 3 correspondences in an iteration */
-    LCD_ICP_BELOW_RATIO = 3           /* everything returned but the transform */
+    LCD_ICP_BELOW_RATIO = 3,          /* everything returned but the transform */
+    LCD_ICP_LOW_COMPLEXITY = 4        /* lcd_register_icp_plane only: strategy 0 on a pair below min_complexity */
 };
 enum lcd_icp_stop {
     LCD_ICP_STOP_NONE = 0,
     LCD_ICP_STOP_ITERATIONS = 1,
     LCD_ICP_STOP_TRANSFORM = 2,
     LCD_ICP_STOP_MSE = 3,
-    LCD_ICP_STOP_FEW_CORRESPONDENCES = 4
+    LCD_ICP_STOP_FEW_CORRESPONDENCES = 4,
+    LCD_ICP_STOP_SINGULAR = 5         /* lcd_register_icp_plane only: the point-to-plane system has no positive pivot */
 };
 enum lcd_icp_search {
     LCD_ICP_SEARCH_AUTO = 0,
@@ -992,6 +995,115 @@ int lcd_register_icp(lcd_engine* h, const lcd_icp_args* a);
 /* points and out_* in DEVICE memory (4-byte aligned, out_variance 8-byte), offsets and guesses on the HOST (read during the call); enqueued on
  * the engine stream, not synchronised */
 int lcd_register_icp_dev(lcd_engine* h, const lcd_icp_args* a);
+
+/* ---- Scan registration (point to plane), stateless: what RegistrationIcp::computeTransformationImpl does with the reference's defaults
+ * (Icp/PointToPlane = true, Icp/Strategy = 0) to a pair of 3-D scans that carry normals (RegistrationIcp.cpp:506-661, :785-853): the
+ * structural-complexity test on the normals of both scans (util3d::computeNormalsComplexity, util3d_surface.cpp:3164-3241), then either
+ * util3d::icpPointToPlane (util3d_registration.cpp:451-492) with the normal-aware computeVarianceAndCorrespondences (:240-301), or -- on a
+ * corridor-like pair -- the point-to-point loop of lcd_register_icp with the translation limited to the well-constrained axes.  What is in
+ * the reference tree is reproduced exactly, integers and control flow: the 2 oi rows handed to the PCA, the `<` of :530 and :539 (the
+ * to-side on equal complexities), the three strategies, removeNaNNormalsFromPointCloud, to3DoF applied after the registered cloud is taken,
+ * the gate's count, the resize before the sort, the missing >= 3 guard.  What is PCL's or OpenCV's is the ENGINE'S rule, modelled on them and
+ * written out here: cv::PCA's eigen decomposition is a cyclic Jacobi, pcl::registration::TransformationEstimationPointToPlaneLLS is solved by
+ * LDL^T with a product of axis quaternions in place of Rz Ry Rx, pcl::getAngle3D is a cosine compared against a cosine.  No bit parity
+ * with a PCL or OpenCV build is claimed.  Stateless exactly as lcd_register_icp: one launch per call, one workgroup of 256 threads per pair,
+ * nothing of a pipelined handle drained.  Arguments that lcd_icp_args has keep their names and meaning.  A caller routes 2-D scans to
+ * lcd_register_icp, as the reference does at :510-518.
+ *
+ * The rule, per pair.  fp32, every operation rounded on its own, IEEE division and square root, only + - x / sqrt; "fp64" marks the few
+ * places that are double.  SUM, T(p), A x B, inverse(T), the search, the threshold and the stops are those of lcd_register_icp ("4n" below
+ * names its steps).
+ *   1. Rotated normals.  n' = R n, each entry ((R_r0 n_x + R_r1 n_y) + R_r2 n_z).  The to-scan's normals are rotated by the guess's
+ *      rotation, the registered cloud's by F's (F as the loop left it, before step 4's force_3dof).
+ *   2. Complexity of a side (the to-side under the guess's rotation).  oi = the number of rows whose three GIVEN normal components are
+ *      finite (whatever their coordinates are).  oi <= 1: complexity 0, no values, no vectors.  Otherwise the PCA over 2 oi rows of which oi
+ *      are zero, as :3221 hands them over: mean_a = SUM(n'_a) / float(2 oi); cov_ab = (SUM((n'_a - mean_a) * (n'_b - mean_b)) + float(oi) *
+ *      (mean_a * mean_b)) / float(2 oi), SUM the 256-lane sum over the row index, rows without a finite normal skipped.  Eigenvalues by
+ *      LCD_ICP_PLANE_SWEEPS sweeps of cyclic Jacobi over the planes (0,1), (0,2), (1,2) -- the rotation of lcd_estimate_motion_3d's step 4 --,
+ *      sorted descending (the lower index first among equals), the vectors as rows.  complexity = third value * 3.0f.  Eigenvector signs
+ *      are not pinned; nothing downstream depends on them (n (v . n) is even in n).
+ *   3. Decision (:522-583).  complexity = the from-side's iff it is < the to-side's, else the to-side's; out_complexity_values and
+ *      out_complexity_vectors are that side's (zeros without a PCA).  complexity < min_complexity is the low-complexity path: second = the
+ *      smaller of the two sides' second values when complexity > 0 (the from-side's iff it is <), else 1.0; strategy 0:
+ *      LCD_ICP_LOW_COMPLEXITY, everything zero but out_complexity, its values and vectors and out_second_eigenvalue; otherwise branch 1
+ *      with that side's vectors when complexity > 0 and none when it is 0.  Otherwise branch 0 and second = 1.0.
+ *   4. Branch 0, the loop.  A row takes part iff its coordinates AND its given normal are finite (removeNaNNormalsFromPointCloud); n_f and
+ *      n_t count those rows; either 0: LCD_ICP_EMPTY.  The search, the threshold, the order of the stops and mse are 4n's steps 2, 3, 5, 6.
+ *      The fit (TransformationEstimationPointToPlaneLLS, uncentred as PCL's): per correspondence (s, d, n) -- source point, target point,
+ *      the target's rotated normal -- a = (s x n, n) with s x n = (s_y n_z - s_z n_y, s_z n_x - s_x n_z, s_x n_y - s_y n_x), b = n.d - n.s,
+ *      dots as ((x x + y y) + z z).  The 21 products a_i a_j (i <= j, row by row) and the 6 a_i b are SUMmed over the row index; x solves
+ *      the 6 x 6 by the LDL^T of lcd_estimate_motion_pnp's step 7.  A pivot that is not positive and finite, or an x that is not finite:
+ *      LCD_ICP_NOT_CONVERGED with LCD_ICP_STOP_SINGULAR, out_iterations = k.  Rotation: PCL builds Rz(x_2) Ry(x_1) Rx(x_0) with sines and
+ *      cosines; the rule has none.  With a = x_0 / 2, b = x_1 / 2, c = x_2 / 2 (0.5f * x) it is the unit quaternion (1 + (a b) c, a - b c,
+ *      b + a c, c - a b) / norm -- the product of the three axis quaternions (1, c k) (1, b j) (1, a i), through lcd_estimate_motion_3d's
+ *      quaternion rotation.  It is an exact rotation by the angles 2 atan(x / 2) = x - x^3 / 12 about the same axes in the same order, so it
+ *      agrees with PCL's matrix to second order; the loop iterates, so the fixed point is the same.  Translation: (x_3, x_4, x_5).
+ *      force_3dof (Transform::to3DoF, :485-489) is applied to F AFTER the registered cloud F(P_0) and its normals are taken: n = sqrt(R00 *
+ *      R00 + R10 * R10), c = R00 / n, s = R10 / n (the identity when n is 0 or not finite), F <- [[c, -s, 0, F_x], [s, c, 0, F_y], [0, 0, 1, 0]].
+ *   5. Branch 0, variance and correspondences (:240-301).  The target is the side with more participating rows, B on equality.  The
+ *      reciprocal correspondences are 4n's step 8.  The gate (normal_gate != 0): with u = v / sqrt(v . v) (v itself when v . v is 0),
+ *      double(u_target . u_source) > min_normal_cos; with the gate off all pass.  out_n_correspondences = count = those passing; out_match
+ *      lists those.  Variance AS WRITTEN: distances.resize(count) precedes the sort, so with count >= 1 out_variance = 2.1981 * double(the d2
+ *      of rank count >> 1 among the FIRST count reciprocal correspondences in ascending source-row order, whichever of them passed).
+ *   6. Branch 1.  4n's loop unchanged over all rows with finite coordinates, force_3dof choosing the 2-D estimator.  Strategy 1 (:789-832):
+ *      C = guess^-1 x F^-1 x guess, v = C's translation, vp = n1 (v . n1), plus n2 (v . n2) iff second >= min_complexity (vp_k = n1_k a + n2_k
+ *      b), vp = 0 without vectors; C's rotation is kept (the Euler round trip of :826-828 returns it); F <- guess x [R_C | vp]^-1 x guess^-1,
+ *      and the registered cloud is this F(P_0).  Strategy 2: F as it is.  Then 4n's steps 8-9 (the >= 3 guard, no gate).
+ *   7. Outputs.  out_ratio's denominator counts the rows with finite COORDINATES (:895); X, out_correction, the gate on
+ *      correspondence_ratio and the zero conventions are 4n's steps 9-10.  out_branch and the complexity outputs are written whatever the
+ *      status; out_branch is 0 with LCD_ICP_LOW_COMPLEXITY.
+ * min_normal_cos is cos(Icp/MaxRotation), computed by the caller (the host mirror does); angle < max is cosine > cos(max).
+ * Out of scope: normal estimation (commonFiltering's computeNormals, Icp/PointToPlaneK, Radius, GroundNormalsUp), 2-D scans with normals
+ * (the reference ignores point to plane for them), and everything lcd_register_icp leaves out.
+ *
+ * Limits and errors: those of lcd_register_icp, and LCD_ERR_INVALID for a min_complexity outside [0, 1], a low_complexity_strategy outside
+ * 0 .. 2, a min_normal_cos that is not finite while the gate is on, and NULL normals where rows exist.  After a refusal nothing was written.
+ * A normal that is not finite is legal on BOTH entries (the reference produces such normals); a coordinate that is not finite is refused by
+ * the host entry and takes no part on the device entry. */
+#define LCD_ICP_PLANE_SWEEPS 5
+typedef struct lcd_icp_plane_args {
+    int32_t struct_size;            /* sizeof(lcd_icp_plane_args) */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t max_iterations;         /* Icp/Iterations, >= 1 */
+    int32_t force_3dof;             /* Reg/Force3DoF */
+    int32_t max_laser_scans;        /* 0 = the ratio is relative to the larger scan */
+    int32_t search;                 /* lcd_icp_search */
+    double max_correspondence_distance; /* Icp/MaxCorrespondenceDistance, finite, > 0 */
+    float epsilon;                  /* Icp/Epsilon, >= 0 */
+    float correspondence_ratio;     /* Icp/CorrespondenceRatio, 0 .. 1 */
+    float min_complexity;           /* Icp/PointToPlaneMinComplexity, 0 .. 1 */
+    int32_t low_complexity_strategy;/* Icp/PointToPlaneLowComplexityStrategy: 0 reject, 1 limit the translation, 2 accept */
+    int32_t normal_gate;            /* != 0: correspondences are counted behind the angle test (Icp/MaxRotation > 0) */
+    int32_t reserved;               /* 0 */
+    double min_normal_cos;          /* cos(Icp/MaxRotation); finite while the gate is on */
+    const float* from_xyz;          /* [Nf x 3] */
+    const float* to_xyz;            /* [Nt x 3] */
+    const float* from_normals;      /* [Nf x 3], in the from-scan's own frame; may hold NaN */
+    const float* to_normals;        /* [Nt x 3], in the to-scan's own frame */
+    const int64_t* from_offsets;    /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    const int64_t* to_offsets;      /* HOST, [n_pairs + 1] */
+    const float* guesses;           /* HOST, [n_pairs x 12], row-major 3 x 4, finite */
+    float* out_transform;           /* [n_pairs x 12] */
+    float* out_icp_transform;       /* [n_pairs x 12] */
+    float* out_correction;          /* [n_pairs x 12] */
+    int32_t* out_status;            /* [n_pairs], lcd_icp_status or LCD_ICP_LOW_COMPLEXITY */
+    int32_t* out_stop;              /* [n_pairs], lcd_icp_stop or LCD_ICP_STOP_SINGULAR */
+    int32_t* out_iterations;        /* [n_pairs] */
+    int32_t* out_n_correspondences; /* [n_pairs] */
+    float* out_ratio;               /* [n_pairs] */
+    double* out_variance;           /* [n_pairs], undivided */
+    int32_t* out_match;             /* [Nf] */
+    int32_t* out_branch;            /* [n_pairs]: 0 = point to plane, 1 = point-to-point fallback */
+    float* out_complexity;          /* [n_pairs] */
+    float* out_complexity_values;   /* [n_pairs x 3], of the less complex side, descending */
+    float* out_complexity_vectors;  /* [n_pairs x 9], its eigenvectors as rows */
+    float* out_second_eigenvalue;   /* [n_pairs] */
+} lcd_icp_plane_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_register_icp_plane(lcd_engine* h, const lcd_icp_plane_args* a);
+/* rows, normals and out_* in DEVICE memory (4-byte aligned, out_variance 8-byte), offsets and guesses on the HOST (read during the call);
+ * enqueued on the engine stream, not synchronised */
+int lcd_register_icp_plane_dev(lcd_engine* h, const lcd_icp_plane_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

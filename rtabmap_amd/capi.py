@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -153,8 +153,21 @@ class LcdIcpArgs(C.Structure):
                 ("out_n_correspondences", C.c_void_p), ("out_ratio", C.c_void_p), ("out_variance", C.c_void_p), ("out_match", C.c_void_p)]
 
 
-LCD_ICP_OK, LCD_ICP_EMPTY, LCD_ICP_NOT_CONVERGED, LCD_ICP_BELOW_RATIO = 0, 1, 2, 3  # lcd_icp_status
-LCD_ICP_STOP_NONE, LCD_ICP_STOP_ITERATIONS, LCD_ICP_STOP_TRANSFORM, LCD_ICP_STOP_MSE, LCD_ICP_STOP_FEW_CORRESPONDENCES = 0, 1, 2, 3, 4  # lcd_icp_stop
+class LcdIcpPlaneArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("max_iterations", C.c_int32), ("force_3dof", C.c_int32),
+                ("max_laser_scans", C.c_int32), ("search", C.c_int32), ("max_correspondence_distance", C.c_double), ("epsilon", C.c_float),
+                ("correspondence_ratio", C.c_float), ("min_complexity", C.c_float), ("low_complexity_strategy", C.c_int32),
+                ("normal_gate", C.c_int32), ("reserved", C.c_int32), ("min_normal_cos", C.c_double), ("from_xyz", C.c_void_p), ("to_xyz", C.c_void_p),
+                ("from_normals", C.c_void_p), ("to_normals", C.c_void_p), ("from_offsets", C.c_void_p), ("to_offsets", C.c_void_p),
+                ("guesses", C.c_void_p), ("out_transform", C.c_void_p), ("out_icp_transform", C.c_void_p), ("out_correction", C.c_void_p),
+                ("out_status", C.c_void_p), ("out_stop", C.c_void_p), ("out_iterations", C.c_void_p), ("out_n_correspondences", C.c_void_p),
+                ("out_ratio", C.c_void_p), ("out_variance", C.c_void_p), ("out_match", C.c_void_p), ("out_branch", C.c_void_p),
+                ("out_complexity", C.c_void_p), ("out_complexity_values", C.c_void_p), ("out_complexity_vectors", C.c_void_p),
+                ("out_second_eigenvalue", C.c_void_p)]
+
+
+LCD_ICP_OK, LCD_ICP_EMPTY, LCD_ICP_NOT_CONVERGED, LCD_ICP_BELOW_RATIO, LCD_ICP_LOW_COMPLEXITY = 0, 1, 2, 3, 4  # lcd_icp_status
+LCD_ICP_STOP_NONE, LCD_ICP_STOP_ITERATIONS, LCD_ICP_STOP_TRANSFORM, LCD_ICP_STOP_MSE, LCD_ICP_STOP_FEW_CORRESPONDENCES, LCD_ICP_STOP_SINGULAR = 0, 1, 2, 3, 4, 5  # lcd_icp_stop
 LCD_ICP_SEARCH_AUTO, LCD_ICP_SEARCH_BRUTE, LCD_ICP_SEARCH_GRID = 0, 1, 2  # lcd_icp_search
 
 
@@ -259,6 +272,8 @@ def load():
     L.lcd_estimate_motion_pnp_dev.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
     L.lcd_register_icp.argtypes = [vp, C.POINTER(LcdIcpArgs)]
     L.lcd_register_icp_dev.argtypes = [vp, C.POINTER(LcdIcpArgs)]
+    L.lcd_register_icp_plane.argtypes = [vp, C.POINTER(LcdIcpPlaneArgs)]
+    L.lcd_register_icp_plane_dev.argtypes = [vp, C.POINTER(LcdIcpPlaneArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -862,6 +877,62 @@ class Engine:
         a.out_status, a.out_stop, a.out_iterations, a.out_n_correspondences = ptr(d_status), ptr(d_stop), ptr(d_iterations), ptr(d_n_correspondences)
         a.out_ratio, a.out_variance, a.out_match = ptr(d_ratio), ptr(d_variance), ptr(d_match)
         self._ck(self.L.lcd_register_icp_dev(self.h, C.byref(a)))
+
+    # ---- scan registration, point to plane with the complexity test and its fallback (stateless; include/lcd.h has the rule)
+    ICP_PLANE_OUT = (("transform", 12, np.float32), ("icp_transform", 12, np.float32), ("correction", 12, np.float32), ("status", 0, np.int32),
+                     ("stop", 0, np.int32), ("iterations", 0, np.int32), ("n_correspondences", 0, np.int32), ("ratio", 0, np.float32),
+                     ("variance", 0, np.float64), ("branch", 0, np.int32), ("complexity", 0, np.float32), ("complexity_values", 3, np.float32),
+                     ("complexity_vectors", 9, np.float32), ("second_eigenvalue", 0, np.float32))
+
+    @staticmethod
+    def _icp_plane_args(n_pairs, max_iterations, force_3dof, max_laser_scans, search, max_correspondence_distance, epsilon, correspondence_ratio,
+                        min_complexity, low_complexity_strategy, normal_gate, min_normal_cos, struct_size):
+        return LcdIcpPlaneArgs(C.sizeof(LcdIcpPlaneArgs) if struct_size is None else struct_size, n_pairs, int(max_iterations), int(bool(force_3dof)),
+                               int(max_laser_scans), int(search), float(max_correspondence_distance), float(epsilon), float(correspondence_ratio),
+                               float(min_complexity), int(low_complexity_strategy), int(bool(normal_gate)), 0, float(min_normal_cos))
+
+    def register_icp_plane(self, from_xyz, from_normals, from_offsets, to_xyz, to_normals, to_offsets, guesses, max_iterations=30, force_3dof=False,
+                           max_laser_scans=0, search=LCD_ICP_SEARCH_AUTO, max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1,
+                           min_complexity=0.02, low_complexity_strategy=1, normal_gate=False, min_normal_cos=0.0, struct_size=None):
+        """lcd_register_icp_plane over host arrays, all pairs concatenated -> dict of ICP_PLANE_OUT's names ([n_pairs] or [n_pairs x k]) and match
+        [Nf]; outputs start as -7 / NaN so that what the call left alone shows"""
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fx, tx = np.ascontiguousarray(from_xyz, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+        fn = None if from_normals is None else np.ascontiguousarray(from_normals, dtype=np.float32).reshape(-1, 3)
+        tn = None if to_normals is None else np.ascontiguousarray(to_normals, dtype=np.float32).reshape(-1, 3)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        n_pairs, n = fo.shape[0] - 1, fx.shape[0]
+        m = max(n_pairs, 1)
+        out = {k: np.full((m, w) if w else m, -7 if dt is np.int32 else np.nan, dt) for k, w, dt in self.ICP_PLANE_OUT}
+        out["match"] = np.full(max(n, 1), -7, np.int32)
+        a = self._icp_plane_args(n_pairs, max_iterations, force_3dof, max_laser_scans, search, max_correspondence_distance, epsilon, correspondence_ratio,
+                                 min_complexity, low_complexity_strategy, normal_gate, min_normal_cos, struct_size)
+        a.from_xyz, a.to_xyz, a.from_offsets, a.to_offsets, a.guesses = _p(fx), _p(tx), fo.ctypes.data, to.ctypes.data, None if gs is None else _p(gs)
+        a.from_normals, a.to_normals = None if fn is None else _p(fn), None if tn is None else _p(tn)
+        for k in out:
+            setattr(a, "out_" + k, _p(out[k]))
+        self._ck(self.L.lcd_register_icp_plane(self.h, C.byref(a)))
+        for k in out:
+            out[k] = out[k][:n] if k == "match" else out[k][:max(n_pairs, 0)]
+        return out
+
+    def register_icp_plane_dev(self, d_from_xyz, d_from_normals, from_offsets, d_to_xyz, d_to_normals, to_offsets, guesses, d_out, max_iterations=30,
+                               force_3dof=False, max_laser_scans=0, search=LCD_ICP_SEARCH_AUTO, max_correspondence_distance=0.1, epsilon=0.0,
+                               correspondence_ratio=0.1, min_complexity=0.02, low_complexity_strategy=1, normal_gate=False, min_normal_cos=0.0):
+        """lcd_register_icp_plane_dev on torch tensors of the engine's device (offsets and guesses stay on the host); d_out maps ICP_PLANE_OUT's
+        names and "match" to the output tensors.  Enqueued, not synchronised."""
+        fo = np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        a = self._icp_plane_args(fo.shape[0] - 1, max_iterations, force_3dof, max_laser_scans, search, max_correspondence_distance, epsilon,
+                                 correspondence_ratio, min_complexity, low_complexity_strategy, normal_gate, min_normal_cos, None)
+        a.from_xyz, a.to_xyz, a.from_offsets, a.to_offsets, a.guesses = ptr(d_from_xyz), ptr(d_to_xyz), fo.ctypes.data, to.ctypes.data, None if gs is None else _p(gs)
+        a.from_normals, a.to_normals = ptr(d_from_normals), ptr(d_to_normals)
+        for k, _, _ in self.ICP_PLANE_OUT + (("match", 0, np.int32),):
+            setattr(a, "out_" + k, ptr(d_out[k]))
+        self._ck(self.L.lcd_register_icp_plane_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

@@ -175,14 +175,9 @@ struct Result {
 //   void set_registered(const float F[12])    the current cloud becomes F(P_0)
 //   int reciprocal(bool from_is_target)   step 8 over the current cloud and Q: writes out_match, returns the number of correspondences
 //   float median(int n)                   the d2 of rank n >> 1 among the n correspondences of reciprocal()
+// steps 3 to 6 over the backend's clouds: F, the iterations and the stop.  false: fewer than three correspondences in an iteration (r is final)
 template <class B>
-M3D_FN void solve(B& b, int max_iterations, bool force_3dof, int max_laser_scans, float epsilon, float correspondence_ratio, const float guess[12], Result& r) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) { r.transform[k] = 0.0f; r.icp[k] = 0.0f; r.correction[k] = 0.0f; }
-    r.stop = STOP_NONE; r.iterations = 0; r.n_correspondences = 0; r.ratio = 0.0f; r.variance = 1.0;
-    const int nf = b.n_from(), nt = b.n_to();
-    if (nf == 0 || nt == 0) { r.status = ST_EMPTY; return; }
-    float F[12];
+M3D_FN bool loop(B& b, int max_iterations, bool force_3dof, float epsilon, float F[12], Result& r) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) F[k] = (k == 0 || k == 5 || k == 10) ? 1.0f : 0.0f;
     const float eps2 = epsilon * epsilon;
@@ -191,7 +186,7 @@ M3D_FN void solve(B& b, int max_iterations, bool force_3dof, int max_laser_scans
     for (;;) {
         float sum_d2;
         const int c = b.correspond(sum_d2);
-        if (c < MIN_CORRESPONDENCES) { r.status = ST_NOT_CONVERGED; r.stop = STOP_FEW_CORRESPONDENCES; return; }
+        if (c < MIN_CORRESPONDENCES) { r.status = ST_NOT_CONVERGED; r.stop = STOP_FEW_CORRESPONDENCES; return false; }
         const float mse = sum_d2 / (float)c;
         float T[12], G[12];
         b.fit(c, force_3dof, T);
@@ -205,11 +200,11 @@ M3D_FN void solve(B& b, int max_iterations, bool force_3dof, int max_laser_scans
         mse_prev = mse;
     }
     r.stop = stop;
-    b.set_registered(F);
-    const int n = b.reciprocal(nf > nt);
-    r.n_correspondences = n;
-    if (n >= MIN_CORRESPONDENCES) r.variance = VARIANCE_FACTOR * (double)b.median(n);
-    const int larger = nf > nt ? nf : nt;
+    return true;
+}
+
+// steps 9 and 10 from F, the number of correspondences kept and the ratio's denominator without max_laser_scans
+M3D_FN void outputs(const float F[12], const float guess[12], int n, int larger, int max_laser_scans, float correspondence_ratio, Result& r) {
     r.ratio = (float)n / (float)(max_laser_scans > 0 ? max_laser_scans : larger);
     float Finv[12], X[12], Ginv[12], C[12];
     invert(F, Finv);
@@ -222,6 +217,26 @@ M3D_FN void solve(B& b, int max_iterations, bool force_3dof, int max_laser_scans
 #pragma unroll
     for (int k = 0; k < 12; ++k) r.transform[k] = X[k];
     r.status = ST_OK;
+}
+
+M3D_FN void clear(Result& r) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { r.transform[k] = 0.0f; r.icp[k] = 0.0f; r.correction[k] = 0.0f; }
+    r.stop = STOP_NONE; r.iterations = 0; r.n_correspondences = 0; r.ratio = 0.0f; r.variance = 1.0;
+}
+
+template <class B>
+M3D_FN void solve(B& b, int max_iterations, bool force_3dof, int max_laser_scans, float epsilon, float correspondence_ratio, const float guess[12], Result& r) {
+    clear(r);
+    const int nf = b.n_from(), nt = b.n_to();
+    if (nf == 0 || nt == 0) { r.status = ST_EMPTY; return; }
+    float F[12];
+    if (!loop(b, max_iterations, force_3dof, epsilon, F, r)) return;
+    b.set_registered(F);
+    const int n = b.reciprocal(nf > nt);
+    r.n_correspondences = n;
+    if (n >= MIN_CORRESPONDENCES) r.variance = VARIANCE_FACTOR * (double)b.median(n);
+    outputs(F, guess, n, nf > nt ? nf : nt, max_laser_scans, correspondence_ratio, r);
 }
 
 }  // namespace icp

@@ -339,64 +339,8 @@ M3D_FN void gn_terms(const float m[12], const Camera& k, float px, float py, flo
     }
 }
 
-// the 6 x 6 system by LDL^T without pivoting; false (delta untouched): a pivot that is not positive and finite, or a solution that is not finite
-M3D_FN bool gn_solve(const float S[SUMS], float delta[6]) {
-    float A[6][6], Lm[6][6], d[6], w[6], z[6], x[6];
-    int o = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) { A[i][j] = S[o]; A[j][i] = S[o]; ++o; }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float acc = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) {
-            w[k] = Lm[j][k] * d[k];
-            const float p = Lm[j][k] * w[k];
-            acc = acc - p;
-        }
-        if (!(acc > 0.0f) || !finite(acc)) return false;
-        d[j] = acc;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            float a = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) {
-                const float p = Lm[i][k] * w[k];
-                a = a - p;
-            }
-            Lm[i][j] = a / acc;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        float a = S[21 + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) {
-            const float p = Lm[i][k] * z[k];
-            a = a - p;
-        }
-        z[i] = a;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        float a = z[i] / d[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) {
-            const float p = Lm[k][i] * x[k];
-            a = a - p;
-        }
-        x[i] = a;
-    }
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) ok = ok && finite(x[i]);
-    if (!ok) return false;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) delta[i] = x[i];
-    return true;
-}
+// the 6 x 6 system of a Gauss-Newton step: motion_rule_common.h's LDL^T
+M3D_FN bool gn_solve(const float S[SUMS], float delta[6]) { return m3d::ldlt6_solve(S, delta); }
 
 // q <- (1, w / 2) (x) q (normalised by the next model_of_pose), t <- t + dt
 M3D_FN void pose_update(float q[4], float t[3], const float delta[6]) {

@@ -1,6 +1,6 @@
 // motion_rule_common.h -- what the rules of lcd_estimate_motion_3d (motion_3d_rule.h), lcd_estimate_motion_pnp (motion_pnp_rule.h) and
-// lcd_register_icp (icp_rule.h) share: the bit helpers, the id keys, the counter-based mix, the three-element sum in the order of the 256-lane
-// sum, the rigid fit (Horn's quaternion by cyclic Jacobi), and a rigid model applied, inverted and composed.  fp32, one rounded operation
+// lcd_register_icp (icp_rule.h, icp_plane_rule.h) share: the bit helpers, the id keys, the counter-based mix, the three-element sum in the order of the 256-lane
+// sum, the rigid fit (Horn's quaternion by cyclic Jacobi), a rigid model applied, inverted and composed, and the 6 x 6 LDL^T solve.  fp32, one rounded operation
 // per statement, never contracted; division and square root are IEEE.  Compiled for the kernels and for the host mirrors alike.  Internal.
 #pragma once
 #include <stdint.h>
@@ -216,6 +216,65 @@ M3D_FN void compose(const float a[12], const float b[12], float out[12]) {
             out[4 * r + c] = c == 3 ? p012 + a[4 * r + 3] : p012;
         }
     }
+}
+
+// The 6 x 6 system A x = b by LDL^T without pivoting: S holds the 21 entries of A's upper triangle row by row, then the 6 of b; false (delta untouched): a pivot that is not positive and finite, or a solution that is not finite
+M3D_FN bool ldlt6_solve(const float S[27], float delta[6]) {
+    float A[6][6], Lm[6][6], d[6], w[6], z[6], x[6];
+    int o = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) { A[i][j] = S[o]; A[j][i] = S[o]; ++o; }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        float acc = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) {
+            w[k] = Lm[j][k] * d[k];
+            const float p = Lm[j][k] * w[k];
+            acc = acc - p;
+        }
+        if (!(acc > 0.0f) || !finite(acc)) return false;
+        d[j] = acc;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            float a = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) {
+                const float p = Lm[i][k] * w[k];
+                a = a - p;
+            }
+            Lm[i][j] = a / acc;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        float a = S[21 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) {
+            const float p = Lm[i][k] * z[k];
+            a = a - p;
+        }
+        z[i] = a;
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        float a = z[i] / d[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) {
+            const float p = Lm[k][i] * x[k];
+            a = a - p;
+        }
+        x[i] = a;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && finite(x[i]);
+    if (!ok) return false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) delta[i] = x[i];
+    return true;
 }
 
 }  // namespace m3d

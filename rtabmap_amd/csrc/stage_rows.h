@@ -28,7 +28,7 @@ inline void unpack_rows(void* dst, const void* src, int64_t n, size_t dst_row, s
 // Regions of one staging buffer, in the order they are named: each starts at the 256-byte-aligned running sum of those before it (a region
 // of zero bytes takes no room), `bytes` is what one copy of all of them moves.  A fixed array: no allocation per call.
 struct RegionLayout {
-    static constexpr int MAX_REGIONS = 12;              // lcd_estimate_motion_pnp names nine outputs, lcd_register_icp ten
+    static constexpr int MAX_REGIONS = 16;              // lcd_estimate_motion_pnp names nine outputs, lcd_register_icp ten, lcd_register_icp_plane fifteen
     size_t off[MAX_REGIONS], len[MAX_REGIONS];
     int n = 0;
     size_t bytes = 0;

@@ -7,13 +7,14 @@
 #include <limits>
 
 #include "../../include/lcd.h"
-#include "../csrc/icp_rule.h"
+#include "../csrc/icp_plane_rule.h"
 
 namespace rtabmap_amd {
 
 namespace {
 
 namespace rule = lcd::icp;
+namespace plane = lcd::icpp;
 
 // SUM over the rows 0 .. n - 1 that has(i) holds for: lane (i mod LANES) adds e(i) in ascending order from +0, a row without is skipped; then
 // the halving tree
@@ -140,6 +141,80 @@ struct CpuBackend {
     }
 };
 
+// the backend of plane::solve as a loop: CpuBackend and the normals
+struct CpuPlaneBackend : CpuBackend {
+    std::vector<float> nrm_from, nrm_to;     // [n x 3]: the from-side's as given (behind register_normals: under F), the to-side's under the guess
+    std::vector<char> nfin_from, nfin_to;    // the rows whose given normal is finite
+    std::vector<char> cpart_from, cpart_to;  // the rows whose coordinates are finite
+    const float* raw_nrm_from;
+    std::vector<uint32_t> first;             // median_first()'s keys
+
+    int rows_from() const { return (int)std::count(cpart_from.begin(), cpart_from.end(), (char)1); }
+    int rows_to() const { return (int)std::count(cpart_to.begin(), cpart_to.end(), (char)1); }
+    int normal_sums(bool to_side, float sum[3]) {
+        const std::vector<float>& nrm = to_side ? nrm_to : nrm_from;
+        const std::vector<char>& fin = to_side ? nfin_to : nfin_from;
+        for (int a = 0; a < 3; ++a)
+            sum[a] = laneTreeSumIf((int)fin.size(), [&](int i) { return fin[(size_t)i] != 0; }, [&](int i) { return nrm[(size_t)3 * i + a]; });
+        return (int)std::count(fin.begin(), fin.end(), (char)1);
+    }
+    void normal_cov(bool to_side, const float mean[3], float C[6]) {
+        const std::vector<float>& nrm = to_side ? nrm_to : nrm_from;
+        const std::vector<char>& fin = to_side ? nfin_to : nfin_from;
+        for (int k = 0; k < 6; ++k)
+            C[k] = laneTreeSumIf((int)fin.size(), [&](int i) { return fin[(size_t)i] != 0; }, [&](int i) {
+                float e[6];
+                plane::cov_terms(&nrm[(size_t)3 * i], mean, e);
+                return e[k];
+            });
+    }
+    void participate(bool with_normals) {
+        for (int i = 0; i < from.n(); ++i) from.part[(size_t)i] = cpart_from[(size_t)i] && (!with_normals || nfin_from[(size_t)i]) ? 1 : 0;
+        for (int j = 0; j < to.n(); ++j) to.part[(size_t)j] = cpart_to[(size_t)j] && (!with_normals || nfin_to[(size_t)j]) ? 1 : 0;
+    }
+    bool fit_plane(float T[12]) {
+        const int n = from.n();
+        auto h = [&](int i) { return has(i); };
+        float S[plane::SUMS];
+        std::vector<float> E((size_t)n * plane::SUMS, 0.0f);
+        for (int i = 0; i < n; ++i)
+            if (has(i)) plane::plane_terms(from.row(i), to.row(from.nn[(size_t)i]), &nrm_to[(size_t)3 * from.nn[(size_t)i]], &E[(size_t)i * plane::SUMS]);
+        for (int k = 0; k < plane::SUMS; ++k) S[k] = laneTreeSumIf(n, h, [&](int i) { return E[(size_t)i * plane::SUMS + k]; });
+        for (int k = 0; k < 12; ++k) T[k] = 0.0f;
+        return plane::plane_fit(S, T);
+    }
+    void register_normals(const float F[12]) {
+        for (int i = 0; i < from.n(); ++i)
+            plane::rotate(F, raw_nrm_from[3 * i], raw_nrm_from[3 * i + 1], raw_nrm_from[3 * i + 2], nrm_from[(size_t)3 * i], nrm_from[(size_t)3 * i + 1],
+                          nrm_from[(size_t)3 * i + 2]);
+    }
+    int reciprocal_gated(bool from_is_target, bool gate, double min_cos) {
+        search(from, to, mode, h);
+        search(to, from, mode, h);
+        Cloud& src = from_is_target ? to : from;
+        const Cloud& tgt = from_is_target ? from : to;
+        const std::vector<float>& nsrc = from_is_target ? nrm_to : nrm_from;
+        const std::vector<float>& ntgt = from_is_target ? nrm_from : nrm_to;
+        first.clear();
+        int count = 0;
+        for (int i = 0; i < src.n(); ++i) {
+            const int row = src.nn[(size_t)i];
+            if (!rule::corresponds(row, src.d2[(size_t)i], thr2) || tgt.nn[(size_t)row] != i) continue;
+            first.push_back(lcd::m3d::bits_of(src.d2[(size_t)i]));
+            if (gate && !plane::gate_passes(&ntgt[(size_t)3 * row], &nsrc[(size_t)3 * i], min_cos)) continue;
+            ++count;
+            if (from_is_target) match[(size_t)row] = i;
+            else match[(size_t)i] = row;
+        }
+        first.resize((size_t)count);                                   // distances.resize(correspondencesOut), before the sort
+        return count;
+    }
+    float median_first(int n) {
+        std::nth_element(first.begin(), first.begin() + (n >> 1), first.end());
+        return lcd::m3d::float_of(first[(size_t)(n >> 1)]);
+    }
+};
+
 void fill(Cloud& c, const float* xyz, int n) {
     c.xyz.assign(xyz, xyz + (size_t)3 * n);
     c.part.resize((size_t)n); c.nn.assign((size_t)n, -1); c.d2.assign((size_t)n, 0.0f);
@@ -184,9 +259,59 @@ bool register_icp_cpu(const float* fromXyz, int nFrom, const float* toXyz, int n
     return true;
 }
 
+bool register_icp_plane_cpu(const float* fromXyz, const float* fromNormals, int nFrom, const float* toXyz, const float* toNormals, int nTo,
+                            const float guess[12], int maxIterations, bool force3DoF, int maxLaserScans, double maxCorrespondenceDistance, float epsilon,
+                            float correspondenceRatio, float minComplexity, int lowComplexityStrategy, bool normalGate, double minNormalCos, int search,
+                            bool deviceEntry, IcpPlaneResult& out) {
+    const double thr2 = maxCorrespondenceDistance * maxCorrespondenceDistance;
+    if (nFrom < 0 || nTo < 0 || nFrom > lcd::m3d::MAX_ROWS || nTo > lcd::m3d::MAX_ROWS || maxIterations < 1 || maxLaserScans < 0 ||
+        (search != rule::SEARCH_AUTO && search != rule::SEARCH_BRUTE && search != rule::SEARCH_GRID) || !std::isfinite(maxCorrespondenceDistance) || !(maxCorrespondenceDistance > 0.0) ||
+        !std::isfinite(thr2) || !std::isfinite(epsilon) || !(epsilon >= 0.0f) || !(correspondenceRatio >= 0.0f) || !(correspondenceRatio <= 1.0f) || !guess ||
+        !(minComplexity >= 0.0f) || !(minComplexity <= 1.0f) || lowComplexityStrategy < 0 || lowComplexityStrategy > 2 || (normalGate && !std::isfinite(minNormalCos)))
+        return false;
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(guess[k])) return false;
+    if ((nFrom > 0 && (!fromXyz || !fromNormals)) || (nTo > 0 && (!toXyz || !toNormals))) return false;
+    CpuPlaneBackend b;
+    fill(b.from, fromXyz, nFrom);
+    fill(b.to, toXyz, nTo);
+    if (!deviceEntry && (b.n_from() != nFrom || b.n_to() != nTo)) return false;
+    b.cpart_from = b.from.part; b.cpart_to = b.to.part;
+    b.nrm_from.assign(fromNormals, fromNormals + (size_t)3 * nFrom);
+    b.nrm_to.resize((size_t)3 * nTo);
+    b.nfin_from.resize((size_t)nFrom); b.nfin_to.resize((size_t)nTo);
+    for (int i = 0; i < nFrom; ++i) b.nfin_from[(size_t)i] = plane::finite3(fromNormals[3 * i], fromNormals[3 * i + 1], fromNormals[3 * i + 2]) ? 1 : 0;
+    for (int j = 0; j < nTo; ++j) {
+        rule::apply(guess, toXyz[3 * j], toXyz[3 * j + 1], toXyz[3 * j + 2], b.to.xyz[(size_t)3 * j], b.to.xyz[(size_t)3 * j + 1], b.to.xyz[(size_t)3 * j + 2]);
+        plane::rotate(guess, toNormals[3 * j], toNormals[3 * j + 1], toNormals[3 * j + 2], b.nrm_to[(size_t)3 * j], b.nrm_to[(size_t)3 * j + 1], b.nrm_to[(size_t)3 * j + 2]);
+        b.nfin_to[(size_t)j] = plane::finite3(toNormals[3 * j], toNormals[3 * j + 1], toNormals[3 * j + 2]) ? 1 : 0;
+    }
+    b.raw_from = fromXyz; b.raw_nrm_from = fromNormals; b.thr2 = thr2; b.mode = search; b.h = rule::cell_size(maxCorrespondenceDistance);
+    b.match.assign((size_t)nFrom, -1);
+    plane::Params p;
+    p.max_iterations = maxIterations; p.max_laser_scans = maxLaserScans; p.strategy = lowComplexityStrategy; p.force_3dof = force3DoF; p.gate = normalGate;
+    p.epsilon = epsilon; p.correspondence_ratio = correspondenceRatio; p.min_complexity = minComplexity; p.min_normal_cos = minNormalCos;
+    plane::Result res;
+    plane::solve(b, p, guess, res);
+    IcpPlaneResult r;
+    for (int k = 0; k < 12; ++k) { r.transform[k] = res.transform[k]; r.icpTransform[k] = res.icp[k]; r.correction[k] = res.correction[k]; }
+    r.status = res.status; r.stop = res.stop; r.iterations = res.iterations; r.correspondences = res.n_correspondences;
+    r.ratio = res.ratio; r.variance = res.variance;
+    r.match = b.match;
+    r.branch = res.branch; r.complexity = res.complexity; r.secondEigenvalue = res.second;
+    for (int k = 0; k < 3; ++k) r.complexityValues[k] = res.values[k];
+    for (int k = 0; k < 9; ++k) r.complexityVectors[k] = res.vectors[k];
+    out = r;
+    return true;
+}
+
 Transform3D RegistrationIcpHip::finish(const IcpResult& r, RegistrationInfoIcp& info) const {
     Transform3D transform;
     char msg[256];
+    if (r.status == LCD_ICP_LOW_COMPLEXITY) {                          // :569-577
+        snprintf(msg, sizeof msg, "Rejecting transform because too low complexity %f (Icp/PointToPlaneLowComplexityStrategy=0)", info.icpStructuralComplexity);
+        info.rejectedMsg = msg;
+        return transform;
+    }
     if (r.status != LCD_ICP_OK && r.status != LCD_ICP_BELOW_RATIO) {   // :962: icpT is null or the loop did not converge
         snprintf(msg, sizeof msg, "Cannot compute transform (converged=false var=%f)", r.variance);
         info.rejectedMsg = msg;
@@ -244,6 +369,40 @@ Transform3D RegistrationIcpHip::computeTransformation(lcd_engine* engine, const 
         return Transform3D();
     }
     r.status = status; r.stop = stop; r.iterations = iterations; r.correspondences = correspondences;
+    return finish(r, info);
+}
+
+Transform3D RegistrationIcpHip::computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, const std::vector<Point3f>& fromNormals,
+                                                      bool fromIs2d, const std::vector<Point3f>& toScan, const std::vector<Point3f>& toNormals, bool toIs2d,
+                                                      const Transform3D& guess, int maxLaserScans, RegistrationInfoIcp& info) const {
+    // :510-524: point to plane is ignored for 2-D scans and needs normals on both sides
+    if (!pointToPlane || fromIs2d || toIs2d || fromNormals.size() != fromScan.size() || toNormals.size() != toScan.size() || fromScan.empty() || toScan.empty())
+        return computeTransformation(engine, fromScan, toScan, guess, maxLaserScans, info);
+    info = RegistrationInfoIcp();
+    const int64_t fromOffsets[2] = {0, (int64_t)fromScan.size()}, toOffsets[2] = {0, (int64_t)toScan.size()};
+    IcpPlaneResult r;
+    r.match.assign(fromScan.size(), -1);
+    int32_t status = 0, stop = 0, iterations = 0, correspondences = 0, branch = 0;
+    lcd_icp_plane_args a;
+    a.struct_size = (int32_t)sizeof a; a.n_pairs = 1; a.max_iterations = maxIterations; a.force_3dof = force3DoF ? 1 : 0;
+    a.max_laser_scans = maxLaserScans; a.search = LCD_ICP_SEARCH_AUTO;
+    a.max_correspondence_distance = maxCorrespondenceDistance; a.epsilon = epsilon; a.correspondence_ratio = correspondenceRatio;
+    a.min_complexity = pointToPlaneMinComplexity; a.low_complexity_strategy = pointToPlaneLowComplexityStrategy;
+    a.normal_gate = maxRotation > 0.0f ? 1 : 0; a.reserved = 0;        // :268: maxCorrespondenceAngle <= 0 counts every correspondence
+    a.min_normal_cos = std::cos((double)maxRotation);                  // angle < max  <=>  cosine > cos(max)
+    a.from_xyz = &fromScan[0].x; a.to_xyz = &toScan[0].x; a.from_normals = &fromNormals[0].x; a.to_normals = &toNormals[0].x;
+    a.from_offsets = fromOffsets; a.to_offsets = toOffsets; a.guesses = guess.data;
+    a.out_transform = r.transform; a.out_icp_transform = r.icpTransform; a.out_correction = r.correction;
+    a.out_status = &status; a.out_stop = &stop; a.out_iterations = &iterations; a.out_n_correspondences = &correspondences;
+    a.out_ratio = &r.ratio; a.out_variance = &r.variance; a.out_match = r.match.data();
+    a.out_branch = &branch; a.out_complexity = &r.complexity; a.out_complexity_values = r.complexityValues; a.out_complexity_vectors = r.complexityVectors;
+    a.out_second_eigenvalue = &r.secondEigenvalue;
+    if (!engine || lcd_register_icp_plane(engine, &a) != LCD_OK) {
+        info.rejectedMsg = "the engine refused the call";
+        return Transform3D();
+    }
+    r.status = status; r.stop = stop; r.iterations = iterations; r.correspondences = correspondences; r.branch = branch;
+    info.icpStructuralComplexity = r.complexity;                       // :531
     return finish(r, info);
 }
 

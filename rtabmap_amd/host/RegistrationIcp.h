@@ -1,4 +1,5 @@
-// RegistrationIcp.h -- RegistrationIcp::computeTransformationImpl, the point-to-point branch with Icp/Strategy = 0 (RegistrationIcp.cpp:662-971),
+// RegistrationIcp.h -- RegistrationIcp::computeTransformationImpl with Icp/Strategy = 0: the point-to-point branch (RegistrationIcp.cpp:662-971) and
+// the point-to-plane branch with its complexity test and low-complexity fallback (:506-661, :785-853),
 // over the project's minimal types: the entry that hands the work to the engine (lcd_register_icp) and applies what the rule leaves to the
 // host (the Icp/MaxTranslation / Icp/MaxRotation gate over Euler angles, variance /= 10, the covariance), and register_icp_cpu, the whole rule
 // of include/lcd.h as plain host code for a process without a device.  The arithmetic is the engine's own (csrc/icp_rule.h, compiled here for
@@ -32,12 +33,25 @@ bool register_icp_cpu(const float* fromXyz, int nFrom, const float* toXyz, int n
                       int maxLaserScans, double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, int search, bool deviceEntry,
                       IcpResult& out);
 
+struct IcpPlaneResult : IcpResult {        // lcd_register_icp_plane's further outputs
+    int branch = 0;                      // 0 = point to plane, 1 = point-to-point fallback
+    float complexity = 0.0f, complexityValues[3] = {0, 0, 0}, complexityVectors[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, secondEigenvalue = 1.0f;
+};
+
+// The rule of lcd_register_icp_plane on the CPU (csrc/icp_plane_rule.h compiled for the host): one pair of 3-D scans with normals as [n x 3]
+// rows.  false (out untouched): what the entry refuses; deviceEntry as above.  A normal that is not finite is legal on both entries.
+// tools/sanitize_register_icp_plane.cpp drives it under the host sanitizers.
+bool register_icp_plane_cpu(const float* fromXyz, const float* fromNormals, int nFrom, const float* toXyz, const float* toNormals, int nTo,
+                            const float guess[12], int maxIterations, bool force3DoF, int maxLaserScans, double maxCorrespondenceDistance, float epsilon,
+                            float correspondenceRatio, float minComplexity, int lowComplexityStrategy, bool normalGate, double minNormalCos, int search,
+                            bool deviceEntry, IcpPlaneResult& out);
+
 // The grid form's cell of each of n coordinates under a correspondence distance, INT_MIN where a coordinate does not fit the key's cell range;
 // returns the cell size.  What the tests prove the one-cell margin of the grid with.
 float icp_cells(const float* x, int n, double maxCorrespondenceDistance, int* outCells);
 
 struct RegistrationInfoIcp {             // the fields of RegistrationInfo that the ICP step fills
-    float icpTranslation = 0.0f, icpRotation = 0.0f, icpInliersRatio = 0.0f;
+    float icpTranslation = 0.0f, icpRotation = 0.0f, icpInliersRatio = 0.0f, icpStructuralComplexity = 0.0f;
     int icpCorrespondences = 0;
     double covariance[36];               // row-major 6 x 6; the identity until a variance is known
     std::string rejectedMsg;
@@ -53,10 +67,19 @@ public:
     float epsilon = 0.0f;                        // Icp/Epsilon
     float correspondenceRatio = 0.1f;            // Icp/CorrespondenceRatio
     bool force3DoF = false;                      // Reg/Force3DoF
+    bool pointToPlane = true;                    // Icp/PointToPlane
+    float pointToPlaneMinComplexity = 0.02f;     // Icp/PointToPlaneMinComplexity
+    int pointToPlaneLowComplexityStrategy = 1;   // Icp/PointToPlaneLowComplexityStrategy
 
     // The reference's shape: both scans as point rows in their base frames, the guess, the scan's maximum number of points (0: the ratio is
     // relative).  A null transform when the registration is rejected (info.rejectedMsg says why) or the engine refuses the call.
     Transform3D computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, const std::vector<Point3f>& toScan, const Transform3D& guess,
+                                      int maxLaserScans, RegistrationInfoIcp& info) const;
+    // The same with the scans' normals (empty: the scan has none) and whether a scan is 2-D: with Icp/PointToPlane, two 3-D scans and normals on
+    // both sides the work goes to lcd_register_icp_plane (the complexity test, point to plane or the low-complexity fallback; the gate's
+    // cosine is cos(Icp/MaxRotation)) and info.icpStructuralComplexity is filled; every other pair goes to the call above, as RegistrationIcp.cpp:510-524 does.
+    Transform3D computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, const std::vector<Point3f>& fromNormals, bool fromIs2d,
+                                      const std::vector<Point3f>& toScan, const std::vector<Point3f>& toNormals, bool toIs2d, const Transform3D& guess,
                                       int maxLaserScans, RegistrationInfoIcp& info) const;
     // RegistrationIcp.cpp:856-961 behind the rule: what computeTransformation does with the engine's (or register_icp_cpu's) result
     Transform3D finish(const IcpResult& r, RegistrationInfoIcp& info) const;

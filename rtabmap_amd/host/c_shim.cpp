@@ -330,6 +330,50 @@ int hicp_compute(void* h, const float* fromXyz, int nFrom, const float* toXyz, i
     return icp_info_out(reg.computeTransformation(((VWDictionaryHip*)h)->engine(), from, to, g, maxLaserScans, info), info, outTransform, outInfo,
                         outCorrespondences, outCovariance);
 }
+// register_icp_plane_cpu (no engine involved).  outTransforms[36] and outScalars as hicp_cpu, outScalars[4] = branch; outComplexity[14] = complexity,
+// values[3], vectors[9], second eigenvalue.  1 = done, 0 = refused
+int hicpp_cpu(const float* fromXyz, const float* fromNormals, int nFrom, const float* toXyz, const float* toNormals, int nTo, const float* guess,
+              int maxIterations, int force3DoF, int maxLaserScans, double maxCorrespondenceDistance, float epsilon, float correspondenceRatio,
+              float minComplexity, int lowComplexityStrategy, int normalGate, double minNormalCos, int search, int deviceEntry, float* outTransforms,
+              int* outScalars, float* outRatio, double* outVariance, int* outMatch, float* outComplexity) {
+    IcpPlaneResult r;
+    if (!register_icp_plane_cpu(fromXyz, fromNormals, nFrom, toXyz, toNormals, nTo, guess, maxIterations, force3DoF != 0, maxLaserScans,
+                                maxCorrespondenceDistance, epsilon, correspondenceRatio, minComplexity, lowComplexityStrategy, normalGate != 0, minNormalCos,
+                                search, deviceEntry != 0, r)) return 0;
+    std::copy(r.transform, r.transform + 12, outTransforms);
+    std::copy(r.icpTransform, r.icpTransform + 12, outTransforms + 12);
+    std::copy(r.correction, r.correction + 12, outTransforms + 24);
+    outScalars[0] = r.status; outScalars[1] = r.stop; outScalars[2] = r.iterations; outScalars[3] = r.correspondences; outScalars[4] = r.branch;
+    *outRatio = r.ratio; *outVariance = r.variance;
+    std::copy(r.match.begin(), r.match.end(), outMatch);
+    outComplexity[0] = r.complexity;
+    std::copy(r.complexityValues, r.complexityValues + 3, outComplexity + 1);
+    std::copy(r.complexityVectors, r.complexityVectors + 9, outComplexity + 4);
+    outComplexity[13] = r.secondEigenvalue;
+    return 1;
+}
+// RegistrationIcpHip::computeTransformation with normals through the dictionary's engine; outputs as hicp_finish, outInfo[3] = icpStructuralComplexity
+int hicpp_compute(void* h, const float* fromXyz, const float* fromNormals, int nFrom, int fromIs2d, const float* toXyz, const float* toNormals, int nTo,
+                  int toIs2d, const float* guess, int maxIterations, int force3DoF, int maxLaserScans, double maxCorrespondenceDistance, float epsilon,
+                  float correspondenceRatio, float maxTranslation, float maxRotation, int pointToPlane, float minComplexity, int lowComplexityStrategy,
+                  float* outTransform, float* outInfo, int* outCorrespondences, double* outCovariance) {
+    auto rows = [](const float* x, int n) {
+        std::vector<Point3f> v((size_t)(x ? n : 0));
+        for (size_t i = 0; i < v.size(); ++i) v[i] = Point3f{x[3 * i], x[3 * i + 1], x[3 * i + 2]};
+        return v;
+    };
+    Transform3D g;
+    std::copy(guess, guess + 12, g.data);
+    RegistrationIcpHip reg;
+    reg.maxIterations = maxIterations; reg.force3DoF = force3DoF != 0; reg.maxCorrespondenceDistance = maxCorrespondenceDistance; reg.epsilon = epsilon;
+    reg.correspondenceRatio = correspondenceRatio; reg.maxTranslation = maxTranslation; reg.maxRotation = maxRotation;
+    reg.pointToPlane = pointToPlane != 0; reg.pointToPlaneMinComplexity = minComplexity; reg.pointToPlaneLowComplexityStrategy = lowComplexityStrategy;
+    RegistrationInfoIcp info;
+    const Transform3D t = reg.computeTransformation(((VWDictionaryHip*)h)->engine(), rows(fromXyz, nFrom), rows(fromNormals, nFrom), fromIs2d != 0,
+                                                    rows(toXyz, nTo), rows(toNormals, nTo), toIs2d != 0, g, maxLaserScans, info);
+    outInfo[3] = info.icpStructuralComplexity;
+    return icp_info_out(t, info, outTransform, outInfo, outCorrespondences, outCovariance);
+}
 // motion_pnp_cpu (no engine involved).  camera[4] = fx, fy, cx, cy; image[2]; local: 12 floats or null; guess: 12 floats or null; toXyz may be null.
 // outTransform[12], outScalars[4] = status, matches, inliers, variance kind; outVariance[2] = linear, cosine; outMatches / outInliers hold nTo ids.
 // 1 = done, 0 = refused

@@ -79,6 +79,8 @@ def lib():
         L.hicp_cells.restype = C.c_float
         L.hicp_finish.argtypes = [vp, vp, cf, C.c_double, cf, cf, cf, vp, vp, vp, vp]
         L.hicp_compute.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, cf, vp, vp, vp, vp]
+        L.hicpp_cpu.argtypes = [vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, ci, ci, C.c_double, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.hicpp_compute.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, cf, ci, cf, ci, vp, vp, vp, vp]
         L.hmem_select_error.argtypes = [vp]
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -288,6 +290,27 @@ def register_icp_cpu(from_xyz, to_xyz, guess=None, max_iterations=30, force_3dof
                 n_correspondences=int(sc[3]), ratio=ratio[0], variance=var[0], match=match[:fx.shape[0]].copy())
 
 
+def register_icp_plane_cpu(from_xyz, from_normals, to_xyz, to_normals, guess=None, max_iterations=30, force_3dof=False, max_laser_scans=0, search=0,
+                           max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1, min_complexity=0.02, low_complexity_strategy=1,
+                           normal_gate=False, min_normal_cos=0.0, device_entry=False):
+    """the rule of lcd_register_icp_plane on the CPU (host/RegistrationIcp.cpp, no device) -> register_icp_cpu's dict and branch, complexity,
+    complexity_values [3], complexity_vectors [9], second_eigenvalue; None where the call is refused"""
+    fx, tx, gs = _scan_arrays(from_xyz, to_xyz, guess)
+    fn, tn = np.ascontiguousarray(from_normals, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(to_normals, dtype=np.float32).reshape(-1, 3)
+    if fx.shape[0] > 8192 or tx.shape[0] > 8192 or fn.shape != fx.shape or tn.shape != tx.shape:
+        return None
+    t, sc, ratio, var = np.zeros(36, np.float32), np.zeros(5, np.int32), np.zeros(1, np.float32), np.zeros(1, np.float64)
+    match, cx = np.zeros(max(fx.shape[0], 1), np.int32), np.zeros(14, np.float32)
+    ok = lib().hicpp_cpu(_p(fx), _p(fn), fx.shape[0], _p(tx), _p(tn), tx.shape[0], _p(gs), int(max_iterations), int(bool(force_3dof)), int(max_laser_scans),
+                         float(max_correspondence_distance), float(epsilon), float(correspondence_ratio), float(min_complexity), int(low_complexity_strategy),
+                         int(bool(normal_gate)), float(min_normal_cos), int(search), int(bool(device_entry)), _p(t), _p(sc), _p(ratio), _p(var), _p(match), _p(cx))
+    if not ok:
+        return None
+    return dict(transform=t[:12].copy(), icp_transform=t[12:24].copy(), correction=t[24:].copy(), status=int(sc[0]), stop=int(sc[1]), iterations=int(sc[2]),
+                n_correspondences=int(sc[3]), ratio=ratio[0], variance=var[0], match=match[:fx.shape[0]].copy(), branch=int(sc[4]), complexity=cx[0],
+                complexity_values=cx[1:4].copy(), complexity_vectors=cx[4:13].copy(), second_eigenvalue=cx[13])
+
+
 def register_icp_cells(x, max_correspondence_distance):
     """the grid form's cell of every coordinate (csrc/icp_rule.h) -> (cells int64 with None-like INT_MIN where out of range, the cell size)"""
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
@@ -456,6 +479,24 @@ class VWDictionaryHip:
                                 float(max_correspondence_distance), float(epsilon), float(correspondence_ratio), float(max_translation), float(max_rotation),
                                 _p(t), _p(info), _p(corr), _p(cov))
         return _icp_info(ok, t, info, corr, cov)
+
+    def register_icp_normals(self, from_scan, from_normals, to_scan, to_normals, guess=None, from_is_2d=False, to_is_2d=False, max_laser_scans=0,
+                             max_iterations=30, force_3dof=False, max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1, max_translation=0.2,
+                             max_rotation=0.78, point_to_plane=True, min_complexity=0.02, low_complexity_strategy=1):
+        """RegistrationIcpHip::computeTransformation over scans with normals ([n x 3], None: the scan has none) and the Icp/PointToPlane* keys:
+        lcd_register_icp_plane for two 3-D scans with normals, register_icp's call otherwise -> (transform [12] or None, info dict with
+        icp_structural_complexity)"""
+        fx, tx, gs = _scan_arrays(from_scan, to_scan, guess)
+        fn = None if from_normals is None else np.ascontiguousarray(from_normals, dtype=np.float32).reshape(-1, 3)
+        tn = None if to_normals is None else np.ascontiguousarray(to_normals, dtype=np.float32).reshape(-1, 3)
+        t, info, corr, cov = np.zeros(12, np.float32), np.zeros(4, np.float32), np.zeros(1, np.int32), np.zeros(36, np.float64)
+        ok = lib().hicpp_compute(self.h, _p(fx), None if fn is None else _p(fn), fx.shape[0], int(bool(from_is_2d)), _p(tx), None if tn is None else _p(tn),
+                                 tx.shape[0], int(bool(to_is_2d)), _p(gs), int(max_iterations), int(bool(force_3dof)), int(max_laser_scans),
+                                 float(max_correspondence_distance), float(epsilon), float(correspondence_ratio), float(max_translation), float(max_rotation),
+                                 int(bool(point_to_plane)), float(min_complexity), int(low_complexity_strategy), _p(t), _p(info), _p(corr), _p(cov))
+        out = _icp_info(ok, t, info, corr, cov)
+        out[1]["icp_structural_complexity"] = info[3]
+        return out
 
     def update(self):
         lib().hvwd_update(self.h)

@@ -22,7 +22,12 @@ after the other; where one call of them over all pairs would take more than a th
 `cpu_pairs` pairs and scaled by pairs / cpu_pairs, which the output says.  The device entry's results are compared
 bit for bit with the round trip's (over the pairs it computed) before a number is reported.  The expectation -- the device entry's wall_ms,
 in a batch of 8 or more, no larger than the round trip's beyond that baseline's own spread over the rounds -- is evaluated and printed as it
-comes out.  One JSON line per case; --out also writes the table."""
+comes out.  One JSON line per case; --out also writes the table.
+
+--plane times lcd_register_icp_plane_dev instead, by the same method, on 1, 8 and 64 pairs of 2000 and 8000 3-D points with normals: dev_ms and
+wall_ms of the device entry, the host round trip through register_icp_plane_cpu (results compared bit for bit), the float64 point-to-plane ICP
+of tests/register_icp_plane_model.py over scipy's kd-tree, and lcd_register_icp_dev (point to point) on the same pairs; both device entries
+also per iteration of the pair that took the most (a call lasts as long as its slowest workgroup)."""
 import argparse
 import json
 import os
@@ -89,6 +94,125 @@ def curve(a, torch, rtabmap_amd, I, stream):
                     fh.write("\n".join(lines) + "\n")
 
 
+def plane(a, torch, rtabmap_amd, stream):
+    from rtabmap_amd import capi, vwdictionary as V
+    import register_icp_plane_inputs as IP
+    import register_icp_plane_model as MP
+    kw = dict(IP.KW)
+    p2p_kw = {k: kw[k] for k in ("max_iterations", "max_correspondence_distance", "epsilon", "correspondence_ratio")}
+    names = [k for k, _, _ in capi.Engine.ICP_PLANE_OUT] + ["match"]
+    tdt = {np.int32: torch.int32, np.float32: torch.float32, np.float64: torch.float64}
+    lines = []
+    for n in (2000, 8000):
+        for n_pairs in (1, 8, 64):
+            pairs = [IP.pair(n, n, 7000 + 64 * n + k, noise=0.005) for k in range(n_pairs)]
+            fx, fn, fo, tx, tn, to, gs = IP.concatenate(pairs)
+            eng = rtabmap_amd.Engine("f32", 64, stream=stream.cuda_stream)
+            with torch.cuda.stream(stream):
+                d_fx, d_fn, d_tx, d_tn = (torch.from_numpy(x).cuda() for x in (fx, fn, tx, tn))
+                d = {k: torch.zeros((n_pairs, w) if w else (n_pairs,), dtype=tdt[dt], device="cuda") for k, w, dt in capi.Engine.ICP_PLANE_OUT}
+                d["match"] = torch.zeros(fx.shape[0], dtype=torch.int32, device="cuda")
+                q = [torch.zeros((n_pairs, 12), device="cuda") for _ in range(3)] + [torch.zeros(n_pairs, dtype=torch.int32, device="cuda") for _ in range(4)] + \
+                    [torch.zeros(n_pairs, dtype=torch.float32, device="cuda"), torch.zeros(n_pairs, dtype=torch.float64, device="cuda"),
+                     torch.zeros(fx.shape[0], dtype=torch.int32, device="cuda")]
+            stream.synchronize()
+
+            def dev():
+                eng.register_icp_plane_dev(d_fx, d_fn, fo, d_tx, d_tn, to, gs, d, **kw)
+
+            def p2p():
+                eng.register_icp_dev(d_fx, fo, d_tx, to, gs, *q, **p2p_kw)
+
+            def events(call):
+                rounds = []
+                for rnd in range(a.rounds):
+                    t = []
+                    for i in range(a.warmup + a.reps):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        with torch.cuda.stream(stream):
+                            e0.record()
+                            call()
+                            e1.record()
+                        e1.synchronize()
+                        if i >= a.warmup:
+                            t.append(e0.elapsed_time(e1))
+                    rounds.append(float(np.median(t)))
+                return rounds
+
+            def wall(call, reps, warm, factor=1.0):
+                rounds = []
+                for rnd in range(a.rounds):
+                    t = []
+                    for i in range(warm + reps):
+                        stream.synchronize()
+                        t0 = time.perf_counter()
+                        call()
+                        stream.synchronize()
+                        if i >= warm:
+                            t.append((time.perf_counter() - t0) * 1e3 * factor)
+                    rounds.append(float(np.median(t)))
+                return rounds
+
+            def cpu(h):
+                out = []
+                for k in range(cpu_pairs):
+                    out.append(V.register_icp_plane_cpu(h[0][fo[k]:fo[k + 1]], h[1][fo[k]:fo[k + 1]], h[2][to[k]:to[k + 1]], h[3][to[k]:to[k + 1]], gs[k], **kw))
+                return out
+
+            def round_trip():
+                stream.synchronize()
+                res = cpu([x.cpu().numpy() for x in (d_fx, d_fn, d_tx, d_tn)])
+                with torch.cuda.stream(stream):
+                    back[0] = torch.from_numpy(np.stack([r["transform"] for r in res])).cuda()
+                return res
+
+            def kd64():
+                for p in pairs[:cpu_pairs]:
+                    MP.icp_plane64(p["from_xyz"], p["to_xyz"], p["to_normals"], p["guess"], max_iterations=kw["max_iterations"],
+                                   max_correspondence_distance=kw["max_correspondence_distance"])
+
+            back = [None]
+            cpu_pairs = 1
+            t0 = time.perf_counter()
+            first = round_trip()
+            one_pair = time.perf_counter() - t0
+            cpu_pairs = int(min(n_pairs, max(1, a.budget / 3 // max(one_pair, 1e-6))))
+            scale = n_pairs / cpu_pairs
+            cpu_reps = int(min(a.reps, max(3, a.budget // max(one_pair * cpu_pairs, 1e-6)))) if one_pair * cpu_pairs <= a.budget else 1
+            res = {"case": "%d x (3-D clouds with normals, %d points a side, at most 30 iterations)" % (n_pairs, n), "pairs": n_pairs, "points": n,
+                   "rounds": a.rounds, "reps": a.reps, "cpu_reps": cpu_reps, "cpu_pairs": cpu_pairs, "launches_per_call": 1}
+            res["plane dev_ms"] = summary(events(dev))
+            res["plane wall_ms"] = summary(wall(dev, a.reps, a.warmup))
+            res["point-to-point dev_ms"] = summary(events(p2p))
+            res["round trip wall_ms"] = summary(wall(round_trip, cpu_reps, 1 if cpu_reps > 1 else 0, scale))
+            res["kd-tree float64 wall_ms"] = summary(wall(kd64, cpu_reps, 1 if cpu_reps > 1 else 0, scale))
+            stream.synchronize()
+            got = {k: v.cpu().numpy() for k, v in d.items()}
+            for k, r in enumerate(round_trip()):                       # the two paths agree, bit for bit, on what was timed
+                for key in names[:-1]:
+                    assert np.array_equal(np.ascontiguousarray(got[key][k]).view(np.uint8), np.ascontiguousarray(r[key], got[key].dtype).view(np.uint8)), key
+                assert np.array_equal(got["match"][fo[k]:fo[k + 1]], r["match"])
+            it_plane, it_p2p = got["iterations"].tolist(), q[5].cpu().numpy().tolist()
+            res["iterations"] = {"plane": it_plane[:8], "point-to-point": it_p2p[:8], "branch": got["branch"].tolist()[:8]}
+            res["per iteration dev_ms"] = {"plane": round(res["plane dev_ms"]["median"] / max(max(it_plane), 1), 4),
+                                           "point-to-point": round(res["point-to-point dev_ms"]["median"] / max(max(it_p2p), 1), 4)}
+            base, dv = res["round trip wall_ms"], res["plane wall_ms"]
+            res["dev no slower than the round trip"] = bool(dv["median"] <= base["median"] + (base["high"] - base["low"]))
+            eng.close()
+            print(json.dumps(res), flush=True)
+            lines.append("    %s: CPU paths over %d of %d pairs%s, %d repetitions of them" % (res["case"], cpu_pairs, n_pairs, "" if cpu_pairs == n_pairs else " and scaled", cpu_reps))
+            lines.append("    iterations plane %s, point to point %s" % (it_plane[:8], it_p2p[:8]))
+            for k in ("plane dev_ms", "plane wall_ms", "point-to-point dev_ms", "round trip wall_ms", "kd-tree float64 wall_ms"):
+                v = res[k]
+                lines.append("    %-26s median %11.4f ms per call   rounds %11.4f .. %11.4f   per pair %10.4f ms" % (k, v["median"], v["low"], v["high"], v["median"] / n_pairs))
+            lines.append("    per iteration of the slowest pair: plane %.4f ms, point to point %.4f ms; dev no slower than the round trip beyond its spread: %s" %
+                         (res["per iteration dev_ms"]["plane"], res["per iteration dev_ms"]["point-to-point"], res["dev no slower than the round trip"]))
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "w") as fh:
+                    fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=60)
@@ -97,6 +221,7 @@ def main():
     ap.add_argument("--budget", type=float, default=1.5)
     ap.add_argument("--out", default="")
     ap.add_argument("--curve", action="store_true", help="only the two search forms' curves over the target size")
+    ap.add_argument("--plane", action="store_true", help="lcd_register_icp_plane_dev instead: 3-D clouds with normals")
     a = ap.parse_args()
     if a.reps < 50 or a.rounds < 5:
         sys.exit("bench_register_icp.py: at least 50 repetitions and 5 rounds")
@@ -112,6 +237,8 @@ def main():
     lines = []
     if a.curve:
         return curve(a, torch, rtabmap_amd, I, stream)
+    if a.plane:
+        return plane(a, torch, rtabmap_amd, stream)
     cases = [(flat, n, n_pairs, "") for flat, n in ((True, 360), (True, 1081), (False, 2000), (False, 8000)) for n_pairs in (1, 8, 64)]
     for flat, n, n_pairs, tag in cases:
         name = "%s%d x (%s, %d points a side, at most 30 iterations)" % (tag, n_pairs, "2-D scans" if flat else "3-D clouds", n)

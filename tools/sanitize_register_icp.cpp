@@ -22,9 +22,11 @@
 
 #include "RegistrationIcp.h"
 
-// RegistrationIcp.cpp's engine entry is linked but never called here
+// RegistrationIcp.cpp's engine entries are linked but never called here
 struct lcd_icp_args;
+struct lcd_icp_plane_args;
 extern "C" int lcd_register_icp(lcd_engine*, const lcd_icp_args*) { return 1; }
+extern "C" int lcd_register_icp_plane(lcd_engine*, const lcd_icp_plane_args*) { return 1; }
 
 using rtabmap_amd::IcpResult;
 using rtabmap_amd::register_icp_cpu;
