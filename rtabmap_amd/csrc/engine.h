@@ -326,7 +326,7 @@ struct lcd_engine {
     lcd::Bayes bayes;                                   // Bayes filter over the signature slots (bayes.h)
     lcd::DevBuf d_adj_scratch;                          // adjusted likelihood when the caller wants the posterior but not that vector
     lcd::DevBuf d_hyp_scratch;                          // hypothesis record when the caller only wants the adjusted vector
-    StatelessScratch pairs;                             // lcd_match_pairs, lcd_match_guided, lcd_select_features, lcd_expand_word_ids (stateless_scratch.h)
+    StatelessScratch pairs;                             // the scratch of every stateless call (stateless_scratch.h lists them)
 
     // ---- inverted index / TF-IDF
     lcd::Tfidf tfidf;

@@ -32,7 +32,7 @@ static inline hipError_t dreserve(lcd_engine* h, lcd::DevBuf& b, size_t bytes, s
 static inline size_t host_row_bytes(const lcd_engine* h) { return (size_t)h->dim * (h->dtype == LCD_F32 ? 4 : 1); }
 static inline bool rows_padded(const lcd_engine* h) { return (size_t)h->row_bytes != host_row_bytes(h); }
 
-// The body of a stateless entry point and of its _dev form (pair_match.hip, guided_match.hip, feature_select.hip): nothing is drained, the
+// The body of a stateless entry point and of its _dev form (stateless_scratch.h lists the calls): nothing is drained, the
 // roctx range carries the base name for both
 template <typename Args>
 static inline int stateless_entry(lcd_engine* h, const char* name, int (*call)(lcd_engine*, const Args*, bool), const Args* a, bool on_device) {

@@ -345,7 +345,8 @@ inline size_t select_lds(int p_max, int n_cells) { return ((size_t)padded(p_max)
 inline size_t ssc_lds(int p_max) { return ((size_t)p_max * 14 + (size_t)p_max / 8 + MAX_WAVES * 4 + 15) & ~(size_t)15; }   // (the keys, 9 p_max bytes, fit below)
 inline size_t expand_lds(int n_max) { return ((size_t)n_max * 4 + MAX_WAVES * 4 + 15) & ~(size_t)15; }
 
-// the largest frames need more than the default 64 KiB of dynamic LDS
+// the largest frames need more than the default 64 KiB of dynamic LDS.  (Not motion_group.cuh's allow_large_lds<kernel>: that sets one
+// limit for every kernel, these three each need their own.)
 void allow_large_lds() {
     static const bool once = [] {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&feature_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -483,22 +484,15 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
     g.out_count = a->out_count; g.out_index = a->out_index; g.out_rows = a->out_rows; g.out_aux = a->out_aux;
 
     // ---- host entry: everything to the device, results back at the end (one synchronisation)
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    int o_rows = 0, o_aux = 0;                                        // copied back by hand: only what each frame selected
-    if (!on_device) {
-        const size_t aux_bytes = with_aux ? (size_t)N * a->aux_bytes : 0;
-        const int i_resp = stage.add_in(a->response, (size_t)N * 4), i_pts = stage.add_in(a->points, with_points ? (size_t)N * 8 : 0);
-        const int i_rows = stage.add_in_rows(a->rows, with_rows ? N : 0), i_aux = stage.add_in(a->aux, aux_bytes);
-        const int i_n = stage.add_in(a->n_in, a->n_in ? (size_t)nf * 4 : 0);
-        const int o_count = stage.add_out(a->out_count, (size_t)nf * 4), o_index = stage.add_out(a->out_index, (size_t)N * 4);
-        o_rows = stage.add_out(nullptr, with_rows ? (size_t)N * h->row_bytes : 0); o_aux = stage.add_out(nullptr, aux_bytes);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        g.response = stage.in<float>(i_resp); g.points = with_points ? stage.in<float2>(i_pts) : nullptr;
-        g.rows = with_rows ? stage.in<char>(i_rows) : nullptr; g.aux = with_aux ? stage.in<char>(i_aux) : nullptr;
-        g.n_in = a->n_in ? stage.in<int32_t>(i_n) : nullptr;
-        g.out_count = stage.out<int32_t>(o_count); g.out_index = stage.out<int32_t>(o_index);
-        g.out_rows = stage.out<char>(o_rows); g.out_aux = stage.out<char>(o_aux);
-    }
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    const size_t aux_bytes = with_aux ? (size_t)N * a->aux_bytes : 0;
+    stage.in(g.response, (size_t)N * 4); stage.in(g.points, with_points ? (size_t)N * 8 : 0);
+    stage.in_rows(g.rows, N); stage.in(g.aux, aux_bytes);
+    stage.in(g.n_in, (size_t)nf * 4);                                  // optional: null stays null
+    stage.out(g.out_count, (size_t)nf * 4); stage.out(g.out_index, (size_t)N * 4);
+    const int o_rows = stage.out_kept(g.out_rows, with_rows ? (size_t)N * h->row_bytes : 0);     // handed out below: only what each frame selected
+    const int o_aux = stage.out_kept(g.out_aux, aux_bytes);
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
     g.row_vec = g.rows && g.row_bytes % 16 == 0 && aligned16(g.rows) && aligned16(g.out_rows) ? 16 : 4;
     g.aux_vec = g.aux && g.aux_bytes % 16 == 0 && aligned16(g.aux) && aligned16(g.out_aux) ? 16 : 4;
 
@@ -514,13 +508,9 @@ int select_features(lcd_engine* h, const lcd_select_args* a, bool on_device) {
         feature_select_kernel<<<dim3((unsigned)nf), dim3((unsigned)block), select_lds(g.p_max, a->grid_rows * a->grid_cols), st>>>(g);
     }
     LCD_HIP(h, hipGetLastError());
-    if (on_device) return LCD_OK;
     LCD_HIP(h, stage.finish(st));
-    for (int f = 0; f < nf && (with_rows || with_aux); ++f) {          // only what the frame wrote: the rest of its region stays as it was
-        const size_t cnt = (size_t)a->out_count[f], first = (size_t)off[f], host_row = host_row_bytes(h), row = (size_t)h->row_bytes;
-        if (with_rows) unpack_rows((char*)a->out_rows + first * host_row, stage.host_out(o_rows) + first * row, (int64_t)cnt, host_row, row);
-        if (with_aux && cnt) std::memcpy((char*)a->out_aux + first * a->aux_bytes, stage.host_out(o_aux) + first * a->aux_bytes, cnt * a->aux_bytes);
-    }
+    stage.hand_out_rows(o_rows, a->out_count, off, nf);                // only what the frame wrote: the rest of its region stays as it was
+    stage.hand_out(o_aux, a->out_count, off, nf, (size_t)a->aux_bytes);
     return LCD_OK;
 }
 
@@ -553,24 +543,17 @@ int expand_word_ids(lcd_engine* h, const lcd_expand_args* a, bool on_device) {
     ExpandArgs g;
     g.count = a->count; g.index = a->index; g.word_ids = a->word_ids; g.first_new_word_id = a->first_new_word_id; g.out_word_ids = a->out_word_ids;
     g.n_features = a->n_features;
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    if (!on_device) {
-        const int i_count = stage.add_in(a->count, (size_t)nf * 4), i_index = stage.add_in(a->index, (size_t)N * 4);
-        const int i_words = stage.add_in(a->word_ids, (size_t)N * 4), i_first = stage.add_in(a->first_new_word_id, a->first_new_word_id ? (size_t)nf * 4 : 0);
-        const int i_n = stage.add_in(a->n_features, a->n_features ? (size_t)nf * 4 : 0);
-        const int o_words = stage.add_out(a->out_word_ids, (size_t)N * 4);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        g.count = stage.in<int32_t>(i_count); g.index = stage.in<int32_t>(i_index); g.word_ids = stage.in<int32_t>(i_words);
-        g.first_new_word_id = a->first_new_word_id ? stage.in<int32_t>(i_first) : nullptr;
-        g.n_features = a->n_features ? stage.in<int32_t>(i_n) : nullptr;
-        g.out_word_ids = stage.out<int32_t>(o_words);
-    }
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    stage.in(g.count, (size_t)nf * 4); stage.in(g.index, (size_t)N * 4); stage.in(g.word_ids, (size_t)N * 4);
+    stage.in(g.first_new_word_id, (size_t)nf * 4); stage.in(g.n_features, (size_t)nf * 4);      // optional: null stays null
+    stage.out(g.out_word_ids, (size_t)N * 4);
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(FrameJob)));
     allow_large_lds();
     const int block = n_max > SMALL_FRAME ? BIG_BLOCK : SMALL_BLOCK;
     expand_word_ids_kernel<<<dim3((unsigned)nf), dim3((unsigned)block), expand_lds(n_max), st>>>(g, n_max);
     LCD_HIP(h, hipGetLastError());
-    if (!on_device) LCD_HIP(h, stage.finish(st));
+    LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 

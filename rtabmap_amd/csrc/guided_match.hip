@@ -257,19 +257,14 @@ int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
     g.out_count = a->out_count; g.out_match = a->out_match; g.out_dist = a->out_dist; g.out_to_owner = (uint32_t*)a->out_to_owner;
 
     // ---- host entry: rows, points and corners to the device, results back at the end (one synchronisation)
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    if (!on_device) {
-        const int i_from = stage.add_in_rows(a->from, nfrom), i_to = stage.add_in_rows(a->to, nto);
-        const int i_cor = stage.add_in(a->corners, (size_t)ncor * 8), i_cfr = stage.add_in(a->corner_from_row, (size_t)ncor * 4);
-        const int i_pts = stage.add_in(a->to_points, (size_t)nto * 8);
-        const int o_count = stage.add_out(a->out_count, (size_t)nquery * 4), o_match = stage.add_out(a->out_match, (size_t)nquery * 4);
-        const int o_dist = stage.add_out(a->out_dist, (size_t)nquery * 8), o_owner = stage.add_out(p2f ? a->out_to_owner : nullptr, (size_t)nto * 4);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        g.from = stage.in<char>(i_from); g.to = stage.in<char>(i_to);
-        g.corners = stage.in<float2>(i_cor); g.corner_from_row = stage.in<int32_t>(i_cfr); g.to_points = stage.in<float2>(i_pts);
-        g.out_count = stage.out<int32_t>(o_count); g.out_match = stage.out<int32_t>(o_match);
-        g.out_dist = a->out_dist ? stage.out<float>(o_dist) : nullptr; g.out_to_owner = stage.out<uint32_t>(o_owner);
-    }
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    stage.in_rows(g.from, nfrom); stage.in_rows(g.to, nto);
+    stage.in(g.corners, (size_t)ncor * 8); stage.in(g.corner_from_row, (size_t)ncor * 4);
+    stage.in(g.to_points, (size_t)nto * 8);
+    stage.out(g.out_count, (size_t)nquery * 4); stage.out(g.out_match, (size_t)nquery * 4);
+    stage.out(g.out_dist, (size_t)nquery * 8);                         // optional: null stays null
+    stage.out(g.out_to_owner, p2f ? (size_t)nto * 4 : 0);              // the first-come rule's alone: no other direction touches it
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
 
     // ---- the job table: one entry per pair
     std::vector<GuidedJob> jobs((size_t)np);
@@ -285,7 +280,7 @@ int match_guided(lcd_engine* h, const lcd_guided_args* a, bool on_device) {
 
     if (p2f && nto > 0) LCD_HIP(h, hipMemsetAsync(g.out_to_owner, 0xFF, (size_t)nto * 4, st));      // -1: nobody's
     LCD_HIP(h, launch_guided(h->dtype, h->kdim, g, blocks, st));
-    if (!on_device) LCD_HIP(h, stage.finish(st));
+    LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 

@@ -194,11 +194,11 @@ int keypoints_3d(lcd_engine* h, const lcd_keypoints_3d_args* a, bool on_device) 
     g.out_rows = a->out_rows; g.out_aux = a->out_aux;
 
     // ---- host entry: everything to the device (every distinct image once, its rows packed), results back at the end (one synchronisation)
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
     std::vector<unsigned char> packed;
-    int o_xyz = 0, o_pts = 0, o_resp = 0, o_rows = 0, o_aux = 0;      // copied back by hand: only what each frame kept
+    std::vector<size_t> at;                                            // where each frame's image lies in `packed`
     if (!on_device) {
-        std::vector<size_t> at((size_t)nf);
+        at.resize((size_t)nf);
         for (int f = 0; f < nf; ++f) {
             const lcd_depth_image& D = a->images[f];
             int same = -1;
@@ -215,23 +215,19 @@ int keypoints_3d(lcd_engine* h, const lcd_keypoints_3d_args* a, bool on_device) 
             }
             jobs[(size_t)f].image.pitch = (int64_t)row;
         }
-        const size_t aux_bytes = g.aux ? (size_t)N * a->aux_bytes : 0;
-        const int i_pts = stage.add_in(a->points, (size_t)N * 8), i_resp = stage.add_in(a->response, g.response ? (size_t)N * 4 : 0);
-        const int i_rows = stage.add_in_rows(a->rows, g.rows ? N : 0), i_aux = stage.add_in(a->aux, aux_bytes);
-        const int i_img = stage.add_in(packed.data(), packed.size());
-        const int o_count = stage.add_out(a->out_count, (size_t)nf * 4), o_index = stage.add_out(a->out_index, (size_t)N * 4);
-        o_xyz = stage.add_out(nullptr, with_xyz ? (size_t)N * 12 : 0); o_pts = stage.add_out(nullptr, filtered ? (size_t)N * 8 : 0);
-        o_resp = stage.add_out(nullptr, g.response ? (size_t)N * 4 : 0);
-        o_rows = stage.add_out(nullptr, g.rows ? (size_t)N * h->row_bytes : 0); o_aux = stage.add_out(nullptr, aux_bytes);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        for (int f = 0; f < nf; ++f) jobs[(size_t)f].image.data = stage.in<unsigned char>(i_img) + at[(size_t)f];
-        g.points = stage.in<float2>(i_pts); g.response = g.response ? stage.in<float>(i_resp) : nullptr;
-        g.rows = g.rows ? stage.in<char>(i_rows) : nullptr; g.aux = g.aux ? stage.in<char>(i_aux) : nullptr;
-        g.out_count = stage.out<int32_t>(o_count); g.out_index = stage.out<int32_t>(o_index);
-        g.out_xyz = with_xyz ? stage.out<float>(o_xyz) : nullptr; g.out_points = filtered ? stage.out<float2>(o_pts) : nullptr;
-        g.out_response = g.response ? stage.out<float>(o_resp) : nullptr;
-        g.out_rows = stage.out<char>(o_rows); g.out_aux = stage.out<char>(o_aux);
     }
+    const size_t aux_bytes = g.aux ? (size_t)N * a->aux_bytes : 0;
+    const unsigned char* images = packed.data();
+    stage.in(g.points, (size_t)N * 8); stage.in(g.response, (size_t)N * 4);
+    stage.in_rows(g.rows, N); stage.in(g.aux, aux_bytes);
+    stage.in(images, packed.size());                                   // a plain region: behind commit(), `images` is where it lies on the device
+    stage.out(g.out_count, (size_t)nf * 4); stage.out(g.out_index, (size_t)N * 4);
+    // handed out below: only what each frame kept
+    const int o_xyz = stage.out_kept(g.out_xyz, (size_t)N * 12), o_pts = stage.out_kept(g.out_points, (size_t)N * 8);
+    const int o_resp = stage.out_kept(g.out_response, (size_t)N * 4);
+    const int o_rows = stage.out_kept(g.out_rows, g.rows ? (size_t)N * h->row_bytes : 0), o_aux = stage.out_kept(g.out_aux, aux_bytes);
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
+    for (size_t f = 0; f < at.size(); ++f) jobs[f].image.data = images + at[f];
     g.row_vec = g.rows && g.row_bytes % 16 == 0 && aligned16(g.rows) && aligned16(g.out_rows) ? 16 : 4;
     g.aux_vec = g.aux && g.aux_bytes % 16 == 0 && aligned16(g.aux) && aligned16(g.out_aux) ? 16 : 4;
 
@@ -240,17 +236,10 @@ int keypoints_3d(lcd_engine* h, const lcd_keypoints_3d_args* a, bool on_device) 
     g.cameras = reinterpret_cast<const kp3d::Camera*>(reinterpret_cast<const char*>(g.jobs) + job_bytes);
     keypoints_3d_kernel<<<dim3((unsigned)nf), dim3(BLOCK), 0, st>>>(g);
     LCD_HIP(h, hipGetLastError());
-    if (on_device) return LCD_OK;
     LCD_HIP(h, stage.finish(st));
-    for (int f = 0; f < nf; ++f) {                                     // only what the frame wrote: the rest of its region stays as it was
-        const size_t cnt = (size_t)a->out_count[f], first = (size_t)off[f], host_row = host_row_bytes(h), row = (size_t)h->row_bytes;
-        if (!cnt) continue;
-        if (with_xyz) std::memcpy(a->out_xyz + first * 3, stage.host_out(o_xyz) + first * 12, cnt * 12);
-        if (filtered) std::memcpy(a->out_points + first * 2, stage.host_out(o_pts) + first * 8, cnt * 8);
-        if (g.out_response) std::memcpy(a->out_response + first, stage.host_out(o_resp) + first * 4, cnt * 4);
-        if (g.rows) unpack_rows((char*)a->out_rows + first * host_row, stage.host_out(o_rows) + first * row, (int64_t)cnt, host_row, row);
-        if (g.aux) std::memcpy((char*)a->out_aux + first * a->aux_bytes, stage.host_out(o_aux) + first * a->aux_bytes, cnt * a->aux_bytes);
-    }
+    // only what the frame wrote: the rest of its region stays as it was
+    stage.hand_out(o_xyz, a->out_count, off, nf, 12); stage.hand_out(o_pts, a->out_count, off, nf, 8); stage.hand_out(o_resp, a->out_count, off, nf, 4);
+    stage.hand_out_rows(o_rows, a->out_count, off, nf); stage.hand_out(o_aux, a->out_count, off, nf, (size_t)a->aux_bytes);
     return LCD_OK;
 }
 

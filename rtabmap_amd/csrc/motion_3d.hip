@@ -218,27 +218,21 @@ int estimate_motion_3d(lcd_engine* h, const lcd_motion_3d_args* a, bool on_devic
     g.out_variance = a->out_variance; g.out_matches = a->out_matches; g.out_inliers = a->out_inliers;
 
     // ---- host entry: everything to the device, results back at the end (one synchronisation)
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    if (!on_device) {
-        const int i_fi = stage.add_in(a->from_word_ids, (size_t)Nf * 4), i_fx = stage.add_in(a->from_xyz, (size_t)Nf * 12);
-        const int i_ti = stage.add_in(a->to_word_ids, (size_t)Nt * 4), i_tx = stage.add_in(a->to_xyz, (size_t)Nt * 12);
-        const int o_t = stage.add_out(a->out_transform, (size_t)np * 48), o_s = stage.add_out(a->out_status, (size_t)np * 4);
-        const int o_nm = stage.add_out(a->out_n_matches, (size_t)np * 4), o_ni = stage.add_out(a->out_n_inliers, (size_t)np * 4);
-        const int o_v = stage.add_out(a->out_variance, (size_t)np * 8);
-        const int o_m = stage.add_out(a->out_matches, (size_t)Nf * 4), o_i = stage.add_out(a->out_inliers, (size_t)Nf * 4);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        g.from_ids = stage.in<int32_t>(i_fi); g.from_xyz = stage.in<float>(i_fx); g.to_ids = stage.in<int32_t>(i_ti); g.to_xyz = stage.in<float>(i_tx);
-        g.out_transform = stage.out<float>(o_t); g.out_status = stage.out<int32_t>(o_s); g.out_n_matches = stage.out<int32_t>(o_nm);
-        g.out_n_inliers = stage.out<int32_t>(o_ni); g.out_variance = stage.out<double>(o_v);
-        g.out_matches = stage.out<int32_t>(o_m); g.out_inliers = stage.out<int32_t>(o_i);
-    }
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    stage.in(g.from_ids, (size_t)Nf * 4); stage.in(g.from_xyz, (size_t)Nf * 12);
+    stage.in(g.to_ids, (size_t)Nt * 4); stage.in(g.to_xyz, (size_t)Nt * 12);
+    stage.out(g.out_transform, (size_t)np * 48); stage.out(g.out_status, (size_t)np * 4);
+    stage.out(g.out_n_matches, (size_t)np * 4); stage.out(g.out_n_inliers, (size_t)np * 4);
+    stage.out(g.out_variance, (size_t)np * 8);
+    stage.out(g.out_matches, (size_t)Nf * 4); stage.out(g.out_inliers, (size_t)Nf * 4);
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
     LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(Nf, 1) * SCRATCH_WORDS * 4));
     g.scratch = S.d_small.as<uint32_t>();
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(M3dJob)));
     allow_large_lds<&motion_3d_kernel>();
     motion_3d_kernel<<<dim3((unsigned)np), dim3(BLOCK), plan.lds, st>>>(g);
     LCD_HIP(h, hipGetLastError());
-    if (!on_device) LCD_HIP(h, stage.finish(st));
+    LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 

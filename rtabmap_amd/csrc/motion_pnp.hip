@@ -324,31 +324,23 @@ int estimate_motion_pnp(lcd_engine* h, const lcd_motion_pnp_args* a, bool on_dev
     g.out_matches = a->out_matches; g.out_inliers = a->out_inliers;
 
     // ---- host entry: everything to the device, results back at the end (one synchronisation)
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    if (!on_device) {
-        const int i_fi = stage.add_in(a->from_word_ids, (size_t)Nf * 4), i_fx = stage.add_in(a->from_xyz, (size_t)Nf * 12);
-        const int i_ti = stage.add_in(a->to_word_ids, (size_t)Nt * 4), i_tp = stage.add_in(a->to_points, (size_t)Nt * 8);
-        const int i_tx = stage.add_in(a->to_xyz, has_to ? (size_t)Nt * 12 : 0);
-        const int o_t = stage.add_out(a->out_transform, (size_t)np * 48), o_s = stage.add_out(a->out_status, (size_t)np * 4);
-        const int o_nm = stage.add_out(a->out_n_matches, (size_t)np * 4), o_ni = stage.add_out(a->out_n_inliers, (size_t)np * 4);
-        const int o_vl = stage.add_out(a->out_variance_lin, (size_t)np * 8), o_vc = stage.add_out(a->out_angle_cos, (size_t)np * 8);
-        const int o_vk = stage.add_out(a->out_variance_kind, (size_t)np * 4);
-        const int o_m = stage.add_out(a->out_matches, (size_t)Nt * 4), o_i = stage.add_out(a->out_inliers, (size_t)Nt * 4);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        g.from_ids = stage.in<int32_t>(i_fi); g.from_xyz = stage.in<float>(i_fx); g.to_ids = stage.in<int32_t>(i_ti); g.to_points = stage.in<float>(i_tp);
-        g.to_xyz = has_to ? stage.in<float>(i_tx) : nullptr;
-        g.out_transform = stage.out<float>(o_t); g.out_status = stage.out<int32_t>(o_s); g.out_n_matches = stage.out<int32_t>(o_nm);
-        g.out_n_inliers = stage.out<int32_t>(o_ni); g.out_variance_lin = stage.out<double>(o_vl); g.out_angle_cos = stage.out<double>(o_vc);
-        g.out_variance_kind = stage.out<int32_t>(o_vk);
-        g.out_matches = stage.out<int32_t>(o_m); g.out_inliers = stage.out<int32_t>(o_i);
-    }
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    stage.in(g.from_ids, (size_t)Nf * 4); stage.in(g.from_xyz, (size_t)Nf * 12);
+    stage.in(g.to_ids, (size_t)Nt * 4); stage.in(g.to_points, (size_t)Nt * 8);
+    stage.in(g.to_xyz, (size_t)Nt * 12);                               // optional: null stays null
+    stage.out(g.out_transform, (size_t)np * 48); stage.out(g.out_status, (size_t)np * 4);
+    stage.out(g.out_n_matches, (size_t)np * 4); stage.out(g.out_n_inliers, (size_t)np * 4);
+    stage.out(g.out_variance_lin, (size_t)np * 8); stage.out(g.out_angle_cos, (size_t)np * 8);
+    stage.out(g.out_variance_kind, (size_t)np * 4);
+    stage.out(g.out_matches, (size_t)Nt * 4); stage.out(g.out_inliers, (size_t)Nt * 4);
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
     LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(Nt, 1) * SCRATCH_WORDS * 4));
     g.scratch = S.d_small.as<uint32_t>();
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(PnpJob)));
     allow_large_lds<&motion_pnp_kernel>();
     motion_pnp_kernel<<<dim3((unsigned)np), dim3(BLOCK), plan.lds, st>>>(g);
     LCD_HIP(h, hipGetLastError());
-    if (!on_device) LCD_HIP(h, stage.finish(st));
+    LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 

@@ -332,16 +332,11 @@ int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
     const void* d_from = a->from; const void* d_to = a->to; const int32_t* d_ids = with_ids ? a->from_word_ids : nullptr;
     int32_t* d_out_a = dict ? a->out_from_word_ids : a->out_to_match;      // per from-row (dictionary) / per to-row (cross-check)
     void* d_out_b = dict ? (void*)a->out_to_word_ids : (void*)a->out_to_dist;
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    if (!on_device) {
-        const int i_from = stage.add_in_rows(a->from, nfrom), i_to = stage.add_in_rows(a->to, nto);
-        const int i_ids = stage.add_in(a->from_word_ids, with_ids ? (size_t)nfrom * 4 : 0);
-        const int o_a = stage.add_out(d_out_a, (size_t)(dict ? nfrom : nto) * 4), o_b = stage.add_out(d_out_b, (size_t)nto * 4);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        d_from = stage.in<char>(i_from); d_to = stage.in<char>(i_to); d_ids = with_ids ? stage.in<int32_t>(i_ids) : nullptr;
-        d_out_a = stage.out<int32_t>(o_a);
-        d_out_b = (!dict && !a->out_to_dist) ? nullptr : stage.out<void>(o_b);
-    }
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    stage.in_rows(d_from, nfrom); stage.in_rows(d_to, nto);
+    stage.in(d_ids, (size_t)nfrom * 4);
+    stage.out(d_out_a, (size_t)(dict ? nfrom : nto) * 4); stage.out(d_out_b, (size_t)nto * 4);    // (cross-check without out_to_dist: null stays null)
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
     MatchArgs m;
     LCD_HIP(h, S.ones_row(&m.ones, MAX_SIDE / 8, st, &h->bytes_device));
 
@@ -391,7 +386,7 @@ int match_pairs(lcd_engine* h, const lcd_match_args* a, bool on_device) {
         LCD_HIP(h, hipGetLastError());
         p0 = p;
     }
-    if (!on_device) LCD_HIP(h, stage.finish(st));
+    LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 

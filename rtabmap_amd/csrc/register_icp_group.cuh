@@ -1,10 +1,14 @@
 // register_icp_group.cuh -- what the one-workgroup-per-pair registration kernels of register_icp.hip and register_icp_plane.hip share, each piece
 // once: the job table's row, a side of the pair in the call's scratch, and the backend of icp::solve as a workgroup -- the staging of a search's
 // target in LDS in both forms, the two searches, the sums of a point-to-point fit, the reciprocal test and the median.  A kernel sets the
-// backend's pointers into its own carve.  Everything is inlined.  Internal.
+// backend's pointers into its own carve.  Everything is inlined.  Behind the backend, the frame of the two host entries: the refusals both
+// make, the job table's fill, the ten outputs both have and their staging.  Internal.
 #pragma once
 #include "icp_rule.h"
 #include "motion_group.cuh"
+
+#include <cmath>
+#include <vector>
 
 namespace lcd {
 
@@ -20,6 +24,29 @@ struct IcpJob {
     float guess[12];
 };
 static_assert(sizeof(IcpJob) == 72, "the job table");
+
+// the ten outputs both calls have, as the kernel arguments of either embed them
+struct IcpOutputs {
+    float* out_transform; float* out_icp_transform; float* out_correction;
+    int32_t* out_status; int32_t* out_stop; int32_t* out_iterations; int32_t* out_n_correspondences;
+    float* out_ratio; double* out_variance; int32_t* out_match;
+};
+// thread 0's write of pair p's result (icp::Result or icpp::Result: the fields of the same names); out_match is the backend's
+template <class R>
+__device__ __forceinline__ void write_result(const IcpOutputs& o, size_t p, const R& r) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        o.out_transform[p * 12 + k] = r.transform[k];
+        o.out_icp_transform[p * 12 + k] = r.icp[k];
+        o.out_correction[p * 12 + k] = r.correction[k];
+    }
+    o.out_status[p] = r.status;
+    o.out_stop[p] = r.stop;
+    o.out_iterations[p] = r.iterations;
+    o.out_n_correspondences[p] = r.n_correspondences;
+    o.out_ratio[p] = r.ratio;
+    o.out_variance[p] = r.variance;
+}
 
 
 __device__ __forceinline__ bool bit_of(const uint32_t* mask, int i) { return (mask[i >> 5] >> (i & 31)) & 1u; }
@@ -54,6 +81,30 @@ struct GroupBackend : Group {
 
     __device__ __forceinline__ int n_from() const { return np_from; }
     __device__ __forceinline__ int n_to() const { return np_to; }
+
+    // The coordinate half of a kernel's first phase, one trip over either side: the from-rows as given to the scratch planes (P_0), Q =
+    // guess(to-rows) likewise, one bit a row that takes part into the masks (cleared by the kernel, behind a barrier), out_match = -1.
+    // from_row(i) / to_row(j) are called in the same trip by the thread that owns the row (the plane kernel's normals).  Ends behind a barrier.
+    template <class FromRow, class ToRow>
+    __device__ __forceinline__ void load_rows(const float* raw_to, const float guess[12], uint32_t* mask_f, uint32_t* mask_t, FromRow from_row, ToRow to_row) {
+        const int nf = from.n, nt = to.n;
+        for (int i = tid; i < nf; i += BLOCK) {
+            const float x = raw_from[(size_t)3 * i], y = raw_from[(size_t)3 * i + 1], z = raw_from[(size_t)3 * i + 2];
+            from.xyz[i] = x; from.xyz[(size_t)nf + i] = y; from.xyz[(size_t)2 * nf + i] = z;
+            if (icp::takes_part(x, y, z)) atomicOr(&mask_f[i >> 5], 1u << (i & 31));
+            from_row(i);
+            out_match[i] = -1;
+        }
+        for (int j = tid; j < nt; j += BLOCK) {
+            const float x = raw_to[(size_t)3 * j], y = raw_to[(size_t)3 * j + 1], z = raw_to[(size_t)3 * j + 2];
+            float qx, qy, qz;
+            icp::apply(guess, x, y, z, qx, qy, qz);
+            to.xyz[j] = qx; to.xyz[(size_t)nt + j] = qy; to.xyz[(size_t)2 * nt + j] = qz;
+            if (icp::takes_part(x, y, z)) atomicOr(&mask_t[j >> 5], 1u << (j & 31));
+            to_row(j);
+        }
+        __syncthreads();
+    }
 
     // the staged target becomes side s; ends behind a barrier, and begins with one: nobody reads the planes any more
     __device__ __forceinline__ void stage(bool is_from) {
@@ -235,5 +286,78 @@ struct GroupBackend : Group {
     // non-negative floats order as their bit patterns; what is no correspondence sorts behind every one
     __device__ __forceinline__ float median(int n) { return m3d::float_of(ranked(keys, n_keys, n >> 1)); }
 };
+
+// ---- the host frame of the two entries, over either argument struct of include/lcd.h (the fields of the same names)
+
+// the parameters both calls have; *thr2: the squared distance.  An entry's own parameter refusals follow this.
+template <class A, class Bad>
+int refuse_icp_params(const A* a, Bad bad, double* thr2) {
+    if (a->max_iterations < 1) return bad(LCD_ERR_INVALID, "max_iterations is >= 1");
+    if (a->max_laser_scans < 0) return bad(LCD_ERR_INVALID, "max_laser_scans is >= 0");
+    if (a->search != LCD_ICP_SEARCH_AUTO && a->search != LCD_ICP_SEARCH_BRUTE && a->search != LCD_ICP_SEARCH_GRID) return bad(LCD_ERR_INVALID, "search is an lcd_icp_search");
+    *thr2 = a->max_correspondence_distance * a->max_correspondence_distance;
+    if (!std::isfinite(a->max_correspondence_distance) || !(a->max_correspondence_distance > 0.0) || !std::isfinite(*thr2))
+        return bad(LCD_ERR_INVALID, "max_correspondence_distance is finite and > 0, squared too");
+    if (!std::isfinite(a->epsilon) || !(a->epsilon >= 0.0f)) return bad(LCD_ERR_INVALID, "epsilon is finite and >= 0");
+    if (!(a->correspondence_ratio >= 0.0f) || !(a->correspondence_ratio <= 1.0f)) return bad(LCD_ERR_INVALID, "correspondence_ratio is in [0, 1]");
+    return LCD_OK;
+}
+
+// what an entry adds to the null checks: whether one of its own arrays is null, and its texts for a side's arrays
+struct IcpOwnArrays {
+    bool null_output, null_from, null_to;
+    const char* from_text; const char* to_text;
+};
+// the pairs of a call that nothing refused; np == 0: nothing to do
+struct IcpPairs {
+    int np = 0, n_max = 0;
+    int64_t Nf = 0, Nt = 0;
+    std::vector<IcpJob> jobs;
+};
+// pairs, offsets, guesses, null outputs, null rows and the host form's finite rows, then the job table
+template <class A, class Bad>
+int refuse_icp_pairs(const lcd_engine* h, const A* a, bool on_device, Bad bad, const IcpOwnArrays& own, IcpPairs& c) {
+    if (const int rc = refuse_pairs(h, a->n_pairs, bad)) return rc;
+    if (a->n_pairs == 0) return LCD_OK;
+    const int np = a->n_pairs;
+    const int64_t* fo = a->from_offsets;
+    const int64_t* to = a->to_offsets;
+    int m_max;
+    if (const int rc = refuse_offsets(np, fo, to, bad, c.n_max, m_max)) return rc;
+    c.Nf = fo[np]; c.Nt = to[np];
+    if (!a->guesses) return bad(LCD_ERR_INVALID, "null guesses");
+    for (int64_t k = 0; k < (int64_t)np * 12; ++k) if (!std::isfinite(a->guesses[k])) return bad(LCD_ERR_INVALID, "a guess that is not finite");
+    if (!a->out_transform || !a->out_icp_transform || !a->out_correction || !a->out_status || !a->out_stop || !a->out_iterations ||
+        !a->out_n_correspondences || !a->out_ratio || !a->out_variance || own.null_output) return bad(LCD_ERR_INVALID, "a null per-pair output");
+    if (c.Nf > 0 && (!a->from_xyz || own.null_from || !a->out_match)) return bad(LCD_ERR_INVALID, own.from_text);
+    if (c.Nt > 0 && (!a->to_xyz || own.null_to)) return bad(LCD_ERR_INVALID, own.to_text);
+    if (!on_device) {                                                  // (a normal that is not finite is legal: the reference produces such normals)
+        for (int64_t k = 0; k < c.Nf * 3; ++k) if (!std::isfinite(a->from_xyz[k])) return bad(LCD_ERR_INVALID, "a from-row that is not finite");
+        for (int64_t k = 0; k < c.Nt * 3; ++k) if (!std::isfinite(a->to_xyz[k])) return bad(LCD_ERR_INVALID, "a to-row that is not finite");
+    }
+    c.jobs.resize((size_t)np);
+    for (int i = 0; i < np; ++i) {
+        IcpJob& j = c.jobs[(size_t)i];
+        j.first_from = fo[i]; j.first_to = to[i]; j.n_from = (int32_t)(fo[i + 1] - fo[i]); j.n_to = (int32_t)(to[i + 1] - to[i]);
+        for (int k = 0; k < 12; ++k) j.guess[k] = a->guesses[(size_t)12 * i + k];
+    }
+    c.np = np;
+    return LCD_OK;
+}
+
+template <class A>
+IcpOutputs icp_outputs(const A* a) {
+    return IcpOutputs{a->out_transform, a->out_icp_transform, a->out_correction, a->out_status, a->out_stop, a->out_iterations,
+                      a->out_n_correspondences, a->out_ratio, a->out_variance, a->out_match};
+}
+// the two coordinate inputs and the ten outputs of a call, bound for the host form
+inline void stage_icp(HostStage& stage, const IcpPairs& c, const float*& from_xyz, const float*& to_xyz, IcpOutputs& o) {
+    const size_t np = (size_t)c.np;
+    stage.in(from_xyz, (size_t)c.Nf * 12); stage.in(to_xyz, (size_t)c.Nt * 12);
+    stage.out(o.out_transform, np * 48); stage.out(o.out_icp_transform, np * 48); stage.out(o.out_correction, np * 48);
+    stage.out(o.out_variance, np * 8); stage.out(o.out_status, np * 4); stage.out(o.out_stop, np * 4);
+    stage.out(o.out_iterations, np * 4); stage.out(o.out_n_correspondences, np * 4); stage.out(o.out_ratio, np * 4);
+    stage.out(o.out_match, (size_t)c.Nf * 4);
+}
 
 }  // namespace lcd

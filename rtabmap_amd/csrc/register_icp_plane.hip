@@ -49,9 +49,7 @@ struct PlaneArgs {
     int64_t n_from_all, n_to_all;
     const float* from_xyz; const float* to_xyz; const float* from_normals; const float* to_normals;
     uint32_t* scratch;                       // [SCRATCH_WORDS x (Nf + Nt)] words, then the normals [3 x (Nf + Nt)]
-    float* out_transform; float* out_icp_transform; float* out_correction;
-    int32_t* out_status; int32_t* out_stop; int32_t* out_iterations; int32_t* out_n_correspondences;
-    float* out_ratio; double* out_variance; int32_t* out_match;
+    IcpOutputs out;
     int32_t* out_branch; float* out_complexity; float* out_complexity_values; float* out_complexity_vectors; float* out_second_eigenvalue;
 };
 
@@ -218,7 +216,7 @@ __global__ __launch_bounds__(BLOCK) void register_icp_plane_kernel(PlaneArgs a) 
     b.wsum = reinterpret_cast<int*>(icpp_smem + OFF_WSUM);
     b.planes = reinterpret_cast<float*>(icpp_smem + OFF_PLANES); b.stride = a.stride;
     b.keys64 = reinterpret_cast<uint64_t*>(icpp_smem + OFF_PLANES); b.search_mode = a.search; b.cell = a.cell;
-    b.thr2 = a.thr2; b.raw_from = raw_from; b.out_match = a.out_match + J.first_from;
+    b.thr2 = a.thr2; b.raw_from = raw_from; b.out_match = a.out.out_match + J.first_from;
     b.from.carve(a.scratch + (size_t)SCRATCH_WORDS * J.first_from, nf, mask_f);
     b.to.carve(a.scratch + (size_t)SCRATCH_WORDS * (a.n_from_all + J.first_to), nt, mask_t);
     b.pmask_f = mask_f; b.pmask_t = mask_t; b.nmask_f = nmask_f; b.nmask_t = nmask_t;
@@ -229,28 +227,19 @@ __global__ __launch_bounds__(BLOCK) void register_icp_plane_kernel(PlaneArgs a) 
     // ---- (a) the rows with finite coordinates, Q and P_0, the normals
     mask_f[tid] = 0u; mask_t[tid] = 0u; nmask_f[tid] = 0u; nmask_t[tid] = 0u;
     __syncthreads();
-    for (int i = tid; i < nf; i += BLOCK) {
-        const float x = raw_from[(size_t)3 * i], y = raw_from[(size_t)3 * i + 1], z = raw_from[(size_t)3 * i + 2];
-        b.from.xyz[i] = x; b.from.xyz[(size_t)nf + i] = y; b.from.xyz[(size_t)2 * nf + i] = z;
-        if (icp::takes_part(x, y, z)) atomicOr(&mask_f[i >> 5], 1u << (i & 31));
-        const float nx = raw_nf[(size_t)3 * i], ny = raw_nf[(size_t)3 * i + 1], nz = raw_nf[(size_t)3 * i + 2];
-        b.nrm_from[i] = nx; b.nrm_from[(size_t)nf + i] = ny; b.nrm_from[(size_t)2 * nf + i] = nz;
-        if (icpp::finite3(nx, ny, nz)) atomicOr(&nmask_f[i >> 5], 1u << (i & 31));
-        b.out_match[i] = -1;
-    }
-    for (int j = tid; j < nt; j += BLOCK) {
-        const float x = raw_to[(size_t)3 * j], y = raw_to[(size_t)3 * j + 1], z = raw_to[(size_t)3 * j + 2];
-        float qx, qy, qz;
-        icp::apply(J.guess, x, y, z, qx, qy, qz);
-        b.to.xyz[j] = qx; b.to.xyz[(size_t)nt + j] = qy; b.to.xyz[(size_t)2 * nt + j] = qz;
-        if (icp::takes_part(x, y, z)) atomicOr(&mask_t[j >> 5], 1u << (j & 31));
-        const float nx = raw_nt[(size_t)3 * j], ny = raw_nt[(size_t)3 * j + 1], nz = raw_nt[(size_t)3 * j + 2];
-        float rx, ry, rz;
-        icpp::rotate(J.guess, nx, ny, nz, rx, ry, rz);
-        b.nrm_to[j] = rx; b.nrm_to[(size_t)nt + j] = ry; b.nrm_to[(size_t)2 * nt + j] = rz;
-        if (icpp::finite3(nx, ny, nz)) atomicOr(&nmask_t[j >> 5], 1u << (j & 31));
-    }
-    __syncthreads();
+    b.load_rows(raw_to, J.guess, mask_f, mask_t,
+        [&](int i) __attribute__((always_inline)) {
+            const float nx = raw_nf[(size_t)3 * i], ny = raw_nf[(size_t)3 * i + 1], nz = raw_nf[(size_t)3 * i + 2];
+            b.nrm_from[i] = nx; b.nrm_from[(size_t)nf + i] = ny; b.nrm_from[(size_t)2 * nf + i] = nz;
+            if (icpp::finite3(nx, ny, nz)) atomicOr(&nmask_f[i >> 5], 1u << (i & 31));
+        },
+        [&](int j) __attribute__((always_inline)) {
+            const float nx = raw_nt[(size_t)3 * j], ny = raw_nt[(size_t)3 * j + 1], nz = raw_nt[(size_t)3 * j + 2];
+            float rx, ry, rz;
+            icpp::rotate(J.guess, nx, ny, nz, rx, ry, rz);
+            b.nrm_to[j] = rx; b.nrm_to[(size_t)nt + j] = ry; b.nrm_to[(size_t)2 * nt + j] = rz;
+            if (icpp::finite3(nx, ny, nz)) atomicOr(&nmask_t[j >> 5], 1u << (j & 31));
+        });
     b.oi_f = b.oi_t = 0;
     for (int w = 0; w < MASK_WORDS; ++w) { b.oi_f += __popc(nmask_f[w]); b.oi_t += __popc(nmask_t[w]); }
     b.np_from = b.np_to = b.rows_f = b.rows_t = 0;
@@ -261,18 +250,7 @@ __global__ __launch_bounds__(BLOCK) void register_icp_plane_kernel(PlaneArgs a) 
 
     if (tid == 0) {
         const size_t p = blockIdx.x;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            a.out_transform[p * 12 + k] = r.transform[k];
-            a.out_icp_transform[p * 12 + k] = r.icp[k];
-            a.out_correction[p * 12 + k] = r.correction[k];
-        }
-        a.out_status[p] = r.status;
-        a.out_stop[p] = r.stop;
-        a.out_iterations[p] = r.iterations;
-        a.out_n_correspondences[p] = r.n_correspondences;
-        a.out_ratio[p] = r.ratio;
-        a.out_variance[p] = r.variance;
+        write_result(a.out, p, r);
         a.out_branch[p] = r.branch;
         a.out_complexity[p] = r.complexity;
 #pragma unroll
@@ -295,87 +273,45 @@ int register_icp_plane(lcd_engine* h, const lcd_icp_plane_args* a, bool on_devic
     auto bad = [&](int code, const char* what) { return h->fail(code, std::string(who) + ": " + what); };
     // ---- everything that can be refused is refused before anything is enqueued or written
     if (!a || a->struct_size != (int32_t)sizeof(lcd_icp_plane_args)) return bad(LCD_ERR_INVALID, "null arguments or wrong struct_size");
-    if (a->max_iterations < 1) return bad(LCD_ERR_INVALID, "max_iterations is >= 1");
-    if (a->max_laser_scans < 0) return bad(LCD_ERR_INVALID, "max_laser_scans is >= 0");
-    if (a->search != LCD_ICP_SEARCH_AUTO && a->search != LCD_ICP_SEARCH_BRUTE && a->search != LCD_ICP_SEARCH_GRID) return bad(LCD_ERR_INVALID, "search is an lcd_icp_search");
-    const double thr2 = a->max_correspondence_distance * a->max_correspondence_distance;
-    if (!std::isfinite(a->max_correspondence_distance) || !(a->max_correspondence_distance > 0.0) || !std::isfinite(thr2))
-        return bad(LCD_ERR_INVALID, "max_correspondence_distance is finite and > 0, squared too");
-    if (!std::isfinite(a->epsilon) || !(a->epsilon >= 0.0f)) return bad(LCD_ERR_INVALID, "epsilon is finite and >= 0");
-    if (!(a->correspondence_ratio >= 0.0f) || !(a->correspondence_ratio <= 1.0f)) return bad(LCD_ERR_INVALID, "correspondence_ratio is in [0, 1]");
+    double thr2;
+    if (const int rc = refuse_icp_params(a, bad, &thr2)) return rc;
     if (!(a->min_complexity >= 0.0f) || !(a->min_complexity <= 1.0f)) return bad(LCD_ERR_INVALID, "min_complexity is in [0, 1]");
     if (a->low_complexity_strategy < 0 || a->low_complexity_strategy > 2) return bad(LCD_ERR_INVALID, "low_complexity_strategy is 0, 1 or 2");
     if (a->normal_gate != 0 && !std::isfinite(a->min_normal_cos)) return bad(LCD_ERR_INVALID, "min_normal_cos is finite while the gate is on");
-    if (const int rc = refuse_pairs(h, a->n_pairs, bad)) return rc;
-    if (a->n_pairs == 0) return LCD_OK;
-    const int np = a->n_pairs;
-    const int64_t* fo = a->from_offsets;
-    const int64_t* to = a->to_offsets;
-    int n_max, m_max;
-    if (const int rc = refuse_offsets(np, fo, to, bad, n_max, m_max)) return rc;
-    const int64_t Nf = fo[np], Nt = to[np];
-    if (!a->guesses) return bad(LCD_ERR_INVALID, "null guesses");
-    for (int64_t k = 0; k < (int64_t)np * 12; ++k) if (!std::isfinite(a->guesses[k])) return bad(LCD_ERR_INVALID, "a guess that is not finite");
-    if (!a->out_transform || !a->out_icp_transform || !a->out_correction || !a->out_status || !a->out_stop || !a->out_iterations ||
-        !a->out_n_correspondences || !a->out_ratio || !a->out_variance || !a->out_branch || !a->out_complexity || !a->out_complexity_values ||
-        !a->out_complexity_vectors || !a->out_second_eigenvalue) return bad(LCD_ERR_INVALID, "a null per-pair output");
-    if (Nf > 0 && (!a->from_xyz || !a->from_normals || !a->out_match)) return bad(LCD_ERR_INVALID, "null from-rows, from-normals or out_match");
-    if (Nt > 0 && (!a->to_xyz || !a->to_normals)) return bad(LCD_ERR_INVALID, "null to-rows or to-normals");
-    if (!on_device) {                                                  // (a normal that is not finite is legal: the reference produces such normals)
-        for (int64_t k = 0; k < Nf * 3; ++k) if (!std::isfinite(a->from_xyz[k])) return bad(LCD_ERR_INVALID, "a from-row that is not finite");
-        for (int64_t k = 0; k < Nt * 3; ++k) if (!std::isfinite(a->to_xyz[k])) return bad(LCD_ERR_INVALID, "a to-row that is not finite");
-    }
+    const IcpOwnArrays own{!a->out_branch || !a->out_complexity || !a->out_complexity_values || !a->out_complexity_vectors || !a->out_second_eigenvalue,
+                           !a->from_normals, !a->to_normals, "null from-rows, from-normals or out_match", "null to-rows or to-normals"};
+    IcpPairs c;
+    if (const int rc = refuse_icp_pairs(h, a, on_device, bad, own, c)) return rc;
+    if (c.np == 0) return LCD_OK;
+    const size_t np = (size_t)c.np;
 
     StatelessScratch& S = h->pairs;
     hipStream_t st = h->stream;
-    std::vector<IcpJob> jobs((size_t)np);
-    for (int i = 0; i < np; ++i) {
-        IcpJob& j = jobs[(size_t)i];
-        j.first_from = fo[i]; j.first_to = to[i]; j.n_from = (int32_t)(fo[i + 1] - fo[i]); j.n_to = (int32_t)(to[i + 1] - to[i]);
-        for (int k = 0; k < 12; ++k) j.guess[k] = a->guesses[(size_t)12 * i + k];
-    }
-
     PlaneArgs g;
     g.p.max_iterations = a->max_iterations; g.p.force_3dof = a->force_3dof != 0; g.p.max_laser_scans = a->max_laser_scans;
     g.p.strategy = a->low_complexity_strategy; g.p.gate = a->normal_gate != 0; g.p.min_normal_cos = a->min_normal_cos;
     g.p.epsilon = a->epsilon; g.p.correspondence_ratio = a->correspondence_ratio; g.p.min_complexity = a->min_complexity;
     g.search = a->search; g.cell = icp::cell_size(a->max_correspondence_distance); g.thr2 = thr2;
-    g.stride = plane_stride(n_max); g.n_from_all = Nf; g.n_to_all = Nt;
+    g.stride = plane_stride(c.n_max); g.n_from_all = c.Nf; g.n_to_all = c.Nt;
     g.from_xyz = a->from_xyz; g.to_xyz = a->to_xyz; g.from_normals = a->from_normals; g.to_normals = a->to_normals;
-    g.out_transform = a->out_transform; g.out_icp_transform = a->out_icp_transform; g.out_correction = a->out_correction;
-    g.out_status = a->out_status; g.out_stop = a->out_stop; g.out_iterations = a->out_iterations; g.out_n_correspondences = a->out_n_correspondences;
-    g.out_ratio = a->out_ratio; g.out_variance = a->out_variance; g.out_match = a->out_match;
+    g.out = icp_outputs(a);
     g.out_branch = a->out_branch; g.out_complexity = a->out_complexity; g.out_complexity_values = a->out_complexity_values;
     g.out_complexity_vectors = a->out_complexity_vectors; g.out_second_eigenvalue = a->out_second_eigenvalue;
 
     // ---- host entry: everything to the device, results back at the end (one synchronisation)
-    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes);
-    if (!on_device) {
-        const int i_f = stage.add_in(a->from_xyz, (size_t)Nf * 12), i_t = stage.add_in(a->to_xyz, (size_t)Nt * 12);
-        const int i_nf = stage.add_in(a->from_normals, (size_t)Nf * 12), i_nt = stage.add_in(a->to_normals, (size_t)Nt * 12);
-        const int o_t = stage.add_out(a->out_transform, (size_t)np * 48), o_i = stage.add_out(a->out_icp_transform, (size_t)np * 48);
-        const int o_c = stage.add_out(a->out_correction, (size_t)np * 48), o_v = stage.add_out(a->out_variance, (size_t)np * 8);
-        const int o_s = stage.add_out(a->out_status, (size_t)np * 4), o_p = stage.add_out(a->out_stop, (size_t)np * 4);
-        const int o_n = stage.add_out(a->out_iterations, (size_t)np * 4), o_k = stage.add_out(a->out_n_correspondences, (size_t)np * 4);
-        const int o_r = stage.add_out(a->out_ratio, (size_t)np * 4), o_m = stage.add_out(a->out_match, (size_t)Nf * 4);
-        const int o_b = stage.add_out(a->out_branch, (size_t)np * 4), o_x = stage.add_out(a->out_complexity, (size_t)np * 4);
-        const int o_cv = stage.add_out(a->out_complexity_values, (size_t)np * 12), o_ce = stage.add_out(a->out_complexity_vectors, (size_t)np * 36);
-        const int o_2 = stage.add_out(a->out_second_eigenvalue, (size_t)np * 4);
-        LCD_HIP(h, stage.commit(st, &h->bytes_device));
-        g.from_xyz = stage.in<float>(i_f); g.to_xyz = stage.in<float>(i_t); g.from_normals = stage.in<float>(i_nf); g.to_normals = stage.in<float>(i_nt);
-        g.out_transform = stage.out<float>(o_t); g.out_icp_transform = stage.out<float>(o_i); g.out_correction = stage.out<float>(o_c);
-        g.out_variance = stage.out<double>(o_v); g.out_status = stage.out<int32_t>(o_s); g.out_stop = stage.out<int32_t>(o_p);
-        g.out_iterations = stage.out<int32_t>(o_n); g.out_n_correspondences = stage.out<int32_t>(o_k); g.out_ratio = stage.out<float>(o_r);
-        g.out_match = stage.out<int32_t>(o_m); g.out_branch = stage.out<int32_t>(o_b); g.out_complexity = stage.out<float>(o_x);
-        g.out_complexity_values = stage.out<float>(o_cv); g.out_complexity_vectors = stage.out<float>(o_ce); g.out_second_eigenvalue = stage.out<float>(o_2);
-    }
-    LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(Nf + Nt, 1) * PLANE_SCRATCH_WORDS * 4));
+    HostStage stage(S, host_row_bytes(h), (size_t)h->row_bytes, on_device);
+    stage_icp(stage, c, g.from_xyz, g.to_xyz, g.out);
+    stage.in(g.from_normals, (size_t)c.Nf * 12); stage.in(g.to_normals, (size_t)c.Nt * 12);
+    stage.out(g.out_branch, np * 4); stage.out(g.out_complexity, np * 4); stage.out(g.out_complexity_values, np * 12);
+    stage.out(g.out_complexity_vectors, np * 36); stage.out(g.out_second_eigenvalue, np * 4);
+    LCD_HIP(h, stage.commit(st, &h->bytes_device));
+    LCD_HIP(h, dreserve(h, S.d_small, (size_t)std::max<int64_t>(c.Nf + c.Nt, 1) * PLANE_SCRATCH_WORDS * 4));
     g.scratch = S.d_small.as<uint32_t>();
-    LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), jobs.size() * sizeof(IcpJob)));
+    LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, c.jobs.data(), c.jobs.size() * sizeof(IcpJob)));
     allow_large_lds<&register_icp_plane_kernel>();
-    register_icp_plane_kernel<<<dim3((unsigned)np), dim3(BLOCK), lds_bytes(n_max), st>>>(g);
+    register_icp_plane_kernel<<<dim3((unsigned)c.np), dim3(BLOCK), lds_bytes(c.n_max), st>>>(g);
     LCD_HIP(h, hipGetLastError());
-    if (!on_device) LCD_HIP(h, stage.finish(st));
+    LCD_HIP(h, stage.finish(st));
     return LCD_OK;
 }
 

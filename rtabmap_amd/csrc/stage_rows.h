@@ -28,7 +28,7 @@ inline void unpack_rows(void* dst, const void* src, int64_t n, size_t dst_row, s
 // Regions of one staging buffer, in the order they are named: each starts at the 256-byte-aligned running sum of those before it (a region
 // of zero bytes takes no room), `bytes` is what one copy of all of them moves.  A fixed array: no allocation per call.
 struct RegionLayout {
-    static constexpr int MAX_REGIONS = 16;              // lcd_estimate_motion_pnp names nine outputs, lcd_register_icp ten, lcd_register_icp_plane fifteen
+    static constexpr int MAX_REGIONS = 16;              // the rule: at least the most inputs, and the most outputs, that one call names
     size_t off[MAX_REGIONS], len[MAX_REGIONS];
     int n = 0;
     size_t bytes = 0;
@@ -39,5 +39,41 @@ struct RegionLayout {
         return n++;
     }
 };
+
+// The staged arrays of one direction of a call, each bound to the pointer field of the kernel arguments that names it.  bind() takes the
+// field holding the caller's pointer: that pointer is the copy's source or destination, the field's address is where patch() writes the
+// region's address in the staging buffer.  The field may be of any object-pointer type; its bytes are copied, never read through another type.
+struct BoundRegions {
+    static constexpr int NONE = -1, FULL = -2;
+    bool on_device = false;                             // the _dev form: the caller's pointers are the device's, nothing is bound or patched
+    RegionLayout lay;
+    void* field[RegionLayout::MAX_REGIONS];             // the bound field's address
+    void* host[RegionLayout::MAX_REGIONS];              // what the field held when it was bound
+    // the region's index; NONE for a null field, which takes no region and stays null; FULL when the array is full (nothing is recorded)
+    template <typename P>
+    int bind(P*& f, size_t region_bytes) {
+        void* p;
+        std::memcpy(&p, &f, sizeof p);
+        if (!p || on_device) return NONE;
+        const int r = lay.add(region_bytes);
+        if (r < 0) return FULL;
+        field[r] = &f; host[r] = p;
+        return r;
+    }
+    void patch(void* base) const {                      // every bound field now points at its region of the buffer at `base`
+        for (int r = 0; r < lay.n; ++r) {
+            char* p = (char*)base + lay.off[r];
+            std::memcpy(field[r], &p, sizeof p);
+        }
+    }
+};
+
+// Of a region of per-frame results (elements at a stride of `stride` bytes), the first count[f] elements of every frame f, which begins at
+// element offsets[f], go to the same place in `dst` as elements of `elem` bytes (handle rows are un-padded: elem <= stride).  What lies
+// behind a frame's count in `dst` stays as it was, and a count of zero copies nothing.
+inline void hand_out_frames(void* dst, const void* src, const int32_t* count, const int64_t* offsets, int n_frames, size_t elem, size_t stride) {
+    for (int f = 0; f < n_frames; ++f)
+        unpack_rows((char*)dst + (size_t)offsets[f] * elem, (const char*)src + (size_t)offsets[f] * stride, count[f], elem, stride);
+}
 
 }  // namespace lcd

@@ -8,10 +8,12 @@
 #include "devbuf.h"
 #include "stage_rows.h"
 
-// Scratch of the calls that do not complete what a pipelined handle owes, with their _dev forms:
+// Scratch of the stateless calls: those that do not complete what a pipelined handle owes, each with a host and a _dev form.  This is the
+// one list of them; other files point here.
 //   lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip),
 //   lcd_select_features and lcd_expand_word_ids (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip),
-//   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip) and lcd_register_icp (register_icp.hip).
+//   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip),
+//   lcd_register_icp (register_icp.hip) and lcd_register_icp_plane (register_icp_plane.hip).
 // Everything they write on the device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The
 // buffers only grow, and a growth frees the old allocation after the engine stream has drained (DevBuf::reserve): work of an earlier call
 // that is still enqueued keeps what it reads.  The protocol is the methods' and HostStage's; the callers own only d_dist and d_small.
@@ -22,6 +24,7 @@ struct StatelessScratch {
     //   lcd_estimate_motion_3d: 36 bytes per from-row (six coordinate planes, d2, two index sets)
     //   lcd_estimate_motion_pnp: 44 bytes per to-row (eight coordinate planes, errors, two index sets)
     //   lcd_register_icp: 20 bytes per row of either side (three coordinate planes, the nearest row, its d2)
+    //   lcd_register_icp_plane: 32 bytes per row of either side (lcd_register_icp's 20 and three normal planes)
     lcd::DevBuf d_small;
     int64_t budget_bytes = 0;                           // lcd_set_option("pair_match_budget"): distance-block bytes per group (0: built-in, 256 MiB)
 
@@ -74,47 +77,68 @@ private:
     lcd::PinBuf h_in, h_out;
 };
 
-// What a host entry does around its launches, for the one call it lives in: the caller names its input and output regions in order,
-// commit() lays them out (lcd::RegionLayout), stages the inputs in pinned memory and enqueues ONE copy to the device, the launches work on
-// in<T>() / out<T>(), finish() enqueues ONE copy back, synchronises ONCE and hands the results out.  The host entries serialise on that
-// synchronisation, which is what lets every one of them use the same four buffers.
+// What a host entry does around its launches, for the one call it lives in.  The entry fills its kernel arguments from the caller's pointers,
+// as the _dev form needs them, and names each staged field ONCE: in() / in_rows() / out() / out_kept() bind the field to a region
+// (lcd::BoundRegions).  commit() lays the regions out, stages the inputs in pinned memory, enqueues ONE copy to the device and points every
+// bound field at its region of d_in / d_out; finish() enqueues ONE copy back, synchronises ONCE and copies every out() region to where its
+// field pointed.  An out_kept() region stays in the pinned buffer for hand_out() / hand_out_rows().  A null field takes no region and stays
+// null.  In the _dev form (on_device) every method does nothing and the fields keep the caller's pointers.  The host entries serialise on
+// the one synchronisation, which is what lets every one of them use the same four buffers.
 struct HostStage {
-    HostStage(StatelessScratch& scratch, size_t host_row_bytes, size_t row_bytes) : S(scratch), host_row(host_row_bytes), dev_row(row_bytes) {}
-    int add_in(const void* src, size_t bytes) { const int r = li.add(bytes); assert(r >= 0); from[r] = src; rows[r] = -1; return r; }
+    HostStage(StatelessScratch& scratch, size_t host_row_bytes, size_t row_bytes, bool on_device) : S(scratch), host_row(host_row_bytes), dev_row(row_bytes), dev(on_device) {
+        i.on_device = o.on_device = on_device;
+    }
+    // (a field need not be a kernel argument: a local pointer is bound the same way and holds its region's device address behind commit())
+    template <typename T> void in(const T*& f, size_t bytes) { bound(i, f, bytes, rows, -1); }
     // `n` host rows of the handle (host_row_bytes each), staged at the stride the kernels walk
-    int add_in_rows(const void* src, int64_t n) { const int r = add_in(src, (size_t)n * dev_row); rows[r] = n; return r; }
-    // dst == nullptr: finish() leaves the region where host_out() finds it
-    int add_out(void* dst, size_t bytes) { const int r = lo.add(bytes); assert(r >= 0); to[r] = dst; return r; }
+    template <typename T> void in_rows(const T*& f, int64_t n) { bound(i, f, (size_t)n * dev_row, rows, n); }
+    template <typename T> void out(T*& f, size_t bytes) { bound(o, f, bytes, kept, 0); }
+    // the region's index for hand_out() / hand_out_rows()
+    template <typename T> int out_kept(T*& f, size_t bytes) { return bound(o, f, bytes, kept, 1); }
 
     hipError_t commit(hipStream_t st, int64_t* bytes_device) {
-        TF_TRY(S.h_in.reserve(li.bytes + 256));
-        TF_TRY(S.h_out.reserve(lo.bytes + 256));
-        TF_TRY(S.d_in.reserve(li.bytes + 256, 0, st, bytes_device));
-        TF_TRY(S.d_out.reserve(lo.bytes + 256, 0, st, bytes_device));
-        for (int r = 0; r < li.n; ++r) {
-            if (!li.len[r]) continue;
-            if (rows[r] >= 0) lcd::pack_rows(S.h_in.as<char>() + li.off[r], from[r], rows[r], host_row, dev_row);
-            else std::memcpy(S.h_in.as<char>() + li.off[r], from[r], li.len[r]);
+        if (dev) return hipSuccess;
+        TF_TRY(S.h_in.reserve(i.lay.bytes + 256));
+        TF_TRY(S.h_out.reserve(o.lay.bytes + 256));
+        TF_TRY(S.d_in.reserve(i.lay.bytes + 256, 0, st, bytes_device));
+        TF_TRY(S.d_out.reserve(o.lay.bytes + 256, 0, st, bytes_device));
+        for (int r = 0; r < i.lay.n; ++r) {
+            if (!i.lay.len[r]) continue;
+            if (rows[r] >= 0) lcd::pack_rows(S.h_in.as<char>() + i.lay.off[r], i.host[r], rows[r], host_row, dev_row);
+            else std::memcpy(S.h_in.as<char>() + i.lay.off[r], i.host[r], i.lay.len[r]);
         }
-        if (li.bytes) TF_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, li.bytes, hipMemcpyHostToDevice, st));
+        if (i.lay.bytes) TF_TRY(hipMemcpyAsync(S.d_in.p, S.h_in.p, i.lay.bytes, hipMemcpyHostToDevice, st));
+        i.patch(S.d_in.p); o.patch(S.d_out.p);
         return hipSuccess;
     }
-    template <typename T> const T* in(int r) const { return (const T*)(S.d_in.as<char>() + li.off[r]); }
-    template <typename T> T* out(int r) const { return (T*)(S.d_out.as<char>() + lo.off[r]); }
 
     hipError_t finish(hipStream_t st) {
-        TF_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, lo.bytes, hipMemcpyDeviceToHost, st));
+        if (dev) return hipSuccess;
+        TF_TRY(hipMemcpyAsync(S.h_out.p, S.d_out.p, o.lay.bytes, hipMemcpyDeviceToHost, st));
         TF_TRY(hipStreamSynchronize(st));
-        for (int r = 0; r < lo.n; ++r) if (to[r] && lo.len[r]) std::memcpy(to[r], host_out(r), lo.len[r]);
+        for (int r = 0; r < o.lay.n; ++r) if (!kept[r] && o.lay.len[r]) std::memcpy(o.host[r], S.h_out.as<char>() + o.lay.off[r], o.lay.len[r]);
         return hipSuccess;
     }
-    const char* host_out(int r) const { return S.h_out.as<char>() + lo.off[r]; }
+    // behind finish(), of the out_kept() region r: the first count[f] elements of `elem` bytes of every frame f, which begins at element
+    // offsets[f], to where the field pointed (lcd::hand_out_frames).  r < 0 (a null field, the _dev form) or an empty region: nothing.
+    void hand_out(int r, const int32_t* count, const int64_t* offsets, int n_frames, size_t elem) { hand_out(r, count, offsets, n_frames, elem, elem); }
+    void hand_out_rows(int r, const int32_t* count, const int64_t* offsets, int n_frames) { hand_out(r, count, offsets, n_frames, host_row, dev_row); }   // handle rows, un-padded
 
 private:
+    template <typename P>
+    int bound(lcd::BoundRegions& side, P*& f, size_t bytes, int64_t* tag, int64_t value) {
+        const int r = side.bind(f, bytes);
+        assert(r != lcd::BoundRegions::FULL);
+        if (r >= 0) tag[r] = value;
+        return r;
+    }
+    void hand_out(int r, const int32_t* count, const int64_t* offsets, int n_frames, size_t elem, size_t stride) {
+        if (r >= 0 && o.lay.len[r]) lcd::hand_out_frames(o.host[r], S.h_out.as<char>() + o.lay.off[r], count, offsets, n_frames, elem, stride);
+    }
     StatelessScratch& S;
     size_t host_row, dev_row;
-    lcd::RegionLayout li, lo;
-    const void* from[lcd::RegionLayout::MAX_REGIONS];
-    int64_t rows[lcd::RegionLayout::MAX_REGIONS];       // >= 0: the region is that many handle rows, to be padded
-    void* to[lcd::RegionLayout::MAX_REGIONS];
+    bool dev;
+    lcd::BoundRegions i, o;
+    int64_t rows[lcd::RegionLayout::MAX_REGIONS];       // inputs.  >= 0: the region is that many handle rows, to be padded
+    int64_t kept[lcd::RegionLayout::MAX_REGIONS];       // outputs.  1: finish() leaves the region in the pinned buffer
 };

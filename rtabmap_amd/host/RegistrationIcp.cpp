@@ -221,6 +221,36 @@ void fill(Cloud& c, const float* xyz, int n) {
     for (int i = 0; i < n; ++i) c.part[(size_t)i] = rule::takes_part(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]) ? 1 : 0;
 }
 
+// What both mirrors do in front of their solve: the refusals of the parameters and arrays both have, then P_0, Q = guess(to-rows) and the
+// search's parameters.  false: refused.
+bool set_up(CpuBackend& b, const float* fromXyz, int nFrom, const float* toXyz, int nTo, const float guess[12], int maxIterations, int maxLaserScans,
+            double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, int search, bool deviceEntry) {
+    const double thr2 = maxCorrespondenceDistance * maxCorrespondenceDistance;
+    if (nFrom < 0 || nTo < 0 || nFrom > lcd::m3d::MAX_ROWS || nTo > lcd::m3d::MAX_ROWS || maxIterations < 1 || maxLaserScans < 0 ||
+        (search != rule::SEARCH_AUTO && search != rule::SEARCH_BRUTE && search != rule::SEARCH_GRID) || !std::isfinite(maxCorrespondenceDistance) || !(maxCorrespondenceDistance > 0.0) ||
+        !std::isfinite(thr2) || !std::isfinite(epsilon) || !(epsilon >= 0.0f) || !(correspondenceRatio >= 0.0f) || !(correspondenceRatio <= 1.0f) || !guess)
+        return false;
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(guess[k])) return false;
+    if ((nFrom > 0 && !fromXyz) || (nTo > 0 && !toXyz)) return false;
+    fill(b.from, fromXyz, nFrom);
+    fill(b.to, toXyz, nTo);
+    if (!deviceEntry && (b.n_from() != nFrom || b.n_to() != nTo)) return false;
+    for (int j = 0; j < nTo; ++j)
+        rule::apply(guess, toXyz[3 * j], toXyz[3 * j + 1], toXyz[3 * j + 2], b.to.xyz[(size_t)3 * j], b.to.xyz[(size_t)3 * j + 1], b.to.xyz[(size_t)3 * j + 2]);
+    b.raw_from = fromXyz; b.thr2 = thr2; b.mode = search; b.h = rule::cell_size(maxCorrespondenceDistance);
+    b.match.assign((size_t)nFrom, -1);
+    return true;
+}
+
+// the ten fields both results have, out of rule::Result or plane::Result
+template <class R>
+void common_result(const R& res, const CpuBackend& b, IcpResult& r) {
+    for (int k = 0; k < 12; ++k) { r.transform[k] = res.transform[k]; r.icpTransform[k] = res.icp[k]; r.correction[k] = res.correction[k]; }
+    r.status = res.status; r.stop = res.stop; r.iterations = res.iterations; r.correspondences = res.n_correspondences;
+    r.ratio = res.ratio; r.variance = res.variance;
+    r.match = b.match;
+}
+
 }  // namespace
 
 float icp_cells(const float* x, int n, double maxCorrespondenceDistance, int* outCells) {
@@ -233,28 +263,12 @@ float icp_cells(const float* x, int n, double maxCorrespondenceDistance, int* ou
 bool register_icp_cpu(const float* fromXyz, int nFrom, const float* toXyz, int nTo, const float guess[12], int maxIterations, bool force3DoF,
                       int maxLaserScans, double maxCorrespondenceDistance, float epsilon, float correspondenceRatio, int search, bool deviceEntry,
                       IcpResult& out) {
-    const double thr2 = maxCorrespondenceDistance * maxCorrespondenceDistance;
-    if (nFrom < 0 || nTo < 0 || nFrom > lcd::m3d::MAX_ROWS || nTo > lcd::m3d::MAX_ROWS || maxIterations < 1 || maxLaserScans < 0 ||
-        (search != rule::SEARCH_AUTO && search != rule::SEARCH_BRUTE && search != rule::SEARCH_GRID) || !std::isfinite(maxCorrespondenceDistance) || !(maxCorrespondenceDistance > 0.0) ||
-        !std::isfinite(thr2) || !std::isfinite(epsilon) || !(epsilon >= 0.0f) || !(correspondenceRatio >= 0.0f) || !(correspondenceRatio <= 1.0f) || !guess)
-        return false;
-    for (int k = 0; k < 12; ++k) if (!std::isfinite(guess[k])) return false;
-    if ((nFrom > 0 && !fromXyz) || (nTo > 0 && !toXyz)) return false;
     CpuBackend b;
-    fill(b.from, fromXyz, nFrom);
-    fill(b.to, toXyz, nTo);
-    if (!deviceEntry && (b.n_from() != nFrom || b.n_to() != nTo)) return false;
-    for (int j = 0; j < nTo; ++j)
-        rule::apply(guess, toXyz[3 * j], toXyz[3 * j + 1], toXyz[3 * j + 2], b.to.xyz[(size_t)3 * j], b.to.xyz[(size_t)3 * j + 1], b.to.xyz[(size_t)3 * j + 2]);
-    b.raw_from = fromXyz; b.thr2 = thr2; b.mode = search; b.h = rule::cell_size(maxCorrespondenceDistance);
-    b.match.assign((size_t)nFrom, -1);
+    if (!set_up(b, fromXyz, nFrom, toXyz, nTo, guess, maxIterations, maxLaserScans, maxCorrespondenceDistance, epsilon, correspondenceRatio, search, deviceEntry)) return false;
     rule::Result res;
     rule::solve(b, maxIterations, force3DoF, maxLaserScans, epsilon, correspondenceRatio, guess, res);
     IcpResult r;
-    for (int k = 0; k < 12; ++k) { r.transform[k] = res.transform[k]; r.icpTransform[k] = res.icp[k]; r.correction[k] = res.correction[k]; }
-    r.status = res.status; r.stop = res.stop; r.iterations = res.iterations; r.correspondences = res.n_correspondences;
-    r.ratio = res.ratio; r.variance = res.variance;
-    r.match = b.match;
+    common_result(res, b, r);
     out = r;
     return true;
 }
@@ -263,40 +277,28 @@ bool register_icp_plane_cpu(const float* fromXyz, const float* fromNormals, int 
                             const float guess[12], int maxIterations, bool force3DoF, int maxLaserScans, double maxCorrespondenceDistance, float epsilon,
                             float correspondenceRatio, float minComplexity, int lowComplexityStrategy, bool normalGate, double minNormalCos, int search,
                             bool deviceEntry, IcpPlaneResult& out) {
-    const double thr2 = maxCorrespondenceDistance * maxCorrespondenceDistance;
-    if (nFrom < 0 || nTo < 0 || nFrom > lcd::m3d::MAX_ROWS || nTo > lcd::m3d::MAX_ROWS || maxIterations < 1 || maxLaserScans < 0 ||
-        (search != rule::SEARCH_AUTO && search != rule::SEARCH_BRUTE && search != rule::SEARCH_GRID) || !std::isfinite(maxCorrespondenceDistance) || !(maxCorrespondenceDistance > 0.0) ||
-        !std::isfinite(thr2) || !std::isfinite(epsilon) || !(epsilon >= 0.0f) || !(correspondenceRatio >= 0.0f) || !(correspondenceRatio <= 1.0f) || !guess ||
-        !(minComplexity >= 0.0f) || !(minComplexity <= 1.0f) || lowComplexityStrategy < 0 || lowComplexityStrategy > 2 || (normalGate && !std::isfinite(minNormalCos)))
+    if (!(minComplexity >= 0.0f) || !(minComplexity <= 1.0f) || lowComplexityStrategy < 0 || lowComplexityStrategy > 2 || (normalGate && !std::isfinite(minNormalCos)) ||
+        (nFrom > 0 && !fromNormals) || (nTo > 0 && !toNormals))
         return false;
-    for (int k = 0; k < 12; ++k) if (!std::isfinite(guess[k])) return false;
-    if ((nFrom > 0 && (!fromXyz || !fromNormals)) || (nTo > 0 && (!toXyz || !toNormals))) return false;
     CpuPlaneBackend b;
-    fill(b.from, fromXyz, nFrom);
-    fill(b.to, toXyz, nTo);
-    if (!deviceEntry && (b.n_from() != nFrom || b.n_to() != nTo)) return false;
+    if (!set_up(b, fromXyz, nFrom, toXyz, nTo, guess, maxIterations, maxLaserScans, maxCorrespondenceDistance, epsilon, correspondenceRatio, search, deviceEntry)) return false;
     b.cpart_from = b.from.part; b.cpart_to = b.to.part;
     b.nrm_from.assign(fromNormals, fromNormals + (size_t)3 * nFrom);
     b.nrm_to.resize((size_t)3 * nTo);
     b.nfin_from.resize((size_t)nFrom); b.nfin_to.resize((size_t)nTo);
     for (int i = 0; i < nFrom; ++i) b.nfin_from[(size_t)i] = plane::finite3(fromNormals[3 * i], fromNormals[3 * i + 1], fromNormals[3 * i + 2]) ? 1 : 0;
     for (int j = 0; j < nTo; ++j) {
-        rule::apply(guess, toXyz[3 * j], toXyz[3 * j + 1], toXyz[3 * j + 2], b.to.xyz[(size_t)3 * j], b.to.xyz[(size_t)3 * j + 1], b.to.xyz[(size_t)3 * j + 2]);
         plane::rotate(guess, toNormals[3 * j], toNormals[3 * j + 1], toNormals[3 * j + 2], b.nrm_to[(size_t)3 * j], b.nrm_to[(size_t)3 * j + 1], b.nrm_to[(size_t)3 * j + 2]);
         b.nfin_to[(size_t)j] = plane::finite3(toNormals[3 * j], toNormals[3 * j + 1], toNormals[3 * j + 2]) ? 1 : 0;
     }
-    b.raw_from = fromXyz; b.raw_nrm_from = fromNormals; b.thr2 = thr2; b.mode = search; b.h = rule::cell_size(maxCorrespondenceDistance);
-    b.match.assign((size_t)nFrom, -1);
+    b.raw_nrm_from = fromNormals;
     plane::Params p;
     p.max_iterations = maxIterations; p.max_laser_scans = maxLaserScans; p.strategy = lowComplexityStrategy; p.force_3dof = force3DoF; p.gate = normalGate;
     p.epsilon = epsilon; p.correspondence_ratio = correspondenceRatio; p.min_complexity = minComplexity; p.min_normal_cos = minNormalCos;
     plane::Result res;
     plane::solve(b, p, guess, res);
     IcpPlaneResult r;
-    for (int k = 0; k < 12; ++k) { r.transform[k] = res.transform[k]; r.icpTransform[k] = res.icp[k]; r.correction[k] = res.correction[k]; }
-    r.status = res.status; r.stop = res.stop; r.iterations = res.iterations; r.correspondences = res.n_correspondences;
-    r.ratio = res.ratio; r.variance = res.variance;
-    r.match = b.match;
+    common_result(res, b, r);
     r.branch = res.branch; r.complexity = res.complexity; r.secondEigenvalue = res.second;
     for (int k = 0; k < 3; ++k) r.complexityValues[k] = res.values[k];
     for (int k = 0; k < 9; ++k) r.complexityVectors[k] = res.vectors[k];
