@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_register_icp with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -925,7 +925,8 @@ int lcd_estimate_motion_pnp_dev(lcd_engine* h, const lcd_motion_pnp_args* a);
  * covariance (eye x variance, the rotation block / 10).
  * Out of scope here: point-to-plane (Icp/PointToPlane, normals, the low-complexity fallback), which is lcd_register_icp_plane below;
  * libpointmatcher and CCCoreLib (Icp/Strategy 1, 2),
- * Icp/Force4DoF, the scan filters in front (Icp/VoxelSize, DownsamplingStep, RangeMin / RangeMax), intensity, scans above 8192 points, sharded
+ * Icp/Force4DoF, the scan filters in front (Icp/VoxelSize, DownsamplingStep, RangeMin / RangeMax), which are lcd_filter_scans below,
+ * intensity, scans above 8192 points, sharded
  * handles, and on the device the Euler-angle gate and the covariance.
  *
  * search: how step 2 is carried out, never what the call returns.  LCD_ICP_SEARCH_BRUTE walks the whole target for every row.
@@ -1053,7 +1054,8 @@ int lcd_register_icp_dev(lcd_engine* h, const lcd_icp_args* a);
  *      correspondence_ratio and the zero conventions are 4n's steps 9-10.  out_branch and the complexity outputs are written whatever the
  *      status; out_branch is 0 with LCD_ICP_LOW_COMPLEXITY.
  * min_normal_cos is cos(Icp/MaxRotation), computed by the caller (the host mirror does); angle < max is cosine > cos(max).
- * Out of scope: normal estimation (commonFiltering's computeNormals, Icp/PointToPlaneK, Radius, GroundNormalsUp), 2-D scans with normals
+ * Out of scope: normal estimation (commonFiltering's computeNormals, Icp/PointToPlaneK, Radius, GroundNormalsUp), which is
+ * lcd_filter_scans below, 2-D scans with normals
  * (the reference ignores point to plane for them), and everything lcd_register_icp leaves out.
  *
  * Limits and errors: those of lcd_register_icp, and LCD_ERR_INVALID for a min_complexity outside [0, 1], a low_complexity_strategy outside
@@ -1104,6 +1106,99 @@ int lcd_register_icp_plane(lcd_engine* h, const lcd_icp_plane_args* a);
 /* rows, normals and out_* in DEVICE memory (4-byte aligned, out_variance 8-byte), offsets and guesses on the HOST (read during the call);
  * enqueued on the engine stream, not synchronised */
 int lcd_register_icp_plane_dev(lcd_engine* h, const lcd_icp_plane_args* a);
+
+/* ---- Scan filtering, stateless: what RegistrationIcp does to each scan in front of the ICP, util3d::commonFiltering
+ * (RegistrationIcp.cpp:362-447, util3d_filtering.cpp:74-332): Icp/DownsamplingStep, Icp/RangeMin / RangeMax, Icp/VoxelSize, the normals of
+ * Icp/PointToPlaneK or Icp/PointToPlaneRadius, and Icp/PointToPlaneGroundNormalsUp -- with the reference's defaults a voxel grid of 0.05 m and
+ * normals from 5 neighbours.  It turns a raw scan into what lcd_register_icp_plane takes and brings it under that call's 8 192 rows.  What is
+ * in the reference tree is reproduced exactly (steps 1, 4 and 5).  pcl::VoxelGrid, pcl::NormalEstimation and the kd-tree are not in the tree:
+ * steps 2 and 3 are the ENGINE'S rule, modelled on PCL's defaults and written out here.  No bit parity with a PCL build is claimed.
+ * Stateless exactly as lcd_register_icp: any number of scans per call, the handle's device and stream borrowed, nothing of its state touched,
+ * nothing of a pipelined handle drained.
+ *
+ * Scan f reads the rows [offsets[f], offsets[f+1]) of xyz and owns the rows [out_offsets[f], out_offsets[f+1]) of out_xyz and out_normals,
+ * its output region; the region's length is its capacity.  The first out_count[f] rows of the region are the result; EVERY remaining row of
+ * the region is written as three quiet NaNs (0x7FC00000), in out_xyz and in out_normals.  The device entries of lcd_register_icp and
+ * lcd_register_icp_plane skip a row with a coordinate that is not finite and count it towards no size, so a caller who gives each scan a
+ * region of at most 8 192 rows passes out_offsets to them as the pair's offsets, with nothing read back.
+ *
+ * The rule, per scan of n rows.  fp32, every operation rounded on its own (nothing fused), IEEE division and square root, only + - x / sqrt
+ * and floor.
+ *   1. Downsampling and range (util3d_filtering.cpp:90-140).  step = downsampling_step; step <= 1 or n <= step gives step = 1.  The sampled
+ *      rows are 0, step, 2 step, .. while i < n - step + 1: n / step of them.  With range_min > 0 || range_max > 0: r = (x*x + y*y) + z*z, with
+ *      is_2d x*x + y*y; a row goes when r is not finite, when range_min > 0 && r < range_min * range_min, or when range_max > 0 && r >
+ *      range_max * range_max (strict, as written).  Order is kept.  The engine's definition for a row with a coordinate that is not finite:
+ *      the host entry refuses it; the device entry drops it here, whether or not a range is set, and it still occupies its sampling slot.
+ *      No row left: LCD_SCAN_EMPTY.
+ *   2. Voxel grid (voxel_size > 0; pcl::VoxelGrid as voxelizeImpl :740-751 configures it).  inv = 1.0f / voxel_size; a coordinate's cell is
+ *      floor(x_a * inv) as an integer -- a floor, so negative coordinates round down.  A cell beyond int32: LCD_SCAN_GRID_TOO_LARGE.  d_a =
+ *      max cell - min cell + 1 in int64; d_x d_y d_z > INT32_MAX: LCD_SCAN_GRID_TOO_LARGE (the reference then splits space into octants,
+ *      :695-737, which is out of scope).  A voxel's index is (c_x - min_x) + (c_y - min_y) d_x + (c_z - min_z) d_x d_y.  The output has one
+ *      row per occupied voxel in ascending index: the centroid, each coordinate summed from +0.0f over the voxel's rows in ascending row
+ *      order, then divided by float(count).
+ *   3. Normals (normal_k > 0 or normal_radius > 0; pcl::NormalEstimation as computeNormalsImpl :2819-2857 configures it).  The cloud C is
+ *      what steps 1-2 left; more than 8 192 rows in C: LCD_SCAN_TOO_MANY_ROWS.  d2 is lcd_register_icp's step 2.  The neighbours of row p in
+ *      K mode: the min(K, |C|) rows with the smallest keys bits(d2) << 32 | row, p itself among them, visited in ascending key; in radius
+ *      mode every row with d2 <= normal_radius * normal_radius, visited in ascending row.  Fewer than 3 neighbours: the normal is three NaNs.
+ *      The sums, each from +0.0f in the visiting order, over u = q - p: S_a = SUM u_a, S_ab = SUM u_a * u_b for the upper triangle; m_a =
+ *      S_a / float(n); cov_ab = S_ab / float(n) - m_a * m_b.  LCD_ICP_PLANE_SWEEPS sweeps of the cyclic Jacobi of lcd_register_icp_plane's
+ *      step 2; the normal is the vector of the smallest value as the Jacobi leaves it (not normalised again; the lower index among equal
+ *      values).  Flip: with v = viewpoint - p the normal is negated iff ((v_x n_x + v_y n_y) + v_z n_z) < 0.
+ *   4. Rows without a normal go (laserScanFromPointCloud(cloud, normals) filters NaNs, :187, :239, :299): a row whose normal is not finite
+ *      is dropped, order kept.  No row left: LCD_SCAN_EMPTY.
+ *   5. Ground normals up (adjustNormalsToViewPoint, util3d_surface.cpp:3573-3606, with the viewpoint (0, 0, 10) of :328; only with
+ *      ground_normals_up > 0 and normals): v = (0, 0, 10) - p; the normal is negated iff ((v_x n_x + v_y n_y) + v_z n_z) < 0 or (n_z <
+ *      -ground_normals_up && p_z < 10.0f).
+ *   6. Outputs.  More rows than the region holds: LCD_SCAN_NO_ROOM.  Every status but LCD_SCAN_OK gives out_count = 0 and an all-NaN region.
+ *      out_stage_counts = the rows after step 1, after step 2 (step 1's without a voxel grid) and the final count, each as far as the scan
+ *      got and 0 behind that; with LCD_SCAN_NO_ROOM the third is the count that found no room.  They let a caller redo the reference's
+ *      maxPoints bookkeeping (util3d_filtering.cpp:159, :180-181; RegistrationIcp.cpp:363-364, :404-405, :879), as the host mirror does.
+ * Out of scope: 2-D normals (computeNormals2D, computeFastOrganizedNormals2D), intensity, RGB and input normals carried through the voxel
+ * grid, the octant split of an over-large grid, libpointmatcher's data-point filters (:377-402), organised scans whose rows outnumber their
+ * columns (:102), scans above 16 384 sampled rows or above 8 192 rows reaching step 3, sharded handles.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable.  LCD_ERR_UNSUPPORTED: more than 16 384 sampled
+ * rows (n / step) in a scan, n_scans > 65535, a handle of a sharded vocabulary, is_2d with normals asked for.  LCD_ERR_INVALID: normal_k > 0
+ * together with normal_radius > 0 (PCL refuses both), normal_k outside 0 .. LCD_SCAN_MAX_K, a float parameter that is not finite, voxel_size,
+ * normal_radius or ground_normals_up below 0, n_scans < 0, offsets that are missing, do not start at 0 or decrease, NULL where rows or outputs
+ * exist, out_normals NULL while normals are asked for (it is not touched when none are), a wrong struct_size, and on the HOST entry a row with
+ * a coordinate that is not finite.  A negative range bound disables that bound, as the reference does.  n_scans == 0 returns LCD_OK.  At most
+ * three kernel launches per call whatever the batch (one without normals): one workgroup per scan for steps 1-2, one per 256 rows of C for
+ * step 3, one per scan for steps 4-6. */
+enum lcd_scan_status {
+    LCD_SCAN_OK = 0,
+    LCD_SCAN_EMPTY = 1,               /* no row left behind step 1 or behind step 4 */
+    LCD_SCAN_GRID_TOO_LARGE = 2,
+    LCD_SCAN_TOO_MANY_ROWS = 3,       /* more than 8 192 rows reach the normals */
+    LCD_SCAN_NO_ROOM = 4              /* the result does not fit the scan's output region */
+};
+#define LCD_SCAN_MAX_K 32
+typedef struct lcd_scan_filter_args {
+    int32_t struct_size;            /* sizeof(lcd_scan_filter_args) */
+    int32_t n_scans;                /* >= 0; 0 returns LCD_OK */
+    int32_t downsampling_step;      /* Icp/DownsamplingStep; <= 1: none */
+    int32_t is_2d;                  /* the range uses x and y only */
+    int32_t normal_k;               /* Icp/PointToPlaneK, 0 .. LCD_SCAN_MAX_K */
+    int32_t reserved;               /* 0 */
+    float range_min, range_max;     /* Icp/RangeMin, RangeMax; <= 0: off */
+    float voxel_size;               /* Icp/VoxelSize; 0: off */
+    float normal_radius;            /* Icp/PointToPlaneRadius; 0: off */
+    float ground_normals_up;        /* Icp/PointToPlaneGroundNormalsUp; 0: off */
+    float viewpoint[3];             /* the reference passes (0, 0, 0) */
+    const float* xyz;               /* [N x 3] */
+    const int64_t* offsets;         /* HOST [n_scans + 1], non-decreasing, [0] == 0 */
+    const int64_t* out_offsets;     /* HOST [n_scans + 1]: each scan's output region, its capacity */
+    float* out_xyz;                 /* [M x 3] */
+    float* out_normals;             /* [M x 3]; NULL iff no normals are asked for */
+    int32_t* out_count;             /* [n_scans] */
+    int32_t* out_stage_counts;      /* [n_scans x 3]: after step 1, after the voxel grid, final */
+    int32_t* out_status;            /* [n_scans], lcd_scan_status */
+} lcd_scan_filter_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_filter_scans(lcd_engine* h, const lcd_scan_filter_args* a);
+/* rows and out_* in DEVICE memory (4-byte aligned), both offset arrays on the HOST (read during the call); enqueued on the engine stream,
+ * not synchronised */
+int lcd_filter_scans_dev(lcd_engine* h, const lcd_scan_filter_args* a);
 
 /* Rtabmap::adjustLikelihood (Rtabmap.cpp:5691-5760) on a likelihood vector whose entry 0 is the virtual place;
  * in/out on the host, reduction on the device.  ("next" row f1 of the scope table) */

@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -166,6 +166,15 @@ class LcdIcpPlaneArgs(C.Structure):
                 ("out_second_eigenvalue", C.c_void_p)]
 
 
+class LcdScanFilterArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_scans", C.c_int32), ("downsampling_step", C.c_int32), ("is_2d", C.c_int32), ("normal_k", C.c_int32),
+                ("reserved", C.c_int32), ("range_min", C.c_float), ("range_max", C.c_float), ("voxel_size", C.c_float), ("normal_radius", C.c_float),
+                ("ground_normals_up", C.c_float), ("viewpoint", C.c_float * 3), ("xyz", C.c_void_p), ("offsets", C.c_void_p), ("out_offsets", C.c_void_p),
+                ("out_xyz", C.c_void_p), ("out_normals", C.c_void_p), ("out_count", C.c_void_p), ("out_stage_counts", C.c_void_p), ("out_status", C.c_void_p)]
+
+
+LCD_SCAN_OK, LCD_SCAN_EMPTY, LCD_SCAN_GRID_TOO_LARGE, LCD_SCAN_TOO_MANY_ROWS, LCD_SCAN_NO_ROOM = 0, 1, 2, 3, 4  # lcd_scan_status
+LCD_SCAN_MAX_K = 32
 LCD_ICP_OK, LCD_ICP_EMPTY, LCD_ICP_NOT_CONVERGED, LCD_ICP_BELOW_RATIO, LCD_ICP_LOW_COMPLEXITY = 0, 1, 2, 3, 4  # lcd_icp_status
 LCD_ICP_STOP_NONE, LCD_ICP_STOP_ITERATIONS, LCD_ICP_STOP_TRANSFORM, LCD_ICP_STOP_MSE, LCD_ICP_STOP_FEW_CORRESPONDENCES, LCD_ICP_STOP_SINGULAR = 0, 1, 2, 3, 4, 5  # lcd_icp_stop
 LCD_ICP_SEARCH_AUTO, LCD_ICP_SEARCH_BRUTE, LCD_ICP_SEARCH_GRID = 0, 1, 2  # lcd_icp_search
@@ -274,6 +283,8 @@ def load():
     L.lcd_register_icp_dev.argtypes = [vp, C.POINTER(LcdIcpArgs)]
     L.lcd_register_icp_plane.argtypes = [vp, C.POINTER(LcdIcpPlaneArgs)]
     L.lcd_register_icp_plane_dev.argtypes = [vp, C.POINTER(LcdIcpPlaneArgs)]
+    L.lcd_filter_scans.argtypes = [vp, C.POINTER(LcdScanFilterArgs)]
+    L.lcd_filter_scans_dev.argtypes = [vp, C.POINTER(LcdScanFilterArgs)]
     L.lcd_adjust_likelihood.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_adjust_likelihood_dev.argtypes = [vp, vp, C.c_int, f32]
     L.lcd_frame_dev.argtypes = [vp, C.POINTER(LcdFrameArgs)]
@@ -933,6 +944,57 @@ class Engine:
         for k, _, _ in self.ICP_PLANE_OUT + (("match", 0, np.int32),):
             setattr(a, "out_" + k, ptr(d_out[k]))
         self._ck(self.L.lcd_register_icp_plane_dev(self.h, C.byref(a)))
+
+    # ---- scan filtering in front of the ICP: downsampling, range, voxel grid, normals (stateless; include/lcd.h has the rule)
+    @staticmethod
+    def _scan_filter_args(n_scans, downsampling_step, is_2d, normal_k, range_min, range_max, voxel_size, normal_radius, ground_normals_up, viewpoint,
+                          struct_size):
+        vp = (C.c_float * 3)(*[float(v) for v in viewpoint])
+        return LcdScanFilterArgs(C.sizeof(LcdScanFilterArgs) if struct_size is None else struct_size, n_scans, int(downsampling_step), int(bool(is_2d)),
+                                 int(normal_k), 0, float(range_min), float(range_max), float(voxel_size), float(normal_radius), float(ground_normals_up), vp)
+
+    def filter_scans(self, xyz, offsets, out_offsets, downsampling_step=1, is_2d=False, normal_k=0, range_min=0.0, range_max=0.0, voxel_size=0.0,
+                     normal_radius=0.0, ground_normals_up=0.0, viewpoint=(0.0, 0.0, 0.0), struct_size=None, with_normals=None):
+        """lcd_filter_scans over host arrays, all scans concatenated -> dict(xyz, normals [M x 3] (None when no normals are asked for), count, status
+        [n_scans], stage_counts [n_scans x 3]); outputs start as -7 / 7.0 so that what the call left alone shows.  with_normals: whether
+        out_normals is handed over (default: iff normals are asked for)"""
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.int64).reshape(-1)
+        x = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        n_scans = (off if off is not None else oo).shape[0] - 1
+        m_rows = int(oo[-1]) if oo is not None and oo.shape[0] else 0
+        if with_normals is None:
+            with_normals = normal_k > 0 or normal_radius > 0
+        m = max(n_scans, 1)
+        out = dict(xyz=np.full((max(m_rows, 1), 3), 7.0, np.float32), normals=np.full((max(m_rows, 1), 3), 7.0, np.float32) if with_normals else None,
+                   count=np.full(m, -7, np.int32), stage_counts=np.full((m, 3), -7, np.int32), status=np.full(m, -7, np.int32))
+        a = self._scan_filter_args(n_scans, downsampling_step, is_2d, normal_k, range_min, range_max, voxel_size, normal_radius, ground_normals_up,
+                                   viewpoint, struct_size)
+        a.xyz = None if x is None or x.shape[0] == 0 else _p(x)
+        a.offsets, a.out_offsets = None if off is None else off.ctypes.data, None if oo is None else oo.ctypes.data
+        for k, v in out.items():
+            setattr(a, "out_" + k, None if v is None else _p(v))
+        self._ck(self.L.lcd_filter_scans(self.h, C.byref(a)))
+        out["xyz"] = out["xyz"][:m_rows]
+        if with_normals:
+            out["normals"] = out["normals"][:m_rows]
+        for k in ("count", "stage_counts", "status"):
+            out[k] = out[k][:max(n_scans, 0)]
+        return out
+
+    def filter_scans_dev(self, d_xyz, offsets, out_offsets, d_out, downsampling_step=1, is_2d=False, normal_k=0, range_min=0.0, range_max=0.0,
+                         voxel_size=0.0, normal_radius=0.0, ground_normals_up=0.0, viewpoint=(0.0, 0.0, 0.0)):
+        """lcd_filter_scans_dev on torch tensors of the engine's device (both offset arrays stay on the host); d_out maps xyz, normals (None
+        without normals), count, stage_counts and status to the output tensors.  Enqueued, not synchronised."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        a = self._scan_filter_args(off.shape[0] - 1, downsampling_step, is_2d, normal_k, range_min, range_max, voxel_size, normal_radius,
+                                   ground_normals_up, viewpoint, None)
+        a.xyz, a.offsets, a.out_offsets = ptr(d_xyz), off.ctypes.data, oo.ctypes.data
+        for k in ("xyz", "normals", "count", "stage_counts", "status"):
+            setattr(a, "out_" + k, ptr(d_out.get(k)))
+        self._ck(self.L.lcd_filter_scans_dev(self.h, C.byref(a)))
 
     # ---- global descriptors: Signature::compareTo's other branch
     @staticmethod

@@ -63,6 +63,22 @@ M3D_FN void pca_mean(int oi, const float sum[3], float mean[3]) {
     for (int a = 0; a < 3; ++a) mean[a] = sum[a] / rows;
 }
 
+// The eigen decomposition of a symmetric 3 x 3 given as its upper triangle (xx, xy, xz, yy, yz, zz): SWEEPS sweeps of the cyclic Jacobi over
+// the planes (0, 1), (0, 2), (1, 2).  The values are left on A's diagonal in no order, value k's vector in column k of V.  Step 2 here and the
+// normals of scan_filter_rule.h call it.
+M3D_FN void jacobi3(const float cov[6], float A[4][4], float V[4][4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { A[r][c] = 0.0f; V[r][c] = r == c ? 1.0f : 0.0f; }
+    A[0][0] = cov[0]; A[0][1] = cov[1]; A[0][2] = cov[2]; A[1][1] = cov[3]; A[1][2] = cov[4]; A[2][2] = cov[5];
+    A[1][0] = cov[1]; A[2][0] = cov[2]; A[2][1] = cov[4];
+#pragma unroll
+    for (int sweep = 0; sweep < SWEEPS; ++sweep) {
+        m3d::jacobi_rotate<0, 1>(A, V); m3d::jacobi_rotate<0, 2>(A, V); m3d::jacobi_rotate<1, 2>(A, V);
+    }
+}
+
 // the covariance from the six sums over the oi rows that carry a normal and the oi zero rows' share, its eigenvalues and vectors
 M3D_FN void pca_of(int oi, const float mean[3], const float C[6], Pca& p) {
     const float rows = (float)(2 * oi), zeros = (float)oi;
@@ -76,16 +92,7 @@ M3D_FN void pca_of(int oi, const float mean[3], const float C[6], Pca& p) {
         cov[k] = s / rows;
     }
     float A[4][4], V[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { A[r][c] = 0.0f; V[r][c] = r == c ? 1.0f : 0.0f; }
-    A[0][0] = cov[0]; A[0][1] = cov[1]; A[0][2] = cov[2]; A[1][1] = cov[3]; A[1][2] = cov[4]; A[2][2] = cov[5];
-    A[1][0] = cov[1]; A[2][0] = cov[2]; A[2][1] = cov[4];
-#pragma unroll
-    for (int sweep = 0; sweep < SWEEPS; ++sweep) {
-        m3d::jacobi_rotate<0, 1>(A, V); m3d::jacobi_rotate<0, 2>(A, V); m3d::jacobi_rotate<1, 2>(A, V);
-    }
+    jacobi3(cov, A, V);
     // descending, the lower index first among equals (a NaN stays where it is); values are selected, never an address
     float v0 = A[0][0], v1 = A[1][1], v2 = A[2][2];
     float e0[3] = {V[0][0], V[1][0], V[2][0]}, e1[3] = {V[0][1], V[1][1], V[2][1]}, e2[3] = {V[0][2], V[1][2], V[2][2]};

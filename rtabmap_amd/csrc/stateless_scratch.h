@@ -13,7 +13,7 @@
 //   lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip),
 //   lcd_select_features and lcd_expand_word_ids (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip),
 //   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip),
-//   lcd_register_icp (register_icp.hip) and lcd_register_icp_plane (register_icp_plane.hip).
+//   lcd_register_icp (register_icp.hip), lcd_register_icp_plane (register_icp_plane.hip) and lcd_filter_scans (scan_filter.hip).
 // Everything they write on the device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The
 // buffers only grow, and a growth frees the old allocation after the engine stream has drained (DevBuf::reserve): work of an earlier call
 // that is still enqueued keeps what it reads.  The protocol is the methods' and HostStage's; the callers own only d_dist and d_small.
@@ -25,6 +25,8 @@ struct StatelessScratch {
     //   lcd_estimate_motion_pnp: 44 bytes per to-row (eight coordinate planes, errors, two index sets)
     //   lcd_register_icp: 20 bytes per row of either side (three coordinate planes, the nearest row, its d2)
     //   lcd_register_icp_plane: 32 bytes per row of either side (lcd_register_icp's 20 and three normal planes)
+    //   lcd_filter_scans: 16 bytes per scan (the counts and the status between its launches), then 36 bytes per sampled row (three
+    //   coordinate planes behind step 1, three behind the voxel grid, three normal planes)
     lcd::DevBuf d_small;
     int64_t budget_bytes = 0;                           // lcd_set_option("pair_match_budget"): distance-block bytes per group (0: built-in, 256 MiB)
 

@@ -408,4 +408,61 @@ Transform3D RegistrationIcpHip::computeTransformation(lcd_engine* engine, const 
     return finish(r, info);
 }
 
+Transform3D RegistrationIcpHip::computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, bool fromIs2d, int fromMaxPoints,
+                                                      const std::vector<Point3f>& toScan, bool toIs2d, int toMaxPoints, const Transform3D& guess,
+                                                      RegistrationInfoIcp& info, FilteredScans* filtered) const {
+    info = RegistrationInfoIcp();
+    FilteredScans fs;
+    fs.fromScan = fromScan; fs.toScan = toScan;
+    int maxFrom = fromMaxPoints > 0 ? fromMaxPoints : (int)fromScan.size(), maxTo = toMaxPoints > 0 ? toMaxPoints : (int)toScan.size();   // :363-364
+    struct Side { const std::vector<Point3f>* raw; std::vector<Point3f>* xyz; std::vector<Point3f>* normals; bool is2d; int* maxScans; };
+    std::vector<Side> sides;
+    if (!fromScan.empty() && (filtersEnabled & 1)) sides.push_back(Side{&fromScan, &fs.fromScan, &fs.fromNormals, fromIs2d, &maxFrom});
+    if (!toScan.empty() && (filtersEnabled & 2)) sides.push_back(Side{&toScan, &fs.toScan, &fs.toNormals, toIs2d, &maxTo});
+    // one call for the sides that agree on 2-D, which is every pair but a mixed one
+    for (size_t first = 0; first < sides.size();) {
+        size_t last = first + 1;
+        while (last < sides.size() && sides[last].is2d == sides[first].is2d) ++last;
+        const int ns = (int)(last - first);
+        const bool normals = pointToPlane && !sides[first].is2d && (pointToPlaneK > 0 || pointToPlaneRadius > 0.0f);
+        std::vector<float> xyz;
+        std::vector<int64_t> offsets(1, 0), outOffsets(1, 0);
+        for (size_t s = first; s < last; ++s) {
+            const std::vector<Point3f>& raw = *sides[s].raw;
+            xyz.insert(xyz.end(), &raw[0].x, &raw[0].x + raw.size() * 3);
+            offsets.push_back(offsets.back() + (int64_t)raw.size());
+            outOffsets.push_back(outOffsets.back() + (int64_t)raw.size());                 // a scan never grows
+        }
+        std::vector<float> outXyz((size_t)outOffsets.back() * 3), outNormals(normals ? outXyz.size() : 0);
+        int32_t count[2] = {0, 0}, stages[6], status[2] = {0, 0};
+        lcd_scan_filter_args a;
+        a.struct_size = (int32_t)sizeof a; a.n_scans = ns; a.downsampling_step = downsamplingStep; a.is_2d = sides[first].is2d ? 1 : 0;
+        a.normal_k = normals ? pointToPlaneK : 0; a.reserved = 0; a.range_min = rangeMin; a.range_max = rangeMax; a.voxel_size = voxelSize;
+        a.normal_radius = normals ? pointToPlaneRadius : 0.0f; a.ground_normals_up = normals ? pointToPlaneGroundNormalsUp : 0.0f;
+        a.viewpoint[0] = a.viewpoint[1] = a.viewpoint[2] = 0.0f;
+        a.xyz = xyz.data(); a.offsets = offsets.data(); a.out_offsets = outOffsets.data(); a.out_xyz = outXyz.data();
+        a.out_normals = normals ? outNormals.data() : nullptr; a.out_count = count; a.out_stage_counts = stages; a.out_status = status;
+        if (!engine || lcd_filter_scans(engine, &a) != LCD_OK) {
+            info.rejectedMsg = "the engine refused the call";
+            return Transform3D();
+        }
+        for (size_t s = first; s < last; ++s) {
+            const size_t k = s - first, n = (size_t)count[k];
+            const Point3f* px = reinterpret_cast<const Point3f*>(outXyz.data()) + outOffsets[k];
+            sides[s].xyz->assign(px, px + n);
+            if (normals) {
+                const Point3f* pn = reinterpret_cast<const Point3f*>(outNormals.data()) + outOffsets[k];
+                sides[s].normals->assign(pn, pn + n);
+            }
+            const float ratio = float(n) / float(sides[s].raw->size());                  // :404-405
+            *sides[s].maxScans = int(float(*sides[s].maxScans) * ratio);
+        }
+        first = last;
+    }
+    fs.maxLaserScans = maxTo ? maxTo : maxFrom;                            // :879
+    const Transform3D t = computeTransformation(engine, fs.fromScan, fs.fromNormals, fromIs2d, fs.toScan, fs.toNormals, toIs2d, guess, fs.maxLaserScans, info);
+    if (filtered) *filtered = fs;
+    return t;
+}
+
 }  // namespace rtabmap_amd

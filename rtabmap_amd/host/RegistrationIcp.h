@@ -58,6 +58,11 @@ struct RegistrationInfoIcp {             // the fields of RegistrationInfo that 
     RegistrationInfoIcp() { for (int k = 0; k < 36; ++k) covariance[k] = k % 7 == 0 ? 1.0 : 0.0; }
 };
 
+struct FilteredScans {                   // what the filters in front handed to the ICP
+    std::vector<Point3f> fromScan, fromNormals, toScan, toNormals;
+    int maxLaserScans = 0;
+};
+
 class RegistrationIcpHip {
 public:
     int maxIterations = 30;                      // Icp/Iterations
@@ -70,6 +75,13 @@ public:
     bool pointToPlane = true;                    // Icp/PointToPlane
     float pointToPlaneMinComplexity = 0.02f;     // Icp/PointToPlaneMinComplexity
     int pointToPlaneLowComplexityStrategy = 1;   // Icp/PointToPlaneLowComplexityStrategy
+    int filtersEnabled = 3;                      // Icp/FiltersEnabled: 1 = the from-scan, 2 = the to-scan
+    int downsamplingStep = 1;                    // Icp/DownsamplingStep
+    float rangeMin = 0.0f, rangeMax = 0.0f;      // Icp/RangeMin, Icp/RangeMax
+    float voxelSize = 0.05f;                     // Icp/VoxelSize
+    int pointToPlaneK = 5;                       // Icp/PointToPlaneK
+    float pointToPlaneRadius = 0.0f;             // Icp/PointToPlaneRadius
+    float pointToPlaneGroundNormalsUp = 0.0f;    // Icp/PointToPlaneGroundNormalsUp
 
     // The reference's shape: both scans as point rows in their base frames, the guess, the scan's maximum number of points (0: the ratio is
     // relative).  A null transform when the registration is rejected (info.rejectedMsg says why) or the engine refuses the call.
@@ -81,6 +93,14 @@ public:
     Transform3D computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, const std::vector<Point3f>& fromNormals, bool fromIs2d,
                                       const std::vector<Point3f>& toScan, const std::vector<Point3f>& toNormals, bool toIs2d, const Transform3D& guess,
                                       int maxLaserScans, RegistrationInfoIcp& info) const;
+    // The same over RAW scans (RegistrationIcp.cpp:362-447): the sides filtersEnabled names go through lcd_filter_scans in one call (two when
+    // one scan is 2-D and the other is not) with K, radius and ground-up passed as 0 without pointToPlane (:374-376) or for a 2-D scan (2-D
+    // normals are out of scope); a scan the filter leaves with a status other than LCD_SCAN_OK is empty.  maxLaserScansFrom / To are the
+    // reference's: maxPoints when > 0 else the raw size, times float(filtered size) / float(raw size) for a filtered side; the ratio is
+    // relative to the to-side's when it is not 0, else the from-side's (:879).  Then the overload above.  `filtered`, when given, receives what
+    // the ICP was handed.
+    Transform3D computeTransformation(lcd_engine* engine, const std::vector<Point3f>& fromScan, bool fromIs2d, int fromMaxPoints, const std::vector<Point3f>& toScan,
+                                      bool toIs2d, int toMaxPoints, const Transform3D& guess, RegistrationInfoIcp& info, struct FilteredScans* filtered = nullptr) const;
     // RegistrationIcp.cpp:856-961 behind the rule: what computeTransformation does with the engine's (or register_icp_cpu's) result
     Transform3D finish(const IcpResult& r, RegistrationInfoIcp& info) const;
 };

@@ -13,6 +13,7 @@
 #include "Motion2D.h"
 #include "Motion3D.h"
 #include "RegistrationIcp.h"
+#include "ScanFilter.h"
 #include "RtabmapHip.h"
 
 using namespace rtabmap_amd;
@@ -371,6 +372,51 @@ int hicpp_compute(void* h, const float* fromXyz, const float* fromNormals, int n
     RegistrationInfoIcp info;
     const Transform3D t = reg.computeTransformation(((VWDictionaryHip*)h)->engine(), rows(fromXyz, nFrom), rows(fromNormals, nFrom), fromIs2d != 0,
                                                     rows(toXyz, nTo), rows(toNormals, nTo), toIs2d != 0, g, maxLaserScans, info);
+    outInfo[3] = info.icpStructuralComplexity;
+    return icp_info_out(t, info, outTransform, outInfo, outCorrespondences, outCovariance);
+}
+// filter_scans_cpu (no engine involved): one scan into a region of `capacity` rows.  viewpoint[3]; outXyz / outNormals [capacity x 3] (outNormals
+// is written only when normals are asked for); outInts[5] = status, count, the three stage counts.  Returns LCD_OK or the refusal's code
+int hsf_cpu(const float* xyz, long long n, int downsamplingStep, int is2d, float rangeMin, float rangeMax, float voxelSize, int normalK, float normalRadius,
+            float groundNormalsUp, const float* viewpoint, long long capacity, int deviceEntry, float* outXyz, float* outNormals, int* outInts) {
+    ScanFilterParams p;
+    p.downsamplingStep = downsamplingStep; p.is2d = is2d != 0; p.rangeMin = rangeMin; p.rangeMax = rangeMax; p.voxelSize = voxelSize;
+    p.normalK = normalK; p.normalRadius = normalRadius; p.groundNormalsUp = groundNormalsUp;
+    std::copy(viewpoint, viewpoint + 3, p.viewpoint);
+    ScanFilterResult r;
+    const int rc = filter_scans_cpu(xyz, n, p, capacity, deviceEntry != 0, r);
+    if (rc != 0) return rc;
+    std::copy(r.xyz.begin(), r.xyz.end(), outXyz);
+    std::copy(r.normals.begin(), r.normals.end(), outNormals);
+    outInts[0] = r.status; outInts[1] = r.count;
+    std::copy(r.stageCounts, r.stageCounts + 3, outInts + 2);
+    return 0;
+}
+// RegistrationIcpHip::computeTransformation over raw scans through the dictionary's engine: the filters of `filtersEnabled` in front (lcd_filter_scans),
+// then hicpp_compute's work.  filter[8] = downsamplingStep, rangeMin, rangeMax, voxelSize, pointToPlaneK, pointToPlaneRadius,
+// pointToPlaneGroundNormalsUp, filtersEnabled; outputs as hicpp_compute, outSizes[3] = the from-scan's and the to-scan's rows behind the filters, maxLaserScans
+int hicpf_compute(void* h, const float* fromXyz, int nFrom, int fromIs2d, int fromMaxPoints, const float* toXyz, int nTo, int toIs2d, int toMaxPoints,
+                  const float* guess, const float* filter, int maxIterations, int force3DoF, double maxCorrespondenceDistance, float epsilon,
+                  float correspondenceRatio, float maxTranslation, float maxRotation, int pointToPlane, float minComplexity, int lowComplexityStrategy,
+                  float* outTransform, float* outInfo, int* outCorrespondences, double* outCovariance, int* outSizes) {
+    auto rows = [](const float* x, int n) {
+        std::vector<Point3f> v((size_t)(x ? n : 0));
+        for (size_t i = 0; i < v.size(); ++i) v[i] = Point3f{x[3 * i], x[3 * i + 1], x[3 * i + 2]};
+        return v;
+    };
+    Transform3D g;
+    std::copy(guess, guess + 12, g.data);
+    RegistrationIcpHip reg;
+    reg.maxIterations = maxIterations; reg.force3DoF = force3DoF != 0; reg.maxCorrespondenceDistance = maxCorrespondenceDistance; reg.epsilon = epsilon;
+    reg.correspondenceRatio = correspondenceRatio; reg.maxTranslation = maxTranslation; reg.maxRotation = maxRotation;
+    reg.pointToPlane = pointToPlane != 0; reg.pointToPlaneMinComplexity = minComplexity; reg.pointToPlaneLowComplexityStrategy = lowComplexityStrategy;
+    reg.downsamplingStep = (int)filter[0]; reg.rangeMin = filter[1]; reg.rangeMax = filter[2]; reg.voxelSize = filter[3]; reg.pointToPlaneK = (int)filter[4];
+    reg.pointToPlaneRadius = filter[5]; reg.pointToPlaneGroundNormalsUp = filter[6]; reg.filtersEnabled = (int)filter[7];
+    RegistrationInfoIcp info;
+    FilteredScans fs;
+    const Transform3D t = reg.computeTransformation(((VWDictionaryHip*)h)->engine(), rows(fromXyz, nFrom), fromIs2d != 0, fromMaxPoints, rows(toXyz, nTo),
+                                                    toIs2d != 0, toMaxPoints, g, info, &fs);
+    outSizes[0] = (int)fs.fromScan.size(); outSizes[1] = (int)fs.toScan.size(); outSizes[2] = fs.maxLaserScans;
     outInfo[3] = info.icpStructuralComplexity;
     return icp_info_out(t, info, outTransform, outInfo, outCorrespondences, outCovariance);
 }

@@ -81,6 +81,8 @@ def lib():
         L.hicp_compute.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, cf, vp, vp, vp, vp]
         L.hicpp_cpu.argtypes = [vp, vp, ci, vp, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, ci, ci, C.c_double, ci, ci, vp, vp, vp, vp, vp, vp]
         L.hicpp_compute.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, ci, ci, ci, C.c_double, cf, cf, cf, cf, ci, cf, ci, vp, vp, vp, vp]
+        L.hicpf_compute.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp, ci, ci, C.c_double, cf, cf, cf, cf, ci, cf, ci, vp, vp, vp, vp, vp]
+        L.hsf_cpu.argtypes = [vp, C.c_longlong, ci, ci, cf, cf, cf, ci, cf, cf, vp, C.c_longlong, ci, vp, vp, vp]
         L.hmem_select_error.argtypes = [vp]
         L.hmem_select_error.restype = C.c_char_p
         L.hfs_limit_keypoints.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp]
@@ -311,6 +313,23 @@ def register_icp_plane_cpu(from_xyz, from_normals, to_xyz, to_normals, guess=Non
                 complexity_values=cx[1:4].copy(), complexity_vectors=cx[4:13].copy(), second_eigenvalue=cx[13])
 
 
+def filter_scans_cpu(xyz, capacity=None, downsampling_step=1, is_2d=False, normal_k=0, range_min=0.0, range_max=0.0, voxel_size=0.0, normal_radius=0.0,
+                     ground_normals_up=0.0, viewpoint=(0.0, 0.0, 0.0), device_entry=False):
+    """the rule of lcd_filter_scans on the CPU (host/ScanFilter.cpp, no device) for one scan and an output region of `capacity` rows (default:
+    the scan's) -> dict(xyz, normals [capacity x 3] (None without normals), count, status, stage_counts [3]); the refusal's code (an int) where
+    the call is refused"""
+    x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    cap = x.shape[0] if capacity is None else int(capacity)
+    normals = normal_k > 0 or normal_radius > 0
+    ox, on, ints = np.full((max(cap, 1), 3), 7.0, np.float32), np.full((max(cap, 1), 3), 7.0, np.float32), np.zeros(5, np.int32)
+    vp = np.asarray(viewpoint, np.float32)
+    rc = lib().hsf_cpu(_p(x), x.shape[0], int(downsampling_step), int(bool(is_2d)), float(range_min), float(range_max), float(voxel_size), int(normal_k),
+                       float(normal_radius), float(ground_normals_up), _p(vp), cap, int(bool(device_entry)), _p(ox), _p(on), _p(ints))
+    if rc != 0:
+        return int(rc)
+    return dict(xyz=ox[:cap], normals=on[:cap] if normals else None, count=int(ints[1]), status=int(ints[0]), stage_counts=ints[2:5].copy())
+
+
 def register_icp_cells(x, max_correspondence_distance):
     """the grid form's cell of every coordinate (csrc/icp_rule.h) -> (cells int64 with None-like INT_MIN where out of range, the cell size)"""
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
@@ -496,6 +515,24 @@ class VWDictionaryHip:
                                  int(bool(point_to_plane)), float(min_complexity), int(low_complexity_strategy), _p(t), _p(info), _p(corr), _p(cov))
         out = _icp_info(ok, t, info, corr, cov)
         out[1]["icp_structural_complexity"] = info[3]
+        return out
+
+    def register_icp_raw(self, from_scan, to_scan, guess=None, from_is_2d=False, to_is_2d=False, from_max_points=0, to_max_points=0, filters_enabled=3,
+                         downsampling_step=1, range_min=0.0, range_max=0.0, voxel_size=0.05, point_to_plane_k=5, point_to_plane_radius=0.0,
+                         ground_normals_up=0.0, max_iterations=30, force_3dof=False, max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1,
+                         max_translation=0.2, max_rotation=0.78, point_to_plane=True, min_complexity=0.02, low_complexity_strategy=1):
+        """RegistrationIcpHip::computeTransformation over RAW scans: lcd_filter_scans on the sides filters_enabled names, the reference's
+        maxLaserScans bookkeeping, then register_icp_normals' work -> (transform [12] or None, info dict with icp_structural_complexity,
+        from_rows, to_rows and max_laser_scans as the ICP got them)"""
+        fx, tx, gs = _scan_arrays(from_scan, to_scan, guess)
+        flt = np.array([downsampling_step, range_min, range_max, voxel_size, point_to_plane_k, point_to_plane_radius, ground_normals_up, filters_enabled], np.float32)
+        t, info, corr, cov, sizes = np.zeros(12, np.float32), np.zeros(4, np.float32), np.zeros(1, np.int32), np.zeros(36, np.float64), np.zeros(3, np.int32)
+        ok = lib().hicpf_compute(self.h, _p(fx), fx.shape[0], int(bool(from_is_2d)), int(from_max_points), _p(tx), tx.shape[0], int(bool(to_is_2d)),
+                                 int(to_max_points), _p(gs), _p(flt), int(max_iterations), int(bool(force_3dof)), float(max_correspondence_distance),
+                                 float(epsilon), float(correspondence_ratio), float(max_translation), float(max_rotation), int(bool(point_to_plane)),
+                                 float(min_complexity), int(low_complexity_strategy), _p(t), _p(info), _p(corr), _p(cov), _p(sizes))
+        out = _icp_info(ok, t, info, corr, cov)
+        out[1].update(icp_structural_complexity=info[3], from_rows=int(sizes[0]), to_rows=int(sizes[1]), max_laser_scans=int(sizes[2]))
         return out
 
     def update(self):

@@ -25,8 +25,10 @@
 // RegistrationIcp.cpp's engine entries are linked but never called here
 struct lcd_icp_args;
 struct lcd_icp_plane_args;
+struct lcd_scan_filter_args;
 extern "C" int lcd_register_icp(lcd_engine*, const lcd_icp_args*) { return 1; }
 extern "C" int lcd_register_icp_plane(lcd_engine*, const lcd_icp_plane_args*) { return 1; }
+extern "C" int lcd_filter_scans(lcd_engine*, const lcd_scan_filter_args*) { return 1; }
 
 using rtabmap_amd::IcpPlaneResult;
 using rtabmap_amd::register_icp_plane_cpu;
