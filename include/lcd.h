@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_keypoints_3d_stereo / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -642,6 +642,125 @@ int lcd_keypoints_3d(lcd_engine* h, const lcd_keypoints_3d_args* a);
  * 16-byte vectors where their addresses and sizes allow); offsets, images and cameras on the HOST (read during the call); enqueued on the
  * engine stream, not synchronised */
 int lcd_keypoints_3d_dev(lcd_engine* h, const lcd_keypoints_3d_args* a);
+
+/* ---- stereo keypoints to 3-D, stateless: lcd_keypoints_3d for a frame that has a right image instead of a depth image (Features2d.cpp:960-1016
+ * with Stereo/OpticalFlow = true).  Stereo::computeCorrespondences tracks every left corner into the right image
+ * (util2d::calcOpticalFlowPyrLKStereo, util2d.cpp:371-736: pyramidal Lucas-Kanade whose correction is forced onto the x axis),
+ * StereoOpticalFlow::updateStatus gates the disparity (Stereo.cpp:240-268), util3d::generateKeypoints3DStereo projects each corner through
+ * the stereo model (util3d_features.cpp:158-203, util3d::projectDisparityTo3D util3d.cpp:2806-2825), and the filter and the compaction
+ * are lcd_keypoints_3d's.  Stateless exactly as lcd_keypoints_3d; frame f owns the features [offsets[f], offsets[f+1]) of every array and
+ * has its own image pair, images[f] (frames may share a pair: its pyramids are built once).
+ *
+ * The rule.  No product is fused into a sum anywhere; int is 32 bits, >> is arithmetic.
+ *   Pyramid -- the ENGINE'S rule, after OpenCV's buildOpticalFlowPyramid with pyrBorder = BORDER_REFLECT_101 and derivBorder =
+ *   BORDER_CONSTANT; nothing of it is in the reference tree:
+ *      Level 0 is the image.  Level l+1 has size ((w+1)/2, (h+1)/2).  Its pixel is
+ *      (SUM_{i,j} k[i]*k[j]*src(reflect101(2y+i-2), reflect101(2x+j-2)) + 128) >> 8, with k = {1,4,6,4,1}.
+ *      Building stops before the first level whose width is <= win_width or whose height is <= win_height.  It stops after level max_level
+ *      at the latest.  Both images get the same number of levels.
+ *      A pixel read outside a level is reflect101 (p < 0 -> -p, p >= n -> 2n-2-p, repeated until inside).  It is read at most win_width
+ *      columns or win_height rows outside.
+ *      The derivative of the LEFT level at a pixel inside is Scharr's, with reflect101 on its own taps:
+ *         dx(x,y) = t0(x+1,y) - t0(x-1,y), where t0(x,y) = (I(x,y-1) + I(x,y+1))*3 + I(x,y)*10.
+ *         dy(x,y) = (t1(x-1,y) + t1(x+1,y))*3 + t1(x,y)*10, where t1(x,y) = I(x,y+1) - I(x,y-1).
+ *      The derivative read outside the level is 0.  All of this is int.
+ *   Tracker -- the reference's, util2d.cpp:504-735, term for term, for every keypoint on its own, level = top .. 0:
+ *      prevPt = pt * float(1/2^level); nextPt = prevPt at the top level, otherwise the previous nextPts * 2.f; nextPts = nextPt (:531-542).
+ *      halfWin = ((w-1)*0.5f, (h-1)*0.5f); prevPt -= halfWin; iprevPt = cvFloor(prevPt).  iprevPt.x < -w || >= cols || iprevPt.y < -h ||
+ *      >= rows: at level 0 the status becomes 0; the level is skipped (nextPts keeps its scaled position) (:545-560).
+ *      a = prevPt.x - iprevPt.x, b likewise; iw00 = cvRound((1.f-a)*(1.f-b)*16384), iw01 = cvRound(a*(1.f-b)*16384), iw10 =
+ *      cvRound((1.f-a)*b*16384), iw11 = 16384 - iw00 - iw01 - iw10; cvRound rounds half to EVEN (:562-569).
+ *      Window pixel (x, y), y outer, x inner (row-major -- that order is the rule for every float sum below): with the four neighbours
+ *      p00 = (X, Y), p01 = (X+1, Y), p10 = (X, Y+1), p11 = (X+1, Y+1), X = iprevPt.x + x, Y = iprevPt.y + y:
+ *      ival = (I00*iw00 + I01*iw01 + I10*iw10 + I11*iw11 + 256) >> 9, ixval and iyval the same of dx and dy with (.. + 8192) >> 14;
+ *      iA11 += float(ixval*ixval), iA12 += float(ixval*iyval), iA22 += float(iyval*iyval), fp32 accumulators, each product an int (:579-606).
+ *      A11 = iA11 * 2^-20, A12, A22 alike; D = A11*A22 - A12*A12; minEig = (A22 + A11 - sqrt((A11-A22)*(A11-A22) + 4.f*A12*A12)) /
+ *      float(2*w*h), sqrt and division correctly rounded fp32.  double(minEig) < min_eig_threshold || D < FLT_EPSILON: at level 0 the
+ *      status becomes 0; the level is skipped.  D = 1.f / D (:608-626).
+ *      nextPt -= halfWin; for j < iterations: inextPt = cvFloor(nextPt); outside as above (with the RIGHT level's cols, rows): at level 0
+ *      status 0; break.  The weights of nextPt; diff = ((J00*iw00 + J01*iw01 + J10*iw10 + J11*iw11 + 256) >> 9) - ival;
+ *      ib1 += float(diff*ixval), ib2 += float(diff*iyval); b1 = ib1 * 2^-20, b2 alike; delta.x = ((A12*b2) - (A22*b1)) * D, delta.y = 0;
+ *      nextPt += delta; nextPts = nextPt + halfWin (both coordinates); double(delta.x)*delta.x + 0.0 <= eps^2: break;
+ *      j > 0 && double(fabsf(delta.x + prevDelta.x)) < 0.01: nextPts.x -= delta.x*0.5f, break; prevDelta = delta (:628-691).
+ *      iterations is clamped to [0, 100], eps to [0, 10] and squared in double (:493-501).
+ *      use_min_eigenvals == 0: at level 0, status still set, the window at nextPts - halfWin (outside: status 0) gives
+ *      err = (SUM float(|diff|)) / float(32*w*h) (:693-731).
+ *      cvFloor of a value that is not finite or not inside int gives INT_MIN (what the reference's x86-64 conversion gives): outside.
+ *   updateStatus (Stereo.cpp:240-268): status set and (use_min_eigenvals != 0 or double(err) < error_threshold): d = left.x - right.x;
+ *      d <= min_disparity || d > max_disparity: status 0.  A keypoint whose err is not below the threshold keeps its status and is gated by
+ *      nothing (the reference only counts it).
+ *   generateKeypoints3DStereo and projectDisparityTo3D: the point is bad (three quiet NaNs) unless status is set, d != 0 and d > 0.
+ *      c = float(right_cx - cx) when both are > 0, otherwise 0.  W = float(baseline / double(d + c)).
+ *      X = float((double(pt.x) - cx) * double(W)).  Y = float((double(pt.y) - cy) * fx / fy * double(W)), evaluated left to right.
+ *      Z = float(fx * double(W)).  Then the range test and transformPoint exactly as lcd_keypoints_3d states them.
+ *   filter: LCD_KP3D_KEEP_ALL or LCD_KP3D_FILTER_3D, the rule lcd_keypoints_3d has.  LCD_KP3D_FILTER_PIXEL has no meaning without a
+ *      depth image: LCD_ERR_INVALID.
+ *   out_right [N x 2] and out_status [N] (both optional): the right corner (nextPts) and the status of every INPUT keypoint by input index,
+ *      behind updateStatus.  A caller who wants only Stereo::computeCorrespondences passes out_xyz and these.
+ *   The engine's definitions, where the reference asserts or is undefined: win_width or win_height < 3 or > 31, max_level outside 0..8,
+ *      width <= win_width or height <= win_height, baseline <= 0 or fx <= 0, a NaN among the parameters, the depth bounds or the camera's
+ *      doubles, min_disparity < 0 or min_disparity > max_disparity: LCD_ERR_INVALID.  A keypoint whose coordinates are not finite or not
+ *      inside (-2^31, 2^31): lcd_keypoints_3d_stereo returns LCD_ERR_INVALID; lcd_keypoints_3d_stereo_dev gives it status 0, the right
+ *      corner (NaN, NaN) and the bad point.
+ * Outputs, limits and errors follow lcd_keypoints_3d (a sharded handle, a _dev call with rows on a padded handle, n_frames > 65535:
+ * LCD_ERR_UNSUPPORTED; NULL pointers, a pitch below the row, a wrong struct_size: LCD_ERR_INVALID; n_frames == 0: LCD_OK).  The depth bounds
+ * are checked as lcd_keypoints_3d checks them.  There is no limit on the features of a frame.
+ * Launches: one per pyramid level for the whole batch, one for the tracker (one wave per keypoint), one for the projection, the filter and
+ * the compaction (one workgroup per frame); nothing is read back between them, no private segment. */
+typedef struct lcd_stereo_camera {  /* HOST; the reference's accessors are double */
+    double fx, fy, cx, cy;          /* the left model */
+    double right_cx;                /* the right model's cx (0: no correction) */
+    double baseline;                /* StereoCameraModel::baseline(), > 0 */
+    int32_t has_local_transform;    /* the caller's !localTransform().isNull() && !localTransform().isIdentity() */
+    int32_t reserved;
+    float local_transform[12];      /* row-major 3 x 4 */
+} lcd_stereo_camera;
+typedef struct lcd_stereo_image {   /* HOST array, one per frame */
+    const void* left;               /* 8-bit single-channel; DEVICE memory for the _dev entry, HOST memory for the host entry */
+    const void* right;
+    int64_t left_pitch_bytes, right_pitch_bytes;   /* bytes between rows, >= width */
+    int32_t width, height;          /* of both images; > win_width, > win_height */
+    const lcd_stereo_camera* camera;   /* HOST */
+} lcd_stereo_image;
+typedef struct lcd_stereo_params {  /* HOST */
+    int32_t win_width, win_height;  /* Stereo/WinWidth 15, Stereo/WinHeight 3; 3..31 */
+    int32_t max_level;              /* Stereo/MaxLevel 5; 0..8 */
+    int32_t iterations;             /* Stereo/Iterations 30 */
+    double eps;                     /* Stereo/Eps 0.01 */
+    int32_t use_min_eigenvals;      /* 1: OPTFLOW_LK_GET_MIN_EIGENVALS; 0: the L1 error against error_threshold */
+    int32_t reserved;
+    double min_eig_threshold;       /* 1e-4 */
+    double error_threshold;         /* 50 */
+    float min_disparity, max_disparity;   /* Stereo/MinDisparity 0.5, Stereo/MaxDisparity 128 */
+} lcd_stereo_params;
+typedef struct lcd_keypoints_3d_stereo_args {
+    int32_t struct_size;            /* sizeof(lcd_keypoints_3d_stereo_args) */
+    int32_t n_frames;               /* >= 0; 0 returns LCD_OK */
+    int32_t filter;                 /* LCD_KP3D_KEEP_ALL or LCD_KP3D_FILTER_3D */
+    int32_t aux_bytes;              /* a multiple of 4, 0..64 */
+    float min_depth, max_depth;
+    const int64_t* offsets;         /* HOST, [n_frames + 1], non-decreasing, [0] == 0 */
+    const lcd_stereo_image* images; /* HOST, [n_frames] */
+    const lcd_stereo_params* params;   /* HOST */
+    const float* points;            /* [N x 2] the left corners (x, y) */
+    const float* response;          /* may be NULL: [N] */
+    const void* rows;               /* may be NULL: [N x dim] of the handle's dtype */
+    const void* aux;                /* may be NULL (aux_bytes == 0): [N x aux_bytes] */
+    int32_t* out_count;             /* [n_frames] */
+    int32_t* out_index;             /* [N]: the kept features in ascending index, the rest of the region -1 */
+    float* out_xyz;                 /* [N x 3] */
+    float* out_points;              /* [N x 2], needed with a filter */
+    float* out_response;            /* [N], needed with a filter and response */
+    void* out_rows;                 /* [N x dim], needed with a filter and rows */
+    void* out_aux;                  /* [N x aux_bytes], needed with a filter and aux */
+    float* out_right;               /* may be NULL: [N x 2] by INPUT index */
+    uint8_t* out_status;            /* may be NULL: [N] by INPUT index */
+} lcd_keypoints_3d_stereo_args;
+/* every pointer on the HOST (the images too; every distinct image is staged once); synchronises the engine stream */
+int lcd_keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a);
+/* the images, points, response, rows, aux and out_* in DEVICE memory (points and out_right 8-byte aligned); offsets, images, cameras and
+ * params on the HOST (read during the call); enqueued on the engine stream, not synchronised */
+int lcd_keypoints_3d_stereo_dev(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a);
 
 /* ---- 3-D to 3-D motion estimation, stateless: the verification behind a loop-closure hypothesis for a caller who holds both frames' word
  * ids and 3-D points in device memory (RegistrationVis.cpp:1823-1871 with Vis/EstimationType = 0).  util3d::estimateMotion3DTo3D

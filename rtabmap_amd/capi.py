@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -134,6 +134,43 @@ class LcdKeypoints3dArgs(C.Structure):
                 ("max_depth", C.c_float), ("offsets", C.c_void_p), ("images", C.POINTER(LcdDepthImage)), ("points", C.c_void_p),
                 ("response", C.c_void_p), ("rows", C.c_void_p), ("aux", C.c_void_p), ("out_count", C.c_void_p), ("out_index", C.c_void_p),
                 ("out_xyz", C.c_void_p), ("out_points", C.c_void_p), ("out_response", C.c_void_p), ("out_rows", C.c_void_p), ("out_aux", C.c_void_p)]
+
+
+class LcdStereoCamera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("right_cx", C.c_double), ("baseline", C.c_double),
+                ("has_local_transform", C.c_int32), ("reserved", C.c_int32), ("local_transform", C.c_float * 12)]
+
+
+class LcdStereoImage(C.Structure):
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("left_pitch_bytes", C.c_int64), ("right_pitch_bytes", C.c_int64), ("width", C.c_int32),
+                ("height", C.c_int32), ("camera", C.POINTER(LcdStereoCamera))]
+
+
+class LcdStereoParams(C.Structure):
+    _fields_ = [("win_width", C.c_int32), ("win_height", C.c_int32), ("max_level", C.c_int32), ("iterations", C.c_int32), ("eps", C.c_double),
+                ("use_min_eigenvals", C.c_int32), ("reserved", C.c_int32), ("min_eig_threshold", C.c_double), ("error_threshold", C.c_double),
+                ("min_disparity", C.c_float), ("max_disparity", C.c_float)]
+
+
+class LcdKeypoints3dStereoArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_frames", C.c_int32), ("filter", C.c_int32), ("aux_bytes", C.c_int32), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("offsets", C.c_void_p), ("images", C.POINTER(LcdStereoImage)), ("params", C.POINTER(LcdStereoParams)),
+                ("points", C.c_void_p), ("response", C.c_void_p), ("rows", C.c_void_p), ("aux", C.c_void_p), ("out_count", C.c_void_p),
+                ("out_index", C.c_void_p), ("out_xyz", C.c_void_p), ("out_points", C.c_void_p), ("out_response", C.c_void_p), ("out_rows", C.c_void_p),
+                ("out_aux", C.c_void_p), ("out_right", C.c_void_p), ("out_status", C.c_void_p)]
+
+
+# lcd_stereo_params: the reference's defaults (Stereo/WinWidth .. Stereo/MaxDisparity)
+STEREO_DEFAULTS = dict(win_width=15, win_height=3, max_level=5, iterations=30, eps=0.01, use_min_eigenvals=1, min_eig_threshold=1e-4,
+                       error_threshold=50.0, min_disparity=0.5, max_disparity=128.0)
+
+
+def stereo_params(params=None):
+    """a dict over STEREO_DEFAULTS -> LcdStereoParams"""
+    v = dict(STEREO_DEFAULTS, **(params or {}))
+    return LcdStereoParams(int(v["win_width"]), int(v["win_height"]), int(v["max_level"]), int(v["iterations"]), float(v["eps"]),
+                           int(v["use_min_eigenvals"]), 0, float(v["min_eig_threshold"]), float(v["error_threshold"]), float(v["min_disparity"]),
+                           float(v["max_disparity"]))
 
 
 class LcdMotion3dArgs(C.Structure):
@@ -275,6 +312,8 @@ def load():
     L.lcd_expand_word_ids_dev.argtypes = [vp, C.POINTER(LcdExpandArgs)]
     L.lcd_keypoints_3d.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
     L.lcd_keypoints_3d_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
+    L.lcd_keypoints_3d_stereo.argtypes = [vp, C.POINTER(LcdKeypoints3dStereoArgs)]
+    L.lcd_keypoints_3d_stereo_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dStereoArgs)]
     L.lcd_estimate_motion_3d.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_pnp.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
@@ -732,6 +771,80 @@ class Engine:
         a.out_count, a.out_index, a.out_xyz, a.out_points = ptr(d_count), ptr(d_index), ptr(d_xyz), ptr(d_out_points)
         a.out_response, a.out_rows, a.out_aux = ptr(d_out_response), ptr(d_out_rows), ptr(d_out_aux)
         self._ck(self.L.lcd_keypoints_3d_dev(self.h, C.byref(a)))
+
+    # ---- stereo keypoints to 3-D (stateless; include/lcd.h has the rule)
+    @staticmethod
+    def _stereo_images(images, data_ptr):
+        """images: one dict per frame -- left, right (2-D uint8 arrays / tensors, possibly views with a row stride), camera (a dict fx, fy, cx,
+        cy, right_cx, baseline and optionally transform (12 floats or None)), optionally width, height, left_pitch_bytes, right_pitch_bytes
+        -> (lcd_stereo_image array, what must stay alive)"""
+        arr = (LcdStereoImage * max(len(images), 1))()
+        keep = []
+        pitch_of = lambda d: 0 if d is None else int(d.strides[0] if hasattr(d, "strides") else d.stride(0) * d.element_size())
+        for f, im in enumerate(images):
+            m = im["camera"]
+            cam = None
+            if m is not None:
+                t = m.get("transform")
+                cam = LcdStereoCamera(m["fx"], m["fy"], m["cx"], m["cy"], m.get("right_cx", 0.0), m["baseline"], 0 if t is None else 1, 0,
+                                      (C.c_float * 12)(*([0.0] * 12 if t is None else [float(v) for v in t])))
+                keep.append(cam)
+            l, r = im["left"], im["right"]
+            arr[f] = LcdStereoImage(None if l is None else data_ptr(l), None if r is None else data_ptr(r),
+                                    int(im["left_pitch_bytes"]) if "left_pitch_bytes" in im else pitch_of(l),
+                                    int(im["right_pitch_bytes"]) if "right_pitch_bytes" in im else pitch_of(r),
+                                    int(im.get("width", l.shape[1] if l is not None else 0)), int(im.get("height", l.shape[0] if l is not None else 0)),
+                                    None if cam is None else C.pointer(cam))
+        return arr, keep
+
+    def keypoints_3d_stereo(self, points, offsets, images, params=None, filter="keep_all", min_depth=0.0, max_depth=0.0, response=None, rows=None,
+                            aux=None, right=True, status=True):
+        """lcd_keypoints_3d_stereo over host arrays -> dict(count [n_frames], index [N], xyz [N x 3], points, response, rows, aux or None,
+        right [N x 2] and status [N] by input index or None); only the first count[f] entries of a frame's region of the compacted
+        arrays are meaningful (outputs start as zeros)."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        n, n_frames = p.shape[0], off.shape[0] - 1
+        r = None if response is None else np.ascontiguousarray(response, dtype=np.float32).reshape(-1)
+        d = None if rows is None else self._rows(rows)
+        x = None if aux is None else np.ascontiguousarray(aux, dtype=np.uint8).reshape(n, -1)
+        flt = KP3D_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        arr, keep = self._stereo_images(images, lambda a: a.ctypes.data)
+        sp = params if isinstance(params, LcdStereoParams) else stereo_params(params)
+        a = LcdKeypoints3dStereoArgs(C.sizeof(LcdKeypoints3dStereoArgs), n_frames, flt, 0 if x is None else x.shape[1], float(min_depth), float(max_depth))
+        a.offsets, a.images, a.params = off.ctypes.data, arr, C.pointer(sp)
+        out = dict(count=np.zeros(max(n_frames, 1), np.int32), index=np.zeros(max(n, 1), np.int32), xyz=np.zeros((max(n, 1), 3), np.float32),
+                   points=np.zeros((max(n, 1), 2), np.float32), response=None if r is None else np.zeros(max(n, 1), np.float32),
+                   rows=None if d is None else np.zeros((max(n, 1), self.dim), self.np_dtype),
+                   aux=None if x is None else np.zeros((max(n, 1), x.shape[1]), np.uint8),
+                   right=np.zeros((max(n, 1), 2), np.float32) if right else None, status=np.zeros(max(n, 1), np.uint8) if status else None)
+        a.points, a.response, a.rows, a.aux = _p(p), _p(r), _p(d), _p(x)
+        a.out_count, a.out_index, a.out_xyz, a.out_points = _p(out["count"]), _p(out["index"]), _p(out["xyz"]), _p(out["points"])
+        a.out_response, a.out_rows, a.out_aux = _p(out["response"]), _p(out["rows"]), _p(out["aux"])
+        a.out_right, a.out_status = _p(out["right"]), _p(out["status"])
+        self._ck(self.L.lcd_keypoints_3d_stereo(self.h, C.byref(a)))
+        out["count"] = out["count"][:n_frames]
+        for k in ("index", "xyz", "points", "response", "rows", "aux", "right", "status"):
+            out[k] = None if out[k] is None else out[k][:n]
+        return out
+
+    def keypoints_3d_stereo_dev(self, d_points, offsets, images, d_count, d_index, d_xyz, params=None, filter="keep_all", min_depth=0.0, max_depth=0.0,
+                                d_response=None, d_rows=None, d_aux=None, aux_bytes=0, d_out_points=None, d_out_response=None, d_out_rows=None,
+                                d_out_aux=None, d_out_right=None, d_out_status=None):
+        """lcd_keypoints_3d_stereo_dev on torch tensors of the engine's device (the images too; offsets, images, cameras and params stay on
+        the host).  Enqueued on the engine stream, not synchronised."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        flt = KP3D_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        arr, keep = self._stereo_images(images, lambda t: t.data_ptr())
+        sp = params if isinstance(params, LcdStereoParams) else stereo_params(params)
+        a = LcdKeypoints3dStereoArgs(C.sizeof(LcdKeypoints3dStereoArgs), off.shape[0] - 1, flt, int(aux_bytes), float(min_depth), float(max_depth))
+        a.offsets, a.images, a.params = off.ctypes.data, arr, C.pointer(sp)
+        a.points, a.response, a.rows, a.aux = ptr(d_points), ptr(d_response), ptr(d_rows), ptr(d_aux)
+        a.out_count, a.out_index, a.out_xyz, a.out_points = ptr(d_count), ptr(d_index), ptr(d_xyz), ptr(d_out_points)
+        a.out_response, a.out_rows, a.out_aux = ptr(d_out_response), ptr(d_out_rows), ptr(d_out_aux)
+        a.out_right, a.out_status = ptr(d_out_right), ptr(d_out_status)
+        self._ck(self.L.lcd_keypoints_3d_stereo_dev(self.h, C.byref(a)))
 
     # ---- 3-D to 3-D motion estimation (stateless; include/lcd.h has the rule)
     def estimate_motion_3d(self, from_ids, from_xyz, from_offsets, to_ids, to_xyz, to_offsets, min_inliers=20, inlier_distance=0.1, iterations=300,

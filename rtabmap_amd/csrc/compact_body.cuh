@@ -1,4 +1,4 @@
-// compact_body.cuh -- what the per-frame kernels of feature_select.hip and keypoints_3d.hip and the motion kernels (motion_3d.hip and
+// compact_body.cuh -- what the per-frame kernels of feature_select.hip, keypoints_3d.hip and keypoints_3d_stereo.hip and the motion kernels (motion_3d.hip and
 // motion_pnp.hip, through motion_join.cuh's sort and motion_group.cuh's compaction and selection) share: the ballot scan that compacts a
 // workgroup's flags in thread order, the gather of rows behind an index list, and the bitonic sort of 64-bit keys in LDS.  Device code only.
 // Internal.
@@ -44,6 +44,20 @@ __device__ __forceinline__ void gather_rows(const void* src, void* dst, const in
 template <typename V>
 __device__ __forceinline__ void gather_rows(const void* src, void* dst, const int32_t* idx, int64_t first, int count, int bytes) {
     gather_rows<V>((const char*)src + first * bytes, (char*)dst + first * bytes, idx, count, bytes);
+}
+
+// What the depth stage and the stereo stage do behind their index list (which the workgroup has just written: the caller's barrier lies in
+// front): the frame's kept rows of `bytes` bytes each, [first, first + count) of dst from the rows idx names of src, in chunks whose element
+// counter fits an int; vec: 16 or 4, the widest copy the addresses and sizes allow
+__device__ __forceinline__ void gather_kept_rows(const void* src_all, void* dst_all, const int32_t* idx, int64_t first, int count, int bytes, int vec) {
+    constexpr int CHUNK = 16384;
+    const char* src = (const char*)src_all + first * bytes;
+    for (int c0 = 0; c0 < count; c0 += CHUNK) {
+        const int c = min(count - c0, CHUNK);
+        char* dst = (char*)dst_all + (first + c0) * bytes;
+        if (vec == 16) gather_rows<uint4>(src, dst, idx + c0, c, bytes);
+        else gather_rows<uint32_t>(src, dst, idx + c0, c, bytes);
+    }
 }
 
 // Where key i lies in LDS: one spare slot behind every eight keys.  The network's threads walk the keys with strides of 8, 64, 512, .. keys

@@ -24,7 +24,6 @@ namespace lcd {
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int GATHER_CHUNK = 16384;          // rows per gather_rows call: its element counter is an int
 
 struct Kp3dJob {
     kp3d::Image image;
@@ -86,21 +85,8 @@ __global__ __launch_bounds__(BLOCK) void keypoints_3d_kernel(Kp3dArgs a) {
     if (tid == 0) a.out_count[blockIdx.x] = count;
     if (!a.rows && !a.aux) return;
     __syncthreads();                                                   // the index list is read back by the threads that gather
-    for (int c0 = 0; c0 < count; c0 += GATHER_CHUNK) {
-        const int c = min(count - c0, GATHER_CHUNK);
-        if (a.rows) {
-            const char* src = (const char*)a.rows + first * a.row_bytes;
-            char* dst = (char*)a.out_rows + (first + c0) * a.row_bytes;
-            if (a.row_vec == 16) gather_rows<uint4>(src, dst, out_index + c0, c, a.row_bytes);
-            else gather_rows<uint32_t>(src, dst, out_index + c0, c, a.row_bytes);
-        }
-        if (a.aux) {
-            const char* src = (const char*)a.aux + first * a.aux_bytes;
-            char* dst = (char*)a.out_aux + (first + c0) * a.aux_bytes;
-            if (a.aux_vec == 16) gather_rows<uint4>(src, dst, out_index + c0, c, a.aux_bytes);
-            else gather_rows<uint32_t>(src, dst, out_index + c0, c, a.aux_bytes);
-        }
-    }
+    if (a.rows) gather_kept_rows(a.rows, a.out_rows, out_index, first, count, a.row_bytes, a.row_vec);
+    if (a.aux) gather_kept_rows(a.aux, a.out_aux, out_index, first, count, a.aux_bytes, a.aux_vec);
 }
 
 }  // namespace

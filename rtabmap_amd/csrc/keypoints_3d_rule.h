@@ -106,6 +106,21 @@ KP3D_FN float get_depth(const Image& im, int col0, float x, float y) {
     return total / sum_weights;
 }
 
+// The range test in front of the local transform (util3d_features.cpp:104-115; generateKeypoints3DStereo's is the same, :186-196) and
+// util3d::transformPoint: out keeps what it holds (the bad point) unless the projected point stands.  lcd_keypoints_3d_stereo shares it.
+KP3D_FN void stand_and_transform(float X, float Y, float Z, float min_depth, float max_depth, bool has_t, const float t[12], float out[3]) {
+    if (!(finite(X) && finite(Y) && finite(Z))) return;
+    if (!((min_depth < 0.0f || Z > min_depth) && (max_depth <= 0.0f || Z <= max_depth))) return;
+    if (!has_t) { out[0] = X; out[1] = Y; out[2] = Z; return; }
+    // util3d::transformPoint (util3d_transforms.cpp:211-220), left to right
+    for (int r = 0; r < 3; ++r) {
+        const float a = t[4 * r] * X, b = t[4 * r + 1] * Y, c = t[4 * r + 2] * Z;
+        const float ab = a + b;
+        const float abc = ab + c;
+        out[r] = abc + t[4 * r + 3];
+    }
+}
+
 // generateKeypoints3DDepth's loop body (util3d_features.cpp:87-116) for the keypoint (px, py): the 3-D point, three quiet NaNs where there is
 // none.  Returns false, reads no pixel and gives the bad point where the reference asserts or is undefined: a coordinate that is not finite
 // or beyond the range of int, or a camera index outside [0, n_cameras).
@@ -128,16 +143,7 @@ KP3D_FN bool point_of(const Image& im, const Camera* cams, float px, float py, f
     const float dx = xs - cx, dy = y - cy;
     const float nx = dx * depth, ny = dy * depth;
     const float X = nx / C.fx, Y = ny / C.fy, Z = depth;
-    if (!(finite(X) && finite(Y) && finite(Z))) return true;
-    if (!((min_depth < 0.0f || Z > min_depth) && (max_depth <= 0.0f || Z <= max_depth))) return true;
-    if (!C.has_t) { out[0] = X; out[1] = Y; out[2] = Z; return true; }
-    // util3d::transformPoint (util3d_transforms.cpp:211-220), left to right
-    for (int r = 0; r < 3; ++r) {
-        const float a = C.t[4 * r] * X, b = C.t[4 * r + 1] * Y, c = C.t[4 * r + 2] * Z;
-        const float ab = a + b;
-        const float abc = ab + c;
-        out[r] = abc + C.t[4 * r + 3];
-    }
+    stand_and_transform(X, Y, Z, min_depth, max_depth, C.has_t != 0, C.t, out);
     return true;
 }
 

@@ -37,6 +37,13 @@ MemoryHip::MemoryHip(const ParametersMap& parameters, int device)
     if ((it = parameters.find("Kp/MinDepth")) != parameters.end()) _minDepth = (float)atof(it->second.c_str());
     if ((it = parameters.find("Kp/MaxDepth")) != parameters.end()) _maxDepth = (float)atof(it->second.c_str());
     if ((it = parameters.find("Kp/GridCols")) != parameters.end()) _gridCols = atoi(it->second.c_str());
+    if ((it = parameters.find("Stereo/WinWidth")) != parameters.end()) _stereo.winWidth = atoi(it->second.c_str());
+    if ((it = parameters.find("Stereo/WinHeight")) != parameters.end()) _stereo.winHeight = atoi(it->second.c_str());
+    if ((it = parameters.find("Stereo/MaxLevel")) != parameters.end()) _stereo.maxLevel = atoi(it->second.c_str());
+    if ((it = parameters.find("Stereo/Iterations")) != parameters.end()) _stereo.iterations = atoi(it->second.c_str());
+    if ((it = parameters.find("Stereo/Eps")) != parameters.end()) _stereo.eps = atof(it->second.c_str());
+    if ((it = parameters.find("Stereo/MinDisparity")) != parameters.end()) _stereo.minDisparity = (float)atof(it->second.c_str());
+    if ((it = parameters.find("Stereo/MaxDisparity")) != parameters.end()) _stereo.maxDisparity = (float)atof(it->second.c_str());
     if ((it = parameters.find("Kp/SSC")) != parameters.end()) _ssc = it->second == "true" || it->second == "1" || it->second == "True" || it->second == "TRUE";
     _workingMem.insert(kIdVirtual);             // Memory.cpp:592
     static const char* names[] = {"TimingMem/Pre_update/ms", "TimingMem/Joining_dictionary_update/ms", "TimingMem/Add_new_words/ms",
@@ -180,6 +187,73 @@ int MemoryHip::update(const Mat& descriptors, const std::vector<float>& response
     } else {
         if (!Keypoints3D::generateKeypoints3DDepth(points.data(), rows, depth, cameras.data(), (int)cameras.size(), _minDepth, _maxDepth, xyz.data())) {
             _selectError = "generateKeypoints3DDepth: an image the cameras do not divide, or a keypoint that is not finite or in no camera's sub-image";
+            return 0;
+        }
+        if (!Keypoints3D::filterKeypointsByDepth(xyz.data(), rows, _minDepth, _maxDepth, kept)) { _selectError = "filterKeypointsByDepth: Kp/MinDepth < 0 or 0 < Kp/MaxDepth <= Kp/MinDepth"; return 0; }
+        std::vector<float> all;
+        all.swap(xyz);
+        for (size_t j = 0; j < kept.size(); ++j) {
+            const size_t i = (size_t)kept[j];
+            xyz.insert(xyz.end(), all.begin() + 3 * i, all.begin() + 3 * i + 3);
+            keptResponses.push_back(responses[i]);
+            keptPoints.push_back(points[2 * i]); keptPoints.push_back(points[2 * i + 1]);
+            keptRows.insert(keptRows.end(), descriptors.ptr((int)i), descriptors.ptr((int)i) + descriptors.rowBytes());
+        }
+    }
+    std::vector<int> ids;
+    const int id = this->update(Mat((int)kept.size(), descriptors.cols, descriptors.type(), keptRows.data()), keptResponses, keptPoints, imageWidth, imageHeight, ids);
+    if (!id) return 0;
+    outIds.swap(ids); keypoints3D.swap(xyz); keptIndex.swap(kept);
+    return id;
+}
+
+int MemoryHip::update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
+                      const GrayImage& left, const GrayImage& right, const StereoCamera& camera, std::vector<int>& outIds, std::vector<float>& keypoints3D,
+                      std::vector<int>& keptIndex) {
+    const int rows = descriptors.rows;
+    _selectError.clear();
+    if ((int)responses.size() != rows || (int)points.size() != 2 * rows) { _selectError = "one response and one point per descriptor"; return 0; }
+    if (left.width != right.width || left.height != right.height) { _selectError = "the left and the right image differ in size"; return 0; }
+    // ---- the stereo stage (Features2d.cpp:960-1016)
+    std::vector<float> xyz((size_t)rows * 3), keptResponses, keptPoints;
+    std::vector<unsigned char> keptRows;
+    std::vector<int> kept;
+    lcd_engine* eng = _vwd->engine();
+    if (eng && rows > 0) {
+        lcd_stereo_camera cam;
+        cam.fx = camera.fx; cam.fy = camera.fy; cam.cx = camera.cx; cam.cy = camera.cy; cam.right_cx = camera.rightCx; cam.baseline = camera.baseline;
+        cam.has_local_transform = camera.hasLocalTransform ? 1 : 0; cam.reserved = 0;
+        std::copy(camera.localTransform, camera.localTransform + 12, cam.local_transform);
+        lcd_stereo_image image;
+        image.left = left.data; image.right = right.data; image.left_pitch_bytes = left.pitchBytes; image.right_pitch_bytes = right.pitchBytes;
+        image.width = left.width; image.height = left.height; image.camera = &cam;
+        lcd_stereo_params sp;
+        sp.win_width = _stereo.winWidth; sp.win_height = _stereo.winHeight; sp.max_level = _stereo.maxLevel; sp.iterations = _stereo.iterations;
+        sp.eps = _stereo.eps; sp.use_min_eigenvals = _stereo.useMinEigenVals ? 1 : 0; sp.reserved = 0; sp.min_eig_threshold = _stereo.minEigThreshold;
+        sp.error_threshold = _stereo.errorThreshold; sp.min_disparity = _stereo.minDisparity; sp.max_disparity = _stereo.maxDisparity;
+        const int64_t offsets[2] = {0, rows};
+        int32_t count = 0;
+        std::vector<int32_t> index((size_t)rows);
+        keptResponses.resize((size_t)rows); keptPoints.resize((size_t)rows * 2); keptRows.resize(descriptors.data.size());
+        lcd_keypoints_3d_stereo_args k;
+        k.struct_size = (int32_t)sizeof(k); k.n_frames = 1; k.filter = LCD_KP3D_FILTER_3D; k.aux_bytes = 0; k.min_depth = _minDepth; k.max_depth = _maxDepth;
+        k.offsets = offsets; k.images = &image; k.params = &sp; k.points = points.data(); k.response = responses.data(); k.rows = descriptors.data.data(); k.aux = 0;
+        k.out_count = &count; k.out_index = index.data(); k.out_xyz = xyz.data(); k.out_points = keptPoints.data(); k.out_response = keptResponses.data();
+        k.out_rows = keptRows.data(); k.out_aux = 0; k.out_right = 0; k.out_status = 0;
+        if (lcd_keypoints_3d_stereo(eng, &k) != LCD_OK) { _selectError = lcd_last_error(eng); return 0; }
+        kept.assign(index.begin(), index.begin() + count);
+        xyz.resize((size_t)count * 3); keptResponses.resize((size_t)count); keptPoints.resize((size_t)count * 2);
+        keptRows.resize((size_t)count * descriptors.rowBytes());
+    } else {
+        const StereoOpticalFlowHip flow(_stereo);
+        std::vector<float> rightCorners((size_t)rows * 2);
+        std::vector<unsigned char> status((size_t)rows);
+        if (!flow.computeCorrespondences(left, right, points.data(), rows, rightCorners.data(), status.data())) {
+            _selectError = "computeCorrespondences: Stereo/* parameters or images the rule refuses, or a keypoint that is not finite";
+            return 0;
+        }
+        if (!StereoOpticalFlowHip::generateKeypoints3DStereo(points.data(), rightCorners.data(), rows, camera, status.data(), _minDepth, _maxDepth, xyz.data())) {
+            _selectError = "generateKeypoints3DStereo: baseline or fx not above 0";
             return 0;
         }
         if (!Keypoints3D::filterKeypointsByDepth(xyz.data(), rows, _minDepth, _maxDepth, kept)) { _selectError = "filterKeypointsByDepth: Kp/MinDepth < 0 or 0 < Kp/MaxDepth <= Kp/MinDepth"; return 0; }

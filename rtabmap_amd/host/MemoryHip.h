@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "Keypoints3D.h"
+#include "Stereo.h"
 #include "VWDictionaryHip.h"
 
 namespace rtabmap_amd {
@@ -49,6 +50,15 @@ public:
     int update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
                const DepthImage& depth, const std::vector<DepthCamera>& cameras, std::vector<int>& wordIds, std::vector<float>& keypoints3D,
                std::vector<int>& keptIndex);
+    // The same for a stereo frame, with the stereo stage in front (Features2d.cpp:960-1016): Stereo::computeCorrespondences, updateStatus and
+    // util3d::generateKeypoints3DStereo with the Stereo/* parameters (WinWidth, WinHeight, MaxLevel, Iterations, Eps, MinDisparity,
+    // MaxDisparity; the reference's defaults) and the 3-D filter with Kp/MinDepth and Kp/MaxDepth -- ONE lcd_keypoints_3d_stereo call (without
+    // an engine: StereoOpticalFlowHip's host code) --, then the selection, the frame and the expansion over the keypoints that are left.
+    int update(const Mat& descriptors, const std::vector<float>& responses, const std::vector<float>& points, int imageWidth, int imageHeight,
+               const GrayImage& left, const GrayImage& right, const StereoCamera& camera, std::vector<int>& wordIds, std::vector<float>& keypoints3D,
+               std::vector<int>& keptIndex);
+    const StereoParams& stereoParams() const { return _stereo; }
+    void setStereoParams(const StereoParams& params) { _stereo = params; }
     float getMinDepth() const { return _minDepth; }
     float getMaxDepth() const { return _maxDepth; }
     int getMaxFeatures() const { return _maxFeatures; }
@@ -147,6 +157,7 @@ private:
     int _maxFeatures, _gridRows, _gridCols;         // Kp/MaxFeatures (500), Kp/GridRows (1), Kp/GridCols (1)
     bool _ssc;                                      // Kp/SSC (false)
     float _minDepth, _maxDepth;                     // Kp/MinDepth (0), Kp/MaxDepth (0)
+    StereoParams _stereo;                           // Stereo/*
     std::string _selectError;
     // quantises `forQuantization` as signature `id` the call-by-call way; rawIndex (may be NULL): its rows' places among the `rows` features
     bool quantizeSelected(const Mat& forQuantization, const std::vector<int>* rawIndex, int rows, int id, std::list<int>& wordIds);

@@ -14,6 +14,7 @@
 #include "Motion3D.h"
 #include "RegistrationIcp.h"
 #include "ScanFilter.h"
+#include "Stereo.h"
 #include "RtabmapHip.h"
 
 using namespace rtabmap_amd;
@@ -244,6 +245,68 @@ int hk3_filter_pixel(const float* points, int n, const void* depth, long long pi
     if (!Keypoints3D::filterKeypointsByDepth(points, n, image, minDepth, maxDepth, kept)) return -1;
     std::copy(kept.begin(), kept.end(), outKept);
     return (int)kept.size();
+}
+// ---- the stereo stage.  params as the Python glue passes them: 10 doubles -- winWidth, winHeight, maxLevel, iterations, eps, useMinEigenVals,
+// minEigThreshold, errorThreshold, minDisparity, maxDisparity (the last two are floats widened); camera: 7 doubles -- fx, fy, cx, cy, rightCx,
+// baseline, hasLocalTransform --, then the 3 x 4 transform as 12 floats
+static StereoParams make_stereo_params(const double* p) {
+    StereoParams s;
+    s.winWidth = (int)p[0]; s.winHeight = (int)p[1]; s.maxLevel = (int)p[2]; s.iterations = (int)p[3]; s.eps = p[4]; s.useMinEigenVals = p[5] != 0.0;
+    s.minEigThreshold = p[6]; s.errorThreshold = p[7]; s.minDisparity = (float)p[8]; s.maxDisparity = (float)p[9];
+    return s;
+}
+static StereoCamera make_stereo_camera(const double* c, const float* transform) {
+    StereoCamera s;
+    s.fx = c[0]; s.fy = c[1]; s.cx = c[2]; s.cy = c[3]; s.rightCx = c[4]; s.baseline = c[5]; s.hasLocalTransform = c[6] != 0.0;
+    std::copy(transform, transform + 12, s.localTransform);
+    return s;
+}
+static GrayImage make_gray(const void* data, long long pitchBytes, int width, int height) {
+    GrayImage g;
+    g.data = (const unsigned char*)data; g.pitchBytes = pitchBytes; g.width = width; g.height = height;
+    return g;
+}
+// StereoOpticalFlowHip (no engine involved).  1 = done, 0 = refused
+int hst_correspondences(const double* params, const void* left, long long leftPitch, const void* right, long long rightPitch, int width, int height,
+                        const float* points, int n, float* outRight, unsigned char* outStatus) {
+    const StereoOpticalFlowHip flow(make_stereo_params(params));
+    return flow.computeCorrespondences(make_gray(left, leftPitch, width, height), make_gray(right, rightPitch, width, height), points, n, outRight, outStatus) ? 1 : 0;
+}
+int hst_generate(const float* points, const float* right, int n, const double* camera, const float* transform, const unsigned char* status,
+                 float minDepth, float maxDepth, float* outXyz) {
+    return StereoOpticalFlowHip::generateKeypoints3DStereo(points, right, n, make_stereo_camera(camera, transform), status, minDepth, maxDepth, outXyz) ? 1 : 0;
+}
+// the pyramid of one image: outLevels receives the levels' packed rows back to back (at most 2 * width * height bytes), outSizes w, h per
+// level; returns the number of levels, 0 = refused
+int hst_pyramid(const void* image, long long pitchBytes, int width, int height, int winWidth, int winHeight, int maxLevel, unsigned char* outLevels, int* outSizes) {
+    std::vector<std::vector<unsigned char> > levels;
+    std::vector<int> w, h;
+    if (!StereoOpticalFlowHip::buildPyramid(make_gray(image, pitchBytes, width, height), winWidth, winHeight, maxLevel, levels, w, h)) return 0;
+    for (size_t l = 0; l < levels.size(); ++l) {
+        outLevels = std::copy(levels[l].begin(), levels[l].end(), outLevels);
+        outSizes[2 * l] = w[l]; outSizes[2 * l + 1] = h[l];
+    }
+    return (int)levels.size();
+}
+void hst_derivative(const void* image, long long pitchBytes, int width, int height, short* outDxDy) {
+    StereoOpticalFlowHip::derivative(make_gray(image, pitchBytes, width, height), outDxDy);
+}
+void hmem_set_stereo_params(void* h, const double* params) { ((MemoryHip*)h)->setStereoParams(make_stereo_params(params)); }
+// a stereo frame through MemoryHip::update; the outputs as hmem_update_depth's
+int hmem_update_stereo(void* h, const void* desc, int rows, int cols, int type, const float* responses, const float* points, int imageWidth,
+                       int imageHeight, const void* left, long long leftPitch, const void* right, long long rightPitch, int width, int height,
+                       const double* camera, const float* transform, int* outIds, float* outXyz, int* outKept, int* outKeptCount) {
+    std::vector<int> ids, kept;
+    std::vector<float> xyz;
+    const int id = ((MemoryHip*)h)->update(make_mat(desc, rows, cols, type), std::vector<float>(responses, responses + rows),
+                                           std::vector<float>(points, points + 2 * (size_t)rows), imageWidth, imageHeight, make_gray(left, leftPitch, width, height),
+                                           make_gray(right, rightPitch, width, height), make_stereo_camera(camera, transform), ids, xyz, kept);
+    *outKeptCount = id ? (int)kept.size() : 0;
+    if (!id) return 0;
+    std::copy(ids.begin(), ids.end(), outIds);
+    std::copy(xyz.begin(), xyz.end(), outXyz);
+    std::copy(kept.begin(), kept.end(), outKept);
+    return id;
 }
 // motion3d_cpu (no engine involved).  outTransform[12], outScalars[3] = status, matches, inliers; outMatches / outInliers hold nFrom ids.  1 = done, 0 = refused
 int hm3_cpu(const int* fromIds, const float* fromXyz, int nFrom, const int* toIds, const float* toXyz, int nTo, int minInliers, double inlierDistance,

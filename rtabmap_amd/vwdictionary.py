@@ -67,6 +67,15 @@ def lib():
         L.hmem_create_depth.restype = vp
         L.hmem_create_depth.argtypes = [ci, ci, cf, ci, ci, ci, ci, ci, ci, cf, cf]
         L.hmem_update_depth.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, C.c_longlong, ci, ci, ci, vp, ci, vp, vp, vp, vp]
+        cd = C.c_double
+        L.hst_correspondences.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, ci, ci, vp, ci, vp, vp]
+        L.hst_generate.argtypes = [vp, vp, ci, vp, vp, vp, cf, cf, vp]
+        L.hst_pyramid.argtypes = [vp, C.c_longlong, ci, ci, ci, ci, ci, vp, vp]
+        L.hst_derivative.argtypes = [vp, C.c_longlong, ci, ci, vp]
+        L.hst_derivative.restype = None
+        L.hmem_set_stereo_params.argtypes = [vp, vp]
+        L.hmem_set_stereo_params.restype = None
+        L.hmem_update_stereo.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, C.c_longlong, vp, C.c_longlong, ci, ci, vp, vp, vp, vp, vp, vp]
         L.hk3_generate.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, vp, ci, cf, cf, vp]
         L.hk3_filter_3d.argtypes = [vp, ci, cf, cf, vp]
         L.hk3_filter_pixel.argtypes = [vp, ci, vp, C.c_longlong, ci, ci, ci, cf, cf, vp]
@@ -236,6 +245,77 @@ def filter_keypoints_by_depth_pixel(points, depth, min_depth=0.0, max_depth=0.0,
     out = np.zeros(max(p.shape[0], 1), np.int32)
     n = lib().hk3_filter_pixel(_p(p), p.shape[0], *dargs, float(min_depth), float(max_depth), _p(out))
     return None if n < 0 else out[:n].copy()
+
+
+# ---- StereoOpticalFlowHip (rtabmap_amd/host/Stereo.h): the stereo stage's rule of include/lcd.h as plain host code, no engine
+STEREO_DEFAULTS = dict(win_width=15, win_height=3, max_level=5, iterations=30, eps=0.01, use_min_eigenvals=1, min_eig_threshold=1e-4,
+                       error_threshold=50.0, min_disparity=0.5, max_disparity=128.0)
+
+
+def _stereo_params_flat(params):
+    v = dict(STEREO_DEFAULTS, **(params or {}))
+    return np.array([v[k] for k in ("win_width", "win_height", "max_level", "iterations", "eps", "use_min_eigenvals", "min_eig_threshold",
+                                    "error_threshold", "min_disparity", "max_disparity")], np.float64)
+
+
+def _stereo_camera_flat(camera):
+    t = camera.get("transform")
+    c = np.array([camera["fx"], camera["fy"], camera["cx"], camera["cy"], camera.get("right_cx", 0.0), camera["baseline"], 0 if t is None else 1], np.float64)
+    return c, (np.zeros(12, np.float32) if t is None else np.ascontiguousarray(t, dtype=np.float32).reshape(12))
+
+
+def _gray_args(image, width=None):
+    g = image if image.strides[1] == 1 else np.ascontiguousarray(image)
+    assert g.dtype == np.uint8 and g.ndim == 2
+    return g, (g.ctypes.data_as(C.c_void_p), g.strides[0]), int(g.shape[1] if width is None else width), g.shape[0]
+
+
+def stereo_correspondences(left, right, points, params=None, width=None):
+    """StereoOpticalFlow::computeCorrespondences, updateStatus included -> (right corners [n x 2] float32, status [n] uint8), or None where
+    the host mirror refuses; left / right may be views with a row stride, width the image's where the arrays are wider"""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    l, largs, w, h = _gray_args(left, width)
+    r, rargs, rw, rh = _gray_args(right, width)
+    if (w, h) != (rw, rh):
+        return None
+    sp = _stereo_params_flat(params)
+    out, st = np.zeros((max(p.shape[0], 1), 2), np.float32), np.zeros(max(p.shape[0], 1), np.uint8)
+    ok = lib().hst_correspondences(_p(sp), *largs, *rargs, w, h, _p(p), p.shape[0], _p(out), _p(st))
+    return (out[:p.shape[0]].copy(), st[:p.shape[0]].copy()) if ok else None
+
+
+def generate_keypoints_3d_stereo(points, right, camera, status=None, min_depth=0.0, max_depth=0.0):
+    """util3d::generateKeypoints3DStereo -> [n x 3] float32, or None where the host mirror refuses"""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(right, dtype=np.float32).reshape(-1, 2)
+    s = None if status is None else np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+    c, t = _stereo_camera_flat(camera)
+    out = np.zeros((max(p.shape[0], 1), 3), np.float32)
+    ok = lib().hst_generate(_p(p), _p(q), p.shape[0], _p(c), _p(t), _p(s), float(min_depth), float(max_depth), _p(out))
+    return out[:p.shape[0]].copy() if ok else None
+
+
+def stereo_pyramid(image, win_width=15, win_height=3, max_level=5, width=None):
+    """the engine's pyramid of one image -> a list of uint8 arrays, or None where refused"""
+    g, gargs, w, h = _gray_args(image, width)
+    levels, sizes = np.zeros(2 * w * h + 16, np.uint8), np.zeros(32, np.int32)
+    n = lib().hst_pyramid(*gargs, w, h, int(win_width), int(win_height), int(max_level), _p(levels), _p(sizes))
+    if not n:
+        return None
+    out, at = [], 0
+    for l in range(n):
+        lw, lh = int(sizes[2 * l]), int(sizes[2 * l + 1])
+        out.append(levels[at:at + lw * lh].reshape(lh, lw).copy())
+        at += lw * lh
+    return out
+
+
+def stereo_derivative(image, width=None):
+    """the Scharr derivative of the rule at every pixel -> (dx, dy) int16 arrays"""
+    g, gargs, w, h = _gray_args(image, width)
+    out = np.zeros((h, w, 2), np.int16)
+    lib().hst_derivative(*gargs, w, h, _p(out))
+    return out[:, :, 0].copy(), out[:, :, 1].copy()
 
 
 def _frame_arrays(ids, xyz):
@@ -656,6 +736,31 @@ class MemoryHip:
         k = C.c_int(0)
         sid = lib().hmem_update_depth(self.h, _p(desc), rows, desc.shape[1], _type_of(desc), _p(r), _p(p), int(image_size[0]), int(image_size[1]),
                                       *dargs, _p(cams), cams.shape[0], _p(ids), _p(xyz), _p(kept), C.addressof(k))
+        return sid, ids[:k.value].tolist(), xyz[:k.value].copy(), kept[:k.value].copy()
+
+    def set_stereo_params(self, params=None):
+        """the Stereo/* parameters update_stereo() honours (a dict over STEREO_DEFAULTS)"""
+        sp = _stereo_params_flat(params)
+        lib().hmem_set_stereo_params(self.h, _p(sp))
+
+    def update_stereo(self, desc, responses, points, image_size, left, right, camera, width=None):
+        """MemoryHip::update for a stereo frame: the stereo stage (Stereo/*, Kp/MinDepth, Kp/MaxDepth), then the selection, the frame and the
+        expansion -> (signature id, one id per KEPT feature, their 3-D points [k x 3], their indices); id 0: refused (select_error())"""
+        desc = np.ascontiguousarray(desc)
+        rows = desc.shape[0]
+        r = np.ascontiguousarray(responses, dtype=np.float32).reshape(-1)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        if r.shape[0] != rows or p.shape[0] != rows:
+            raise ValueError("update_stereo: one response and one point per descriptor")
+        l, largs, w, h = _gray_args(left, width)
+        rt, rargs, rw, rh = _gray_args(right, width)
+        if (w, h) != (rw, rh):
+            raise ValueError("update_stereo: the images differ in size")
+        c, t = _stereo_camera_flat(camera)
+        ids, xyz, kept = np.zeros(max(rows, 1), np.int32), np.zeros((max(rows, 1), 3), np.float32), np.zeros(max(rows, 1), np.int32)
+        k = C.c_int(0)
+        sid = lib().hmem_update_stereo(self.h, _p(desc), rows, desc.shape[1], _type_of(desc), _p(r), _p(p), int(image_size[0]), int(image_size[1]),
+                                       *largs, *rargs, w, h, _p(c), _p(t), _p(ids), _p(xyz), _p(kept), C.addressof(k))
         return sid, ids[:k.value].tolist(), xyz[:k.value].copy(), kept[:k.value].copy()
 
     def select_error(self):
