@@ -1,8 +1,10 @@
 """Inputs of the lcd_register_icp_plane tests: 3-D scans with normals, the hand-made cases of every branch of the rule, and the batches of the
-GPU tests.  tests/test_register_icp_plane_inputs.py proves with tests/register_icp_plane_model.py that each case takes its branch."""
+GPU tests, among them the cases at block, batch and region edges.  tests/test_register_icp_plane_inputs.py proves with
+tests/register_icp_plane_model.py that each case takes its branch."""
 import numpy as np
 
-from register_icp_inputs import F, IDENTITY, bits, motion, inverse, moved  # noqa: F401
+from register_icp_inputs import F, IDENTITY, GRID_KW, bits, motion, inverse, moved  # noqa: F401
+from register_icp_inputs import grid_edge_pairs as _p2p_grid_edge_pairs
 
 SIZES = (0, 1, 2, 3, 5, 6, 7, 255, 256, 257, 511, 512, 513)
 KW = dict(max_iterations=30, max_correspondence_distance=0.3, epsilon=0.0, correspondence_ratio=0.1, min_complexity=0.02, low_complexity_strategy=1)
@@ -172,3 +174,201 @@ def size_batch():
         out.append(pair(n, max(other, 7) if n else other, 100 + k, noise=0.004))
         out.append(pair(max(other, 7), n, 200 + k, noise=0.004))
     return out
+
+
+# ---- the branches at block, batch and region edges.  Every generator builds its pairs once: the same objects come back on every call, so that
+# a cache keyed by the pair serves every test of a module.
+
+EDGE_SIZES = (255, 256, 257, 511, 512, 513, 1025)
+GATE_COS = float(np.cos(0.78))
+GATE_KW = dict(KW, normal_gate=True, min_normal_cos=GATE_COS)
+_built = {}
+
+
+def _once(name, make):
+    if name not in _built:
+        _built[name] = make()
+    return _built[name]
+
+
+def swapped(p):
+    """the pair with its sides exchanged; the guess has to be the identity, which it stays"""
+    assert np.array_equal(p["guess"], IDENTITY)
+    return changed(p, from_xyz=p["to_xyz"].copy(), from_normals=p["to_normals"].copy(), to_xyz=p["from_xyz"].copy(), to_normals=p["from_normals"].copy())
+
+
+def low_complexity_sizes():
+    """name -> (pairs, kw).  Corridor pairs -- walls, a little floor and a trace of an end wall -- with a from-side of every EDGE_SIZES against a
+    to-side 20 rows smaller, and each of them with its sides exchanged: 0 < complexity < min_complexity, so under strategies 1 and 2 the
+    point-to-point loop runs inside the plane kernel and completes.  The same pairs with min_complexity = 0.5 (the second value below it too),
+    under strategy 2 and with force_3dof; and one pair of 513 x 493 rows whose normals are all [0, 1, 0]: complexity 0 exactly, no vectors"""
+    def make():
+        pairs = []
+        for n in EDGE_SIZES:
+            p = pair(n, n - 20, 300 + n, noise=0.004, scene=corridor, floor=0.12, end=0.01)
+            pairs += [p, swapped(p)]
+        flat = changed(pairs[10])
+        assert (flat["from_xyz"].shape[0], flat["to_xyz"].shape[0]) == (513, 493)
+        flat["from_normals"][:], flat["to_normals"][:] = [0, 1, 0], [0, 1, 0]
+        return dict(strategy_1=(pairs, dict(KW)), second_below=(pairs, dict(KW, min_complexity=0.5)), strategy_2=(pairs, dict(KW, low_complexity_strategy=2)),
+                    force_3dof=(pairs, dict(KW, force_3dof=True)), exact_zero=([flat], dict(KW)))
+    return _once("low", make)
+
+
+def gate_sizes():
+    """(pairs, kw): room pairs with noisy normals at the sizes of low_complexity_sizes(), both ways round, the gate on; every fifth from-normal
+    is negated, so failing correspondences stand between passing ones in every trip of 256 source rows -- source rows are from-rows where
+    nf <= nt, and to-rows, whose from-row carries the negated normal, where nf > nt"""
+    def make():
+        pairs = []
+        for n in EDGE_SIZES:
+            p = pair(n, n - 20, 400 + n, noise=0.004, normal_noise=0.05)
+            pairs += [flipped(p, np.arange(0, n, 5)), flipped(swapped(p), np.arange(0, n - 20, 5))]
+        return pairs, dict(GATE_KW)
+    return _once("gate", make)
+
+
+def swap_turned_by_normals():
+    """([300 x 280 with every fourth from-normal NaN, its mirror image], kw): 225 rows take part against 280, so the from-side is step 5's
+    source although it has more rows; in the mirror image 280 rows stand against 225 and the to-side is the source although it has more.
+    Reciprocity and the gate's cosine are symmetric in the two sides, so neither out_match nor the count depends on which side is the source;
+    what does is the variance under the gate once a correspondence fails -- the median is taken over the first `count` reciprocal
+    correspondences in the SOURCE's row order.  Hence the gate is on, and the normals of the rows 1, 5, 9, ... of the same side are negated"""
+    def make():
+        p = pair(300, 280, 11, noise=0.004)
+        p["from_normals"][::4] = np.nan
+        p["from_normals"][1::4] *= np.float32(-1)
+        return [p, swapped(p)], dict(GATE_KW)
+    return _once("swap", make)
+
+
+def _mostly_elsewhere(p, kept):
+    """the pair with all but the first `kept` from-rows moved 100 m away: they find nothing, and the ratio falls below 0.1"""
+    q = changed(p)
+    q["from_xyz"][kept:, 0] += np.float32(100)
+    return q
+
+
+def mixed_batch():
+    """{strategy: (pairs, kw)} for the strategies 0 and 1, the same pairs in the same order.  (branch, status) per pair:
+
+        pair                                   strategy 0                strategy 1
+        room 513 x 257                         (0, OK)                   (0, OK)
+        corridor 400 x 380                     (0, LOW_COMPLEXITY)       (1, OK)
+        0 x 7 rows                             (0, LOW_COMPLEXITY)       (1, EMPTY)
+        room 300 x 280, 25 rows in reach       (0, BELOW_RATIO)          (0, BELOW_RATIO)
+        room 1030 x 700                        (0, OK)                   (0, OK)
+        corridor 257 x 237                     (0, LOW_COMPLEXITY)       (1, OK)
+        room 256 x 300, 100 m apart            (0, NOT_CONVERGED)        (0, NOT_CONVERGED)
+        corridor 300 x 280, 25 rows in reach   (0, LOW_COMPLEXITY)       (1, BELOW_RATIO)
+        corridor 512 x 492, 100 m apart        (0, LOW_COMPLEXITY)       (1, NOT_CONVERGED)
+        room 255 x 275                         (0, OK)                   (0, OK)
+
+    A side without rows has no normals and the complexity 0: under strategy 0 the empty pair returns early as the corridors do, and EMPTY is not
+    reachable there through the host entry (a side of which no row takes part has no finite normal).  The largest pair stands in the middle:
+    the stride and the LDS size of every other workgroup are not its own."""
+    def make():
+        cor = dict(noise=0.004, scene=corridor, floor=0.12, end=0.01)
+        apart = lambda p: changed(p, to_xyz=p["to_xyz"] + np.float32(100))
+        pairs = [pair(513, 257, 601, noise=0.004), pair(400, 380, 602, **cor), pair(0, 7, 603), _mostly_elsewhere(pair(300, 280, 604, noise=0.004), 25),
+                 pair(1030, 700, 605, noise=0.004), pair(257, 237, 606, **cor), apart(pair(256, 300, 607, noise=0.004)),
+                 _mostly_elsewhere(pair(300, 280, 608, **cor), 25), apart(pair(512, 492, 609, **cor)), pair(255, 275, 610, noise=0.004)]
+        return {0: (pairs, dict(KW, low_complexity_strategy=0)), 1: (pairs, dict(KW, low_complexity_strategy=1))}
+    return _once("mixed", make)
+
+
+MIXED = {0: [(0, 0), (0, 4), (0, 4), (0, 3), (0, 0), (0, 4), (0, 2), (0, 4), (0, 4), (0, 0)],
+         1: [(0, 0), (1, 0), (1, 1), (0, 3), (0, 0), (1, 0), (0, 2), (1, 3), (1, 2), (0, 0)]}         # (branch, status) as the docstring lists them
+
+
+def padded(p, region):
+    """the pair as lcd_filter_scans_dev leaves it: each side in the first rows of a region of `region` rows, quiet NaNs behind, in coordinates
+    and normals alike"""
+    q = changed(p)
+    for k in ("from_xyz", "from_normals", "to_xyz", "to_normals"):
+        a = np.full((region, 3), np.nan, np.float32)
+        a[:p[k].shape[0]] = p[k]
+        q[k] = a
+    return q
+
+
+def padded_regions():
+    """[(region, padded pairs, the same pairs without the padding, kw)].  Regions of 1 024 rows hold 900 x 880 and 1 023 x 1 000 points: the
+    sort is sized by the region, and AUTO, which counts the rows that take part, stays brute.  Regions of 2 048 rows hold 1 100 x 1 080 points
+    (AUTO takes the grid form) and 600 x 1 030 (brute towards the from-side, grid towards the to-side)"""
+    def make():
+        out = []
+        for region, sizes, kw in ((1024, ((900, 880), (1023, 1000)), dict(KW)), (2048, ((1100, 1080), (600, 1030)), dict(KW, max_iterations=3))):
+            plain = [pair(nf, nt, 700 + nf, noise=0.004) for nf, nt in sizes]
+            out.append((region, [padded(p, region) for p in plain], plain, kw))
+        return out
+    return _once("padded", make)
+
+
+def spun_normals(n, phase):
+    """n unit normals, each a function of its row index alone, no two neighbours alike"""
+    i = np.arange(n, dtype=np.float64)
+    a, b = 0.7 * i + phase, 0.3 * i
+    return np.column_stack([np.cos(a), np.sin(a) * np.cos(b), np.sin(a) * np.sin(b)]).astype(np.float32).reshape(-1, 3)
+
+
+GRID_EDGE_KW = dict(GRID_KW, min_complexity=0.0, low_complexity_strategy=1)
+GRID_EDGE_ONCE_KW = dict(GRID_EDGE_KW, max_iterations=1)                   # the first fit goes straight to the outputs
+GRID_CELL = 0.265625                                                       # the cell of register_icp_inputs.GRID_THR, exact
+
+
+def grid_edge_pairs():
+    """name -> register_icp_inputs.grid_edge_pairs()'s 3-D pairs with spun_normals on both sides: the normal fit_plane reads is that of the
+    row the search found, so a wrong row changes the sums.  With min_complexity = 0 every pair takes branch 0.  diagonal_neighbour has four
+    from-rows, too few for the six unknowns of the plane fit: it stays, as diagonal_neighbour_singular, and diagonal_neighbour is three copies
+    of it, eight cells apart along x and along y"""
+    def make():
+        with_normals = lambda f, t, g=None: raw(f, spun_normals(f.shape[0], 0.4), t, spun_normals(t.shape[0], 1.3), g)
+        out = {}
+        for name, p in _p2p_grid_edge_pairs().items():
+            if not p["flat"]:
+                out[name] = with_normals(p["from_xyz"], p["to_xyz"], p["guess"])
+        four = out["diagonal_neighbour_singular"] = out["diagonal_neighbour"]
+        steps = np.array([[0, 0, 0], [8 * GRID_CELL, 0, 0], [0, 8 * GRID_CELL, 0]], np.float32)
+        out["diagonal_neighbour"] = with_normals(np.concatenate([four["from_xyz"] + s for s in steps]), np.concatenate([four["to_xyz"] + s for s in steps]))
+        return out
+    return _once("grid_edges", make)
+
+
+def non_finite_coordinates():
+    """600 x 600 rows (brute under AUTO) and 1 100 x 1 100 (grid) with rows 255, 256 and 511 of the from-side and 255 and 511 of the to-side not
+    finite in a coordinate, and the latter with two more from-rows and seven of every eight to-rows NaN: the region asks for the grid form,
+    the rows that take part do not, and the from-side becomes step 5's target -- device entry only"""
+    def make():
+        out = []
+        for n in (600, 1100):
+            q = pair(n, n, 800 + n, noise=0.004)
+            q["from_xyz"][[255, 256, 511], [0, 1, 2]] = [np.nan, np.inf, -np.inf]
+            q["to_xyz"][[255, 511], [1, 2]] = [np.nan, np.inf]
+            out.append(q)
+        few = changed(out[1])
+        few["from_xyz"][[3, 1099], [0, 2]] = np.nan
+        few["to_xyz"][np.arange(1100) % 8 != 5, 1] = np.nan
+        out.append(few)
+        return out
+    return _once("non_finite", make)
+
+
+def rows_8192():
+    """(corridor 8192 x 8100, room 8192 x 8000 with noisy normals and every fifth from-normal negated, a 257 x 513 room pair to stand between
+    them, kw): max_iterations = 2 and the gate on, which the low-complexity branch does not read"""
+    def make():
+        low = pair(8192, 8100, 901, noise=0.004, scene=corridor, floor=0.12, end=0.01)
+        gate = flipped(pair(8192, 8000, 902, noise=0.003, normal_noise=0.05), np.arange(0, 8192, 5))
+        return low, gate, pair(257, 513, 903, noise=0.004), dict(GATE_KW, max_iterations=2)
+    return _once("8192", make)
+
+
+FILTER_KW = dict(voxel_size=0.15, normal_k=8)
+FILTER_REGION = 2048
+
+
+def filter_chain():
+    """(pair, the filter's kw, the region size): two room scans of 3 000 and 2 900 points that a voxel grid of FILTER_KW's leaf brings to between
+    1 100 and 1 900 points a scan, in regions of 2 048 rows; the ICP over them runs with max_iterations = 3"""
+    return _once("chain", lambda: (pair(3000, 2900, 905, noise=0.004), dict(FILTER_KW), FILTER_REGION))

@@ -140,10 +140,12 @@ def check_plane_args(min_complexity, low_complexity_strategy, normal_gate, min_n
 
 def register(from_xyz, from_normals, to_xyz, to_normals, guess=None, max_iterations=30, force_3dof=False, max_laser_scans=0, search=SEARCH_AUTO,
              max_correspondence_distance=0.1, epsilon=0.0, correspondence_ratio=0.1, min_complexity=0.02, low_complexity_strategy=1, normal_gate=False,
-             min_normal_cos=0.0, device_entry=False, sweeps=SWEEPS):
+             min_normal_cos=0.0, device_entry=False, sweeps=SWEEPS, source_is_to=None):
     """one pair -> dict of the call's outputs (transform, icp_transform, correction, status, stop, iterations, n_correspondences, ratio, variance,
     match, branch, complexity, complexity_values, complexity_vectors, second_eigenvalue) and, for the tests: pca_from, pca_to, counts,
-    reciprocal_d2 (the reciprocal correspondences' d2 in source-row order), reciprocal_pass, reciprocal_dots"""
+    from_is_target (step 5's decision, None where step 5 is not reached), reciprocal_d2 (the reciprocal correspondences' d2 in source-row
+    order), reciprocal_rows (their source rows), reciprocal_pass, reciprocal_dots.  source_is_to is no part of the rule: a bool forces step 5's
+    source side, so that a test can show what the other decision would have given"""
     P0 = np.ascontiguousarray(from_xyz, np.float32).reshape(-1, 3)
     T0 = np.ascontiguousarray(to_xyz, np.float32).reshape(-1, 3)
     N0 = np.ascontiguousarray(from_normals, np.float32).reshape(-1, 3)
@@ -156,7 +158,8 @@ def register(from_xyz, from_normals, to_xyz, to_normals, guess=None, max_iterati
     zeros = np.zeros(12, np.float32)
     r = dict(transform=zeros.copy(), icp_transform=zeros.copy(), correction=zeros.copy(), status=OK, stop=STOP_NONE, iterations=0, n_correspondences=0,
              ratio=F(0), variance=D(1.0), match=np.full(P0.shape[0], -1, np.int32), branch=0, second_eigenvalue=F(1), counts=[],
-             reciprocal_d2=np.zeros(0, np.float32), reciprocal_pass=np.zeros(0, bool), reciprocal_dots=np.zeros(0, np.float32))
+             reciprocal_d2=np.zeros(0, np.float32), reciprocal_pass=np.zeros(0, bool), reciprocal_dots=np.zeros(0, np.float32),
+             reciprocal_rows=np.zeros(0, np.int64), from_is_target=None)
     fin_f, fin_t = np.isfinite(N0).all(axis=1), np.isfinite(NT).all(axis=1)
     NQ = rotate(guess, NT)
     pf, pt = pca(N0, fin_f, sweeps), pca(NQ, fin_t, sweeps)
@@ -215,7 +218,8 @@ def register(from_xyz, from_normals, to_xyz, to_normals, guess=None, max_iterati
         Fm = to_3dof(Fm)
     row_a, d2_a = nearest(A, part_f, Q, part_t)
     row_q, d2_q = nearest(Q, part_t, A, part_f)
-    from_is_target = nf > nt
+    from_is_target = nf > nt if source_is_to is None else bool(source_is_to)
+    r["from_is_target"] = from_is_target
     if from_is_target:
         src_row, src_d2, tgt_row, n_src, n_tgt = row_q, d2_q, row_a, NQ, NA
     else:
@@ -224,6 +228,7 @@ def register(from_xyz, from_normals, to_xyz, to_normals, guess=None, max_iterati
     keep = (src_row >= 0) & (src_d2.astype(np.float64) <= thr2)
     keep &= tgt_row[np.maximum(src_row, 0)] == idx
     kept = idx[keep]                                                   # ascending source rows
+    r["reciprocal_rows"] = kept
     if r["branch"] == 0:
         dots = gate_dots(n_tgt[src_row[kept]], n_src[kept])
         ok = dots.astype(np.float64) > D(min_normal_cos) if normal_gate else np.ones(kept.shape[0], bool)

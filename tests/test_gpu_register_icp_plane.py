@@ -6,89 +6,10 @@ import torch
 
 import register_icp_plane_inputs as I
 import register_icp_plane_model as M
+from register_icp_plane_device import (LCD_ERR_INVALID, LCD_ERR_UNSUPPORTED, SEARCHES, expected, assert_same, stage_dev, launch_dev, to_host, run_dev, run_host,
+                                       check_both, refused as _refused)
 
 pytestmark = pytest.mark.gpu
-
-LCD_ERR_INVALID, LCD_ERR_UNSUPPORTED = 1, 5
-INTS = ("status", "stop", "iterations", "n_correspondences", "branch")
-FLOATS = ("transform", "icp_transform", "correction", "ratio", "complexity", "complexity_values", "complexity_vectors", "second_eigenvalue")
-PER_PAIR = INTS + FLOATS + ("variance",)
-SEARCHES = (M.SEARCH_AUTO, M.SEARCH_BRUTE, M.SEARCH_GRID)
-_model_cache = {}
-
-
-def model_of(pair, **kw):
-    key = (id(pair), tuple(sorted(kw.items())))
-    if key not in _model_cache:
-        _model_cache[key] = (pair, M.register(*I.scans(pair), **kw))       # the pair is kept so that its id stays its own
-    return _model_cache[key][1]
-
-
-def expected(pairs, device_entry=False, **kw):
-    rs = [model_of(p, device_entry=device_entry, **kw) for p in pairs]
-    out = {k: np.stack([np.asarray(r[k]) for r in rs]) for k in PER_PAIR}
-    out["match"] = np.concatenate([r["match"] for r in rs] + [np.zeros(0, np.int32)])
-    return out
-
-
-def assert_same(got, want, what=""):
-    for k in INTS + ("match",):
-        np.testing.assert_array_equal(got[k], want[k], err_msg="%s %s" % (what, k))
-    for k in FLOATS:
-        np.testing.assert_array_equal(I.bits(got[k]).reshape(-1), I.bits(want[k]).reshape(-1), err_msg="%s %s" % (what, k))
-    np.testing.assert_array_equal(np.ascontiguousarray(got["variance"]).view(np.uint64), np.ascontiguousarray(want["variance"], np.float64).view(np.uint64),
-                                  err_msg=what + " variance")
-
-
-def stage_dev(pairs):
-    """the batch on the device, outputs canary-filled, uploaded and synchronised"""
-    from rtabmap_amd import capi
-    fx, fn, fo, tx, tn, to, gs = I.concatenate(pairs)
-    n, nf = len(pairs), fx.shape[0]
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    st = dict(fx=dev(fx), fn=dev(fn), fo=fo, tx=dev(tx), tn=dev(tn), to=to, gs=gs, out={})
-    for k, w, dt in capi.Engine.ICP_PLANE_OUT:
-        tdt = {np.int32: torch.int32, np.float32: torch.float32, np.float64: torch.float64}[dt]
-        st["out"][k] = torch.full((n, w) if w else (n,), -7 if dt is np.int32 else float("nan"), dtype=tdt, device="cuda")
-    st["out"]["match"] = torch.full((max(nf, 1),), -7, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    return st
-
-
-def launch_dev(eng, st, **kw):
-    eng.register_icp_plane_dev(st["fx"], st["fn"], st["fo"], st["tx"], st["tn"], st["to"], st["gs"], st["out"], **kw)
-    return st
-
-
-def to_host(eng, st):
-    eng.synchronize()
-    out = {k: v.cpu().numpy() for k, v in st["out"].items()}
-    out["match"] = out["match"][:int(st["fo"][-1])]
-    return out
-
-
-def run_dev(eng, pairs, **kw):
-    return to_host(eng, launch_dev(eng, stage_dev(pairs), **kw))
-
-
-def run_host(eng, pairs, **kw):
-    fx, fn, fo, tx, tn, to, gs = I.concatenate(pairs)
-    return eng.register_icp_plane(fx, fn, fo, tx, tn, to, gs, **kw)
-
-
-def check_both(eng, pairs, what="", searches=(M.SEARCH_AUTO,), **kw):
-    want = expected(pairs, **kw)
-    for search in searches:
-        assert_same(run_dev(eng, pairs, search=search, **kw), want, "%s dev, search %d" % (what, search))
-        assert_same(run_host(eng, pairs, search=search, **kw), want, "%s host, search %d" % (what, search))
-    return want
-
-
-def _refused(status, call, *args, **kw):
-    from rtabmap_amd import capi
-    with pytest.raises(capi.LcdError) as err:
-        call(*args, **kw)
-    assert err.value.status == status, err.value
 
 
 @pytest.fixture(scope="module")

@@ -1,11 +1,13 @@
 """The host mirror of lcd_register_icp_plane (rtabmap_amd/host/RegistrationIcp.cpp, through c_shim.cpp) against
-tests/register_icp_plane_model.py bit for bit on every hand-made case and size under all three search values, the refusals, what the mirror
+tests/register_icp_plane_model.py bit for bit on every hand-made case, size and block, batch and region edge under all three search values,
+the refusals, what the mirror
 does behind the rule, the sweep count, and the fp32 rule against an independent point-to-plane ICP.  No GPU."""
 import numpy as np
 import pytest
 
 import register_icp_plane_inputs as I
 import register_icp_plane_model as M
+from register_icp_plane_device import model_of
 
 F = np.float32
 INTS = ("status", "stop", "iterations", "n_correspondences", "branch")
@@ -154,3 +156,75 @@ def test_the_fp32_rule_against_a_float64_icp():
     print("largest difference to the float64 ICP: rule %.3g, the same ICP in float32 %.3g" % (worst, noise))
     assert noise <= ICP64_FP32_NOISE * 1.0001, "the measured fp32 noise of the reference moved: the bound is stated for %.3g" % ICP64_FP32_NOISE
     assert worst <= ICP64_BOUND
+
+
+# ---- the cases of the block, batch and region edges (tests/register_icp_plane_inputs.py; tests/test_register_icp_plane_inputs.py proves what
+# each of them does): the mirror under all three search values against the model, whose results the two modules share
+
+def cached(p, **kw):
+    want = model_of(p, **kw)
+    for search in (M.SEARCH_AUTO, M.SEARCH_BRUTE, M.SEARCH_GRID):
+        assert_same(mirror(p, **dict(kw, search=search)), want, "search %d" % search)
+    return want
+
+
+@pytest.mark.parametrize("name", sorted(I.low_complexity_sizes()))
+def test_the_mirror_equals_the_model_in_the_low_complexity_branch_at_every_block_edge(name):
+    pairs, kw = I.low_complexity_sizes()[name]
+    assert all(cached(p, **kw)["branch"] == 1 for p in pairs)
+
+
+def test_the_mirror_equals_the_model_under_the_gate_at_every_block_edge():
+    pairs, kw = I.gate_sizes()
+    for p in pairs:
+        want = cached(p, **kw)
+        assert 0 < want["n_correspondences"] < len(want["reciprocal_pass"])
+
+
+def test_the_mirror_takes_the_source_side_from_the_rows_that_take_part():
+    pairs, kw = I.swap_turned_by_normals()
+    for p in pairs:
+        want = cached(p, **kw)
+        assert want["from_is_target"] == (p["from_xyz"].shape[0] < p["to_xyz"].shape[0])
+
+
+def test_the_mirror_equals_the_model_on_the_mixed_batches():
+    for strategy, (pairs, kw) in I.mixed_batch().items():
+        assert [(r["branch"], r["status"]) for r in (cached(p, **kw) for p in pairs)] == I.MIXED[strategy]
+
+
+def test_the_mirror_skips_the_padding_of_a_region_and_the_host_rule_refuses_it():
+    for region, pads, plain, kw in I.padded_regions():
+        for a, b in zip(pads, plain):
+            want = cached(a, device_entry=True, **kw)
+            assert (want["match"][b["from_xyz"].shape[0]:] == -1).all()
+            assert mirror(a, **kw) is None
+            cached(b, **kw)
+
+
+def test_the_mirror_skips_coordinates_that_are_not_finite_at_600_and_1100_rows():
+    for p in I.non_finite_coordinates():
+        assert cached(p, device_entry=True, **I.KW)["status"] == M.OK
+        assert mirror(p, **I.KW) is None
+
+
+@pytest.mark.parametrize("name", sorted(I.grid_edge_pairs()))
+def test_the_grid_form_equals_the_model_at_its_edges_with_normals(name):
+    p = I.grid_edge_pairs()[name]
+    assert cached(p, **I.GRID_EDGE_KW)["branch"] == 0 and cached(p, **I.GRID_EDGE_ONCE_KW)["branch"] == 0
+
+
+def test_the_mirror_equals_the_model_at_8192_rows_in_branch_1_and_under_the_gate():
+    low, gate, between, kw = I.rows_8192()
+    assert cached(low, **kw)["branch"] == 1
+    want = cached(gate, **kw)
+    assert 0 < want["n_correspondences"] < len(want["reciprocal_pass"])
+    cached(between, **kw)
+
+
+def test_the_mirror_equals_the_model_behind_the_filter():
+    import scan_filter_model as SM
+    p, kw, region = I.filter_chain()
+    f = SM.filter_scans([p["from_xyz"], p["to_xyz"]], [region, region], device_entry=True, **kw)
+    q = I.raw(f["xyz"][:region], f["normals"][:region], f["xyz"][region:], f["normals"][region:], p["guess"])
+    assert cached(q, device_entry=True, **dict(I.KW, max_iterations=3))["status"] == M.OK
