@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_keypoints_3d_stereo / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_keypoints_3d_stereo / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_refine_motion_ba / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -932,7 +932,7 @@ int lcd_estimate_motion_3d_dev(lcd_engine* h, const lcd_motion_3d_args* a);
  *  11. Twelve zero floats mean no transform; then out_status != LCD_PNP_OK, out_variance_lin = out_angle_cos = 1.0 and out_variance_kind = 0.
  * Outputs: in the pair's TO-region of out_matches the ids ascending, of out_inliers the ids in correspondence order, the rest of both 0.
  * Out of scope: lens distortion (the struct carries no D; the registration's images are rectified), the multi-camera overload (OpenGV),
- * splitLinearCovarianceComponents, to3DoF and bundle adjustment.
+ * splitLinearCovarianceComponents and to3DoF.  The bundle adjustment behind this step is lcd_refine_motion_ba, below.
  *
  * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on a side of a pair,
  * n_pairs > 65535, iterations > 65535 or a handle of a sharded vocabulary: LCD_ERR_UNSUPPORTED; iterations < 1, a reproj_error that is not
@@ -983,6 +983,144 @@ int lcd_estimate_motion_pnp(lcd_engine* h, const lcd_motion_pnp_args* a);
 /* ids, points and out_* in DEVICE memory (4-byte aligned, the doubles 8-byte), offsets, cameras and guesses on the HOST (read during the
  * call); enqueued on the engine stream, not synchronised */
 int lcd_estimate_motion_pnp_dev(lcd_engine* h, const lcd_motion_pnp_args* a);
+
+/* ---- Two-view bundle adjustment, stateless: the link of RegistrationVis::computeTransformationImpl between the PnP and the ICP
+ * (RegistrationVis.cpp:1873-2188 with Vis/BundleAdjustment = 1, the reference's default): the transform of lcd_estimate_motion_pnp (or
+ * lcd_estimate_motion_3d) is refined over its inliers by OptimizerG2O::optimizeBA (OptimizerG2O.cpp:1429-2117) with root 1 and one neighbour
+ * link, the inliers the adjustment marks as outliers are dropped, Vis/MinInliers is tested again, and the gates Vis/MeanInliersDistance and
+ * Vis/MinInliersDistribution decide.  What is in the reference tree is reproduced as written; what it calls in g2o (the projections, the
+ * camera edge's error, the robust kernel, Levenberg-Marquardt and its linear solver) and in OpenCV (cv::PCA) is not in the tree and is the
+ * ENGINE'S rule, written out here.  No parity with a g2o build is claimed.  Stateless exactly as lcd_estimate_motion_pnp; pair i owns the
+ * rows [from_offsets[i], from_offsets[i+1]) of the from-arrays, [to_offsets[i], to_offsets[i+1]) of the to-arrays, of `inliers` and of
+ * out_inliers, cameras_from[i], cameras_to[i], transforms[12 i ..], n_inliers[i], prior_variance[2 i ..] and baselines[2 i ..].
+ *
+ * The rule, per pair.  fp32, every operation rounded on its own, IEEE division and square root, only + - x / sqrt; "fp64" marks what is
+ * double.  T(p), A x B, inverse(T), the quaternion of a rotation, the rotation of a quaternion, the pose update and the 6 x 6 LDL^T are those
+ * of lcd_estimate_motion_pnp (its preamble and steps 3, 7, 8).  SUM is the sum of lcd_estimate_motion_3d (step 4 there: 256 lane partials in
+ * ascending order from +0, then the halving tree); SUM64 the same in fp64.
+ *   1. Input.  n = n_inliers[i].  Twelve zero floats in transforms[12 i ..] or n == 0: LCD_BA_NO_INPUT, out_inliers = the first max(n, 0)
+ *      ids of `inliers` as they are (at most the pair's to-rows), out_n_inliers = their number, everything else 0.  n < 0, n above the pair's to-rows, an id among the first n that does
+ *      not occur exactly once in the from-frame and exactly once in the to-frame, or a from-point with a coordinate that is not finite (the
+ *      reference asserts): LCD_BA_BAD_INLIER, nothing is refined, outputs as for LCD_BA_NO_INPUT.  lcd_estimate_motion_pnp produces neither.
+ *      Repeats WITHIN the list are not checked: an id given twice makes two points with the same observations (the reference's map would
+ *      keep one); lcd_estimate_motion_pnp's list has none.
+ *   2. Graph (:1885-2027).  Pose 1 is the identity and fixed, pose 2 the transform T; the cameras' poses are C1 = local_from, C2 = T x
+ *      local_to (a camera without local transform: the identity).  The engine holds a camera as the model M = inverse(C) that maps points
+ *      into it: M1 = inverse(local_from), M2 = inverse(T x local_to).  Point k is inlier k's from-point P0_k.  Its observations:
+ *      from-side, only with from_points: depth = z of M1(P0_k), keypoint (u, v) of the from-row; to-side: depth = z of
+ *      inverse(local_to)(to-point), 0 without to_xyz, keypoint of the to-row.  An edge is stereo iff its depth is finite and > 0 and the
+ *      camera's baseline b (fp64) is > 0 (OptimizerG2O.cpp:1862); then obs = (u, v, u - float(b x double(fx) / double(depth))) (fp64,
+ *      :1880); otherwise mono, obs = (u, v).  Information I / pixel_variance: info = float(1 / pixel_variance).  One camera-to-camera edge
+ *      with measurement inverse(C1) x T x local_to, information diag(inf_lin x 3, inf_ang x 3) with inf = float(1 / max(variance, floor)),
+ *      floors 1e-8 and 3e-8 (Registration.cpp:36-37); 1 and 1 without prior_variance (Optimizer/VarianceIgnored).
+ *   3. Projection and chi2 (engine).  Under a model M: (Mx, My, Mz) = R p, (X, Y, Z) = that + t, iz = 1 / Z, x = X iz, y = Y iz,
+ *      projection (fx x + cx, fy y + cy, fx ((X - float(b)) iz) + cx); r = obs - projection; chi2 = info x ((ru ru + rv rv) + rd rd), the
+ *      last term only for a stereo edge.  Nothing is special about Z <= 0.
+ *   4. Robust kernel (engine): Huber as IRLS.  delta = float(robust_delta), delta2 = delta x delta.  For chi2 <= delta2 (or delta == 0) the
+ *      weight is 1 and the cost chi2; otherwise the weight is delta / sqrt(chi2) and the cost (2 delta) sqrt(chi2) - delta2.  No second-order
+ *      term.
+ *   5. Camera edge (engine).  E = M2 x C2_0, C2_0 = T x local_to as given.  Error e = (translation of E, 2 (x, y, z) of E's quaternion
+ *      divided by its norm, negated when w < 0).  Cost inf_lin x ((e0 e0 + e1 e1) + e2 e2) + inf_ang x ((e3 e3 + e4 e4) + e5 e5).  Jacobian
+ *      with respect to (w, dt) of step 8's update: rows 0-2 (-[R t0]x | I), rows 3-5 (w_E I - [v_E]x | 0), R t0 = R applied to C2_0's
+ *      translation.  Its 21 + 6 entries: per entry the six rows in order, (J_ki J_kj) x inf_k, added from +0; the right-hand side subtracts
+ *      (J_ki e_k) x inf_k.
+ *   6. Cost.  F = SUM64 over the points of (double(cost of the from-edge) + double(cost of the to-edge)), active edges only, then
+ *      + double(the camera edge's cost).
+ *   7. Normal equations (engine), per point with an active edge, under the current M2 and point: per active edge W = info x weight; rows
+ *      g = (a, 0, -(a x)), (0, c, -(c y)), (a, 0, -(a xb)) with a = fx iz, c = fy iz, xb = (X - b) iz; point Jacobian Jp_k = g_k R (each entry
+ *      a product minus a product), camera Jacobian of the to-edge as lcd_estimate_motion_pnp's step 8 with the third row (-(a xb) My,
+ *      a Mz + (a xb) Mx, -(a My), a, 0, -(a xb)).  Every entry of the 3 x 3 block Hpp, the gradient bp, the 6 x 3 coupling Hcp, the camera
+ *      block Hcc and gradient bc is, per edge, ((J_0 J'_0 + J_1 J'_1) + J_2 J'_2) x W added to the entry, the from-edge first.
+ *      Levenberg-Marquardt on the Schur complement: inverse of (Hpp + lambda I) by cofactors over the determinant, Y = Hcp inverse, the
+ *      point's 27 terms Hcc_ij - ((Y_i0 Hcp_j0 + Y_i1 Hcp_j1) + Y_i2 Hcp_j2) and bc_i - (Y_i . bp); their SUM over the points; plus the
+ *      camera edge's entries; lambda added to the six diagonal entries; the LDL^T.  Back-substitution per point: dp = inverse (bp - Hcp^T
+ *      dc), the inner products in ascending index.  p <- p + dp; the pose update of lcd_estimate_motion_pnp's step 8 (q <- (1, w / 2) (x) q,
+ *      t <- t + dt), M2 = [R(q / |q|) | t].
+ *   8. Nielsen's schedule (engine).  At the start of a stage lambda = 1e-5f x the largest of: every point's three Hpp diagonal entries, and
+ *      the six SUMs of the Hcc diagonal entries plus the camera edge's; nu = 2.  Per iteration up to 10 trials: solve with lambda (no
+ *      solution counts as a rejected trial); F' = the cost of the moved state; scale = SUM64 over the points of (sum_a dp_a (lambda dp_a +
+ *      bp_a) + sum_i dc_i bc_i) + sum_i dc_i (lambda dc_i + the camera edge's right-hand side i), fp64; rho = (F - F') / (scale + 1e-3),
+ *      fp64.  Accepted iff rho > 0 and F' is finite: F = F', lambda = float(double(lambda) x max(1/3, 1 - (2 rho - 1)^3)), nu = 2.
+ *      Otherwise the state is restored, lambda <- lambda nu, nu <- 2 nu.  Ten rejected trials end the stage.
+ *   9. Stages and outliers (OptimizerG2O.cpp:1946-2027).  robust_delta > 0: two stages, 5 iterations, then `iterations`; otherwise one stage
+ *      of `iterations`.  After each stage: F is NaN: LCD_BA_DIVERGED (:1954); after the second, F > 1e12 or not finite: LCD_BA_DIVERGED
+ *      (:1962); otherwise, with a kernel, every active edge whose UN-ROBUSTIFIED chi2 is > delta -- delta, not delta2, as written at :1972 --
+ *      leaves (level 1), its point goes back to P0_k and is an outlier (both edges are tested on the chi2 they had before either reset).  The
+ *      second stage starts from the cost of what is left.  After the last stage F > 1e12: LCD_BA_DIVERGED (:2023).  out_chi2_before is the
+ *      first F, out_chi2_after the last.  LCD_BA_DIVERGED: no transform, the inliers as they came.
+ *  10. Result (RegistrationVis.cpp:2033-2063).  out_inliers = the ids whose point is no outlier, in input order; fewer than min_inliers:
+ *      LCD_BA_BELOW_MIN_INLIERS, no transform.  Otherwise transform = inverse(local_to x M2) (:2049), inverse(M2) without local transform.
+ *      iterations == 0: no adjustment; out_transform is the input, bit for bit, and the gates below decide.
+ *  11. Gates (:2090-2188), with a transform and at least one inlier.  max_inliers_mean_distance > 0 and to_xyz given: the depths z of
+ *      inverse(local_to)(to-point) of the surviving inliers whose to-point has three finite coordinates, in inlier order; uMean (UMath.h:
+ *      a float accumulator from the first to the last, / float(count)); none: no test.  mean > max: LCD_BA_MEAN_DISTANCE_REJECTED.
+ *      min_inliers_distribution > 0 and the to-camera has fx, fy, cx, cy > 0 and an image size (isValidForReprojection): x = float((double(u)
+ *      - double(cx)) / double(width)), y alike with cy and height (:2154-2155, fp64); mean = SUM / float(n); covariance entries SUM of the
+ *      products of the centred coordinates / float(n); out_inliers_distribution = the smaller eigenvalue (a + c) / 2 - sqrt(((a - c) / 2)^2 +
+ *      b b); below the threshold: LCD_BA_DISTRIBUTION_REJECTED.  A rejected pair has no transform; its inliers and figures stay.
+ * Precision: the 27 sums and the 6 x 6 solve are fp32, as lcd_estimate_motion_pnp's and lcd_register_icp_plane's.
+ * Out of scope: multi-camera rigs (cameraIndex is 0), Reg/Force3DoF (the plane prior) and gravity links, cvsba and Ceres
+ * (Vis/BundleAdjustment 2 and 3), full 6 x 6 priors, handing back the refined points (the reference discards them too), lens distortion,
+ * the epipolar estimation type.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on a side of a pair,
+ * n_pairs > 65535, iterations > 65535 or a handle of a sharded vocabulary: LCD_ERR_UNSUPPORTED; iterations < 0, min_inliers < 0, a pixel_variance that is not
+ * finite and > 0 (itself and float(1 / it)), a robust_delta, gate or prior variance that is negative or not finite (float(robust_delta)
+ * squared too), a baseline that is not finite, n_pairs < 0, offsets that are missing, do not start at 0 or decrease, NULL cameras, a camera
+ * whose fx or fy is not finite or is 0, a NULL pointer where rows, pairs or outputs exist (from_points, to_xyz, prior_variance and baselines
+ * may be NULL), or a wrong struct_size: LCD_ERR_INVALID.  n_pairs == 0 returns LCD_OK.  One kernel launch per call whatever the batch: one
+ * workgroup of 256 threads per pair.  out_inliers must not overlap `inliers`. */
+enum lcd_motion_ba_status {
+    LCD_BA_OK = 0,
+    LCD_BA_NO_INPUT = 1,              /* no transform came in, or no inliers: passed through */
+    LCD_BA_BAD_INLIER = 2,            /* an inlier id that is not unique in both frames, or a count outside the region */
+    LCD_BA_DIVERGED = 3,              /* the cost is NaN or above 1e12: no transform, the inliers as they came */
+    LCD_BA_BELOW_MIN_INLIERS = 4,     /* survivors returned, no transform */
+    LCD_BA_MEAN_DISTANCE_REJECTED = 5,
+    LCD_BA_DISTRIBUTION_REJECTED = 6
+};
+typedef struct lcd_motion_ba_args {
+    int32_t struct_size;            /* sizeof(lcd_motion_ba_args) */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t min_inliers;            /* Vis/MinInliers, >= 0 */
+    int32_t iterations;             /* Optimizer/Iterations, 0 .. 65535; 0 = no adjustment, gates only */
+    double pixel_variance;          /* g2o/PixelVariance, finite, > 0 */
+    double robust_delta;            /* g2o/RobustKernelDelta, finite, >= 0; 0 = no kernel, one stage */
+    double default_baseline;        /* g2o/Baseline, finite; used where baselines is NULL */
+    float max_inliers_mean_distance;   /* Vis/MeanInliersDistance, 0 = off */
+    float min_inliers_distribution;    /* Vis/MinInliersDistribution, 0 = off */
+    const int32_t* from_word_ids;   /* [Nf] */
+    const float* from_xyz;          /* [Nf x 3] */
+    const float* from_points;       /* [Nf x 2] the from keypoints; NULL = none (the reference's empty getWordsKpts()) */
+    const int32_t* to_word_ids;     /* [Nt] */
+    const float* to_points;         /* [Nt x 2] */
+    const float* to_xyz;            /* [Nt x 3]; may be NULL */
+    const int32_t* inliers;         /* [Nt]: lcd_estimate_motion_pnp's out_inliers */
+    const int32_t* n_inliers;       /* [n_pairs]: its out_n_inliers */
+    const float* transforms;        /* [n_pairs x 12]: its out_transform */
+    const double* prior_variance;   /* HOST, [n_pairs x 2] linear, angular; NULL = identity information */
+    const int64_t* from_offsets;    /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    const int64_t* to_offsets;      /* HOST, [n_pairs + 1] */
+    const lcd_camera* cameras_from; /* HOST, [n_pairs] */
+    const lcd_camera* cameras_to;   /* HOST, [n_pairs] */
+    const double* baselines;        /* HOST, [n_pairs x 2] from, to; NULL = default_baseline; <= 0: mono edges only */
+    float* out_transform;           /* [n_pairs x 12]; twelve zeros = rejected */
+    int32_t* out_status;            /* [n_pairs], lcd_motion_ba_status */
+    int32_t* out_inliers;           /* [Nt]: the surviving ids in input order, zeros behind them */
+    int32_t* out_n_inliers;         /* [n_pairs] */
+    int32_t* out_n_outliers;        /* [n_pairs] */
+    double* out_chi2_before;        /* [n_pairs] the robust cost before the first stage */
+    double* out_chi2_after;         /* [n_pairs] and behind the last */
+    int32_t* out_lm_accepted;       /* [n_pairs] accepted Levenberg-Marquardt steps */
+    float* out_inliers_mean_distance;   /* [n_pairs]; 0 when the gate is off or has nothing to test */
+    float* out_inliers_distribution;    /* [n_pairs]; 0 when the gate is off */
+} lcd_motion_ba_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_refine_motion_ba(lcd_engine* h, const lcd_motion_ba_args* a);
+/* ids, points, inliers, n_inliers, transforms and out_* in DEVICE memory (4-byte aligned, the doubles 8-byte): the PnP's outputs go in with
+ * nothing read back; offsets, cameras, prior_variance and baselines on the HOST (read during the call); enqueued on the engine stream, not
+ * synchronised */
+int lcd_refine_motion_ba_dev(lcd_engine* h, const lcd_motion_ba_args* a);
 
 /* ---- Scan registration (point-to-point ICP), stateless: the other half of the registration step, Reg/Strategy = 1 (ICP) and 2 (visual, then
  * ICP), for a caller who holds both laser scans in device memory.  RegistrationIcp::computeTransformationImpl, the point-to-point branch

@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -233,6 +233,22 @@ class LcdMotionPnpArgs(C.Structure):
 LCD_PNP_OK, LCD_PNP_FEW_CORRESPONDENCES, LCD_PNP_NO_MODEL, LCD_PNP_BELOW_MIN_INLIERS, LCD_PNP_VARIANCE_REJECTED = 0, 1, 2, 3, 4  # lcd_motion_pnp_status
 
 
+class LcdMotionBaArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("min_inliers", C.c_int32), ("iterations", C.c_int32),
+                ("pixel_variance", C.c_double), ("robust_delta", C.c_double), ("default_baseline", C.c_double),
+                ("max_inliers_mean_distance", C.c_float), ("min_inliers_distribution", C.c_float), ("from_word_ids", C.c_void_p),
+                ("from_xyz", C.c_void_p), ("from_points", C.c_void_p), ("to_word_ids", C.c_void_p), ("to_points", C.c_void_p), ("to_xyz", C.c_void_p),
+                ("inliers", C.c_void_p), ("n_inliers", C.c_void_p), ("transforms", C.c_void_p), ("prior_variance", C.c_void_p),
+                ("from_offsets", C.c_void_p), ("to_offsets", C.c_void_p), ("cameras_from", C.c_void_p), ("cameras_to", C.c_void_p),
+                ("baselines", C.c_void_p), ("out_transform", C.c_void_p), ("out_status", C.c_void_p), ("out_inliers", C.c_void_p),
+                ("out_n_inliers", C.c_void_p), ("out_n_outliers", C.c_void_p), ("out_chi2_before", C.c_void_p), ("out_chi2_after", C.c_void_p),
+                ("out_lm_accepted", C.c_void_p), ("out_inliers_mean_distance", C.c_void_p), ("out_inliers_distribution", C.c_void_p)]
+
+
+LCD_BA_OK, LCD_BA_NO_INPUT, LCD_BA_BAD_INLIER, LCD_BA_DIVERGED, LCD_BA_BELOW_MIN_INLIERS, LCD_BA_MEAN_DISTANCE_REJECTED, LCD_BA_DISTRIBUTION_REJECTED = \
+    0, 1, 2, 3, 4, 5, 6  # lcd_motion_ba_status
+
+
 KP3D_FILTERS = {"keep_all": LCD_KP3D_KEEP_ALL, "filter_3d": LCD_KP3D_FILTER_3D, "filter_pixel": LCD_KP3D_FILTER_PIXEL}
 
 
@@ -318,6 +334,8 @@ def load():
     L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_pnp.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
     L.lcd_estimate_motion_pnp_dev.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
+    L.lcd_refine_motion_ba.argtypes = [vp, C.POINTER(LcdMotionBaArgs)]
+    L.lcd_refine_motion_ba_dev.argtypes = [vp, C.POINTER(LcdMotionBaArgs)]
     L.lcd_register_icp.argtypes = [vp, C.POINTER(LcdIcpArgs)]
     L.lcd_register_icp_dev.argtypes = [vp, C.POINTER(LcdIcpArgs)]
     L.lcd_register_icp_plane.argtypes = [vp, C.POINTER(LcdIcpPlaneArgs)]
@@ -956,6 +974,78 @@ class Engine:
         a.out_variance_lin, a.out_angle_cos, a.out_variance_kind = ptr(d_variance_lin), ptr(d_angle_cos), ptr(d_variance_kind)
         a.out_matches, a.out_inliers = ptr(d_matches), ptr(d_inliers)
         self._ck(self.L.lcd_estimate_motion_pnp_dev(self.h, C.byref(a)))
+
+    # ---- two-view bundle adjustment behind the motion estimate (stateless; include/lcd.h has the rule)
+    def _ba_args(self, n_pairs, fo, to, cams_from, cams_to, prior_variance, baselines, min_inliers, iterations, pixel_variance, robust_delta,
+                 default_baseline, max_inliers_mean_distance, min_inliers_distribution, struct_size=None):
+        """the host-side fields; the second value keeps their arrays alive for the call"""
+        a = LcdMotionBaArgs(C.sizeof(LcdMotionBaArgs) if struct_size is None else struct_size, n_pairs, int(min_inliers), int(iterations),
+                            float(pixel_variance), float(robust_delta), float(default_baseline), float(max_inliers_mean_distance),
+                            float(min_inliers_distribution))
+        pv = None if prior_variance is None else np.ascontiguousarray(prior_variance, dtype=np.float64).reshape(-1, 2)
+        bl = None if baselines is None else np.ascontiguousarray(baselines, dtype=np.float64).reshape(-1, 2)
+        a.from_offsets, a.to_offsets = None if fo is None else fo.ctypes.data, None if to is None else to.ctypes.data
+        a.cameras_from = None if cams_from is None else C.cast(cams_from, C.c_void_p)
+        a.cameras_to = None if cams_to is None else C.cast(cams_to, C.c_void_p)
+        a.prior_variance, a.baselines = None if pv is None else pv.ctypes.data, None if bl is None else bl.ctypes.data
+        return a, (pv, bl)
+
+    def refine_motion_ba(self, from_ids, from_xyz, from_offsets, to_ids, to_points, to_offsets, inliers, n_inliers, transforms, cameras_from, cameras_to,
+                         from_points=None, to_xyz=None, prior_variance=None, baselines=None, min_inliers=20, iterations=20, pixel_variance=1.0,
+                         robust_delta=8.0, default_baseline=0.075, max_inliers_mean_distance=0.0, min_inliers_distribution=0.0, struct_size=None):
+        """lcd_refine_motion_ba over host arrays, all pairs concatenated -> dict(transform [n_pairs x 12], status, n_inliers, n_outliers,
+        chi2_before, chi2_after, lm_accepted, inliers_mean_distance, inliers_distribution [n_pairs], inliers [Nt]); outputs start as -1 / NaN
+        so that what the call left alone shows"""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fi, ti = np.ascontiguousarray(from_ids, dtype=np.int32).reshape(-1), np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
+        fx, tp = np.ascontiguousarray(from_xyz, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
+        fp = None if from_points is None else np.ascontiguousarray(from_points, dtype=np.float32).reshape(-1, 2)
+        tx = None if to_xyz is None else np.ascontiguousarray(to_xyz, dtype=np.float32).reshape(-1, 3)
+        il = None if inliers is None else np.ascontiguousarray(inliers, dtype=np.int32).reshape(-1)
+        ni = None if n_inliers is None else np.ascontiguousarray(n_inliers, dtype=np.int32).reshape(-1)
+        tr = None if transforms is None else np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+        n_pairs, n = (to if to is not None else fo).shape[0] - 1, ti.shape[0]
+        np1 = max(n_pairs, 1)
+        out = dict(transform=np.full((np1, 12), np.nan, np.float32), status=np.full(np1, -1, np.int32), n_inliers=np.full(np1, -1, np.int32),
+                   n_outliers=np.full(np1, -1, np.int32), chi2_before=np.full(np1, np.nan, np.float64), chi2_after=np.full(np1, np.nan, np.float64),
+                   lm_accepted=np.full(np1, -1, np.int32), inliers_mean_distance=np.full(np1, np.nan, np.float32),
+                   inliers_distribution=np.full(np1, np.nan, np.float32), inliers=np.full(max(n, 1), -1, np.int32))
+        a, keep = self._ba_args(n_pairs, fo, to, self._pnp_cameras(cameras_from, n_pairs), self._pnp_cameras(cameras_to, n_pairs), prior_variance, baselines,
+                                min_inliers, iterations, pixel_variance, robust_delta, default_baseline, max_inliers_mean_distance, min_inliers_distribution,
+                                struct_size)
+        opt = lambda v: None if v is None else _p(v)
+        a.from_word_ids, a.from_xyz, a.from_points, a.to_word_ids, a.to_points, a.to_xyz = _p(fi), _p(fx), opt(fp), _p(ti), _p(tp), opt(tx)
+        a.inliers, a.n_inliers, a.transforms = opt(il), opt(ni), opt(tr)
+        a.out_transform, a.out_status, a.out_inliers, a.out_n_inliers = _p(out["transform"]), _p(out["status"]), _p(out["inliers"]), _p(out["n_inliers"])
+        a.out_n_outliers, a.out_chi2_before, a.out_chi2_after = _p(out["n_outliers"]), _p(out["chi2_before"]), _p(out["chi2_after"])
+        a.out_lm_accepted, a.out_inliers_mean_distance, a.out_inliers_distribution = \
+            _p(out["lm_accepted"]), _p(out["inliers_mean_distance"]), _p(out["inliers_distribution"])
+        self._ck(self.L.lcd_refine_motion_ba(self.h, C.byref(a)))
+        for k in out:
+            out[k] = out[k][:n] if k == "inliers" else out[k][:max(n_pairs, 0)]
+        return out
+
+    def refine_motion_ba_dev(self, d_from_ids, d_from_xyz, from_offsets, d_to_ids, d_to_points, to_offsets, d_inliers, d_n_inliers, d_transforms,
+                             cameras_from, cameras_to, d_out_transform, d_out_status, d_out_inliers, d_out_n_inliers, d_out_n_outliers,
+                             d_out_chi2_before, d_out_chi2_after, d_out_lm_accepted, d_out_mean_distance, d_out_distribution, d_from_points=None,
+                             d_to_xyz=None, prior_variance=None, baselines=None, min_inliers=20, iterations=20, pixel_variance=1.0, robust_delta=8.0,
+                             default_baseline=0.075, max_inliers_mean_distance=0.0, min_inliers_distribution=0.0):
+        """lcd_refine_motion_ba_dev on torch tensors of the engine's device: d_inliers, d_n_inliers and d_transforms are what
+        estimate_motion_pnp_dev wrote (offsets, cameras, prior_variance and baselines stay on the host).  Enqueued, not synchronised."""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        n_pairs = (to if to is not None else fo).shape[0] - 1
+        a, keep = self._ba_args(n_pairs, fo, to, self._pnp_cameras(cameras_from, n_pairs), self._pnp_cameras(cameras_to, n_pairs), prior_variance, baselines,
+                                min_inliers, iterations, pixel_variance, robust_delta, default_baseline, max_inliers_mean_distance, min_inliers_distribution)
+        a.from_word_ids, a.from_xyz, a.from_points = ptr(d_from_ids), ptr(d_from_xyz), ptr(d_from_points)
+        a.to_word_ids, a.to_points, a.to_xyz = ptr(d_to_ids), ptr(d_to_points), ptr(d_to_xyz)
+        a.inliers, a.n_inliers, a.transforms = ptr(d_inliers), ptr(d_n_inliers), ptr(d_transforms)
+        a.out_transform, a.out_status, a.out_inliers, a.out_n_inliers = ptr(d_out_transform), ptr(d_out_status), ptr(d_out_inliers), ptr(d_out_n_inliers)
+        a.out_n_outliers, a.out_chi2_before, a.out_chi2_after = ptr(d_out_n_outliers), ptr(d_out_chi2_before), ptr(d_out_chi2_after)
+        a.out_lm_accepted, a.out_inliers_mean_distance, a.out_inliers_distribution = ptr(d_out_lm_accepted), ptr(d_out_mean_distance), ptr(d_out_distribution)
+        self._ck(self.L.lcd_refine_motion_ba_dev(self.h, C.byref(a)))
 
     # ---- scan registration, point-to-point ICP (stateless; include/lcd.h has the rule)
     @staticmethod

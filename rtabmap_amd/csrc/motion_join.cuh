@@ -1,6 +1,6 @@
-// motion_join.cuh -- the unique-id join of two frames for motion_3d.hip and motion_pnp.hip: both frames' 64-bit keys (id || row) sorted in LDS
-// (compact_body.cuh's network), and the lookup of one side's sorted position in the other.  Its one caller is motion_group.cuh's join_compact,
-// which walks a side and compacts the survivors.  Device code only.  Internal.
+// motion_join.cuh -- the unique-id join of two frames for motion_3d.hip, motion_pnp.hip and motion_ba.hip: both frames' 64-bit keys (id || row) sorted in LDS
+// (compact_body.cuh's network), and the lookup of one side's sorted position in the other.  join_lookup's one caller is motion_group.cuh's join_compact,
+// which walks a side and compacts the survivors; join_find_unique is motion_ba.hip's, which looks a list of ids up in both frames.  Device code only.  Internal.
 #pragma once
 #include "compact_body.cuh"
 #include "motion_rule_common.h"
@@ -35,6 +35,21 @@ __device__ __forceinline__ bool join_lookup(const uint64_t* keys_a, int na, cons
     const uint64_t bk = keys_b[padded(lo)];
     row_b = (uint32_t)bk;
     return (uint32_t)(bk >> 32) == idk && (lo + 1 >= nb || (uint32_t)(keys_b[padded(lo + 1)] >> 32) != idk);
+}
+
+// The row of the id with key idk among a frame's n sorted keys; false unless the id occurs exactly once (motion_ba.hip looks up a list of ids
+// in both frames)
+__device__ __forceinline__ bool join_find_unique(const uint64_t* keys, int n, uint32_t idk, uint32_t& row) {
+    int lo = 0, hi = n;                                                // the first key whose id is not below
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((uint32_t)(keys[padded(mid)] >> 32) < idk) lo = mid + 1; else hi = mid;
+    }
+    row = 0;
+    if (lo >= n) return false;
+    const uint64_t k = keys[padded(lo)];
+    row = (uint32_t)k;
+    return (uint32_t)(k >> 32) == idk && (lo + 1 >= n || (uint32_t)(keys[padded(lo + 1)] >> 32) != idk);
 }
 
 }  // namespace lcd

@@ -13,7 +13,7 @@
 //   lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip),
 //   lcd_select_features and lcd_expand_word_ids (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip),
 //   lcd_keypoints_3d_stereo (keypoints_3d_stereo.hip),
-//   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip),
+//   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip), lcd_refine_motion_ba (motion_ba.hip),
 //   lcd_register_icp (register_icp.hip), lcd_register_icp_plane (register_icp_plane.hip) and lcd_filter_scans (scan_filter.hip).
 // Everything they write on the device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The
 // buffers only grow, and a growth frees the old allocation after the engine stream has drained (DevBuf::reserve): work of an earlier call
@@ -24,6 +24,7 @@ struct StatelessScratch {
     //   the matching calls: per pair the to-rows' 2-NN among the from-words, word ranks, candidate bit rows / the cross-check keys
     //   lcd_estimate_motion_3d: 36 bytes per from-row (six coordinate planes, d2, two index sets)
     //   lcd_estimate_motion_pnp: 44 bytes per to-row (eight coordinate planes, errors, two index sets)
+    //   lcd_refine_motion_ba: 68 bytes per to-row (a point's state: initial, current and saved estimate, two observations, flags, to-depth)
     //   lcd_register_icp: 20 bytes per row of either side (three coordinate planes, the nearest row, its d2)
     //   lcd_register_icp_plane: 32 bytes per row of either side (lcd_register_icp's 20 and three normal planes)
     //   lcd_filter_scans: 16 bytes per scan (the counts and the status between its launches), then 36 bytes per sampled row (three

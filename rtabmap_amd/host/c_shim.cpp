@@ -12,6 +12,7 @@
 #include "MemoryHip.h"
 #include "Motion2D.h"
 #include "Motion3D.h"
+#include "MotionBA.h"
 #include "RegistrationIcp.h"
 #include "ScanFilter.h"
 #include "Stereo.h"
@@ -530,6 +531,68 @@ int hmp_estimate(void* h, const int* idsA, const float* xyzA, int nA, const int*
     outCounts[0] = (int)matches.size(); outCounts[1] = (int)inliers.size();
     std::copy(matches.begin(), matches.end(), outMatches);
     std::copy(inliers.begin(), inliers.end(), outInliers);
+    return t.isNull() ? 0 : 1;
+}
+static lcd_camera shim_camera(const float* camera, const int* image, const float* local) {
+    lcd_camera cam = {};
+    cam.fx = camera[0]; cam.fy = camera[1]; cam.cx = camera[2]; cam.cy = camera[3]; cam.image_width = image[0]; cam.image_height = image[1];
+    cam.has_local_transform = local ? 1 : 0;
+    if (local) std::copy(local, local + 12, cam.local_transform);
+    return cam;
+}
+static MotionBAParams shim_ba_params(const double* params, int iterations, int minInliers) {
+    MotionBAParams p;
+    p.pixelVariance = params[0]; p.robustDelta = params[1]; p.baselineFrom = params[2]; p.baselineTo = params[3];
+    p.maxInliersMeanDistance = (float)params[4]; p.minInliersDistribution = (float)params[5];
+    p.iterations = iterations; p.minInliers = minInliers;
+    return p;
+}
+// motion_ba_cpu (no engine involved).  cameras as hmp_cpu's, one per side; fromPoints, toXyz, priorVariance[2], the locals may be null;
+// params[6] = pixelVariance, robustDelta, baselineFrom, baselineTo, maxInliersMeanDistance, minInliersDistribution.  outTransform[12],
+// outInts[4] = status, inliers, outliers, accepted steps; outChi2[2]; outGates[2] = mean distance, distribution; outInliers holds nTo ids.
+// 1 = done, 0 = refused
+int hmba_cpu(const int* fromIds, const float* fromXyz, const float* fromPoints, int nFrom, const int* toIds, const float* toPoints, const float* toXyz, int nTo,
+             const int* inliers, int nInliers, const float* transform, const double* priorVariance, const float* cameraFrom, const int* imageFrom,
+             const float* localFrom, const float* cameraTo, const int* imageTo, const float* localTo, const double* params, int iterations, int minInliers,
+             float* outTransform, int* outInts, double* outChi2, float* outGates, int* outInliers) {
+    MotionBAResult r;
+    if (!motion_ba_cpu(fromIds, fromXyz, fromPoints, nFrom, toIds, toPoints, toXyz, nTo, inliers, nInliers, transform, priorVariance,
+                       shim_camera(cameraFrom, imageFrom, localFrom), shim_camera(cameraTo, imageTo, localTo), shim_ba_params(params, iterations, minInliers), r))
+        return 0;
+    std::copy(r.transform, r.transform + 12, outTransform);
+    outInts[0] = r.status; outInts[1] = (int)r.inliers.size(); outInts[2] = r.nOutliers; outInts[3] = r.lmAccepted;
+    outChi2[0] = r.chi2Before; outChi2[1] = r.chi2After;
+    outGates[0] = r.inliersMeanDistance; outGates[1] = r.inliersDistribution;
+    std::copy(r.inliers.begin(), r.inliers.end(), outInliers);
+    return 1;
+}
+// MotionBA::refine through the dictionary's engine, the frames as parallel arrays (pointsA and xyzB may be null); variance[2] = linear, the
+// cosine, as the PnP left them.  inliers: nInliers ids in, the survivors out; outInts[2] = status, survivors.  Returns 1 with a transform
+int hmba_refine(void* h, const int* idsA, const float* xyzA, const float* pointsA, int nA, const int* idsB, const float* pointsB, const float* xyzB, int nB,
+                int* inliers, int nInliers, const float* transform, int varianceKind, const double* variance, const float* cameraFrom, const int* imageFrom,
+                const float* localFrom, const float* cameraTo, const int* imageTo, const float* localTo, const double* params, int iterations, int minInliers,
+                float* outTransform, int* outInts, float* outGates) {
+    std::multimap<int, Point3f> a3, b3;
+    std::multimap<int, Point2f> a2, b2;
+    for (int i = 0; i < nA; ++i) {
+        a3.insert(std::make_pair(idsA[i], Point3f{xyzA[3 * i], xyzA[3 * i + 1], xyzA[3 * i + 2]}));
+        if (pointsA) a2.insert(std::make_pair(idsA[i], Point2f{pointsA[2 * i], pointsA[2 * i + 1]}));
+    }
+    for (int i = 0; i < nB; ++i) {
+        b2.insert(std::make_pair(idsB[i], Point2f{pointsB[2 * i], pointsB[2 * i + 1]}));
+        if (xyzB) b3.insert(std::make_pair(idsB[i], Point3f{xyzB[3 * i], xyzB[3 * i + 1], xyzB[3 * i + 2]}));
+    }
+    Transform3D t0;
+    std::copy(transform, transform + 12, t0.data);
+    std::vector<int> in(inliers, inliers + nInliers);
+    MotionBAInfo info;
+    const Transform3D t = MotionBA::refine(((VWDictionaryHip*)h)->engine(), a3, a2, b2, b3, shim_camera(cameraFrom, imageFrom, localFrom),
+                                           shim_camera(cameraTo, imageTo, localTo), t0, in, varianceKind, variance[0], variance[1],
+                                           shim_ba_params(params, iterations, minInliers), &info);
+    std::copy(t.data, t.data + 12, outTransform);
+    std::copy(in.begin(), in.end(), inliers);
+    outInts[0] = info.status; outInts[1] = (int)in.size();
+    outGates[0] = info.inliersMeanDistance; outGates[1] = info.inliersDistribution;
     return t.isNull() ? 0 : 1;
 }
 const char* hmem_select_error(void* h) { return ((MemoryHip*)h)->lastSelectError().c_str(); }

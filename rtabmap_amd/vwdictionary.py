@@ -82,6 +82,8 @@ def lib():
         L.hm3_cpu.argtypes = [vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, ci, vp, vp, vp, vp, vp]
         L.hm3_estimate.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, ci, C.c_uint, vp, vp, vp, vp, vp]
         L.hmp_cpu.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, C.c_double, ci, ci, cf, C.c_uint, ci, vp, vp, vp, vp, vp]
+        L.hmba_cpu.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        L.hmba_refine.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
         L.hmp_estimate.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, C.c_double, ci, ci, cf, C.c_uint, vp, vp, vp, vp, vp]
         L.hicp_cpu.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, C.c_double, cf, cf, ci, ci, vp, vp, vp, vp, vp]
         L.hicp_cells.argtypes = [vp, ci, C.c_double, vp]
@@ -473,6 +475,51 @@ def motion_pnp_cpu(from_ids, from_xyz, to_ids, to_points, to_xyz=None, camera=(5
                 inliers=oi[:sc[2]].copy())
 
 
+def _ba_camera(camera):
+    """a camera dict(fx, fy, cx, cy[, image_width, image_height, local_transform]) as the shim's three arrays"""
+    cam = np.array([camera["fx"], camera["fy"], camera["cx"], camera["cy"]], np.float32)
+    img = np.array([camera.get("image_width", 0), camera.get("image_height", 0)], np.int32)
+    loc = camera.get("local_transform")
+    return cam, img, None if loc is None else np.ascontiguousarray(loc, dtype=np.float32).reshape(12)
+
+
+def _ba_params(pixel_variance, robust_delta, baselines, max_inliers_mean_distance, min_inliers_distribution):
+    return np.array([pixel_variance, robust_delta, baselines[0], baselines[1], max_inliers_mean_distance, min_inliers_distribution], np.float64)
+
+
+DEFAULT_CAMERA = dict(fx=525.0, fy=525.0, cx=319.5, cy=239.5)
+
+
+def motion_ba_cpu(from_ids, from_xyz, to_ids, to_points, inliers, transform, from_points=None, to_xyz=None, prior_variance=None, camera_from=DEFAULT_CAMERA,
+                  camera_to=DEFAULT_CAMERA, baselines=(0.075, 0.075), n_inliers=None, min_inliers=20, iterations=20, pixel_variance=1.0, robust_delta=8.0,
+                  max_inliers_mean_distance=0.0, min_inliers_distribution=0.0):
+    """the rule of lcd_refine_motion_ba on the CPU (host/MotionBA.cpp, no device) -> dict(transform [12], status, n_outliers, lm_accepted,
+    chi2_before, chi2_after, inliers_mean_distance, inliers_distribution, inliers), or None where the call is refused.  n_inliers: the
+    count that goes with `inliers` when it is not their number (the device's out_n_inliers)."""
+    fi, fx = _frame_arrays(from_ids, from_xyz)
+    ti, tp, tx, _, _, _, _ = _pnp_arrays(to_ids, to_points, to_xyz, (0, 0, 0, 0), (0, 0), None, None)
+    fp = None if from_points is None else np.ascontiguousarray(from_points, dtype=np.float32).reshape(-1, 2)
+    if fi.shape[0] > 8192 or ti.shape[0] > 8192:
+        return None
+    n = max(ti.shape[0], 1)
+    il = np.zeros(n, np.int32)
+    given = np.ascontiguousarray(inliers, dtype=np.int32).reshape(-1)[:n]
+    il[:given.shape[0]] = given
+    count = given.shape[0] if n_inliers is None else int(n_inliers)
+    tr = np.ascontiguousarray(transform, dtype=np.float32).reshape(12)
+    pv = None if prior_variance is None else np.ascontiguousarray(prior_variance, dtype=np.float64).reshape(2)
+    cf, imf, lf = _ba_camera(camera_from)
+    ct, imt, lt = _ba_camera(camera_to)
+    prm = _ba_params(pixel_variance, robust_delta, baselines, max_inliers_mean_distance, min_inliers_distribution)
+    t, ints, chi, gates, oi = np.zeros(12, np.float32), np.zeros(4, np.int32), np.zeros(2, np.float64), np.zeros(2, np.float32), np.zeros(n, np.int32)
+    ok = lib().hmba_cpu(_p(fi), _p(fx), _pn(fp), fi.shape[0], _p(ti), _p(tp), _pn(tx), ti.shape[0], _p(il), count, _p(tr), _pn(pv), _p(cf), _p(imf), _pn(lf),
+                        _p(ct), _p(imt), _pn(lt), _p(prm), int(iterations), int(min_inliers), _p(t), _p(ints), _p(chi), _p(gates), _p(oi))
+    if not ok:
+        return None
+    return dict(transform=t, status=int(ints[0]), n_outliers=int(ints[2]), lm_accepted=int(ints[3]), chi2_before=chi[0], chi2_after=chi[1],
+                inliers_mean_distance=gates[0], inliers_distribution=gates[1], inliers=oi[:ints[1]].copy())
+
+
 class VWDictionaryHip:
     def __init__(self, strategy=kNNBruteForceHIP, incremental=True, nndr=0.8, new_words_compared_together=True,
                  dictionary_path="", device=0, _handle=None, _owner=None):
@@ -567,6 +614,31 @@ class VWDictionaryHip:
                                 int(min_inliers), int(iterations), float(reproj_error), int(refine_iterations), int(variance_median_ratio),
                                 float(max_variance), int(seed) & 0xFFFFFFFF, _p(t), _p(cov), _p(counts), _p(om), _p(oi))
         return (t if ok else None), cov.reshape(6, 6), om[:counts[0]].tolist(), oi[:counts[1]].tolist()
+
+    def refine_motion_ba(self, words3a, kpts_b, inliers, transform, kpts_a=None, words3b=None, variance_kind=0, variance_lin=1.0, angle_cos=1.0,
+                         camera_from=DEFAULT_CAMERA, camera_to=DEFAULT_CAMERA, baselines=(0.075, 0.075), min_inliers=20, iterations=20, pixel_variance=1.0,
+                         robust_delta=8.0, max_inliers_mean_distance=0.0, min_inliers_distribution=0.0):
+        """MotionBA::refine (RegistrationVis.cpp:1873-2188, Vis/BundleAdjustment = 1) over this dictionary's long-lived engine handle: the
+        transform, the inliers and the covariance's inputs as estimate_motion_pnp's call left them; words3a is (word ids, [n x 3] points),
+        kpts_b (word ids, [n x 2] keypoints), kpts_a None or the [n x 2] keypoints of words3a's rows, words3b None or the [n x 3] points of
+        kpts_b's rows.  -> (transform [12] or None, surviving inliers, info dict(status, inliers_mean_distance, inliers_distribution))"""
+        ia, xa = _frame_arrays(*words3a)
+        ib, pb, xb, _, _, _, _ = _pnp_arrays(kpts_b[0], kpts_b[1], words3b, (0, 0, 0, 0), (0, 0), None, None)
+        pa = None if kpts_a is None else np.ascontiguousarray(kpts_a, dtype=np.float32).reshape(-1, 2)
+        il = np.ascontiguousarray(inliers, dtype=np.int32).reshape(-1).copy()
+        buf = np.zeros(max(il.shape[0], 1), np.int32)
+        buf[:il.shape[0]] = il
+        tr = np.ascontiguousarray(transform, dtype=np.float32).reshape(12)
+        cf, imf, lf = _ba_camera(camera_from)
+        ct, imt, lt = _ba_camera(camera_to)
+        prm = _ba_params(pixel_variance, robust_delta, baselines, max_inliers_mean_distance, min_inliers_distribution)
+        var = np.array([variance_lin, angle_cos], np.float64)
+        t, ints, gates = np.zeros(12, np.float32), np.zeros(2, np.int32), np.zeros(2, np.float32)
+        ok = lib().hmba_refine(self.h, _p(ia), _p(xa), _pn(pa), ia.shape[0], _p(ib), _p(pb), _pn(xb), ib.shape[0], _p(buf), il.shape[0], _p(tr),
+                               int(variance_kind), _p(var), _p(cf), _p(imf), _pn(lf), _p(ct), _p(imt), _pn(lt), _p(prm), int(iterations), int(min_inliers),
+                               _p(t), _p(ints), _p(gates))
+        return (t if ok else None), buf[:ints[1]].tolist(), dict(status=int(ints[0]), inliers_mean_distance=float(gates[0]),
+                                                                  inliers_distribution=float(gates[1]))
 
     def register_icp(self, from_scan, to_scan, guess=None, max_laser_scans=0, max_iterations=30, force_3dof=False, max_correspondence_distance=0.1,
                      epsilon=0.0, correspondence_ratio=0.1, max_translation=0.2, max_rotation=0.78):
