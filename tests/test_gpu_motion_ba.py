@@ -27,14 +27,24 @@ def model_of(pair, from_points, to_xyz, prior, baselines, **kw):
     return _model_cache[key][1]
 
 
+def rows_of(v, n):
+    """[n x 2] float64 of one tuple for every pair or of a row per pair; None stays None"""
+    if v is None:
+        return None
+    a = np.asarray(v, np.float64)
+    return np.tile(a, (n, 1)) if a.ndim == 1 else a.reshape(n, 2).copy()
+
+
 def expected(pairs, from_points=True, to_xyz=True, prior=None, baselines=None, **kw):
-    """the model's results laid out as the call lays its outputs out; prior / baselines: one tuple for every pair"""
+    """the model's results laid out as the call lays its outputs out; prior / baselines: one tuple for every pair, or [n x 2] rows"""
     n = len(pairs)
+    prior, baselines = rows_of(prior, n), rows_of(baselines, n)
+    row = lambda rows, k: None if rows is None else tuple(float(v) for v in rows[k])
     out = dict(transform=np.zeros((n, 12), np.float32), status=np.zeros(n, np.int32), n_inliers=np.zeros(n, np.int32), n_outliers=np.zeros(n, np.int32),
                chi2_before=np.zeros(n, np.float64), chi2_after=np.zeros(n, np.float64), lm_accepted=np.zeros(n, np.int32),
                inliers_mean_distance=np.zeros(n, np.float32), inliers_distribution=np.zeros(n, np.float32), inliers=[])
     for k, p in enumerate(pairs):
-        r = model_of(p, from_points, to_xyz, prior, baselines, **kw)
+        r = model_of(p, from_points, to_xyz, row(prior, k), row(baselines, k), **kw)
         for name in PER_PAIR:
             if name != "n_inliers":
                 out[name][k] = r[name]
@@ -55,11 +65,11 @@ def assert_same(got, want, what=""):
 
 def call_kw(n, prior, baselines, kw):
     k = dict(kw)
-    k["prior_variance"] = None if prior is None else np.tile(np.asarray(prior, np.float64), (n, 1))
+    k["prior_variance"] = rows_of(prior, n)
     if baselines is None:
         k["default_baseline"] = I.BASELINE
     else:
-        k["baselines"] = np.tile(np.asarray(baselines, np.float64), (n, 1))
+        k["baselines"] = rows_of(baselines, n)
     return k
 
 

@@ -14,6 +14,8 @@ import motion_ba_model as M
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # Measured on I.accuracy_pairs(): the largest entry difference between ba64's own float32 and float64 runs, over the twelve pairs
 RECORDED_NOISE = 6.148e-06
+# Measured on I.two_camera_accuracy_pairs(): the same figure over the twelve two-camera pairs, the yardstick's BLAS on one thread
+RECORDED_TWO_CAMERA_NOISE = 5.665e-06
 SANITIZER_CASES = 148                                                      # tools/sanitize_motion_ba.cpp prints "ok 148"
 
 
@@ -62,6 +64,40 @@ def test_the_mirror_equals_the_model_on_every_status():
     assert both(pairs[0], iterations=0, **I.STATUS_KW)["transform"].tobytes() == pairs[0]["transform"].tobytes()
     for n in (-1, pairs[0]["to_ids"].shape[0] + 1):
         assert both(dict(pairs[0], n_inliers=n))["status"] == M.BAD_INLIER
+
+
+TWO_KW = dict(baselines=I.TWO_BASELINES, prior_variance=(1e-4, 4e-4))
+GATES_ON = dict(max_inliers_mean_distance=100.0, min_inliers_distribution=1e-4)
+
+
+def shape_runs(group):
+    """[(pair, keyword arguments)] of one group of tests/test_gpu_motion_ba_shapes.py's inputs"""
+    if group == "two_cameras":
+        return [(p, kw) for p in I.two_camera_batch() for kw in (TWO_KW, dict(TWO_KW, **GATES_ON), dict(TWO_KW, from_points=False, to_xyz=False, robust_delta=0.0))]
+    if group == "extreme_ids":
+        return [(p, {}) for p, _ in I.extreme_id_pairs().values()]
+    if group == "to_points":
+        return [(p, I.GATES_KW) for p in [I.to_edge_pair(kind) for kind in I.TO_EDGE_KINDS] + [I.no_finite_to_pair(), I.far_narrow_pair()]] + \
+            [(I.no_finite_to_pair(), dict(max_inliers_mean_distance=0.5))]
+    if group == "gate_cameras":
+        return [(p, dict(I.GATES_KW, baselines=I.TWO_BASELINES)) for p in I.gate_camera_pairs()]
+    if group == "per_pair":
+        pairs = I.many_pairs()
+        rows = I.per_pair_kw(pairs * 3, period=I.MANY_PERIOD)
+        return [(p, dict(prior_variance=tuple(rows["prior"][k]), baselines=tuple(rows["baselines"][k]))) for k, p in enumerate(pairs * 3)]
+    if group == "staging":
+        return [(p, {}) for p in I.staging_pairs() + [I.wide_pair(), I.nine_row_pair()]]
+    assert group == "iterations"
+    return [(p, dict(iterations=it, prior_variance=(1e-4, 4e-4))) for p in I.count_pairs()[3:6] for it in (1, 6)]
+
+
+@pytest.mark.parametrize("group", ("two_cameras", "extreme_ids", "to_points", "gate_cameras", "per_pair", "staging", "iterations"))
+def test_the_mirror_equals_the_model_on_the_shape_inputs(group):
+    """every input of tests/test_gpu_motion_ba_shapes.py: the mirror keeps the two sides apart in the same places as the kernel"""
+    runs = shape_runs(group)
+    assert runs
+    for p, kw in runs:
+        both(p, **kw)
 
 
 REFUSALS = (dict(iterations=-1), dict(iterations=65536), dict(min_inliers=-1), dict(pixel_variance=0.0), dict(pixel_variance=-1.0),
@@ -126,5 +162,44 @@ def test_the_rule_is_as_accurate_as_the_yardstick_allows():
     print("noise %.4g" % noise)
     assert len(kept) >= 11                                                 # at most 10 % of twelve left out
     assert 0.5 * RECORDED_NOISE <= noise <= 1.25 * RECORDED_NOISE
+    for m, err in kept:
+        assert err <= 4 * noise, (m, err, noise)
+
+
+def test_the_rule_is_as_accurate_as_the_yardstick_allows_between_two_cameras():
+    """The test above on I.two_camera_accuracy_pairs(): its sizes and recipe, two different cameras, baselines 0.12 / 0.075, the local
+    transform on the to side, the from side and on none in turn.  The noise is the largest entry difference between ba64's own float32 and
+    float64 runs over the pairs that are kept, the bound on every kept pair 4 x that; a pair whose outlier set differs between the
+    yardstick's two runs is left out, at most 10 %.  The yardstick runs with its BLAS on one thread: its float32 run ends a stage when no
+    halving lowers the objective any more, which on the pairs of 100 inliers and more depends on how lstsq's sums are split among threads
+    (the 300-inlier pair: 1.6e-7 on one thread, 1.0e-6 on eight, 6.2e-6 on sixteen), so that the figure would be another one on every
+    machine.  Measured: none is left out, the noise is 5.665e-6 (per pair 1.6e-7 .. 5.7e-6), the rule's largest difference
+    4.74e-6 (per pair 4.8e-8 .. 4.7e-6), and the rule flags the yardstick's set on every pair.  Twelve pairs, not six: the noise is the
+    largest of a figure that spreads over a factor of 25 from pair to pair, and six pairs of the same seed (60, 84, 128, 160, 220, 300
+    inliers) measured 3.7e-7 on eight threads."""
+    from threadpoolctl import threadpool_limits
+    kept, noise = [], 0.0
+    pairs = I.two_camera_accuracy_pairs()
+    assert len(pairs) == 12 and min(p["m"] for p in pairs) == 60 and max(p["m"] for p in pairs) == 300
+    assert [p["local_side"] for p in pairs] == list(I.LOCAL_SIDES) * 4
+    for p in pairs:
+        a, k = I.args(p, prior_variance=I.ACCURACY_PRIOR, baselines=I.TWO_BASELINES)
+        assert k["camera_from"]["fx"] != k["camera_to"]["fx"] and len(p["planted"]) == max(2, p["m"] // 40)
+        yk = {name: k[name] for name in ("from_points", "to_xyz", "prior_variance", "camera_from", "camera_to", "baselines")}
+        with threadpool_limits(limits=1, user_api="blas"):
+            y64, y32 = M.ba64(*a, dtype=np.float64, **yk), M.ba64(*a, dtype=np.float32, **yk)
+        if y64["outliers"] != y32["outliers"]:
+            continue
+        r = M.refine(*a, **k)
+        assert r["status"] == M.OK
+        own = float(np.abs(y32["transform"].astype(np.float64) - y64["transform"]).max())
+        err = float(np.abs(r["transform"].astype(np.float64) - y64["transform"]).max())
+        print("%d inliers, local transform on %s: yardstick float32 - float64 %.3g, rule - float64 %.3g, same outliers %s" %
+              (p["m"], p["local_side"], own, err, sorted(y64["outliers"]) == sorted(np.flatnonzero(~np.isin(p["inliers"], r["inliers"])).tolist())))
+        noise = max(noise, own)
+        kept.append((p["m"], err))
+    print("noise %.4g" % noise)
+    assert len(kept) >= 11                                                 # at most 10 % of twelve left out
+    assert 0.5 * RECORDED_TWO_CAMERA_NOISE <= noise <= 1.25 * RECORDED_TWO_CAMERA_NOISE
     for m, err in kept:
         assert err <= 4 * noise, (m, err, noise)
