@@ -1061,7 +1061,7 @@ int lcd_estimate_motion_pnp_dev(lcd_engine* h, const lcd_motion_pnp_args* a);
  * Precision: the 27 sums and the 6 x 6 solve are fp32, as lcd_estimate_motion_pnp's and lcd_register_icp_plane's.
  * Out of scope: multi-camera rigs (cameraIndex is 0), Reg/Force3DoF (the plane prior) and gravity links, cvsba and Ceres
  * (Vis/BundleAdjustment 2 and 3), full 6 x 6 priors, handing back the refined points (the reference discards them too), lens distortion,
- * the epipolar estimation type.
+ * the epipolar estimation type (Vis/EstimationType = 2; the hypothesis check of VhEp/Enabled is lcd_verify_epipolar, below).
  *
  * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on a side of a pair,
  * n_pairs > 65535, iterations > 65535 or a handle of a sharded vocabulary: LCD_ERR_UNSUPPORTED; iterations < 0, min_inliers < 0, a pixel_variance that is not
@@ -1121,6 +1121,91 @@ int lcd_refine_motion_ba(lcd_engine* h, const lcd_motion_ba_args* a);
  * nothing read back; offsets, cameras, prior_variance and baselines on the HOST (read during the call); enqueued on the engine stream, not
  * synchronised */
 int lcd_refine_motion_ba_dev(lcd_engine* h, const lcd_motion_ba_args* a);
+
+/* ---- Epipolar hypothesis check, stateless: the one geometric verification of the appearance-only mode, EpipolarGeometry::check
+ * (EpipolarGeometry.cpp:65-102, :298-379) as Rtabmap::process calls it under VhEp/Enabled (Rtabmap.cpp:2193): the unique word pairs of two
+ * signatures, a fundamental matrix by RANSAC over their keypoints, accepted with at least VhEp/MatchCountMin inliers.  What is in the
+ * reference tree is reproduced exactly: the pairing, the thresholds, the accept rule, the parameter meanings, and "more than 7" of
+ * util3d::extractXYZCorrespondencesRANSAC (util3d_correspondences.cpp:85).  cv::findFundamentalMat is not in the tree: the estimator is the
+ * ENGINE'S rule, written out here.  No parity with an OpenCV build is claimed.  Stateless exactly as lcd_estimate_motion_pnp; pair i owns the
+ * rows [from_offsets[i], from_offsets[i+1]) of the from-arrays and [to_offsets[i], to_offsets[i+1]) of the to-arrays.
+ *
+ * The rule, per pair.  fp32, every operation rounded on its own (nothing fused), IEEE division and square root, only + - x / sqrt.  SUM and
+ * mix are those of lcd_estimate_motion_3d (steps 3 and 4 there).  rtabmap_amd/csrc/epipolar_rule.h is the normative order of operations.
+ *   1. Pairs (EpipolarGeometry.h:158-186, findPairsUnique with ignoreNegativeIds).  A word id takes part iff it is >= 0 and occurs exactly
+ *      once in `from` and exactly once in `to`; the correspondences in ascending id, m their number.  Keypoints are not tested for
+ *      finiteness here; a NaN is never an inlier later.  m < match_count_min (:77), or m < 8: LCD_EPI_FEW_PAIRS, nothing is estimated.
+ *      (OpenCV with exactly seven points runs its solver once; with the default VhEp/MatchCountMin = 8 the two never differ.)
+ *   2. Normalisation, once per pair over all m correspondences, per image: centroid (cx, cy) = (SUM(u), SUM(v)) / float(m); d = SUM(sqrt((u -
+ *      cx)^2 + (v - cy)^2)) / float(m); s = 1.41421356f / d; T = [s 0 -(s cx); 0 s -(s cy); 0 0 1]; a normalised coordinate is (s u) + T_02.
+ *      A d that is 0 or not finite in either image: LCD_EPI_NO_MODEL.
+ *   3. Hypothesis h = 0 .. iterations - 1: seven distinct indices, draw k = mix(mix(seed + h) * 8 + k) % m, k = 0, 1, .., a draw equal to an
+ *      earlier kept one skipped, invalid after 32 draws.  The 7 x 9 matrix has the rows (x'x, x'y, x', y'x, y'y, y', x, y, 1) in normalised
+ *      coordinates, x of `from`, x' of `to`.  Gauss-Jordan elimination with complete pivoting: in step k the pivot is the entry of largest
+ *      magnitude in rows k .., columns k .. (the lowest row, then the lowest column on ties; a NaN is never chosen); row and column are
+ *      exchanged with row and column k; a pivot that is 0 or not finite makes the sample invalid; the pivot row's entries behind the pivot
+ *      are divided by it, and every other row r gets A_rc - (A_rk A_kc), element by element.  The two null vectors F1 and F2 have the free
+ *      columns set to (1, 0) and (0, 1), the others the negated entries of the two remaining columns, put back into the columns' own order.
+ *      det(x F1 + F2) = c3 x^3 + c2 x^2 + c1 x + c0 from four determinants: c0 = det F2, c3 = det F1, c2 = 0.5 (det(F1 + F2) + det(F2 -
+ *      F1)) - c0, c1 = 0.5 (det(F1 + F2) - det(F2 - F1)) - c3; det M = ((M0 (M4 M8 - M5 M7)) - (M1 (M3 M8 - M5 M6))) + (M2 (M3 M7 - M4 M6)).
+ *      c3 == 0 or a coefficient that is not finite: invalid.  Real roots as lcd_estimate_motion_pnp finds its quartic's: B = 1 + max |c_i /
+ *      c3| (not finite: invalid); the breakpoints k1 <= k2 are the closed-form roots of the derivative when its discriminant (2 c2)^2 - 4 ((3
+ *      c3) c1) is > 0, clamped to [-B, B] (a NaN to B), otherwise both are B; the brackets [-B, k1], [k1, k2], [k2, B]; a bracket holds a
+ *      root iff (p(lo) < 0) != (p(hi) < 0) (Horner from c3), found by LCD_EPI_BISECT halvings and then the middle of what is left.
+ *      Candidate c = 3 h + r is the r-th root found, in the brackets' order, with F^ = (x F1) + F2; an absent root: an invalid candidate.
+ *      F = T'^T (F^ T): first G = F^ T with G_r2 = ((F^_r0 T_02) + (F^_r1 T_12)) + F^_r2, then T'^T G alike.
+ *   4. Error and inlier.  l' = F (u, v, 1), l = F^T (u', v', 1), each component ((a u) + (b v)) + c; e = max((p'.l')^2 / (l'_x^2 + l'_y^2),
+ *      (p.l)^2 / (l_x^2 + l_y^2)); an inlier iff both quotients are <= float(thr) * float(thr) (a NaN is no inlier).  thr is
+ *      VhEp/RansacParam1, in pixels.
+ *   5. Winner.  The candidate with most inliers wins, the lowest candidate on ties.  All candidates are scored: there is no adaptive stop,
+ *      so VhEp/RansacParam2 (the confidence) has no effect on the device; the host mirror keeps the parameter and passes iterations = 1000,
+ *      OpenCV's cap for this method.  A best count of 0: LCD_EPI_NO_MODEL.  As in current OpenCV the winning sample's matrix is the result;
+ *      there is no refit over the inliers.
+ *   6. Result.  inliers >= match_count_min: LCD_EPI_OK, otherwise LCD_EPI_FEW_INLIERS (:91-96).  In the pair's TO-region of out_matches the
+ *      ids of all pairs ascending, of out_inliers the inliers' ids in correspondence order, the rest of both 0.  out_fundamental: the
+ *      winner's F divided by its Frobenius norm (the squares added in index order), negated when its largest-magnitude entry (the lowest
+ *      index on ties) is negative; nine zeros mean no model.
+ * Out of scope: Vis/EstimationType = 2 (util3d::generateWords3DMono: the five-point essential matrix, recoverPose, the scale from words3 --
+ * its solver in the reference tree is a generated coefficient matrix that cannot be taken over), findEpipolesFromF, findPFromE and the
+ * triangulations, LMedS, lens distortion, sharded handles.
+ *
+ * Limits and errors -- after each of them nothing was written and the handle stays usable: more than 8192 rows on a side of a pair,
+ * n_pairs > 65535, iterations > 65535 or a handle of a sharded vocabulary: LCD_ERR_UNSUPPORTED; iterations < 1, a ransac_threshold whose
+ * float or its square is not finite and > 0, match_count_min < 1, n_pairs < 0, offsets that are missing, do not start at 0 or decrease, a
+ * NULL pointer where rows or outputs exist (out_fundamental, out_matches and out_inliers may be NULL), or a wrong struct_size:
+ * LCD_ERR_INVALID.  n_pairs == 0 returns LCD_OK.  One kernel launch per call whatever the batch: one workgroup of 256 threads per pair. */
+#define LCD_EPI_BISECT 26
+enum lcd_epipolar_status {
+    LCD_EPI_OK = 0,
+    LCD_EPI_FEW_PAIRS = 1,            /* m < match_count_min, or m < 8 */
+    LCD_EPI_NO_MODEL = 2,             /* a degenerate normalisation, or no candidate with an inlier */
+    LCD_EPI_FEW_INLIERS = 3           /* inliers and matrix returned, fewer than match_count_min */
+};
+typedef struct lcd_epipolar_args {
+    int32_t struct_size;            /* sizeof(lcd_epipolar_args) */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t match_count_min;        /* VhEp/MatchCountMin, >= 1 */
+    int32_t iterations;             /* 1 .. 65535 */
+    uint32_t seed;
+    double ransac_threshold;        /* VhEp/RansacParam1, pixels, finite, > 0 */
+    const int32_t* from_word_ids;   /* [Nf] */
+    const float* from_points;       /* [Nf x 2] cv::KeyPoint::pt, the layout lcd_keypoints_3d writes as out_points */
+    const int32_t* to_word_ids;     /* [Nt] */
+    const float* to_points;         /* [Nt x 2] */
+    const int64_t* from_offsets;    /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    const int64_t* to_offsets;      /* HOST, [n_pairs + 1] */
+    float* out_fundamental;         /* [n_pairs x 9], row-major; may be NULL */
+    int32_t* out_status;            /* [n_pairs], lcd_epipolar_status */
+    int32_t* out_n_pairs;           /* [n_pairs] */
+    int32_t* out_n_inliers;         /* [n_pairs] */
+    int32_t* out_matches;           /* [Nt]; may be NULL */
+    int32_t* out_inliers;           /* [Nt]; may be NULL */
+} lcd_epipolar_args;
+/* every pointer on the HOST; synchronises the engine stream */
+int lcd_verify_epipolar(lcd_engine* h, const lcd_epipolar_args* a);
+/* ids, points and out_* in DEVICE memory (4-byte aligned), the offsets on the HOST (read during the call): the outputs of
+ * lcd_select_features / lcd_keypoints_3d go in where they lie; enqueued on the engine stream, not synchronised */
+int lcd_verify_epipolar_dev(lcd_engine* h, const lcd_epipolar_args* a);
 
 /* ---- Scan registration (point-to-point ICP), stateless: the other half of the registration step, Reg/Strategy = 1 (ICP) and 2 (visual, then
  * ICP), for a caller who holds both laser scans in device memory.  RegistrationIcp::computeTransformationImpl, the point-to-point branch

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liblcd_hip.so")
-SOURCES = ["knn2_kernels.hip", "knn_mfma_kernels.hip", "knn_hamming_mfma.hip", "resolve_kernels.hip", "tfidf.hip", "similarity.hip", "global_similarity.hip","postings_keys.hip", "bayes.hip", "engine.hip", "frame_pipeline.hip", "pair_match.hip", "guided_match.hip", "feature_select.hip", "keypoints_3d.hip", "keypoints_3d_stereo.hip", "motion_3d.hip", "motion_pnp.hip", "motion_ba.hip", "register_icp.hip", "register_icp_plane.hip", "scan_filter.hip"]
+SOURCES = ["knn2_kernels.hip", "knn_mfma_kernels.hip", "knn_hamming_mfma.hip", "resolve_kernels.hip", "tfidf.hip", "similarity.hip", "global_similarity.hip","postings_keys.hip", "bayes.hip", "engine.hip", "frame_pipeline.hip", "pair_match.hip", "guided_match.hip", "feature_select.hip", "keypoints_3d.hip", "keypoints_3d_stereo.hip", "motion_3d.hip", "motion_pnp.hip", "motion_ba.hip", "register_icp.hip", "register_icp_plane.hip", "scan_filter.hip", "epipolar.hip"]
 # -ffp-contract=off: the L2 distance must round every product and sum like the reference (no FMA contraction)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          # MFMA results straight into VGPRs: the top-3 epilogue of knn_mfma_filter_kernel reads them with VALU, and an
@@ -80,7 +80,7 @@ def _build_locked(verbose):
 
 
 HOST_OUT = os.path.join(HERE, "liblcd_host.so")
-HOST_SOURCES = ["VWDictionaryHip.cpp", "FeatureSelect.cpp", "Keypoints3D.cpp", "Stereo.cpp", "Motion3D.cpp", "Motion2D.cpp", "MotionBA.cpp", "RegistrationIcp.cpp", "ScanFilter.cpp", "MemoryHip.cpp", "BayesFilterHip.cpp", "RtabmapHip.cpp", "DbLoaderHip.cpp", "c_shim.cpp"]
+HOST_SOURCES = ["VWDictionaryHip.cpp", "FeatureSelect.cpp", "Keypoints3D.cpp", "Stereo.cpp", "Motion3D.cpp", "Motion2D.cpp", "MotionBA.cpp", "EpipolarGeometryHip.cpp", "RegistrationIcp.cpp", "ScanFilter.cpp", "MemoryHip.cpp", "BayesFilterHip.cpp", "RtabmapHip.cpp", "DbLoaderHip.cpp", "c_shim.cpp"]
 
 
 def build_host(force=False, verbose=False):

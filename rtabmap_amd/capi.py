@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_verify_epipolar", "lcd_verify_epipolar_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -233,6 +233,17 @@ class LcdMotionPnpArgs(C.Structure):
 LCD_PNP_OK, LCD_PNP_FEW_CORRESPONDENCES, LCD_PNP_NO_MODEL, LCD_PNP_BELOW_MIN_INLIERS, LCD_PNP_VARIANCE_REJECTED = 0, 1, 2, 3, 4  # lcd_motion_pnp_status
 
 
+class LcdEpipolarArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("match_count_min", C.c_int32), ("iterations", C.c_int32), ("seed", C.c_uint32),
+                ("ransac_threshold", C.c_double), ("from_word_ids", C.c_void_p), ("from_points", C.c_void_p), ("to_word_ids", C.c_void_p),
+                ("to_points", C.c_void_p), ("from_offsets", C.c_void_p), ("to_offsets", C.c_void_p), ("out_fundamental", C.c_void_p),
+                ("out_status", C.c_void_p), ("out_n_pairs", C.c_void_p), ("out_n_inliers", C.c_void_p), ("out_matches", C.c_void_p),
+                ("out_inliers", C.c_void_p)]
+
+
+LCD_EPI_OK, LCD_EPI_FEW_PAIRS, LCD_EPI_NO_MODEL, LCD_EPI_FEW_INLIERS = 0, 1, 2, 3  # lcd_epipolar_status
+
+
 class LcdMotionBaArgs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("min_inliers", C.c_int32), ("iterations", C.c_int32),
                 ("pixel_variance", C.c_double), ("robust_delta", C.c_double), ("default_baseline", C.c_double),
@@ -334,6 +345,8 @@ def load():
     L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_pnp.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
     L.lcd_estimate_motion_pnp_dev.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
+    L.lcd_verify_epipolar.argtypes = [vp, C.POINTER(LcdEpipolarArgs)]
+    L.lcd_verify_epipolar_dev.argtypes = [vp, C.POINTER(LcdEpipolarArgs)]
     L.lcd_refine_motion_ba.argtypes = [vp, C.POINTER(LcdMotionBaArgs)]
     L.lcd_refine_motion_ba_dev.argtypes = [vp, C.POINTER(LcdMotionBaArgs)]
     L.lcd_register_icp.argtypes = [vp, C.POINTER(LcdIcpArgs)]
@@ -974,6 +987,48 @@ class Engine:
         a.out_variance_lin, a.out_angle_cos, a.out_variance_kind = ptr(d_variance_lin), ptr(d_angle_cos), ptr(d_variance_kind)
         a.out_matches, a.out_inliers = ptr(d_matches), ptr(d_inliers)
         self._ck(self.L.lcd_estimate_motion_pnp_dev(self.h, C.byref(a)))
+
+    # ---- epipolar hypothesis check (stateless; include/lcd.h has the rule)
+    OUTPUTS_EPIPOLAR = ("fundamental", "status", "n_pairs", "n_inliers", "matches", "inliers")
+
+    def verify_epipolar(self, from_ids, from_points, from_offsets, to_ids, to_points, to_offsets, match_count_min=8, iterations=1000,
+                        ransac_threshold=3.0, seed=0, struct_size=None, leave_out=()):
+        """lcd_verify_epipolar over host arrays, all pairs concatenated -> dict(fundamental [n_pairs x 9], status, n_pairs, n_inliers [n_pairs],
+        matches [Nt], inliers [Nt]); outputs start as -1 / NaN so that what the call left alone shows; leave_out: names of outputs passed as NULL"""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fi, ti = np.ascontiguousarray(from_ids, dtype=np.int32).reshape(-1), np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
+        fp, tp = np.ascontiguousarray(from_points, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
+        n_pairs, n = (to if to is not None else fo).shape[0] - 1, ti.shape[0]
+        np1 = max(n_pairs, 1)
+        out = dict(fundamental=np.full((np1, 9), np.nan, np.float32), status=np.full(np1, -1, np.int32), n_pairs=np.full(np1, -1, np.int32),
+                   n_inliers=np.full(np1, -1, np.int32), matches=np.full(max(n, 1), -1, np.int32), inliers=np.full(max(n, 1), -1, np.int32))
+        a = LcdEpipolarArgs(C.sizeof(LcdEpipolarArgs) if struct_size is None else struct_size, n_pairs, int(match_count_min), int(iterations),
+                            int(seed) & 0xFFFFFFFF, float(ransac_threshold))
+        a.from_offsets, a.to_offsets = None if fo is None else fo.ctypes.data, None if to is None else to.ctypes.data
+        a.from_word_ids, a.from_points, a.to_word_ids, a.to_points = _p(fi), _p(fp), _p(ti), _p(tp)
+        for k in self.OUTPUTS_EPIPOLAR:
+            setattr(a, "out_" + k, None if k in leave_out else _p(out[k]))
+        self._ck(self.L.lcd_verify_epipolar(self.h, C.byref(a)))
+        for k in ("fundamental", "status", "n_pairs", "n_inliers"):
+            out[k] = out[k][:max(n_pairs, 0)]
+        out["matches"], out["inliers"] = out["matches"][:n], out["inliers"][:n]
+        return out
+
+    def verify_epipolar_dev(self, d_from_ids, d_from_points, from_offsets, d_to_ids, d_to_points, to_offsets, d_fundamental, d_status, d_n_pairs,
+                            d_n_inliers, d_matches, d_inliers, match_count_min=8, iterations=1000, ransac_threshold=3.0, seed=0):
+        """lcd_verify_epipolar_dev on torch tensors of the engine's device (the offsets stay on the host; d_fundamental, d_matches and d_inliers
+        may be None).  Enqueued, not synchronised."""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        n_pairs = (to if to is not None else fo).shape[0] - 1
+        a = LcdEpipolarArgs(C.sizeof(LcdEpipolarArgs), n_pairs, int(match_count_min), int(iterations), int(seed) & 0xFFFFFFFF, float(ransac_threshold))
+        a.from_offsets, a.to_offsets = None if fo is None else fo.ctypes.data, None if to is None else to.ctypes.data
+        a.from_word_ids, a.from_points, a.to_word_ids, a.to_points = ptr(d_from_ids), ptr(d_from_points), ptr(d_to_ids), ptr(d_to_points)
+        a.out_fundamental, a.out_status, a.out_n_pairs, a.out_n_inliers = ptr(d_fundamental), ptr(d_status), ptr(d_n_pairs), ptr(d_n_inliers)
+        a.out_matches, a.out_inliers = ptr(d_matches), ptr(d_inliers)
+        self._ck(self.L.lcd_verify_epipolar_dev(self.h, C.byref(a)))
 
     # ---- two-view bundle adjustment behind the motion estimate (stateless; include/lcd.h has the rule)
     def _ba_args(self, n_pairs, fo, to, cams_from, cams_to, prior_variance, baselines, min_inliers, iterations, pixel_variance, robust_delta,

@@ -9,11 +9,13 @@ namespace rtabmap_amd {
 
 RtabmapHip::RtabmapHip(const ParametersMap& parameters, int device)
     : _memory(new MemoryHip(parameters, device)), _bayesFilter(new BayesFilterHip(parameters)), _loopThr(0.11f), _loopRatio(0.0f),
-      _virtualPlaceLikelihoodRatio(0), _loopClosureHypothesis(0, 0.0f), _highestHypothesis(0, 0.0f), _lastLocationId(0) {
+      _virtualPlaceLikelihoodRatio(0), _verifyLoopClosureHypothesis(false), _epipolarGeometry(new EpipolarGeometryHip(parameters)),
+      _loopClosureHypothesis(0, 0.0f), _highestHypothesis(0, 0.0f), _lastLocationId(0) {
     this->parseParameters(parameters);   // Parameters.h:197-200 defaults above
 }
 
 RtabmapHip::~RtabmapHip() {
+    delete _epipolarGeometry;
     delete _bayesFilter;
     delete _memory;
 }
@@ -23,6 +25,8 @@ void RtabmapHip::parseParameters(const ParametersMap& parameters) {
     if ((it = parameters.find("Rtabmap/LoopThr")) != parameters.end()) _loopThr = uStr2Float(it->second);
     if ((it = parameters.find("Rtabmap/LoopRatio")) != parameters.end()) _loopRatio = uStr2Float(it->second);
     if ((it = parameters.find("Rtabmap/VirtualPlaceLikelihoodRatio")) != parameters.end()) _virtualPlaceLikelihoodRatio = atoi(it->second.c_str());
+    if ((it = parameters.find("VhEp/Enabled")) != parameters.end()) _verifyLoopClosureHypothesis = it->second == "true" || it->second == "1" || it->second == "True" || it->second == "TRUE";
+    _epipolarGeometry->parseParameters(parameters);
 }
 
 // Rtabmap::adjustLikelihood :5691-5757: the statistics, the rescaling and the virtual place's value are one device pass over the
@@ -42,7 +46,24 @@ void RtabmapHip::adjustLikelihood(std::map<int, float>& likelihood) const {
     for (std::map<int, float>::iterator i = likelihood.begin(); i != likelihood.end(); ++i, ++k) i->second = values[k];
 }
 
-bool RtabmapHip::process(const Mat& descriptors) {
+bool RtabmapHip::process(const Mat& descriptors) { return this->process(descriptors, nullptr); }
+
+bool RtabmapHip::process(const Mat& descriptors, const std::vector<float>& keypoints) {
+    if (keypoints.size() != (size_t)descriptors.rows * 2) {
+        fprintf(stderr, "[ERROR] process: one keypoint (x, y) per descriptor row\n");
+        return false;
+    }
+    return this->process(descriptors, &keypoints);
+}
+
+// EpipolarGeometry::check (Rtabmap.cpp:2193) on the words the two signatures were created with
+bool RtabmapHip::checkEpipolar(int newId, int oldId) const {
+    const std::map<int, EpipolarWords>::const_iterator a = _epipolarWords.find(newId), b = _epipolarWords.find(oldId);
+    if (a == _epipolarWords.end() || b == _epipolarWords.end()) return false;   // a signature that came without keypoints has no pairs
+    return _epipolarGeometry->check(_memory->getVWDictionary()->engine(), a->second.wordIds, a->second.points, b->second.wordIds, b->second.points);
+}
+
+bool RtabmapHip::process(const Mat& descriptors, const std::vector<float>* keypoints) {
     // :1263-1265
     _loopClosureHypothesis = std::pair<int, float>(0, 0.0f);
     const std::pair<int, float> lastHighestHypothesis = _highestHypothesis;
@@ -51,6 +72,18 @@ bool RtabmapHip::process(const Mat& descriptors) {
 
     _lastLocationId = _memory->update(descriptors, -1, _lastWordIds);       // Memory::update :1470-1477
     if (_lastLocationId <= 0) return false;
+    if (_verifyLoopClosureHypothesis && keypoints && _lastWordIds.size() * 2 == keypoints->size()) {
+        EpipolarWords& w = _epipolarWords[_lastLocationId];                 // the signature's words and their keypoints, as created
+        w.wordIds = _lastWordIds;
+        w.points = *keypoints;
+    }
+    const std::set<int>& stm = _memory->getStMem();
+    const std::set<int>& kept = _memory->getWorkingMem();
+    if (_epipolarWords.size() > stm.size() + kept.size() - kept.count(MemoryHip::kIdVirtual)) {               // a location the memory dropped (MemoryHip::forget) takes its words along
+        for (std::map<int, EpipolarWords>::iterator i = _epipolarWords.begin(); i != _epipolarWords.end();) {
+            if (stm.count(i->first) || kept.count(i->first)) ++i; else _epipolarWords.erase(i++);
+        }
+    }
     if (descriptors.rows == 0) return true;   // a signature without features is a bad signature: "Ignoring likelihood and loop closure hypotheses" (:2234-2237)
     const std::set<int>& wm = _memory->getWorkingMem();
     if (wm.size() > 1) {                                                    // getWorkingMemSize(): signatures besides the virtual place
@@ -63,11 +96,13 @@ bool RtabmapHip::process(const Mat& descriptors) {
         if (_posterior.size() && _bayesFilter->lastUpdateOk()) {            // :2147-2158 (the device selected it in the same pass); a failed
             _highestHypothesis = _bayesFilter->getHighestHypothesis();      // update leaves (0, 0): no acceptance on a stale posterior
         }
-        if (_highestHypothesis.first > 0) {                                 // :2162-2222 without the RGB-D and epipolar branches
+        if (_highestHypothesis.first > 0) {                                 // :2162-2222 without the RGB-D branch
             const float loopThr = _loopThr;
             if (_highestHypothesis.second >= loopThr) {
                 if (_posterior.size() <= 2 && loopThr > 0.0f) {
                     // rejected hypothesis: single hypothesis
+                } else if (_verifyLoopClosureHypothesis && !this->checkEpipolar(_lastLocationId, _highestHypothesis.first)) {   // :2193
+                    fprintf(stderr, "[ WARN] rejected hypothesis: by epipolar geometry\n");
                 } else if (_loopRatio > 0.0f && lastHighestHypothesis.second && _highestHypothesis.second < _loopRatio * lastHighestHypothesis.second) {
                     fprintf(stderr, "[ WARN] rejected hypothesis: not satisfying hypothesis ratio (%f < %f * %f)\n", _highestHypothesis.second, _loopRatio,
                             lastHighestHypothesis.second);

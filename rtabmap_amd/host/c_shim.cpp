@@ -908,6 +908,78 @@ int hrtab_vector(void* r, int which, int* outIds, float* out, int cap) {
     for (std::map<int, float>::const_iterator i = m.begin(); i != m.end(); ++i, ++k) if (k < cap) { outIds[k] = i->first; out[k] = i->second; }
     return (int)m.size();
 }
+// hrtab_create with the epipolar check's parameters: VhEp/Enabled, VhEp/MatchCountMin, VhEp/RansacParam1
+void* hrtab_create_epipolar(float loopThr, float loopRatio, int virtualPlaceLikelihoodRatio, int stmSize, const char* predictionLC, float virtualPlacePrior,
+                            int device, int epipolarEnabled, int matchCountMin, float ransacParam1) {
+    ParametersMap p = make_params(5, 1, 0.8f, 1, "");
+    p["Rtabmap/LoopThr"] = std::to_string(loopThr);
+    p["Rtabmap/LoopRatio"] = std::to_string(loopRatio);
+    p["Rtabmap/VirtualPlaceLikelihoodRatio"] = std::to_string(virtualPlaceLikelihoodRatio);
+    p["Mem/STMSize"] = std::to_string(stmSize);
+    if (predictionLC && predictionLC[0]) p["Bayes/PredictionLC"] = predictionLC;
+    p["Bayes/VirtualPlacePriorThr"] = std::to_string(virtualPlacePrior);
+    p["VhEp/Enabled"] = epipolarEnabled ? "true" : "false";
+    p["VhEp/MatchCountMin"] = std::to_string(matchCountMin);
+    p["VhEp/RansacParam1"] = std::to_string(ransacParam1);
+    return new RtabmapHip(p, device);
+}
+// hrtab_process with the frame's keypoints, [rows x 2]
+int hrtab_process_keypoints(void* r, const void* desc, int rows, int cols, int type, const float* keypoints, int* out4, float* outValues2) {
+    RtabmapHip* R = (RtabmapHip*)r;
+    const std::vector<float> kp(keypoints, keypoints + (size_t)rows * 2);
+    const bool ok = R->process(make_mat(desc, rows, cols, type), kp);
+    out4[0] = R->getLastLocationId(); out4[1] = R->getHighestHypothesisId(); out4[2] = R->getLoopClosureId(); out4[3] = ok ? 1 : 0;
+    outValues2[0] = R->getHighestHypothesisValue(); outValues2[1] = R->getLoopClosureValue();
+    return ok ? 1 : 0;
+}
+// epipolar_cpu (no engine involved).  outFundamental[9], outScalars[3] = status, pairs, inliers; outMatches / outInliers hold nTo ids.  1 = done, 0 = refused
+int hepi_cpu(const int* fromIds, const float* fromPoints, int nFrom, const int* toIds, const float* toPoints, int nTo, int matchCountMin, int iterations,
+             double ransacParam1, unsigned seed, float* outFundamental, int* outScalars, int* outMatches, int* outInliers) {
+    EpipolarParams p;
+    p.matchCountMin = matchCountMin; p.iterations = iterations; p.ransacParam1 = ransacParam1; p.seed = seed;
+    EpipolarResult r;
+    if (!epipolar_cpu(fromIds, fromPoints, nFrom, toIds, toPoints, nTo, p, r)) return 0;
+    std::copy(r.fundamental, r.fundamental + 9, outFundamental);
+    outScalars[0] = r.status; outScalars[1] = (int)r.matches.size(); outScalars[2] = (int)r.inliers.size();
+    std::copy(r.matches.begin(), r.matches.end(), outMatches);
+    std::copy(r.inliers.begin(), r.inliers.end(), outInliers);
+    return 1;
+}
+// EpipolarGeometryHip::check and findFFromWords through the dictionary's engine.  outStatus: one byte per pair (cap nB); outScalars[3] = the
+// engine's status, pairs, accepted; returns 1 when the engine took the call
+int hepi_check(void* h, const int* idsA, const float* pointsA, int nA, const int* idsB, const float* pointsB, int nB, int matchCountMin, double ransacParam1,
+               double ransacParam2, unsigned seed, float* outFundamental, unsigned char* outStatus, int* outPairs, int* outScalars) {
+    ParametersMap p;
+    p["VhEp/MatchCountMin"] = std::to_string(matchCountMin);
+    p["VhEp/RansacParam1"] = std::to_string(ransacParam1);
+    p["VhEp/RansacParam2"] = std::to_string(ransacParam2);
+    const EpipolarGeometryHip epi(p);
+    const std::vector<int> a(idsA, idsA + nA), b(idsB, idsB + nB);
+    const std::vector<float> pa(pointsA, pointsA + (size_t)nA * 2), pb(pointsB, pointsB + (size_t)nB * 2);
+    lcd_engine* engine = ((VWDictionaryHip*)h)->engine();
+    std::vector<unsigned char> status;
+    std::vector<int> pairs;
+    int st = 0;
+    if (!epi.findFFromWords(engine, a, pa, b, pb, outFundamental, status, &pairs, &st, seed)) return 0;
+    std::copy(status.begin(), status.end(), outStatus);
+    std::copy(pairs.begin(), pairs.end(), outPairs);
+    outScalars[0] = st; outScalars[1] = (int)pairs.size();
+    return 1;
+}
+// EpipolarGeometryHip::check alone: 1 accepted, 0 rejected or refused
+int hepi_accept(void* h, const int* idsA, const float* pointsA, int nA, const int* idsB, const float* pointsB, int nB, int matchCountMin, double ransacParam1,
+                double ransacParam2, unsigned seed) {
+    ParametersMap p;
+    p["VhEp/MatchCountMin"] = std::to_string(matchCountMin);
+    p["VhEp/RansacParam1"] = std::to_string(ransacParam1);
+    p["VhEp/RansacParam2"] = std::to_string(ransacParam2);
+    const EpipolarGeometryHip epi(p);
+    const std::vector<int> a(idsA, idsA + nA), b(idsB, idsB + nB);
+    const std::vector<float> pa(pointsA, pointsA + (size_t)nA * 2), pb(pointsB, pointsB + (size_t)nB * 2);
+    return epi.check(((VWDictionaryHip*)h)->engine(), a, pa, b, pb, seed) ? 1 : 0;
+}
+// the number of signatures whose words and keypoints a RtabmapHip keeps for the epipolar check
+int hrtab_epipolar_kept(void* r) { return ((RtabmapHip*)r)->getEpipolarKept(); }
 int hrtab_last_word_ids(void* r, int* out, int cap) {
     const std::vector<int>& v = ((RtabmapHip*)r)->getLastWordIds();
     for (size_t i = 0; i < v.size() && (int)i < cap; ++i) out[i] = v[i];

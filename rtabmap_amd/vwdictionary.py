@@ -138,6 +138,13 @@ def lib():
         L.hrtab_memory.argtypes = [vp]
         L.hrtab_process.argtypes = [vp, vp, ci, ci, ci, vp, vp]
         L.hrtab_vector.argtypes = [vp, ci, vp, vp, ci]
+        L.hrtab_create_epipolar.restype = vp
+        L.hrtab_create_epipolar.argtypes = [cf, cf, ci, ci, C.c_char_p, cf, ci, ci, ci, cf]
+        L.hrtab_process_keypoints.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
+        L.hepi_cpu.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, C.c_double, C.c_uint, vp, vp, vp, vp]
+        L.hepi_check.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, C.c_double, C.c_uint, vp, vp, vp, vp]
+        L.hepi_accept.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, C.c_double, C.c_uint]
+        L.hrtab_epipolar_kept.argtypes = [vp]
         L.hrtab_last_word_ids.argtypes = [vp, vp, ci]
         L.hmem_destroy.argtypes = [vp]
         L.hmem_vwd.restype = vp
@@ -475,6 +482,29 @@ def motion_pnp_cpu(from_ids, from_xyz, to_ids, to_points, to_xyz=None, camera=(5
                 inliers=oi[:sc[2]].copy())
 
 
+def _kp_arrays(ids, points):
+    i = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    x = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    if x.shape[0] != i.shape[0]:
+        raise ValueError("one keypoint per word id")
+    return i, x
+
+
+def epipolar_cpu(from_ids, from_points, to_ids, to_points, match_count_min=8, iterations=1000, ransac_threshold=3.0, seed=0):
+    """the rule of lcd_verify_epipolar on the CPU (host/EpipolarGeometryHip.cpp, no device) -> dict(fundamental [9], status, matches,
+    inliers), or None where the call is refused"""
+    fi, fp = _kp_arrays(from_ids, from_points)
+    ti, tp = _kp_arrays(to_ids, to_points)
+    n = max(ti.shape[0], 1)
+    f, sc = np.zeros(9, np.float32), np.zeros(3, np.int32)
+    om, oi = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ok = lib().hepi_cpu(_p(fi), _p(fp), fi.shape[0], _p(ti), _p(tp), ti.shape[0], int(match_count_min), int(iterations), float(ransac_threshold),
+                        int(seed) & 0xFFFFFFFF, _p(f), _p(sc), _p(om), _p(oi))
+    if not ok:
+        return None
+    return dict(fundamental=f, status=int(sc[0]), matches=om[:sc[1]].copy(), inliers=oi[:sc[2]].copy())
+
+
 def _ba_camera(camera):
     """a camera dict(fx, fy, cx, cy[, image_width, image_height, local_transform]) as the shim's three arrays"""
     cam = np.array([camera["fx"], camera["fy"], camera["cx"], camera["cy"]], np.float32)
@@ -614,6 +644,27 @@ class VWDictionaryHip:
                                 int(min_inliers), int(iterations), float(reproj_error), int(refine_iterations), int(variance_median_ratio),
                                 float(max_variance), int(seed) & 0xFFFFFFFF, _p(t), _p(cov), _p(counts), _p(om), _p(oi))
         return (t if ok else None), cov.reshape(6, 6), om[:counts[0]].tolist(), oi[:counts[1]].tolist()
+
+    def verify_epipolar(self, kpts_a, kpts_b, match_count_min=8, ransac_param1=3.0, ransac_param2=0.99, seed=0):
+        """EpipolarGeometryHip::check / findFFromWords (EpipolarGeometry.cpp:65-102, :298-379) over this dictionary's long-lived engine handle;
+        kpts_a and kpts_b are (word ids, [n x 2] keypoints); an id may repeat.  -> (accepted, fundamental [9], pairs' ids, one status byte per
+        pair, the engine's status), or None where the engine refuses the call"""
+        ia, pa = _kp_arrays(*kpts_a)
+        ib, pb = _kp_arrays(*kpts_b)
+        n = max(ib.shape[0], 1)
+        f, st, pairs, sc = np.zeros(9, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.int32), np.zeros(3, np.int32)
+        ok = lib().hepi_check(self.h, _p(ia), _p(pa), ia.shape[0], _p(ib), _p(pb), ib.shape[0], int(match_count_min), float(ransac_param1),
+                              float(ransac_param2), int(seed) & 0xFFFFFFFF, _p(f), _p(st), _p(pairs), _p(sc))
+        if not ok:
+            return None
+        return int(sc[0]) == 0, f, pairs[:sc[1]].tolist(), st[:sc[1]].copy(), int(sc[0])
+
+    def check_epipolar(self, kpts_a, kpts_b, match_count_min=8, ransac_param1=3.0, ransac_param2=0.99, seed=0):
+        """EpipolarGeometryHip::check alone: the accept decision (False also where the engine refuses the call)"""
+        ia, pa = _kp_arrays(*kpts_a)
+        ib, pb = _kp_arrays(*kpts_b)
+        return bool(lib().hepi_accept(self.h, _p(ia), _p(pa), ia.shape[0], _p(ib), _p(pb), ib.shape[0], int(match_count_min), float(ransac_param1),
+                                      float(ransac_param2), int(seed) & 0xFFFFFFFF))
 
     def refine_motion_ba(self, words3a, kpts_b, inliers, transform, kpts_a=None, words3b=None, variance_kind=0, variance_lin=1.0, angle_cos=1.0,
                          camera_from=DEFAULT_CAMERA, camera_to=DEFAULT_CAMERA, baselines=(0.075, 0.075), min_inliers=20, iterations=20, pixel_variance=1.0,
@@ -1027,9 +1078,15 @@ class RtabmapHip:
     hypothesis and the accepted loop closure out."""
 
     def __init__(self, loop_thr=0.11, loop_ratio=0.0, virtual_place_likelihood_ratio=0, stm_size=10, prediction_lc="",
-                 virtual_place_prior=0.9, device=0):
-        self.h = lib().hrtab_create(float(loop_thr), float(loop_ratio), int(virtual_place_likelihood_ratio), int(stm_size),
-                                    prediction_lc.encode(), float(virtual_place_prior), device)
+                 virtual_place_prior=0.9, device=0, epipolar=None):
+        """epipolar: None, or dict(enabled, match_count_min, ransac_param1) -- VhEp/Enabled, VhEp/MatchCountMin, VhEp/RansacParam1"""
+        if epipolar is None:
+            self.h = lib().hrtab_create(float(loop_thr), float(loop_ratio), int(virtual_place_likelihood_ratio), int(stm_size),
+                                        prediction_lc.encode(), float(virtual_place_prior), device)
+        else:
+            self.h = lib().hrtab_create_epipolar(float(loop_thr), float(loop_ratio), int(virtual_place_likelihood_ratio), int(stm_size),
+                                                 prediction_lc.encode(), float(virtual_place_prior), device, 1 if epipolar.get("enabled", True) else 0,
+                                                 int(epipolar.get("match_count_min", 8)), float(epipolar.get("ransac_param1", 3.0)))
         self.memory = MemoryHip(_handle=lib().hrtab_memory(self.h), _owner=self)
 
     def close(self):
@@ -1044,13 +1101,23 @@ class RtabmapHip:
         except Exception:
             pass
 
-    def process(self, desc):
-        """-> dict(id, highest=(id, value), loop=(id, value))"""
+    def process(self, desc, keypoints=None):
+        """keypoints: None, or [rows x 2] positions for the epipolar check (VhEp/Enabled) -> dict(id, highest=(id, value), loop=(id, value))"""
         desc = np.ascontiguousarray(desc)
         out4 = np.zeros(4, np.int32)
         val2 = np.zeros(2, np.float32)
-        lib().hrtab_process(self.h, _p(desc), desc.shape[0], desc.shape[1], _type_of(desc), _p(out4), _p(val2))
+        if keypoints is None:
+            lib().hrtab_process(self.h, _p(desc), desc.shape[0], desc.shape[1], _type_of(desc), _p(out4), _p(val2))
+        else:
+            kp = np.ascontiguousarray(keypoints, dtype=np.float32).reshape(-1, 2)
+            if kp.shape[0] != desc.shape[0]:
+                raise ValueError("one keypoint per descriptor row")
+            lib().hrtab_process_keypoints(self.h, _p(desc), desc.shape[0], desc.shape[1], _type_of(desc), _p(kp), _p(out4), _p(val2))
         return {"id": int(out4[0]), "highest": (int(out4[1]), float(val2[0])), "loop": (int(out4[2]), float(val2[1])), "ok": bool(out4[3])}
+
+    def epipolar_kept(self):
+        """the number of signatures whose word ids and keypoints are kept for the epipolar check"""
+        return int(lib().hrtab_epipolar_kept(self.h))
 
     def vector(self, which):
         """which: "raw" | "likelihood" | "posterior" of the last frame -> (ids, values) in std::map order"""
