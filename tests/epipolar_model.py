@@ -12,6 +12,7 @@ MIN_PAIRS = 8
 OK, FEW_PAIRS, NO_MODEL, FEW_INLIERS = 0, 1, 2, 3
 SQRT2 = F(1.41421356)
 ERR = dict(divide="ignore", invalid="ignore", over="ignore", under="ignore")
+TINY = np.finfo(np.float32).tiny                                           # the smallest normal float32
 
 
 def correspondences(from_ids, from_points, to_ids, to_points):
@@ -34,14 +35,23 @@ def correspondences(from_ids, from_points, to_ids, to_points):
     return np.array(ids, np.int32), X
 
 
-def normalisation(P):
-    """step 2 for one image, P [m x 2] -> (ok, s, tx, ty)"""
+def subnormal(*arrays):
+    """whether any value is a nonzero subnormal float32"""
+    return any(bool(((a != 0) & (np.abs(a) < TINY)).any()) for a in map(np.asarray, arrays))
+
+
+def normalisation(P, info=None):
+    """step 2 for one image, P [m x 2] -> (ok, s, tx, ty); info (a list): whether a distance square was subnormal is appended"""
     m = F(P.shape[0])
     with np.errstate(**ERR):
         sums = lane_sum(P)
         cx, cy = sums[0] / m, sums[1] / m
         dx, dy = P[:, 0] - cx, P[:, 1] - cy
-        dist = np.sqrt(dx * dx + dy * dy)
+        xx, yy = dx * dx, dy * dy
+        dd = xx + yy
+        if info is not None:
+            info.append(subnormal(xx, yy, dd))
+        dist = np.sqrt(dd)
         d = lane_sum(dist) / m
         if not (d > F(0)) or not np.isfinite(d):
             return False, F(0), F(0), F(0)
@@ -132,8 +142,9 @@ def bisect(c, lo, hi):
     return has, F(0.5) * (a + b)
 
 
-def cubic_roots(c):
-    """-> ok [H], n [H], roots [H x 3] (the first n are the roots found, in the brackets' order)"""
+def cubic_roots(c, info=None):
+    """-> ok [H], n [H], roots [H x 3] (the first n are the roots found, in the brackets' order); info (a dict) receives per hypothesis
+    `clamped` (two real roots of the derivative and k1 or k2 is not the root itself but +-B) and `disc_nonpos` (disc <= 0, or NaN)"""
     c3 = c[:, 3]
     q = np.abs(c[:, :3] / c3[:, None])
     m01 = np.where(q[:, 0] > q[:, 1], q[:, 0], q[:, 1])
@@ -151,6 +162,8 @@ def cubic_roots(c):
     lo1, hi1 = np.where(lo < nB, nB, lo), np.where(hi < nB, nB, hi)
     k1, k2 = np.where(lo1 > B, B, lo1), np.where(hi1 > B, B, hi1)
     k1, k2 = np.where(k1 == k1, k1, B), np.where(k2 == k2, k2, B)
+    if info is not None:
+        info.update(clamped=two & ((k1 != lo) | (k2 != hi)), disc_nonpos=~two)
     k1, k2 = np.where(two, k1, B), np.where(two, k2, B)
     H = c.shape[0]
     n = np.zeros(H, np.int64)
@@ -180,13 +193,22 @@ def denormalise(Fn, nf, nt):
     return out
 
 
-def line_error(f, u, v, pu, pv):
-    """f: nine [C x 1] entries in the order the line is built from; points [1 x m]"""
+def line_parts(f, u, v, pu, pv):
+    """f: nine [C x 1] entries in the order the line is built from; points [1 x m] -> (dd, n), the error's numerator and denominator"""
     lx = (f[0] * u + f[1] * v) + f[2]
     ly = (f[3] * u + f[4] * v) + f[5]
     lz = (f[6] * u + f[7] * v) + f[8]
     d = (pu * lx + pv * ly) + lz
-    return (d * d) / (lx * lx + ly * ly)
+    return d * d, lx * lx + ly * ly
+
+
+def line_error(f, u, v, pu, pv):
+    dd, n = line_parts(f, u, v, pu, pv)
+    return dd / n
+
+
+def transposed(f):
+    return [f[0], f[3], f[6], f[1], f[4], f[7], f[2], f[5], f[8]]
 
 
 def inliers_of(models, X, thr2):
@@ -195,15 +217,28 @@ def inliers_of(models, X, thr2):
     u, v, up, vp = (X[None, :, k] for k in range(4))
     with np.errstate(**ERR):
         e1 = line_error(f, u, v, up, vp)
-        e2 = line_error([f[0], f[3], f[6], f[1], f[4], f[7], f[2], f[5], f[8]], up, vp, u, v)
+        e2 = line_error(transposed(f), up, vp, u, v)
         return (e1 <= thr2) & (e2 <= thr2)
+
+
+def line_subnormal(model, X):
+    """whether dd or n of either line error of one model [9] is a nonzero subnormal for some correspondence"""
+    f = [model[None, k, None] for k in range(9)]
+    u, v, up, vp = (X[None, :, k] for k in range(4))
+    with np.errstate(**ERR):
+        return subnormal(*line_parts(f, u, v, up, vp), *line_parts(transposed(f), up, vp, u, v))
+
+
+def lead_of(Fm):
+    """the largest-magnitude entry, the lowest index on ties"""
+    return Fm[int(np.argmax(np.abs(Fm)))]
 
 
 def unit_matrix(Fm):
     total = F(0)
     for k in range(9):
         total = total + Fm[k] * Fm[k]
-    lead = Fm[int(np.argmax(np.abs(Fm)))]
+    lead = lead_of(Fm)
     n = np.sqrt(total)
     return (Fm / (-n if lead < F(0) else n)).astype(np.float32)
 
@@ -230,25 +265,29 @@ def candidates(X, seed, iterations, nf, nt, trace=None):
         A = np.stack([xp * x, xp * y, xp, yp * x, yp * y, yp, x, y, np.ones_like(x)], axis=2).astype(np.float32)
         pivots, F1, F2 = null_space(A)
         cubic, c = cubic_of(F1, F2)
-        bounded, n, roots = cubic_roots(c)
+        info = {}
+        bounded, n, roots = cubic_roots(c, info)
         ok = drawn & pivots & cubic & bounded
         Fn = roots[:, :, None] * F1[:, None, :] + F2[:, None, :]          # [H x 3 x 9]
         models = denormalise(Fn, nf, nt)
     valid = ok[:, None] & (np.arange(3)[None, :] < n[:, None])
     if trace is not None:
         trace.update(not_drawn=int((~drawn).sum()), no_pivot=int((drawn & ~pivots).sum()), c3_zero=int((drawn & pivots & (c[:, 3] == 0)).sum()),
-                     bad_cubic=int((drawn & pivots & ~cubic).sum()), one_root=int((ok & (n == 1)).sum()), three_roots=int((ok & (n == 3)).sum()))
+                     bad_cubic=int((drawn & pivots & ~cubic).sum()), one_root=int((ok & (n == 1)).sum()), three_roots=int((ok & (n == 3)).sum()),
+                     per_hypothesis=dict(n_roots=np.where(ok, n, 0), **info))
     return valid.reshape(-1), models.reshape(-1, 9)
 
 
-def best_candidate(valid, models, X, thr2, chunk=1 << 21):
-    """step 5 -> (count, candidate) of the winner; count 0: none"""
+def best_candidate(valid, models, X, thr2, chunk=1 << 21, trace=None):
+    """step 5 -> (count, candidate) of the winner; count 0: none; trace receives `tied`, every valid candidate that reaches the count, ascending"""
     counts = np.zeros(valid.shape[0], np.int64)
     step = max(chunk // max(X.shape[0], 1), 1)
     for c0 in range(0, valid.shape[0], step):
         counts[c0:c0 + step] = inliers_of(models[c0:c0 + step], X, thr2).sum(axis=1)
     counts = np.where(valid, counts, 0)
     best = int(np.argmax(counts)) if counts.size else 0
+    if trace is not None:
+        trace.update(tied=[int(c) for c in np.nonzero(valid & (counts == counts[best]) & (counts > 0))[0]] if counts.size else [])
     return (int(counts[best]) if counts.size else 0), best
 
 
@@ -273,12 +312,16 @@ def verify(from_ids, from_points, to_ids, to_points, match_count_min=8, iteratio
     if m < match_count_min or m < MIN_PAIRS:
         return out
     out["status"] = NO_MODEL
-    okf, *nf = normalisation(X[:, :2])
-    okt, *nt = normalisation(X[:, 2:])
+    squares = []
+    okf, *nf = normalisation(X[:, :2], squares)
+    okt, *nt = normalisation(X[:, 2:], squares)
     if not (okf and okt):
         return out
+    if trace is not None:
+        trace.update(subnormal=dict(distance=any(squares), thr2=subnormal(thr2), line=False))
     valid, models = candidates(X, seed, iterations, nf, nt, trace)
-    count, best = best_candidate(valid, models, X, thr2)
+    count, best = best_candidate(valid, models, X, thr2, trace=trace)
+    per = trace.pop("per_hypothesis") if trace is not None else None
     if count == 0:
         return out
     inl = inliers_of(models[best:best + 1], X, thr2)[0]
@@ -287,7 +330,9 @@ def verify(from_ids, from_points, to_ids, to_points, match_count_min=8, iteratio
         out["fundamental"] = unit_matrix(models[best])
     out["status"] = OK if count >= match_count_min else FEW_INLIERS
     if trace is not None:
-        trace.update(best=best, count=count)
+        trace.update(best=best, count=count, root=best % 3, n_roots=int(per["n_roots"][best // 3]), lead_negative=bool(lead_of(models[best]) < F(0)),
+                     clamped=dict(clamped=bool(per["clamped"][best // 3]), disc_nonpos=bool(per["disc_nonpos"][best // 3])))
+        trace["subnormal"]["line"] = line_subnormal(models[best], X)
     return out
 
 

@@ -12,7 +12,7 @@ import epipolar_inputs as I
 import epipolar_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZER_CASES = 69                                                       # tools/sanitize_epipolar.cpp prints "ok 69"
+SANITIZER_CASES = 83                                                       # tools/sanitize_epipolar.cpp prints "ok 83"
 # Measured on I.accuracy_scenes(): the largest difference between the yardstick's own float32 and float64 inlier counts
 RECORDED_D = 1
 
@@ -37,6 +37,15 @@ CASES = [("ids", I.id_cases, {}), ("m7", lambda: I.with_m(7), {}), ("m8", lambda
          ("c3_zero", I.c3_zero, {}), ("nan", I.nan_keypoint, {}), ("planar", lambda: I.scene(4, 120, planar=True), {}),
          ("outliers", lambda: I.scene(1, 120), dict(iterations=200)), ("all_outliers", lambda: I.scene(5, 40, outliers=1.0), dict(match_count_min=30)),
          ("large", lambda: I.scene(6, 1100, extra=40), dict(iterations=20)), ("thr", lambda: I.scene(8, 90), dict(ransac_threshold=0.75, seed=0xFFFFFFF0))]
+# the generators of the shape tests (test_gpu_epipolar_shapes.py): the model is right where squares go subnormal or overflow before the device is asked
+SCALES = (-74, -70, -66, -64, -62, -20, 20, 55, 60, 62)
+CASES += [("scale%+d" % k, lambda k=k: I.scaled(I.scene(3, 100), k), dict(ransac_threshold=3.0 * 2.0 ** k, seed=5)) for k in SCALES]
+CASES += [("scale%+d_m8" % k, lambda k=k: I.scaled(I.with_m(8), k), dict(ransac_threshold=3.0 * 2.0 ** k, seed=5)) for k in SCALES]
+CASES += [("census%d" % k, lambda k=k: I.census_batch()[0][k], dict(iterations=I.CENSUS_ITERATIONS, seed=I.CENSUS_SEED)) for k in (0, 1, 40, 41, 42, 43)]
+CASES += [("tie%d_%d" % (k, it), lambda k=k: I.tie_pairs()[0][k], dict(iterations=it, seed=I.TIE_SEED)) for k in range(4) for it in (86, 300)]
+CASES += [("draw_failure", lambda: I.draw_failure()[0], dict(seed=I.DRAW_FAILURE_SEED, iterations=I.DRAW_FAILURE_ITERATIONS))]
+CASES += [("inf%+d_%s" % (sign, side), lambda sign=sign, side=side: I.inf_keypoint(sign, side), {}) for sign in (1, -1) for side in ("from", "to")]
+CASES += [("nan_unpaired", lambda: I.nan_unpaired()[0], {}), ("nan_unpaired_twin", lambda: I.nan_unpaired()[1], {})]
 
 
 @pytest.mark.parametrize("name,make,kw", CASES, ids=[c[0] for c in CASES])

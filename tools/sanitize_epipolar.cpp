@@ -7,8 +7,9 @@
 //
 // Frames whose buffers end with their last row (a read past a frame is a heap overflow): 0 to 9 pairs, negative ids, ids that occur twice on
 // one side or on both, ids of one side only, INT_MIN and INT_MAX ids, every keypoint at one position, collinear keypoints, NaN, infinite and
-// huge coordinates, pairs that are all outliers, 1 / 85 / 86 / 300 iterations, 8192 rows, every status, and the refused arguments.  Every result
-// is checked against what the rule promises whatever the numbers are; exit status 0 and "ok" with the number of cases when all hold.
+// huge coordinates, pairs that are all outliers, 1 / 85 / 86 / 300 iterations, 8192 rows, scenes times 2^-74 .. 2^+60, a hypothesis without seven
+// distinct draws, every status, and the refused arguments.  Every result is checked against what the rule promises whatever the numbers are;
+// exit status 0 and "ok" with the number of cases when all hold.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -50,7 +51,8 @@ bool run(const Frame& f, const Frame& t, const EpipolarParams& p, EpipolarResult
     return epipolar_cpu(fi.data(), fp.data(), f.n(), ti.data(), tp.data(), t.n(), p, r);
 }
 
-void check(const Frame& f, const Frame& t, const EpipolarParams& p, int tag) {
+// unit_norm false: keypoints so small that the squares of the matrix' entries overflow, where the rule's division by the norm leaves zeros
+void check(const Frame& f, const Frame& t, const EpipolarParams& p, int tag, bool unit_norm = true) {
     ++cases;
     EpipolarResult a, b;
     expect(run(f, t, p, a), "accepted", tag);
@@ -76,7 +78,7 @@ void check(const Frame& f, const Frame& t, const EpipolarParams& p, int tag) {
     if (a.status == 0 || a.status == 3) {
         double n2 = 0.0;
         for (float v : a.fundamental) n2 += (double)v * (double)v;
-        expect(std::fabs(n2 - 1.0) < 1e-3, "a matrix of unit norm", tag);
+        expect(unit_norm ? std::fabs(n2 - 1.0) < 1e-3 : n2 == 0.0, unit_norm ? "a matrix of unit norm" : "a matrix of zeros", tag);
     }
 }
 
@@ -160,6 +162,32 @@ int main() {
         f.ids.resize(8192); f.uv.resize(8192 * 2); t.ids.resize(8192); t.uv.resize(8192 * 2);
         EpipolarParams p = base;
         p.iterations = 10; p.matchCountMin = 20;
+        check(f, t, p, ++tag);
+    }
+    // one scene times 2^k with the threshold scaled alike: squares that go subnormal (k <= -64), that vanish (-74) and that overflow (+60)
+    for (int k : {-74, -70, -66, -64, -62, -20, 20, 55, 60}) {
+        std::mt19937 same(11);
+        Frame f, t;
+        scene(same, 100, 0.4, f, t);
+        for (float& w : f.uv) w = std::ldexp(w, k);
+        for (float& w : t.uv) w = std::ldexp(w, k);
+        EpipolarParams p = base;
+        p.ransacParam1 = std::ldexp(3.0, k);
+        check(f, t, p, ++tag, k > -62);
+    }
+    // one infinite coordinate among the pairs, either sign, either frame
+    for (int side = 0; side < 2; ++side)
+        for (float w : {INFINITY, -INFINITY}) {
+            Frame f, t;
+            scene(rng, 40, 0.0, f, t);
+            (side ? t : f).uv[7] = w;
+            check(f, t, base, ++tag);
+        }
+    {   // eight pairs: hypothesis 3 of seed 301 (seed + h = 304) does not find seven distinct indices in its 32 draws
+        Frame f, t;
+        scene(rng, 8, 0.0, f, t);
+        EpipolarParams p = base;
+        p.seed = 301;
         check(f, t, p, ++tag);
     }
     ++cases;
