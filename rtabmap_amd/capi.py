@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_verify_epipolar", "lcd_verify_epipolar_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_verify_epipolar", "lcd_verify_epipolar_dev", "lcd_estimate_motion_mono", "lcd_estimate_motion_mono_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -244,6 +244,20 @@ class LcdEpipolarArgs(C.Structure):
 LCD_EPI_OK, LCD_EPI_FEW_PAIRS, LCD_EPI_NO_MODEL, LCD_EPI_FEW_INLIERS = 0, 1, 2, 3  # lcd_epipolar_status
 
 
+class LcdMotionMonoArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("min_inliers", C.c_int32), ("iterations", C.c_int32), ("seed", C.c_uint32),
+                ("variance_median_ratio", C.c_int32), ("reproj_threshold", C.c_double), ("distance_threshold", C.c_double),
+                ("max_variance", C.c_float), ("reserved", C.c_int32), ("from_word_ids", C.c_void_p), ("from_points", C.c_void_p),
+                ("from_points3", C.c_void_p), ("to_word_ids", C.c_void_p), ("to_points", C.c_void_p), ("from_offsets", C.c_void_p),
+                ("to_offsets", C.c_void_p), ("cameras", C.c_void_p), ("guesses", C.c_void_p), ("out_transform", C.c_void_p),
+                ("out_status", C.c_void_p), ("out_n_matches", C.c_void_p), ("out_n_inliers", C.c_void_p), ("out_variance", C.c_void_p),
+                ("out_matches", C.c_void_p), ("out_inliers", C.c_void_p), ("out_points3", C.c_void_p)]
+
+
+LCD_MONO_OK, LCD_MONO_FEW_FEATURES, LCD_MONO_FEW_PAIRS, LCD_MONO_NO_MODEL, LCD_MONO_FEW_INLIERS, LCD_MONO_HIGH_VARIANCE = 0, 1, 2, 3, 4, 5  # lcd_motion_mono_status
+LCD_MONO_BISECT = 56
+
+
 class LcdMotionBaArgs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("min_inliers", C.c_int32), ("iterations", C.c_int32),
                 ("pixel_variance", C.c_double), ("robust_delta", C.c_double), ("default_baseline", C.c_double),
@@ -347,6 +361,8 @@ def load():
     L.lcd_estimate_motion_pnp_dev.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
     L.lcd_verify_epipolar.argtypes = [vp, C.POINTER(LcdEpipolarArgs)]
     L.lcd_verify_epipolar_dev.argtypes = [vp, C.POINTER(LcdEpipolarArgs)]
+    L.lcd_estimate_motion_mono.argtypes = [vp, C.POINTER(LcdMotionMonoArgs)]
+    L.lcd_estimate_motion_mono_dev.argtypes = [vp, C.POINTER(LcdMotionMonoArgs)]
     L.lcd_refine_motion_ba.argtypes = [vp, C.POINTER(LcdMotionBaArgs)]
     L.lcd_refine_motion_ba_dev.argtypes = [vp, C.POINTER(LcdMotionBaArgs)]
     L.lcd_register_icp.argtypes = [vp, C.POINTER(LcdIcpArgs)]
@@ -1029,6 +1045,69 @@ class Engine:
         a.out_fundamental, a.out_status, a.out_n_pairs, a.out_n_inliers = ptr(d_fundamental), ptr(d_status), ptr(d_n_pairs), ptr(d_n_inliers)
         a.out_matches, a.out_inliers = ptr(d_matches), ptr(d_inliers)
         self._ck(self.L.lcd_verify_epipolar_dev(self.h, C.byref(a)))
+
+    # ---- monocular motion estimation, Vis/EstimationType = 2 (stateless; include/lcd.h has the rule)
+    OUTPUTS_MONO = ("transform", "status", "n_matches", "n_inliers", "variance", "matches", "inliers", "points3")
+
+    def _mono_args(self, n_pairs, fo, to, cams, guesses, min_inliers, iterations, seed, variance_median_ratio, reproj_threshold, distance_threshold,
+                   max_variance, struct_size=None):
+        a = LcdMotionMonoArgs(C.sizeof(LcdMotionMonoArgs) if struct_size is None else struct_size, n_pairs, int(min_inliers), int(iterations),
+                              int(seed) & 0xFFFFFFFF, int(variance_median_ratio), float(reproj_threshold), float(distance_threshold),
+                              float(max_variance), 0)
+        a.from_offsets, a.to_offsets = None if fo is None else fo.ctypes.data, None if to is None else to.ctypes.data
+        a.cameras = None if cams is None else C.cast(cams, C.c_void_p)
+        a.guesses = None if guesses is None else guesses.ctypes.data
+        return a
+
+    def estimate_motion_mono(self, from_ids, from_points, from_offsets, to_ids, to_points, to_offsets, cameras, from_points3=None, guesses=None,
+                             min_inliers=20, iterations=1000, reproj_threshold=2.0, variance_median_ratio=4, max_variance=0.1,
+                             distance_threshold=50.0, seed=0, struct_size=None, leave_out=()):
+        """lcd_estimate_motion_mono over host arrays, all pairs concatenated -> dict(transform [n_pairs x 12], status, n_matches, n_inliers,
+        variance [n_pairs], matches [Nt], inliers [Nt], points3 [Nt x 3]); outputs start as -1 / NaN so that what the call left alone shows;
+        leave_out: names of outputs passed as NULL"""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        fi, ti = np.ascontiguousarray(from_ids, dtype=np.int32).reshape(-1), np.ascontiguousarray(to_ids, dtype=np.int32).reshape(-1)
+        fp, tp = np.ascontiguousarray(from_points, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(to_points, dtype=np.float32).reshape(-1, 2)
+        f3 = None if from_points3 is None else np.ascontiguousarray(from_points3, dtype=np.float32).reshape(-1, 3)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        n_pairs, n = (to if to is not None else fo).shape[0] - 1, ti.shape[0]
+        np1 = max(n_pairs, 1)
+        out = dict(transform=np.full((np1, 12), np.nan, np.float32), status=np.full(np1, -1, np.int32), n_matches=np.full(np1, -1, np.int32),
+                   n_inliers=np.full(np1, -1, np.int32), variance=np.full(np1, np.nan, np.float64), matches=np.full(max(n, 1), -1, np.int32),
+                   inliers=np.full(max(n, 1), -1, np.int32), points3=np.full((max(n, 1), 3), np.nan, np.float32))
+        cams = self._pnp_cameras(cameras, n_pairs)
+        a = self._mono_args(n_pairs, fo, to, cams, gs, min_inliers, iterations, seed, variance_median_ratio, reproj_threshold, distance_threshold,
+                            max_variance, struct_size)
+        a.from_word_ids, a.from_points, a.to_word_ids, a.to_points = _p(fi), _p(fp), _p(ti), _p(tp)
+        a.from_points3 = None if f3 is None else (f3.ctypes.data if f3.size == 0 else _p(f3))
+        for k in self.OUTPUTS_MONO:
+            setattr(a, "out_" + k, None if k in leave_out else _p(out[k]))
+        self._ck(self.L.lcd_estimate_motion_mono(self.h, C.byref(a)))
+        for k in ("transform", "status", "n_matches", "n_inliers", "variance"):
+            out[k] = out[k][:max(n_pairs, 0)]
+        out["matches"], out["inliers"], out["points3"] = out["matches"][:n], out["inliers"][:n], out["points3"][:n]
+        return out
+
+    def estimate_motion_mono_dev(self, d_from_ids, d_from_points, from_offsets, d_to_ids, d_to_points, to_offsets, cameras, d_transform, d_status,
+                                 d_n_matches, d_n_inliers, d_variance, d_matches=None, d_inliers=None, d_points3=None, d_from_points3=None,
+                                 guesses=None, min_inliers=20, iterations=1000, reproj_threshold=2.0, variance_median_ratio=4, max_variance=0.1,
+                                 distance_threshold=50.0, seed=0):
+        """lcd_estimate_motion_mono_dev on torch tensors of the engine's device (offsets, cameras and guesses stay on the host; d_matches,
+        d_inliers, d_points3 and d_from_points3 may be None).  Enqueued, not synchronised."""
+        fo = None if from_offsets is None else np.ascontiguousarray(from_offsets, dtype=np.int64).reshape(-1)
+        to = None if to_offsets is None else np.ascontiguousarray(to_offsets, dtype=np.int64).reshape(-1)
+        gs = None if guesses is None else np.ascontiguousarray(guesses, dtype=np.float32).reshape(-1, 12)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        n_pairs = (to if to is not None else fo).shape[0] - 1
+        cams = self._pnp_cameras(cameras, n_pairs)
+        a = self._mono_args(n_pairs, fo, to, cams, gs, min_inliers, iterations, seed, variance_median_ratio, reproj_threshold, distance_threshold,
+                            max_variance)
+        a.from_word_ids, a.from_points, a.to_word_ids, a.to_points = ptr(d_from_ids), ptr(d_from_points), ptr(d_to_ids), ptr(d_to_points)
+        a.from_points3 = None if d_from_points3 is None else d_from_points3.data_ptr()
+        a.out_transform, a.out_status, a.out_n_matches, a.out_n_inliers = ptr(d_transform), ptr(d_status), ptr(d_n_matches), ptr(d_n_inliers)
+        a.out_variance, a.out_matches, a.out_inliers, a.out_points3 = ptr(d_variance), ptr(d_matches), ptr(d_inliers), ptr(d_points3)
+        self._ck(self.L.lcd_estimate_motion_mono_dev(self.h, C.byref(a)))
 
     # ---- two-view bundle adjustment behind the motion estimate (stateless; include/lcd.h has the rule)
     def _ba_args(self, n_pairs, fo, to, cams_from, cams_to, prior_variance, baselines, min_inliers, iterations, pixel_variance, robust_delta,

@@ -13,6 +13,7 @@
 #include "Motion2D.h"
 #include "Motion3D.h"
 #include "MotionBA.h"
+#include "MotionMono.h"
 #include "RegistrationIcp.h"
 #include "ScanFilter.h"
 #include "Stereo.h"
@@ -977,6 +978,55 @@ int hepi_accept(void* h, const int* idsA, const float* pointsA, int nA, const in
     const std::vector<int> a(idsA, idsA + nA), b(idsB, idsB + nB);
     const std::vector<float> pa(pointsA, pointsA + (size_t)nA * 2), pb(pointsB, pointsB + (size_t)nB * 2);
     return epi.check(((VWDictionaryHip*)h)->engine(), a, pa, b, pb, seed) ? 1 : 0;
+}
+// motion_mono_cpu (no engine involved).  camera[4] = fx, fy, cx, cy; local, guess: NULL or 12 floats; fromPoints3 may be NULL.  outScalars[3] =
+// status, matches, inliers; outMatches / outInliers hold nTo ids, outPoints3 nTo x 3 floats.  1 = done, 0 = refused
+int hmono_cpu(const int* fromIds, const float* fromPoints, const float* fromPoints3, int nFrom, const int* toIds, const float* toPoints, int nTo,
+              int minInliers, int iterations, unsigned seed, double reprojThreshold, int varianceMedianRatio, float maxVariance, double distanceThreshold,
+              const float* camera, const float* local, const float* guess, float* outTransform, double* outVariance, int* outScalars, int* outMatches,
+              int* outInliers, float* outPoints3) {
+    MotionMonoParams p;
+    p.minInliers = minInliers; p.iterations = iterations; p.seed = seed; p.reprojThreshold = reprojThreshold; p.varianceMedianRatio = varianceMedianRatio;
+    p.maxVariance = maxVariance; p.distanceThreshold = distanceThreshold;
+    p.fx = camera[0]; p.fy = camera[1]; p.cx = camera[2]; p.cy = camera[3];
+    p.hasLocalTransform = local != nullptr;
+    if (local) std::copy(local, local + 12, p.localTransform);
+    p.hasGuess = guess != nullptr;
+    if (guess) std::copy(guess, guess + 12, p.guess);
+    MotionMonoResult r;
+    if (!motion_mono_cpu(fromIds, fromPoints, fromPoints3, nFrom, toIds, toPoints, nTo, p, r)) return 0;
+    std::copy(r.transform, r.transform + 12, outTransform);
+    *outVariance = r.variance;
+    outScalars[0] = r.status; outScalars[1] = (int)r.matches.size(); outScalars[2] = (int)r.inliers.size();
+    std::copy(r.matches.begin(), r.matches.end(), outMatches);
+    std::copy(r.inliers.begin(), r.inliers.end(), outInliers);
+    std::copy(r.points3.begin(), r.points3.end(), outPoints3);
+    return 1;
+}
+// MotionMonoHip::estimate through the dictionary's engine; arguments and outputs as hmono_cpu's; returns 1 when the engine took the call
+int hmono_estimate(void* h, const int* idsA, const float* pointsA, const float* points3A, int nA, const int* idsB, const float* pointsB, int nB,
+                   int minInliers, double reprojThreshold, int varianceMedianRatio, float maxVariance, unsigned seed, const float* camera,
+                   const float* local, const float* guess, float* outTransform, double* outVariance, int* outScalars, int* outMatches, int* outInliers,
+                   float* outPoints3) {
+    MotionMonoHip mono;                                                 // the values as they are: a decimal string would round them
+    mono.setMinInliers(minInliers); mono.setReprojThreshold(reprojThreshold); mono.setVarianceMedianRatio(varianceMedianRatio);
+    mono.setMaxVariance(maxVariance);
+    const std::vector<int> a(idsA, idsA + nA), b(idsB, idsB + nB);
+    const std::vector<float> pa(pointsA, pointsA + (size_t)nA * 2), pb(pointsB, pointsB + (size_t)nB * 2);
+    const std::vector<float> p3 = points3A ? std::vector<float>(points3A, points3A + (size_t)nA * 3) : std::vector<float>();
+    lcd_camera cam;
+    cam.fx = camera[0]; cam.fy = camera[1]; cam.cx = camera[2]; cam.cy = camera[3];
+    cam.image_width = 0; cam.image_height = 0; cam.has_local_transform = local ? 1 : 0; cam.reserved = 0;
+    for (int k = 0; k < 12; ++k) cam.local_transform[k] = local ? local[k] : 0.0f;
+    MotionMonoResult r;
+    if (!mono.estimate(((VWDictionaryHip*)h)->engine(), a, pa, p3, b, pb, cam, guess, r, seed)) return 0;
+    std::copy(r.transform, r.transform + 12, outTransform);
+    *outVariance = r.variance;
+    outScalars[0] = r.status; outScalars[1] = (int)r.matches.size(); outScalars[2] = (int)r.inliers.size();
+    std::copy(r.matches.begin(), r.matches.end(), outMatches);
+    std::copy(r.inliers.begin(), r.inliers.end(), outInliers);
+    std::copy(r.points3.begin(), r.points3.end(), outPoints3);
+    return 1;
 }
 // the number of signatures whose words and keypoints a RtabmapHip keeps for the epipolar check
 int hrtab_epipolar_kept(void* r) { return ((RtabmapHip*)r)->getEpipolarKept(); }

@@ -143,6 +143,8 @@ def lib():
         L.hrtab_process_keypoints.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
         L.hepi_cpu.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, C.c_double, C.c_uint, vp, vp, vp, vp]
         L.hepi_check.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, C.c_double, C.c_uint, vp, vp, vp, vp]
+        L.hmono_cpu.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, C.c_uint, C.c_double, ci, cf, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hmono_estimate.argtypes = [vp, vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, ci, cf, C.c_uint, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.hepi_accept.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, C.c_double, C.c_double, C.c_uint]
         L.hrtab_epipolar_kept.argtypes = [vp]
         L.hrtab_last_word_ids.argtypes = [vp, vp, ci]
@@ -505,6 +507,39 @@ def epipolar_cpu(from_ids, from_points, to_ids, to_points, match_count_min=8, it
     return dict(fundamental=f, status=int(sc[0]), matches=om[:sc[1]].copy(), inliers=oi[:sc[2]].copy())
 
 
+def _mono_arrays(camera, local_transform, guess, from_points3, n_from):
+    cam = np.array([camera[k] for k in ("fx", "fy", "cx", "cy")] if isinstance(camera, dict) else list(camera), np.float32).reshape(4)
+    loc = None if local_transform is None else np.ascontiguousarray(local_transform, dtype=np.float32).reshape(12)
+    gs = None if guess is None else np.ascontiguousarray(guess, dtype=np.float32).reshape(12)
+    f3 = None if from_points3 is None else np.ascontiguousarray(from_points3, dtype=np.float32).reshape(-1, 3)
+    if f3 is not None and f3.shape[0] != n_from:
+        raise ValueError("one 3-D point per from word id")
+    return cam, loc, gs, f3
+
+
+def _mono_result(ok, t, var, sc, om, oi, p3):
+    if not ok:
+        return None
+    return dict(transform=t, status=int(sc[0]), variance=float(var[0]), matches=om[:sc[1]].copy(), inliers=oi[:sc[2]].copy(), points3=p3[:sc[2]].copy())
+
+
+def motion_mono_cpu(from_ids, from_points, to_ids, to_points, camera=(525.0, 525.0, 319.5, 239.5), from_points3=None, local_transform=None, guess=None,
+                    min_inliers=20, iterations=1000, reproj_threshold=2.0, variance_median_ratio=4, max_variance=0.1, distance_threshold=50.0, seed=0):
+    """the rule of lcd_estimate_motion_mono on the CPU (host/MotionMono.cpp, no device) -> dict(transform [12], status, variance, matches,
+    inliers, points3 [inliers x 3]), or None where the call is refused"""
+    fi, fp = _kp_arrays(from_ids, from_points)
+    ti, tp = _kp_arrays(to_ids, to_points)
+    cam, loc, gs, f3 = _mono_arrays(camera, local_transform, guess, from_points3, fi.shape[0])
+    n = max(ti.shape[0], 1)
+    t, var, sc = np.zeros(12, np.float32), np.zeros(1, np.float64), np.zeros(3, np.int32)
+    om, oi, p3 = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+    f3p = None if f3 is None else f3.ctypes.data
+    ok = lib().hmono_cpu(_p(fi), _p(fp), f3p, fi.shape[0], _p(ti), _p(tp), ti.shape[0], int(min_inliers), int(iterations), int(seed) & 0xFFFFFFFF,
+                         float(reproj_threshold), int(variance_median_ratio), float(max_variance), float(distance_threshold), _p(cam), _pn(loc), _pn(gs),
+                         _p(t), _p(var), _p(sc), _p(om), _p(oi), _p(p3))
+    return _mono_result(ok, t, var, sc, om, oi, p3)
+
+
 def _ba_camera(camera):
     """a camera dict(fx, fy, cx, cy[, image_width, image_height, local_transform]) as the shim's three arrays"""
     cam = np.array([camera["fx"], camera["fy"], camera["cx"], camera["cy"]], np.float32)
@@ -658,6 +693,24 @@ class VWDictionaryHip:
         if not ok:
             return None
         return int(sc[0]) == 0, f, pairs[:sc[1]].tolist(), st[:sc[1]].copy(), int(sc[0])
+
+    def estimate_motion_mono(self, kpts_a, kpts_b, words3a=None, camera=(525.0, 525.0, 319.5, 239.5), local_transform=None, guess=None, min_inliers=20,
+                             reproj_threshold=2.0, variance_median_ratio=4, max_variance=0.1, seed=0):
+        """MotionMonoHip::estimate (util3d_features.cpp:209-413 behind RegistrationVis.cpp:1584-1675, Vis/EstimationType = 2) over this
+        dictionary's long-lived engine handle; kpts_a and kpts_b are (word ids, [n x 2] keypoints), words3a None or the [n x 3] points of
+        kpts_a's rows (for the scale); an id may repeat.  -> dict(transform [12] (zeros: none), status, variance, matches, inliers, points3), or
+        None where the engine refuses the call"""
+        ia, pa = _kp_arrays(*kpts_a)
+        ib, pb = _kp_arrays(*kpts_b)
+        cam, loc, gs, f3 = _mono_arrays(camera, local_transform, guess, words3a, ia.shape[0])
+        n = max(ib.shape[0], 1)
+        t, var, sc = np.zeros(12, np.float32), np.zeros(1, np.float64), np.zeros(3, np.int32)
+        om, oi, p3 = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+        f3p = None if f3 is None or f3.shape[0] == 0 else f3.ctypes.data
+        ok = lib().hmono_estimate(self.h, _p(ia), _p(pa), f3p, ia.shape[0], _p(ib), _p(pb), ib.shape[0], int(min_inliers), float(reproj_threshold),
+                                  int(variance_median_ratio), float(max_variance), int(seed) & 0xFFFFFFFF, _p(cam), _pn(loc), _pn(gs), _p(t), _p(var),
+                                  _p(sc), _p(om), _p(oi), _p(p3))
+        return _mono_result(ok, t, var, sc, om, oi, p3)
 
     def check_epipolar(self, kpts_a, kpts_b, match_count_min=8, ransac_param1=3.0, ransac_param2=0.99, seed=0):
         """EpipolarGeometryHip::check alone: the accept decision (False also where the engine refuses the call)"""
