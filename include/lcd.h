@@ -106,7 +106,7 @@ typedef struct lcd_config {
                                   lcd_bayes_set_neighbors are queued behind the owed stages of the frame they follow, so they keep their
                                   place in the call order.  Results are identical with and without.  The one exception to "any other
                                   call completes the owed stages": lcd_match_pairs / lcd_match_pairs_dev, lcd_match_guided / lcd_match_guided_dev and
-                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_keypoints_3d_stereo / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_estimate_motion_mono / lcd_refine_motion_ba / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
+                                  lcd_select_features / lcd_expand_word_ids / lcd_keypoints_3d / lcd_keypoints_3d_stereo / lcd_track_flow / lcd_estimate_motion_3d / lcd_estimate_motion_pnp / lcd_estimate_motion_mono / lcd_refine_motion_ba / lcd_register_icp / lcd_register_icp_plane / lcd_filter_scans with their _dev forms
                                   touch no engine state and complete nothing -- they are enqueued on the engine stream where the call lands, with scratch of their own. */
     int32_t reserved1;
 } lcd_config;
@@ -761,6 +761,94 @@ int lcd_keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a
 /* the images, points, response, rows, aux and out_* in DEVICE memory (points and out_right 8-byte aligned); offsets, images, cameras and
  * params on the HOST (read during the call); enqueued on the engine stream, not synchronised */
 int lcd_keypoints_3d_stereo_dev(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a);
+
+/* ---- optical-flow correspondences, stateless: the other way RegistrationVis finds the correspondences of two frames, Vis/CorType = 1
+ * (RegistrationVis.cpp:510-780).  Every corner of the FROM image is tracked into the TO image by pyramidal Lucas-Kanade on both axes
+ * (cv::calcOpticalFlowPyrLK at :697), the tracked corners that land inside the image are kept (:709-724), and both corner lists with the
+ * caller's payload (the word id, the from-side 3-D point) go on to the estimators.  Stateless exactly as lcd_keypoints_3d_stereo; pair p owns
+ * the features [offsets[p], offsets[p+1]) of every array and has its own two images, pairs[p].  Pairs may share images: every DISTINCT image
+ * (pointer, pitch and size) gets one pyramid, built to the highest level any of its pairs needs (A->B and B->C build B once).
+ *
+ * The rule.  OpenCV's text is not in the reference tree, so the tracker is the ENGINE'S rule: lcd_keypoints_3d_stereo's tracker with the y
+ * correction restored and the sums in the engine's lane-tree order.  No product is fused into a sum anywhere.
+ *   Unchanged from lcd_keypoints_3d_stereo's rule, by reference: the pyramid, the Scharr derivative, reflect101, the 14-bit weights with
+ *      half to even, ival / ixval / iyval of a window pixel, the bounds test, cvFloor, A11 / A12 / A22 -> D and minEig with their two tests,
+ *      the clamping of iterations and eps.  Both images of a pair get the same number of levels: the stereo rule's count for width, height,
+ *      the window and pairs[p].max_level.
+ *   Start: at the top level nextPt = prevPt; with pairs[p].use_initial nextPt = initial * float(1/2^level) on both coordinates.  Below the top
+ *      level it is the previous nextPts * 2.f.
+ *   Sums: A11, A12, A22, b1, b2 and the L1 error are added in the lane-tree order the motion rules use (lcd_estimate_motion_3d step 4) with
+ *      64 parts: with p the row-major index of the window pixel, part p % 64 adds its terms in ascending p from +0, then the 64 parts are
+ *      added by the halving tree (part l += part l + s for l < s; s = 32, 16, .. 1).  Each term is float(int product) as in the stereo
+ *      rule.  The stereo rule's row-major chain is NOT used here.
+ *   Step: delta.x = ((A12*b2) - (A22*b1)) * D, delta.y = ((A12*b1) - (A11*b2)) * D, one operation per statement; nextPt += delta;
+ *      nextPts = nextPt + halfWin.
+ *   Stop: double(delta.x)*double(delta.x) + double(delta.y)*double(delta.y) <= eps^2.
+ *   Oscillation: j > 0 && double(fabsf(delta.x + prevDelta.x)) < 0.01 && double(fabsf(delta.y + prevDelta.y)) < 0.01:
+ *      nextPts -= delta * 0.5f on both coordinates, break.
+ *   Error: use_min_eigenvals == 0: the L1 error of the stereo rule at level 0.  use_min_eigenvals == 1: out_err is minEig of the last level
+ *      (the lowest) whose window at prevPt was inside, 0 where none was.
+ *   Status: 0 exactly where the stereo rule sets it -- the window outside at level 0, the eigen test at level 0, leaving during the
+ *      iterations at level 0, the error window outside.
+ *   Keep (RegistrationVis.cpp:709-724): the status is set; to.x is finite, !(to.x < 0.f) and !(to.x >= float(width)); the same for to.y with
+ *      height; use_min_eigenvals != 0 or err < error_threshold, compared in float.  The kept inputs are compacted in input order: out_from
+ *      gets the input corner, out_to the tracked one, out_aux the payload, out_index the input index.
+ *   out_track [N x 2], out_status [N] and out_err [N] (all optional): calcOpticalFlowPyrLK's own three outputs for every INPUT corner by
+ *      input index.
+ *   The engine's definitions, where OpenCV asserts or is undefined: the limits and the LCD_ERR_INVALID / LCD_ERR_UNSUPPORTED table of
+ *      lcd_keypoints_3d_stereo apply (win_width or win_height outside 3..31, max_level outside 0..8, width <= win_width or height <=
+ *      win_height, a NaN among eps, min_eig_threshold and error_threshold, a pitch below the row, NULL pointers, a wrong struct_size,
+ *      aux_bytes: LCD_ERR_INVALID; a sharded handle, n_pairs > 65535: LCD_ERR_UNSUPPORTED; n_pairs == 0: LCD_OK).  use_initial set with
+ *      initial == NULL: LCD_ERR_INVALID.  A corner, or with use_initial a start position, whose coordinates are not finite or not inside
+ *      (-2^31, 2^31): lcd_track_flow returns LCD_ERR_INVALID; lcd_track_flow_dev gives it status 0, the track (NaN, NaN), err 0 and does
+ *      not keep it.
+ * Out of scope: the projection of the guess (cv::projectPoints, :589-651 -- the caller supplies initial, as lcd_match_guided's caller
+ * supplies the projections), colour conversion, Vis/CorFlowGpu, sharded handles.
+ * Launches: one per pyramid level for the whole batch, one for the tracker (one wave per corner), one for the keep test and the compaction
+ * (one workgroup per pair; out_count is written on the device, so it can be lcd_select_args.n_in of a selection behind this call); nothing is
+ * read back between them, no private segment. */
+typedef struct lcd_flow_pair {      /* HOST array, one per pair */
+    const void* from;               /* 8-bit single-channel; DEVICE memory for the _dev entry, HOST memory for the host entry */
+    const void* to;
+    int64_t from_pitch_bytes, to_pitch_bytes;   /* bytes between rows, >= width */
+    int32_t width, height;          /* of both images; > win_width, > win_height */
+    int32_t max_level;              /* 0..8; the caller writes guessSet ? 0 : Vis/CorFlowMaxLevel (3), as :695 does */
+    int32_t use_initial;            /* OPTFLOW_USE_INITIAL_FLOW: the pair's rows of `initial` are the start positions */
+} lcd_flow_pair;
+typedef struct lcd_flow_params {    /* HOST */
+    int32_t win_width, win_height;  /* both Vis/CorFlowWinSize 16; 3..31 */
+    int32_t iterations;             /* Vis/CorFlowIterations 30 */
+    int32_t use_min_eigenvals;      /* 1 (RegistrationVis passes OPTFLOW_LK_GET_MIN_EIGENVALS); 0: the L1 error against error_threshold */
+    double eps;                     /* Vis/CorFlowEps 0.01 */
+    double min_eig_threshold;       /* 1e-4 */
+    float error_threshold;          /* 20, compared in float as :714 does */
+    int32_t reserved;
+} lcd_flow_params;
+typedef struct lcd_track_flow_args {
+    int32_t struct_size;            /* sizeof(lcd_track_flow_args) */
+    int32_t n_pairs;                /* >= 0; 0 returns LCD_OK */
+    int32_t aux_bytes;              /* a multiple of 4, 0..64 */
+    int32_t reserved;
+    const int64_t* offsets;         /* HOST, [n_pairs + 1], non-decreasing, [0] == 0 */
+    const lcd_flow_pair* pairs;     /* HOST, [n_pairs] */
+    const lcd_flow_params* params;  /* HOST */
+    const float* points;            /* [N x 2] the from corners (x, y) */
+    const float* initial;           /* [N x 2] the start positions; may be NULL when no pair sets use_initial */
+    const void* aux;                /* may be NULL (aux_bytes == 0): [N x aux_bytes], e.g. the word id and the from-side 3-D point */
+    int32_t* out_count;             /* [n_pairs] */
+    int32_t* out_index;             /* [N]: the kept inputs in ascending index, the rest of the region -1 */
+    float* out_from;                /* [N x 2] */
+    float* out_to;                  /* [N x 2] */
+    void* out_aux;                  /* [N x aux_bytes], needed with aux */
+    float* out_track;               /* may be NULL: [N x 2] by INPUT index */
+    uint8_t* out_status;            /* may be NULL: [N] by INPUT index */
+    float* out_err;                 /* may be NULL: [N] by INPUT index */
+} lcd_track_flow_args;
+/* every pointer on the HOST (the images too; every distinct image is staged once); synchronises the engine stream */
+int lcd_track_flow(lcd_engine* h, const lcd_track_flow_args* a);
+/* the images, points, initial, aux and out_* in DEVICE memory (points, initial, out_from, out_to and out_track 8-byte aligned); offsets,
+ * pairs and params on the HOST (read during the call); enqueued on the engine stream, not synchronised */
+int lcd_track_flow_dev(lcd_engine* h, const lcd_track_flow_args* a);
 
 /* ---- 3-D to 3-D motion estimation, stateless: the verification behind a loop-closure hypothesis for a caller who holds both frames' word
  * ids and 3-D points in device memory (RegistrationVis.cpp:1823-1871 with Vis/EstimationType = 0).  util3d::estimateMotion3DTo3D

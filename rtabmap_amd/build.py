@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liblcd_hip.so")
-SOURCES = ["knn2_kernels.hip", "knn_mfma_kernels.hip", "knn_hamming_mfma.hip", "resolve_kernels.hip", "tfidf.hip", "similarity.hip", "global_similarity.hip","postings_keys.hip", "bayes.hip", "engine.hip", "frame_pipeline.hip", "pair_match.hip", "guided_match.hip", "feature_select.hip", "keypoints_3d.hip", "keypoints_3d_stereo.hip", "motion_3d.hip", "motion_pnp.hip", "motion_ba.hip", "register_icp.hip", "register_icp_plane.hip", "scan_filter.hip", "epipolar.hip", "motion_mono.hip"]
+SOURCES = ["knn2_kernels.hip", "knn_mfma_kernels.hip", "knn_hamming_mfma.hip", "resolve_kernels.hip", "tfidf.hip", "similarity.hip", "global_similarity.hip","postings_keys.hip", "bayes.hip", "engine.hip", "frame_pipeline.hip", "pair_match.hip", "guided_match.hip", "feature_select.hip", "keypoints_3d.hip", "keypoints_3d_stereo.hip", "flow_track.hip", "motion_3d.hip", "motion_pnp.hip", "motion_ba.hip", "register_icp.hip", "register_icp_plane.hip", "scan_filter.hip", "epipolar.hip", "motion_mono.hip"]
 # -ffp-contract=off: the L2 distance must round every product and sum like the reference (no FMA contraction)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          # MFMA results straight into VGPRs: the top-3 epilogue of knn_mfma_filter_kernel reads them with VALU, and an
@@ -80,7 +80,7 @@ def _build_locked(verbose):
 
 
 HOST_OUT = os.path.join(HERE, "liblcd_host.so")
-HOST_SOURCES = ["VWDictionaryHip.cpp", "FeatureSelect.cpp", "Keypoints3D.cpp", "Stereo.cpp", "Motion3D.cpp", "Motion2D.cpp", "MotionBA.cpp", "EpipolarGeometryHip.cpp", "MotionMono.cpp", "RegistrationIcp.cpp", "ScanFilter.cpp", "MemoryHip.cpp", "BayesFilterHip.cpp", "RtabmapHip.cpp", "DbLoaderHip.cpp", "c_shim.cpp"]
+HOST_SOURCES = ["VWDictionaryHip.cpp", "FeatureSelect.cpp", "Keypoints3D.cpp", "Stereo.cpp", "FlowTrack.cpp", "Motion3D.cpp", "Motion2D.cpp", "MotionBA.cpp", "EpipolarGeometryHip.cpp", "MotionMono.cpp", "RegistrationIcp.cpp", "ScanFilter.cpp", "MemoryHip.cpp", "BayesFilterHip.cpp", "RtabmapHip.cpp", "DbLoaderHip.cpp", "c_shim.cpp"]
 
 
 def build_host(force=False, verbose=False):
@@ -93,7 +93,7 @@ def build_host(force=False, verbose=False):
         if all(os.path.getmtime(d) <= t for d in deps):
             return HOST_OUT
     cxx = shutil.which("g++") or "g++"
-    # -ffp-contract=off: Keypoints3D, Stereo, Motion3D, Motion2D, MotionBA, MotionMono, RegistrationIcp and ScanFilter compute the engine's fp32 rules, which fuse no product into a sum
+    # -ffp-contract=off: Keypoints3D, Stereo, FlowTrack, Motion3D, Motion2D, MotionBA, MotionMono, RegistrationIcp and ScanFilter compute the engine's fp32 rules, which fuse no product into a sum
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", "-o", HOST_OUT] + [os.path.join(hdir, s) for s in HOST_SOURCES] + \
           ["-L" + HERE, "-llcd_hip", "-ldl", "-Wl,-rpath,$ORIGIN"]
     if verbose:

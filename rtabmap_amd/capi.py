@@ -31,7 +31,7 @@ SYMBOLS = [
     "lcd_vocab_clear", "lcd_vocab_append", "lcd_vocab_remove", "lcd_vocab_remove_unused", "lcd_vocab_remove_unused_async", "lcd_vocab_rebuild", "lcd_vocab_count", "lcd_vocab_read",
     "lcd_knn2", "lcd_selfdist", "lcd_quantize", "lcd_find_nn",
     "lcd_sig_add", "lcd_sig_remove", "lcd_sig_add_bulk", "lcd_sig_count", "lcd_word_nrefs",
-    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_verify_epipolar", "lcd_verify_epipolar_dev", "lcd_estimate_motion_mono", "lcd_estimate_motion_mono_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
+    "lcd_likelihood", "lcd_similarity", "lcd_similarity_dev", "lcd_sig_set_globals", "lcd_sig_set_globals_dev", "lcd_sig_set_global_bulk", "lcd_sig_clear_globals", "lcd_compare_to", "lcd_compare_to_dev", "lcd_match_pairs", "lcd_match_pairs_dev", "lcd_match_guided", "lcd_match_guided_dev", "lcd_select_features", "lcd_select_features_dev", "lcd_expand_word_ids", "lcd_expand_word_ids_dev", "lcd_keypoints_3d", "lcd_keypoints_3d_dev", "lcd_keypoints_3d_stereo", "lcd_keypoints_3d_stereo_dev", "lcd_track_flow", "lcd_track_flow_dev", "lcd_estimate_motion_3d", "lcd_estimate_motion_3d_dev", "lcd_estimate_motion_pnp", "lcd_estimate_motion_pnp_dev", "lcd_verify_epipolar", "lcd_verify_epipolar_dev", "lcd_estimate_motion_mono", "lcd_estimate_motion_mono_dev", "lcd_refine_motion_ba", "lcd_refine_motion_ba_dev", "lcd_register_icp", "lcd_register_icp_dev", "lcd_register_icp_plane", "lcd_register_icp_plane_dev", "lcd_filter_scans", "lcd_filter_scans_dev", "lcd_adjust_likelihood", "lcd_adjust_likelihood_dev", "lcd_frame_dev", "lcd_frame_host", "lcd_slot_count", "lcd_knn2_dev", "lcd_shard_knn2_dev", "lcd_shard_frame_dev", "lcd_finalize_dev", "lcd_slots_dev", "lcd_stream", "lcd_get_stats", "lcd_profile_begin", "lcd_profile_read", "lcd_profile_read_likelihood", "lcd_profile_score_work", "lcd_set_option", "lcd_record_event", "lcd_trace_push", "lcd_trace_pop",
     "lcd_bayes_configure", "lcd_bayes_reset", "lcd_bayes_set_neighbors", "lcd_bayes_update_dev", "lcd_bayes_update", "lcd_bayes_posterior",
 ]
 
@@ -171,6 +171,34 @@ def stereo_params(params=None):
     return LcdStereoParams(int(v["win_width"]), int(v["win_height"]), int(v["max_level"]), int(v["iterations"]), float(v["eps"]),
                            int(v["use_min_eigenvals"]), 0, float(v["min_eig_threshold"]), float(v["error_threshold"]), float(v["min_disparity"]),
                            float(v["max_disparity"]))
+
+
+class LcdFlowPair(C.Structure):
+    _fields_ = [("from_", C.c_void_p), ("to", C.c_void_p), ("from_pitch_bytes", C.c_int64), ("to_pitch_bytes", C.c_int64), ("width", C.c_int32),
+                ("height", C.c_int32), ("max_level", C.c_int32), ("use_initial", C.c_int32)]
+
+
+class LcdFlowParams(C.Structure):
+    _fields_ = [("win_width", C.c_int32), ("win_height", C.c_int32), ("iterations", C.c_int32), ("use_min_eigenvals", C.c_int32), ("eps", C.c_double),
+                ("min_eig_threshold", C.c_double), ("error_threshold", C.c_float), ("reserved", C.c_int32)]
+
+
+class LcdTrackFlowArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("aux_bytes", C.c_int32), ("reserved", C.c_int32), ("offsets", C.c_void_p),
+                ("pairs", C.POINTER(LcdFlowPair)), ("params", C.POINTER(LcdFlowParams)), ("points", C.c_void_p), ("initial", C.c_void_p),
+                ("aux", C.c_void_p), ("out_count", C.c_void_p), ("out_index", C.c_void_p), ("out_from", C.c_void_p), ("out_to", C.c_void_p),
+                ("out_aux", C.c_void_p), ("out_track", C.c_void_p), ("out_status", C.c_void_p), ("out_err", C.c_void_p)]
+
+
+# lcd_flow_params: the reference's defaults (Vis/CorFlowWinSize .. Vis/CorFlowErrorThreshold)
+FLOW_DEFAULTS = dict(win_width=16, win_height=16, iterations=30, eps=0.01, use_min_eigenvals=1, min_eig_threshold=1e-4, error_threshold=20.0)
+
+
+def flow_params(params=None):
+    """a dict over FLOW_DEFAULTS -> LcdFlowParams"""
+    v = dict(FLOW_DEFAULTS, **(params or {}))
+    return LcdFlowParams(int(v["win_width"]), int(v["win_height"]), int(v["iterations"]), int(v["use_min_eigenvals"]), float(v["eps"]),
+                         float(v["min_eig_threshold"]), float(v["error_threshold"]), 0)
 
 
 class LcdMotion3dArgs(C.Structure):
@@ -355,6 +383,8 @@ def load():
     L.lcd_keypoints_3d_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dArgs)]
     L.lcd_keypoints_3d_stereo.argtypes = [vp, C.POINTER(LcdKeypoints3dStereoArgs)]
     L.lcd_keypoints_3d_stereo_dev.argtypes = [vp, C.POINTER(LcdKeypoints3dStereoArgs)]
+    L.lcd_track_flow.argtypes = [vp, C.POINTER(LcdTrackFlowArgs)]
+    L.lcd_track_flow_dev.argtypes = [vp, C.POINTER(LcdTrackFlowArgs)]
     L.lcd_estimate_motion_3d.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_3d_dev.argtypes = [vp, C.POINTER(LcdMotion3dArgs)]
     L.lcd_estimate_motion_pnp.argtypes = [vp, C.POINTER(LcdMotionPnpArgs)]
@@ -892,6 +922,65 @@ class Engine:
         a.out_response, a.out_rows, a.out_aux = ptr(d_out_response), ptr(d_out_rows), ptr(d_out_aux)
         a.out_right, a.out_status = ptr(d_out_right), ptr(d_out_status)
         self._ck(self.L.lcd_keypoints_3d_stereo_dev(self.h, C.byref(a)))
+
+    # ---- optical-flow correspondences (stateless; include/lcd.h has the rule)
+    @staticmethod
+    def _flow_pairs(pairs, data_ptr):
+        """pairs: one dict per pair -- from, to (2-D uint8 arrays / tensors, possibly views with a row stride), optionally max_level (3),
+        use_initial (0), width, height, from_pitch_bytes, to_pitch_bytes -> the lcd_flow_pair array"""
+        arr = (LcdFlowPair * max(len(pairs), 1))()
+        pitch_of = lambda d: 0 if d is None else int(d.strides[0] if hasattr(d, "strides") else d.stride(0) * d.element_size())
+        for k, pr in enumerate(pairs):
+            f, t = pr["from"], pr["to"]
+            some = f if f is not None else t
+            arr[k] = LcdFlowPair(None if f is None else data_ptr(f), None if t is None else data_ptr(t),
+                                 int(pr["from_pitch_bytes"]) if "from_pitch_bytes" in pr else pitch_of(f),
+                                 int(pr["to_pitch_bytes"]) if "to_pitch_bytes" in pr else pitch_of(t),
+                                 int(pr.get("width", some.shape[1] if some is not None else 0)), int(pr.get("height", some.shape[0] if some is not None else 0)),
+                                 int(pr.get("max_level", 3)), int(pr.get("use_initial", 0)))
+        return arr
+
+    def track_flow(self, points, offsets, pairs, params=None, initial=None, aux=None, track=True, status=True, err=True):
+        """lcd_track_flow over host arrays -> dict(count [n_pairs], index [N], from, to [N x 2], aux or None, track [N x 2], status [N] and
+        err [N] by input index or None); only the first count[p] entries of a pair's region of the compacted arrays are meaningful
+        (outputs start as zeros)."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        q = None if initial is None else np.ascontiguousarray(initial, dtype=np.float32).reshape(-1, 2)
+        n, n_pairs = p.shape[0], off.shape[0] - 1
+        x = None if aux is None else np.ascontiguousarray(aux, dtype=np.uint8).reshape(n, -1)
+        arr = self._flow_pairs(pairs, lambda a: a.ctypes.data)
+        fp = params if isinstance(params, LcdFlowParams) else flow_params(params)
+        a = LcdTrackFlowArgs(C.sizeof(LcdTrackFlowArgs), n_pairs, 0 if x is None else x.shape[1], 0)
+        a.offsets, a.pairs, a.params = off.ctypes.data, arr, C.pointer(fp)
+        m = max(n, 1)
+        out = {"count": np.zeros(max(n_pairs, 1), np.int32), "index": np.zeros(m, np.int32), "from": np.zeros((m, 2), np.float32),
+               "to": np.zeros((m, 2), np.float32), "aux": None if x is None else np.zeros((m, x.shape[1]), np.uint8),
+               "track": np.zeros((m, 2), np.float32) if track else None, "status": np.zeros(m, np.uint8) if status else None,
+               "err": np.zeros(m, np.float32) if err else None}
+        a.points, a.initial, a.aux = _p(p), _p(q), _p(x)
+        a.out_count, a.out_index, a.out_from, a.out_to, a.out_aux = _p(out["count"]), _p(out["index"]), _p(out["from"]), _p(out["to"]), _p(out["aux"])
+        a.out_track, a.out_status, a.out_err = _p(out["track"]), _p(out["status"]), _p(out["err"])
+        self._ck(self.L.lcd_track_flow(self.h, C.byref(a)))
+        out["count"] = out["count"][:n_pairs]
+        for k in ("index", "from", "to", "aux", "track", "status", "err"):
+            out[k] = None if out[k] is None else out[k][:n]
+        return out
+
+    def track_flow_dev(self, d_points, offsets, pairs, d_count, d_index, d_from, d_to, params=None, d_initial=None, d_aux=None, aux_bytes=0,
+                       d_out_aux=None, d_out_track=None, d_out_status=None, d_out_err=None):
+        """lcd_track_flow_dev on torch tensors of the engine's device (the images too; offsets, pairs and params stay on the host).
+        Enqueued on the engine stream, not synchronised."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        arr = self._flow_pairs(pairs, lambda t: t.data_ptr())
+        fp = params if isinstance(params, LcdFlowParams) else flow_params(params)
+        a = LcdTrackFlowArgs(C.sizeof(LcdTrackFlowArgs), off.shape[0] - 1, int(aux_bytes), 0)
+        a.offsets, a.pairs, a.params = off.ctypes.data, arr, C.pointer(fp)
+        a.points, a.initial, a.aux = ptr(d_points), ptr(d_initial), ptr(d_aux)
+        a.out_count, a.out_index, a.out_from, a.out_to, a.out_aux = ptr(d_count), ptr(d_index), ptr(d_from), ptr(d_to), ptr(d_out_aux)
+        a.out_track, a.out_status, a.out_err = ptr(d_out_track), ptr(d_out_status), ptr(d_out_err)
+        self._ck(self.L.lcd_track_flow_dev(self.h, C.byref(a)))
 
     # ---- 3-D to 3-D motion estimation (stateless; include/lcd.h has the rule)
     def estimate_motion_3d(self, from_ids, from_xyz, from_offsets, to_ids, to_xyz, to_offsets, min_inliers=20, inlier_distance=0.1, iterations=300,

@@ -1,4 +1,4 @@
-// compact_body.cuh -- what the per-frame kernels of feature_select.hip, keypoints_3d.hip and keypoints_3d_stereo.hip and the motion kernels (motion_3d.hip and
+// compact_body.cuh -- what the per-frame kernels of feature_select.hip, keypoints_3d.hip, keypoints_3d_stereo.hip and flow_track.hip and the motion kernels (motion_3d.hip and
 // motion_pnp.hip, through motion_join.cuh's sort and motion_group.cuh's compaction and selection) share: the ballot scan that compacts a
 // workgroup's flags in thread order, the gather of rows behind an index list, and the bitonic sort of 64-bit keys in LDS.  Device code only.
 // Internal.

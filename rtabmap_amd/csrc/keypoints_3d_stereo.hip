@@ -1,9 +1,9 @@
 // keypoints_3d_stereo.hip -- lcd_keypoints_3d_stereo and its _dev form: lcd_keypoints_3d for a frame with a right image instead of a depth
 // image (reference Features2d.cpp:960-1016 with Stereo/OpticalFlow = true).  The rule is include/lcd.h's; its arithmetic is
 // stereo_flow_rule.h's, compiled here for the device and in rtabmap_amd/host/Stereo.cpp for the host mirror.
-//   stereo_pyramid_kernel: one launch per level for the whole batch.  A workgroup takes a 32 x 8 tile of the new level of one image: the
-//     source rows with their two-pixel halo go to LDS, the horizontal pass goes once into LDS, then the vertical pass.  No derivative image
-//     is written: the tracker takes the derivatives from the patch it stages anyway.
+//   stereo_pyramid_kernel (pyramid_kernel.cuh, shared with flow_track.hip): one launch per level for the whole batch.  A workgroup takes a
+//     32 x 8 tile of the new level of one image: the source rows with their two-pixel halo go to LDS, the horizontal pass goes once into LDS,
+//     then the vertical pass.  No derivative image is written: the tracker takes the derivatives from the patch it stages anyway.
 //   stereo_track_kernel: one wave per keypoint, four waves per workgroup, the levels top down inside the kernel.  The wave stages the left
 //     (w + 3) x (h + 3) patch and computes I, dx and dy of the window into LDS as shorts; in each iteration the lanes compute the window's int
 //     terms in parallel (64 window pixels at a time) and the fp32 sums run in the rule's order over those terms by lane broadcast -- ordered
@@ -14,7 +14,7 @@
 // table (frames with their cameras, then image pairs) and the host entry's staging are StatelessScratch's (stateless_scratch.h).
 #include "engine_impl.h"
 #include "compact_body.cuh"
-#include "stereo_flow_rule.h"
+#include "pyramid_kernel.cuh"
 
 #include <vector>
 
@@ -28,66 +28,21 @@ namespace {
 
 namespace rule = lcd::stereo;
 
-constexpr int BLOCK = 256;
-constexpr int TILE_W = 32, TILE_H = 8;       // a pyramid workgroup's tile of the new level
-constexpr int SRC_W = 2 * TILE_W + 3, SRC_H = 2 * TILE_H + 3;
+using pyramid::BLOCK;
+using pyramid::PatchPx;
+using pyramid::stereo_pyramid_kernel;
 constexpr int TRACK_WAVES = 4;
 
-struct StereoPair {
-    rule::Level left[rule::MAX_LEVELS], right[rule::MAX_LEVELS];
-    int32_t n_levels, pad;
+struct StereoPair {                          // two images of pyramid_kernel.cuh's table, with the same number of levels
+    pyramid::Image left, right;
 };
 struct StereoJob {
     int64_t first;                           // the frame's first feature in every array
     int32_t n, pair;
     rule::Camera cam;
 };
-static_assert(sizeof(rule::Level) == 24 && sizeof(StereoJob) % 8 == 0 && sizeof(StereoPair) % 8 == 0, "the job table: frames, then pairs, back to back");
+static_assert(sizeof(StereoJob) % 8 == 0 && sizeof(StereoPair) == 2 * sizeof(pyramid::Image), "the job table: frames, then pairs (two images each), back to back");
 static_assert(sizeof(rule::Track) == 16, "16 bytes per keypoint in d_small");
-
-// a staged piece of a level: pixel (x, y) of the level lies at p[(y - y0) * stride + (x - x0)], the border already reflected
-struct PatchPx {
-    const unsigned char* p;
-    int x0, y0, stride;
-    __device__ __forceinline__ int operator()(int x, int y) const { return p[(y - y0) * stride + (x - x0)]; }
-};
-
-// blockIdx.x: image * max_tiles + tile, the images being every pair's left and right one in turn
-__global__ __launch_bounds__(BLOCK) void stereo_pyramid_kernel(const StereoPair* pairs, int level, unsigned max_tiles) {
-    __shared__ unsigned char src[SRC_H * SRC_W];
-    __shared__ unsigned short hor[SRC_H * TILE_W];
-    const unsigned image = blockIdx.x / max_tiles;
-    const int tile = (int)(blockIdx.x - image * max_tiles);
-    const StereoPair& P = pairs[image >> 1];
-    if (level >= P.n_levels) return;
-    const rule::Level S = (image & 1) ? P.right[level - 1] : P.left[level - 1];
-    const rule::Level D = (image & 1) ? P.right[level] : P.left[level];
-    const int tiles_x = (D.w + TILE_W - 1) / TILE_W, tiles_y = (D.h + TILE_H - 1) / TILE_H;
-    if (tile >= tiles_x * tiles_y) return;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int ox = tx * TILE_W, oy = ty * TILE_H, sx0 = 2 * ox - 2, sy0 = 2 * oy - 2;
-    const int tid = threadIdx.x;
-    const int cols = min(TILE_W, D.w - ox), rows = min(TILE_H, D.h - oy);      // what of the tile exists
-    const int src_cols = 2 * cols + 3, src_rows = 2 * rows + 3;
-    const rule::GlobalPx px{S};
-    for (int e = tid; e < src_rows * src_cols; e += BLOCK) {
-        const int r = e / src_cols, c = e - r * src_cols;
-        src[r * SRC_W + c] = (unsigned char)px(sx0 + c, sy0 + r);
-    }
-    __syncthreads();
-    const PatchPx sp{src, sx0, sy0, SRC_W};
-    for (int e = tid; e < src_rows * cols; e += BLOCK) {
-        const int r = e / cols, c = e - r * cols;
-        hor[r * TILE_W + c] = (unsigned short)rule::pyr_row(sp, ox + c, sy0 + r);
-    }
-    __syncthreads();
-    const int r = tid / TILE_W, c = tid - r * TILE_W;
-    if (r < rows && c < cols) {
-        const unsigned short* h0 = hor + (2 * r) * TILE_W + c;
-        const int v = rule::pyr_col(h0[0], h0[TILE_W], h0[2 * TILE_W], h0[3 * TILE_W], h0[4 * TILE_W]);
-        const_cast<unsigned char*>(D.data)[(int64_t)(oy + r) * D.pitch + ox + c] = (unsigned char)v;
-    }
-}
 
 struct TrackArgs {
     const StereoJob* jobs;
@@ -126,12 +81,12 @@ __global__ __launch_bounds__(TRACK_WAVES * 64) void stereo_track_kernel(TrackArg
         return;
     }
     const float hx = (float)(ww - 1) * 0.5f, hy = (float)(wh - 1) * 0.5f;
-    const int levels = Pr.n_levels;
+    const int levels = Pr.left.n_levels;
     int status = 1;
     float err = 0.0f, nx = 0.0f, ny = 0.0f;
     // the body below is stereo::track_point's, statement for statement; only the window loops are the wave's
     for (int level = levels - 1; level >= 0; --level) {
-        const rule::GlobalPx pi{Pr.left[level]}, pj{Pr.right[level]};
+        const rule::GlobalPx pi{Pr.left.level[level]}, pj{Pr.right.level[level]};
         const int cols = pi.L.w, rows = pi.L.h;
         const float scale = 1.0f / (float)(1 << level);
         float px = pt.x * scale, py = pt.y * scale;
@@ -372,9 +327,9 @@ int keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a, bo
             same = (int)pairs.size();
             StereoPair Q;
             std::memset(&Q, 0, sizeof Q);
-            Q.n_levels = rule::n_levels(S.width, S.height, P.win_w, P.win_h, P.max_level);
-            Q.left[0] = rule::Level{(const unsigned char*)S.left, (int32_t)S.left_pitch_bytes, S.width, S.height, 0};
-            Q.right[0] = rule::Level{(const unsigned char*)S.right, (int32_t)S.right_pitch_bytes, S.width, S.height, 0};
+            Q.left.n_levels = Q.right.n_levels = rule::n_levels(S.width, S.height, P.win_w, P.win_h, P.max_level);
+            Q.left.level[0] = rule::Level{(const unsigned char*)S.left, (int32_t)S.left_pitch_bytes, S.width, S.height, 0};
+            Q.right.level[0] = rule::Level{(const unsigned char*)S.right, (int32_t)S.right_pitch_bytes, S.width, S.height, 0};
             pairs.push_back(Q);
             pair_frame.push_back(f);
         }
@@ -411,9 +366,9 @@ int keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a, bo
     std::vector<size_t> at_left, at_right;
     if (!on_device)
         for (StereoPair& Q : pairs) {
-            at_left.push_back(stage_image(Q.left[0].data, Q.left[0].pitch, Q.left[0].w, Q.left[0].h));
-            at_right.push_back(stage_image(Q.right[0].data, Q.right[0].pitch, Q.right[0].w, Q.right[0].h));
-            Q.left[0].pitch = Q.right[0].pitch = Q.left[0].w;
+            at_left.push_back(stage_image(Q.left.level[0].data, Q.left.level[0].pitch, Q.left.level[0].w, Q.left.level[0].h));
+            at_right.push_back(stage_image(Q.right.level[0].data, Q.right.level[0].pitch, Q.right.level[0].w, Q.right.level[0].h));
+            Q.left.level[0].pitch = Q.right.level[0].pitch = Q.left.level[0].w;
         }
     const size_t aux_bytes = g.aux ? (size_t)N * a->aux_bytes : 0;
     const unsigned char* images = packed.data();
@@ -427,7 +382,7 @@ int keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a, bo
     const int o_resp = stage.out_kept(g.out_response, (size_t)N * 4);
     const int o_rows = stage.out_kept(g.out_rows, g.rows ? (size_t)N * h->row_bytes : 0), o_aux = stage.out_kept(g.out_aux, aux_bytes);
     LCD_HIP(h, stage.commit(st, &h->bytes_device));
-    for (size_t e = 0; e < at_left.size(); ++e) { pairs[e].left[0].data = images + at_left[e]; pairs[e].right[0].data = images + at_right[e]; }
+    for (size_t e = 0; e < at_left.size(); ++e) { pairs[e].left.level[0].data = images + at_left[e]; pairs[e].right.level[0].data = images + at_right[e]; }
     g.row_vec = g.rows && g.row_bytes % 16 == 0 && aligned16(g.rows) && aligned16(g.out_rows) ? 16 : 4;
     g.aux_vec = g.aux && g.aux_bytes % 16 == 0 && aligned16(g.aux) && aligned16(g.out_aux) ? 16 : 4;
 
@@ -436,20 +391,12 @@ int keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a, bo
     int top = 1;                                                       // the most levels a pair has
     unsigned max_tiles = 1;
     for (StereoPair& Q : pairs) {
-        top = std::max(top, (int)Q.n_levels);
-        for (int l = 1; l < Q.n_levels; ++l) {
-            const int w = (Q.left[l - 1].w + 1) / 2, ht = (Q.left[l - 1].h + 1) / 2, pitch = (w + 15) & ~15;
-            for (rule::Level* L : {&Q.left[l], &Q.right[l]}) {
-                *L = rule::Level{reinterpret_cast<const unsigned char*>(small), pitch, w, ht, 0};      // an offset until d_small is known
-                small += (size_t)pitch * (size_t)ht;
-            }
-            max_tiles = std::max(max_tiles, (unsigned)(((w + TILE_W - 1) / TILE_W) * ((ht + TILE_H - 1) / TILE_H)));
-        }
+        top = std::max(top, (int)Q.left.n_levels);
+        pyramid::place_levels(Q.left, &small, &max_tiles);             // offsets until d_small is known
+        pyramid::place_levels(Q.right, &small, &max_tiles);
     }
     LCD_HIP(h, S.d_small.reserve(small, 0, st, &h->bytes_device));
-    for (StereoPair& Q : pairs)
-        for (int l = 1; l < Q.n_levels; ++l)
-            for (rule::Level* L : {&Q.left[l], &Q.right[l]}) L->data = S.d_small.as<unsigned char>() + reinterpret_cast<size_t>(L->data);
+    for (StereoPair& Q : pairs) { pyramid::rebase(Q.left, S.d_small.as<unsigned char>()); pyramid::rebase(Q.right, S.d_small.as<unsigned char>()); }
 
     const size_t job_bytes = jobs.size() * sizeof(StereoJob);
     LCD_HIP(h, S.upload_table(&g.jobs, st, &h->bytes_device, jobs.data(), job_bytes, pairs.data(), pairs.size() * sizeof(StereoPair)));
@@ -459,7 +406,7 @@ int keypoints_3d_stereo(lcd_engine* h, const lcd_keypoints_3d_stereo_args* a, bo
         const uint64_t blocks = (uint64_t)max_tiles * 2u * pairs.size();
         if (blocks > 0x7fffffffu) return bad(LCD_ERR_UNSUPPORTED, "more than 2^31 - 1 pyramid tiles in a call");
         for (int l = 1; l < top; ++l) {
-            stereo_pyramid_kernel<<<dim3((unsigned)(blocks)), dim3(BLOCK), 0, st>>>(d_pairs, l, max_tiles);
+            stereo_pyramid_kernel<<<dim3((unsigned)(blocks)), dim3(BLOCK), 0, st>>>(reinterpret_cast<const pyramid::Image*>(d_pairs), l, max_tiles);
             LCD_HIP(h, hipGetLastError());
         }
         TrackArgs t;

@@ -12,7 +12,7 @@
 // one list of them; other files point here.
 //   lcd_match_pairs (pair_match.hip), lcd_match_guided (guided_match.hip),
 //   lcd_select_features and lcd_expand_word_ids (feature_select.hip), lcd_keypoints_3d (keypoints_3d.hip),
-//   lcd_keypoints_3d_stereo (keypoints_3d_stereo.hip),
+//   lcd_keypoints_3d_stereo (keypoints_3d_stereo.hip), lcd_track_flow (flow_track.hip),
 //   lcd_estimate_motion_3d (motion_3d.hip), lcd_estimate_motion_pnp (motion_pnp.hip), lcd_refine_motion_ba (motion_ba.hip),
 //   lcd_register_icp (register_icp.hip), lcd_register_icp_plane (register_icp_plane.hip) and lcd_filter_scans (scan_filter.hip).
 // Everything they write on the device lives here and nowhere else, so they can be enqueued between the stages of frames in flight.  The
@@ -31,6 +31,8 @@ struct StatelessScratch {
     //   coordinate planes behind step 1, three behind the voxel grid, three normal planes)
     //   lcd_keypoints_3d_stereo: 16 bytes per keypoint (the right corner, the status and the L1 error between the tracker and the
     //   projection), then the levels 1.. of every distinct image pair's two pyramids (rows at a pitch of 16 bytes)
+    //   lcd_track_flow: 16 bytes per corner (the tracked corner, the status and the error between the tracker and the keep step), then
+    //   the levels 1.. of every distinct image's pyramid (rows at a pitch of 16 bytes)
     lcd::DevBuf d_small;
     int64_t budget_bytes = 0;                           // lcd_set_option("pair_match_budget"): distance-block bytes per group (0: built-in, 256 MiB)
 

@@ -17,6 +17,7 @@
 #include "RegistrationIcp.h"
 #include "ScanFilter.h"
 #include "Stereo.h"
+#include "FlowTrack.h"
 #include "RtabmapHip.h"
 
 using namespace rtabmap_amd;
@@ -292,6 +293,19 @@ int hst_pyramid(const void* image, long long pitchBytes, int width, int height, 
 }
 void hst_derivative(const void* image, long long pitchBytes, int width, int height, short* outDxDy) {
     StereoOpticalFlowHip::derivative(make_gray(image, pitchBytes, width, height), outDxDy);
+}
+// ---- the optical-flow correspondences (FlowTrack.h; no engine involved).  params: 7 doubles -- winWidth, winHeight, iterations, eps,
+// useMinEigenVals, minEigThreshold, errorThreshold (a float widened).  initial may be NULL.  outKept [n].  Returns the number kept, -1 = refused
+int hflow_track(const double* params, const void* from, long long fromPitch, const void* to, long long toPitch, int width, int height, int maxLevel,
+                const float* points, const float* initial, int n, int asDevice, float* outTrack, unsigned char* outStatus, float* outErr, int* outKept) {
+    FlowParams p;
+    p.winWidth = (int)params[0]; p.winHeight = (int)params[1]; p.iterations = (int)params[2]; p.eps = params[3]; p.useMinEigenVals = params[4] != 0.0;
+    p.minEigThreshold = params[5]; p.errorThreshold = (float)params[6];
+    std::vector<int> kept;
+    if (!flow_track_cpu(make_gray(from, fromPitch, width, height), make_gray(to, toPitch, width, height), maxLevel, points, initial, n, p, asDevice != 0,
+                        outTrack, outStatus, outErr, kept)) return -1;
+    std::copy(kept.begin(), kept.end(), outKept);
+    return (int)kept.size();
 }
 void hmem_set_stereo_params(void* h, const double* params) { ((MemoryHip*)h)->setStereoParams(make_stereo_params(params)); }
 // a stereo frame through MemoryHip::update; the outputs as hmem_update_depth's

@@ -73,6 +73,7 @@ def lib():
         L.hst_pyramid.argtypes = [vp, C.c_longlong, ci, ci, ci, ci, ci, vp, vp]
         L.hst_derivative.argtypes = [vp, C.c_longlong, ci, ci, vp]
         L.hst_derivative.restype = None
+        L.hflow_track.argtypes = [vp, vp, C.c_longlong, vp, C.c_longlong, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
         L.hmem_set_stereo_params.argtypes = [vp, vp]
         L.hmem_set_stereo_params.restype = None
         L.hmem_update_stereo.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, C.c_longlong, vp, C.c_longlong, ci, ci, vp, vp, vp, vp, vp, vp]
@@ -327,6 +328,27 @@ def stereo_derivative(image, width=None):
     out = np.zeros((h, w, 2), np.int16)
     lib().hst_derivative(*gargs, w, h, _p(out))
     return out[:, :, 0].copy(), out[:, :, 1].copy()
+
+
+# ---- flow_track_cpu (rtabmap_amd/host/FlowTrack.h): lcd_track_flow's rule of include/lcd.h as plain host code, no engine
+from .capi import FLOW_DEFAULTS  # noqa: E402  (lcd_flow_params' defaults, stated once)
+
+
+def flow_track_cpu(image_from, image_to, points, params=None, max_level=3, initial=None, width=None, as_device=False):
+    """one pair through the host mirror -> dict(track [n x 2] float32, status [n] uint8, err [n] float32, kept: the indices RegistrationVis
+    keeps), or None where the mirror refuses; the images may be views with a row stride, width the image's where the arrays are wider"""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+    q = None if initial is None else np.ascontiguousarray(initial, dtype=np.float32).reshape(-1, 2)
+    f, fargs, w, h = _gray_args(image_from, width)
+    t, targs, tw, th = _gray_args(image_to, width)
+    if (w, h) != (tw, th):
+        return None
+    v = dict(FLOW_DEFAULTS, **(params or {}))
+    fp = np.array([v[k] for k in ("win_width", "win_height", "iterations", "eps", "use_min_eigenvals", "min_eig_threshold", "error_threshold")], np.float64)
+    n = p.shape[0]
+    track, status, err, kept = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
+    k = lib().hflow_track(_p(fp), *fargs, *targs, w, h, int(max_level), _p(p), _p(q), n, 1 if as_device else 0, _p(track), _p(status), _p(err), _p(kept))
+    return None if k < 0 else dict(track=track[:n].copy(), status=status[:n].copy(), err=err[:n].copy(), kept=kept[:k].copy())
 
 
 def _frame_arrays(ids, xyz):
